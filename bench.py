@@ -10,8 +10,16 @@ witness of each txn is generated on the GPU inside generate_txn_proof, as genera
 inside the reference's call (proof_gen.rs:44-52).  `python3 bench.py --gpus N` without a launcher
 starts its own N ranks (torch.distributed.run) before it touches the GPU.
 
-The timed region runs first.  Everything that is measured ALONE on the chip runs afterwards in a
-fresh child process (`--leg-only`) and is merged into the one JSON line:
+A plain run does only what the headline figure needs: build the prover state, warm up, time the
+--steps blocks, write the last block's outputs (--dump-outputs DIR) and print the JSON line.
+`--dump-outputs DIR` writes what the last timed step returned to its caller, the block proof, as
+DIR/block_proof.npy (one float32 per byte, exact) and DIR/block_height.npy (float64).
+
+Everything else runs only with --full: the verification of the last block proof, the engine
+clock held in the timed region and the VALU-issue estimate built on it, the CPU baseline, and the
+alone-on-the-chip figures.  With --full the timed region runs first.  Everything that is measured
+ALONE on the chip runs afterwards in a fresh child process (`--leg-only`) and is merged into the
+one JSON line:
   roofline      -- the coset-LDE NTT kernel family (the HBM-roofline kernel the metric names): HIP events on the
                    kernel's own stream over a single-stream leg (2 txn proofs, nothing else on the chip); traffic =
                    algorithmic bytes x the PMC-measured ratio of a tracked profiles/ summary;
@@ -97,6 +105,13 @@ def main():
                     help="concurrent provers (HIP streams) per GPU; 0 = at most 20, dividing the shard into equally full "
                          "rounds: measured optimum (profiles/r4_sweep_threads.txt); the waits sleep, so the count is not "
                          "tied to host cores")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the last block proof and measure everything beyond the headline figure: engine "
+                         "clock and VALU issue, the CPU baseline, the alone-on-the-chip roofline leg (each of the last "
+                         "two can still be switched off with --no-cpu-baseline / --no-profile)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's block proof to DIR/block_proof.npy (float32, one value per byte) "
+                         "and DIR/block_height.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event kernel timing (roofline leg)")
     ap.add_argument("--in-situ-profile", action="store_true",
@@ -139,6 +154,9 @@ def main():
     args = ap.parse_args()
     if args.txns < 2:
         raise SystemExit("--txns must be >= 2 (a block needs an aggregation: decoding.rs:304-347 pads to two)")
+    if (args.leg_first or args.in_situ_profile) and not (args.full or args.leg_only):
+        raise SystemExit("--leg-first and --in-situ-profile shape the profiling of --full: add --full")
+    profile = args.full and not args.no_profile
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` without a launcher: this process has not touched the GPU (no torch.cuda, no
@@ -360,7 +378,7 @@ def main():
                   file=sys.stderr, flush=True)
 
     roofline = alu_kernel = None
-    if args.leg_first and not args.no_profile and rank == 0:
+    if args.leg_first and profile and rank == 0:
         phase("single-stream leg")
         roofline, alu_kernel, _, _ = single_stream_leg()
     phase("state build")
@@ -388,13 +406,13 @@ def main():
     phase("warmup")
     for b in range(args.warmup):
         last = driver.prove_block_distributed(blocks[b], rank, world, gather)
-    in_situ = args.in_situ_profile and not args.no_profile and not args.no_in_situ_profile
+    in_situ = args.in_situ_profile and profile and not args.no_in_situ_profile
     if in_situ:
         L.bp_profile_reset()
         L.bp_profile_enable(1)
     barrier()
     step_ms = []
-    clock = ClockSampler(torch, local_rank) if rank == 0 else None   # engine clock actually held in the timed region
+    clock = ClockSampler(torch, local_rank) if rank == 0 and args.full else None   # engine clock actually held in the timed region
     t0 = time.perf_counter()
     for b in range(args.warmup, args.warmup + args.steps):
         phase("timed step %d" % (b - args.warmup))
@@ -417,7 +435,9 @@ def main():
                                        "the chip, mostly with integer-ALU-bound Poseidon kernels, so a launch's "
                                        "duration is not the kernel's own cost" % args.threads, leg=False)
 
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    if rank == 0 and args.full:
         # acceptance: the block proof verifies (VerifierState::verify, verifier_state.rs:56-71)
         pg.VerifierState.from_prover_state(state).verify(last)
     L.bp_host_wait_mode.restype = C.c_int
@@ -459,9 +479,10 @@ def main():
                    "ms_of_each_step_rank0": step_ms, "host_waits": host_waits, **t_build_info},
     }
     out["engine_clock"] = clock_held
-    out["valu_issue"] = block_valu_issue(out["value"], clock_held, synthetic_rec=args.synthetic_rec, real_airs=args.real_airs or args.keccak_air)
+    out["valu_issue"] = block_valu_issue(out["value"], clock_held, synthetic_rec=args.synthetic_rec,
+                                         real_airs=args.real_airs or args.keccak_air) if args.full else None
     alone = {}
-    if not args.no_profile:
+    if profile:
         if args.leg_first:
             alone = {"roofline": roofline, "alu_kernel": alu_kernel}
             if world == 1:
@@ -496,7 +517,7 @@ def main():
     for k in ("hbm_kernels", "k5", "real_airs", "synthetic_rec", "roofline_isolated", "ntt_hbm_gbps"):
         if k in alone:
             out[k] = alone[k]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(blocks[args.warmup][0], synthetic_rec=args.synthetic_rec)
     print(json.dumps(out), flush=True)
 
@@ -710,6 +731,25 @@ def ntt_gbps(pkg, torch):
         out["2^%d x %d" % (log_n, cols)] = {"GB/s": round(gbps, 1), "frac": round(gbps / HBM_PEAK_GBPS, 4)}
         del v
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, block_proof):
+    """--dump-outputs: what the last timed step handed its caller (a GeneratedBlockProof), in float types that hold it
+    exactly -- the proof's bytes one float32 each, the block height as float64 -- so that two builds can be compared
+    output for output.  An array over its share of 64 MB is replaced by a fixed, seeded sample of its elements."""
+    import numpy as np
+    arrays = {"block_proof": np.frombuffer(block_proof.intern, dtype=np.uint8).astype(np.float32),
+              "block_height": np.array([block_proof.b_height], dtype=np.float64)}
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)   # 4 KiB per file for the .npy header
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def usable_cores():

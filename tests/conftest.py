@@ -1,5 +1,6 @@
 import os
 import sys
+import tempfile
 
 import pytest
 
@@ -39,7 +40,9 @@ def pytest_runtest_logstart(nodeid, location):
         import faulthandler
         if _WATCHDOG_FILE is None:  # pytest captures fd 2 while a test runs: the dump goes to a file of its own
             d = os.path.join(ROOT, "gpurun_out")
-            _WATCHDOG_FILE = open(os.path.join(d if os.path.isdir(d) else "/tmp", "test_watchdog.txt"), "w")
+            # in the shared temporary directory the name carries the user id: another user's file cannot be opened
+            _WATCHDOG_FILE = open(os.path.join(d, "test_watchdog.txt") if os.path.isdir(d) else
+                                  os.path.join(tempfile.gettempdir(), "test_watchdog.%d.txt" % os.getuid()), "w")
         _WATCHDOG_FILE.seek(0)
         _WATCHDOG_FILE.truncate()
         _WATCHDOG_FILE.write("watchdog armed for %s (%d s)\n" % (nodeid, _WATCHDOG_S))

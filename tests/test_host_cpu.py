@@ -402,6 +402,19 @@ def test_bench_spawns_its_own_ranks_when_started_without_a_launcher(monkeypatch)
         bench.main()
 
 
+def test_bench_profiling_knobs_need_full(monkeypatch):
+    """--leg-first and --in-situ-profile only shape the measurements of --full: without it they are refused before any
+    device work instead of being ignored."""
+    import importlib
+    import sys as _sys
+    _sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    for knob in ("--leg-first", "--in-situ-profile"):
+        monkeypatch.setattr(_sys, "argv", ["bench.py", knob])
+        with pytest.raises(SystemExit, match="add --full"):
+            bench.main()
+
+
 def test_witness_entry_points_check_their_arguments_before_any_device_work():
     """bp_keccak_trace / bp_logic_trace / bp_memory_trace / bp_arithmetic_trace / bp_byte_packing_trace and the IR flag setters: null outputs,
     heights out of range and tables of the wrong width are refused with BP_ERR_INVALID_INPUT (-2) and a message, without a

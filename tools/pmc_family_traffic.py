@@ -3,10 +3,10 @@ from two rocprofv3 counter passes (MI355X_MICROARCH.md, HBM section: FETCH_SIZE 
 separate passes, both in KiB; FETCH_SIZE counts half on gfx950 -> x2, see the calibration copy in
 profiles/r1_pmc_fetch_write_lde_2e14x2432.csv; WRITE_SIZE is exact).
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -- \\
-      python bench.py --txns 2 --threads 1 --steps 1 --warmup 0 --no-cpu-baseline > gpurun_out/pmc_f.log
-  (same with WRITE_SIZE into gpurun_out/pmc_w)
-  python tools/pmc_family_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w gpurun_out/pmc_f.log
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_f -- \\
+      python bench.py --txns 2 --threads 1 --steps 1 --warmup 0 --full --no-cpu-baseline > OUT/pmc_f.log
+  (same with WRITE_SIZE into OUT/pmc_w; OUT is any output directory)
+  python tools/pmc_family_traffic.py OUT/pmc_f OUT/pmc_w OUT/pmc_f.log
 
 bench.py brackets its single-stream roofline leg with two one-word `calib_copy_u64_kernel` marker
 dispatches; the family launches between them are the leg, and their algorithmic bytes come from the

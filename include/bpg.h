@@ -270,6 +270,33 @@ int bp_quotient_eval(uint32_t air_id, const struct bp_stark_cfg* shape, const ui
                      const uint64_t* d_aux_lde, const uint64_t* d_const_lde, const uint64_t ctl[4],
                      const uint64_t alphas[2], uint64_t* d_scratch, uint64_t* d_qvals_out, void* stream);
 
+/* The AIR trace checker: which rows of a witness violate which constraints of its AIR, without proving it (upstream's
+ * debugging aid check_constraints).  The AIR is evaluated on the TRACE domain: row i with the next row (i + 1) mod n and
+ * x = w_n^i; all-rows constraints on every row, transition constraints on every row but n - 1, first-row constraints
+ * on row 0, last-row constraints on row n - 1.  Only the AIR's own constraints are checked: not the lookup constraints
+ * of its auxiliary columns, not AIR 8's copy constraints.
+ * shape: validated exactly as bp_quotient_eval's (a fixed-width AIR's own width; a valid configuration).  d_trace:
+ * canonical words, column-major, n_cols columns x 2^log_n rows, column stride `stride` (>= 2^log_n).  d_consts:
+ * n_const columns, column stride 2^log_n (AIR 0 with constant columns, AIR 8: bp_plonk_constants), else NULL.  pub:
+ * AIR 8's four public inputs, else NULL.
+ * Out: *n_violated_rows = how many rows violate a constraint; rows_out[0 .. min(that, max_rows)) = the first of them in
+ * row order; viol_out = the violations of those rows in row order, then constraint index (at most max_viol written);
+ * *n_viol = how many those rows have in all.  value = the constraint's value before its row selector (the sum of what
+ * the evaluator emits for that index); family = its index into bp_air_describe's families, kind its kind.
+ * The device entry marks the rows with a kernel (the constraints folded with fresh random challenges, one bit per row)
+ * and names the constraints of the first max_rows of them on the host; it allocates its own scratch and returns after
+ * the stream has drained.  The _host entry takes host pointers and does everything on the CPU, row by row. */
+typedef struct bp_air_violation {
+  uint32_t row, constraint, family, kind;
+  uint64_t value;
+} bp_air_violation;
+int bp_air_check_trace(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* d_trace, uint64_t stride,
+                       const uint64_t* d_consts, const uint64_t pub[4], uint32_t max_rows, uint64_t* n_violated_rows,
+                       uint32_t* rows_out, bp_air_violation* viol_out, uint32_t max_viol, uint32_t* n_viol, void* stream);
+int bp_air_check_trace_host(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* trace, uint64_t stride,
+                            const uint64_t* consts, const uint64_t pub[4], uint32_t max_rows, uint64_t* n_violated_rows,
+                            uint32_t* rows_out, bp_air_violation* viol_out, uint32_t max_viol, uint32_t* n_viol);
+
 /* Witness of AIR 1 (generate_traces is inside the reference's call too, proof_gen.rs:44-52): n = 2^log_n rows x 2431
  * columns (the last one, the lookup's filter, zero), column-major, row r = round r % 24 of permutation r / 24.  d_inputs: [ceil(n / 24)][25] input lanes
  * (any u64; lane x + 5y), or NULL to draw them from `seed` (splitmix64(seed ^ (lane << 32) ^ permutation)). */
@@ -513,6 +540,37 @@ int bp_verify_txn_table_proofs(const bp_config* cfg, const uint8_t* table_proofs
  * from the blob, i.e. from the prover: its caller must compare that header with what it expects. */
 int bp_verify_txn_table_proofs_for(const bp_config* cfg, const uint8_t* ir, size_t ir_len, const uint8_t* table_proofs,
                                    size_t len);
+/* The transaction witness pre-flight: what bp_generate_txn_proof_witness would say about the same inputs, without
+ * committing or proving anything.  The seven traces are built by the prover's own code (the same refusals, statuses
+ * BP_ERR_INVALID_INPUT / BP_ERR_RANGE); every table proven by its AIR is checked row by row (bp_air_check_trace), and
+ * the three lookups (keccak_sponge -> keccak_f, byte_packing -> memory, keccak_sponge -> logic) as multisets of tuples,
+ * compressed on the device with fresh challenges (the columns air::ctl selects) and compared on the host.  Status: BP_OK
+ * when the prover would accept the data, BP_ERR_VERIFY when it would not -- a given table that violates its AIR (its
+ * row and constraint in the message), else the first lookup that does not hold (its first unmatched rows) -- and out
+ * holds everything found either way.  Takes one of the state's workers, as a proof call does. */
+typedef struct bp_witness_table {
+  uint32_t checked;            /* 1: the table is proven by its AIR and was checked */
+  uint32_t given;              /* 1: made from the caller's data (0: drawn from the seed or derived) */
+  uint64_t n_violated_rows;
+  uint32_t n_viol;             /* violations in viol[] (the first rows', row order) */
+  bp_air_violation viol[8];
+} bp_witness_table;
+typedef struct bp_witness_lookup {
+  uint32_t checked;            /* 1: both tables are proven by their AIRs */
+  uint32_t holds;
+  uint64_t n_looking, n_looked;  /* tuples on each side */
+  int64_t first_looking_row;   /* first looking row whose tuple the looked table does not expose; -1: none */
+  int64_t first_looked_row;    /* first looked row nobody asks for; -1: none */
+} bp_witness_lookup;
+typedef struct bp_witness_report {
+  bp_witness_table table[7];   /* by table index (prover_state.rs:85-93) */
+  bp_witness_lookup lookup[3]; /* keccak_sponge -> keccak_f, byte_packing -> memory, keccak_sponge -> logic */
+} bp_witness_report;
+int bp_check_txn_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
+                         bp_witness_report* out);
+/* the same for bp_generate_txn_proof_keccak's inputs */
+int bp_check_txn_witness_keccak(const bp_state* s, const uint8_t* ir, size_t ir_len, const uint64_t* keccak_inputs,
+                                size_t n_perms, bp_witness_report* out);
 /* the same call taking the reference's own flag: Arc<AtomicBool> is ONE byte, `flag.as_ptr()` binds here directly */
 int bp_generate_txn_proof_u8(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile uint8_t* abort_flag,
                              uint8_t** out, size_t* out_len);

@@ -39,6 +39,11 @@ class AirDesc(C.Structure):
                 + [("families", AirFamily * 24)])
 
 
+class AirViolation(C.Structure):
+    """bp_air_violation: one constraint a row of a trace breaks (bp_air_check_trace)."""
+    _fields_ = [(n, C.c_uint32) for n in ("row", "constraint", "family", "kind")] + [("value", C.c_uint64)]
+
+
 def take_buffer(ptr, length):
     """Copy a library-allocated buffer into bytes and release it with bp_free_buffer."""
     try:
@@ -76,6 +81,10 @@ def lib():
     L.bp_quotient_eval.argtypes = [u32, C.POINTER(StarkCfg), vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]
     L.bp_air_count.restype = u32
     L.bp_air_describe.argtypes = [u32, u32, u32, u32, C.POINTER(AirDesc)]
+    check_args = [u32, C.POINTER(StarkCfg), vp, u64, vp, C.POINTER(u64), u32, C.POINTER(u64), C.POINTER(u32),
+                  C.POINTER(AirViolation), u32, C.POINTER(u32)]
+    L.bp_air_check_trace.argtypes = check_args + [vp]
+    L.bp_air_check_trace_host.argtypes = check_args
     L.bp_keccak_trace.argtypes = [vp, u64, u32, vp, vp]
     L.bp_logic_trace.argtypes = [vp, u64, u32, vp, vp]
     L.bp_memory_trace.argtypes = [vp, u64, u32, vp, vp]

@@ -1,0 +1,272 @@
+// air_check.hip -- the AIR trace checker's device pass: air.hpp's evaluators instantiated a third time, on the TRACE
+// domain (the prover's K5 evaluates them on the LDE coset, the verifier over the extension field at zeta).
+//
+// A lane owns row i of the n = 2^log_n-row trace: loc = row i, nxt = row (i + 1) mod n, x = w_n^i.  The constraints are
+// folded with two fresh challenges exactly as K5's consumer does (alpha-power table, gl::DotAcc), with the selectors of
+// the trace domain: all-rows constraints everywhere, transition constraints on every row but n - 1, first-row ones on
+// row 0, last-row ones on row n - 1.  A row is violated when either fold is non-zero.  Only a fold is a statement:
+// units emit partial sums of one constraint several times (AIRS.md section 1), so no single emission is tested.
+// What the units emit past the AIR's own list (the lookup shares of the logic and sponge tables, AIR 8's copy
+// constraints) is dropped, and the auxiliary columns read as zero: the AIR's own values do not depend on them.
+// Output: one bitmap word per 64 rows, written by the wave that owns them (__ballot), and the violated-row count.
+// Which constraint a violated row breaks is the host's question (air_check.cpp).
+#include <algorithm>
+#include "air_check.hpp"
+#include "common.hpp"
+#include "gl.hpp"
+#include "air.hpp"
+
+namespace {
+
+using bpg::CheckArgs;
+
+struct CheckRow {  // row i of the trace (lanes = consecutive rows: coalesced), no auxiliary columns
+  const uint64_t *trace, *cst_;
+  uint64_t ts, cs, pos, pos_next;
+  uint64_t xv;
+  const uint64_t* pub_;
+  __device__ __forceinline__ uint64_t x() const { return xv; }
+  __device__ __forceinline__ uint64_t pub(uint32_t j) const { return pub_[j]; }
+  __device__ __forceinline__ uint64_t loc(uint32_t c) const { return trace[(uint64_t)c * ts + pos]; }
+  __device__ __forceinline__ uint64_t nxt(uint32_t c) const { return trace[(uint64_t)c * ts + pos_next]; }
+  __device__ __forceinline__ uint64_t cst(uint32_t k) const { return cst_[(uint64_t)k * cs + pos]; }
+  __device__ __forceinline__ uint64_t aux(uint32_t) const { return 0; }
+  __device__ __forceinline__ uint64_t aux_nxt(uint32_t) const { return 0; }
+};
+struct CheckEmit {  // K5's consumer (stark_kernels.hip, DevEmit) with the trace domain's selectors as masks
+  const uint64_t* apow;  // [2][T]
+  uint32_t T;
+  uint64_t m_tr, m_first, m_last;  // all ones where the selector is 1, else zero
+  gl::DotAcc acc[4];
+  uint64_t pend_v;
+  uint32_t pend_e;
+  bool has;
+  __device__ __forceinline__ void push(uint32_t idx, uint64_t v) {
+    if (idx >= T) return;  // a lookup share: not the AIR's own constraint
+    const uint32_t e = T - 1 - idx;
+    if (!has) {
+      pend_v = v; pend_e = e; has = true;
+      return;
+    }
+    const uint64_t a[4] = {pend_v, pend_v, v, v};
+    const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], apow[e], apow[T + e]};
+    gl::dot_mad4(acc, a, w);
+    has = false;
+  }
+  __device__ __forceinline__ void all(uint32_t idx, uint64_t v) { push(idx, v); }
+  __device__ __forceinline__ void transition(uint32_t idx, uint64_t v) { push(idx, v & m_tr); }
+  __device__ __forceinline__ void first(uint32_t idx, uint64_t v) { push(idx, v & m_first); }
+  __device__ __forceinline__ void last(uint32_t idx, uint64_t v) { push(idx, v & m_last); }
+  __device__ __forceinline__ uint64_t result(int j) {
+    if (has) {
+      const uint64_t a[4] = {pend_v, pend_v, 0, 0};
+      const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], 0, 0};
+      gl::dot_mad4(acc, a, w);
+      has = false;
+    }
+    return gl::addc(gl::dot_reduce(acc[j]), gl::dot_reduce(acc[2 + j]));
+  }
+};
+__device__ __forceinline__ CheckEmit check_emit(const CheckArgs& a, uint64_t pos) {
+  const uint64_t last = ((uint64_t)1 << a.log_n) - 1;
+  return CheckEmit{a.apow, a.T, pos != last ? ~0ull : 0ull, pos == 0 ? ~0ull : 0ull, pos == last ? ~0ull : 0ull,
+                   {gl::dot_zero(), gl::dot_zero(), gl::dot_zero(), gl::dot_zero()}, 0, 0, false};
+}
+__device__ __forceinline__ CheckRow check_row(const CheckArgs& a, uint64_t pos, bool with_x) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  return CheckRow{a.trace, a.consts, a.stride, n, pos, (pos + 1) & (n - 1),
+                  with_x ? gl::pow(gl::root(a.log_n), pos) : 0, a.pub};
+}
+// bit `pos % 64` of word `pos / 64` = bad; lane 0 of each wave (its row is a multiple of 64) writes the wave's word.
+// Every lane of the wave must get here (no early return before it).
+__device__ __forceinline__ void flag_rows(const CheckArgs& a, uint64_t pos, bool bad) {
+  const unsigned long long b = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && pos < ((uint64_t)1 << a.log_n)) {
+    a.bitmap[pos >> 6] = b;
+    if (b) atomicAdd(a.count, (unsigned long long)__popcll(b));
+  }
+}
+
+// grid = (ceil(n / 256), wg_rows): workgroup row y evaluates units [y * units_per_wg, ...) of the AIR's list (AIR 8:
+// its ten chunk units; the Poseidon gate is air_check_plonk_hash_kernel's).  One workgroup row: the row's fold is
+// complete and tested here; several: the partial folds go to `partial` and air_check_reduce_kernel tests their sum.
+template <uint32_t AIR>
+__global__ void __launch_bounds__(256) air_check_kernel(CheckArgs a) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  uint64_t r0 = 0, r1 = 0;
+  if (pos < n) {
+    CheckEmit out = check_emit(a, pos);
+    const CheckRow row = check_row(a, pos, AIR == bpg::air::PLONK);
+    const bpg::air::Shape shape{AIR, a.n_cols, a.n_const, a.deg_pow};
+    const uint64_t ctl[4] = {0, 0, 0, 0};  // (only the dropped lookup shares read them)
+    const uint32_t u0 = blockIdx.y * a.units_per_wg, u1 = min(u0 + a.units_per_wg, a.n_units);
+#pragma unroll 1
+    for (uint32_t u = u0; u < u1; u++) {
+      if constexpr (AIR == bpg::air::KECCAK_F) bpg::air::keccak::eval_unit<uint64_t>(u, row, out);
+      else if constexpr (AIR == bpg::air::LOGIC) bpg::air::logic::eval_unit<uint64_t>(u, a.T, ctl, row, out);
+      else if constexpr (AIR == bpg::air::MEMORY) bpg::air::memory::eval_unit<uint64_t>(row, out);
+      else if constexpr (AIR == bpg::air::ARITHMETIC) bpg::air::arithmetic::eval_unit<uint64_t>(u, row, out);
+      else if constexpr (AIR == bpg::air::BYTE_PACKING) bpg::air::byte_packing::eval_unit<uint64_t>(u, row, out);
+      else if constexpr (AIR == bpg::air::KECCAK_SPONGE) bpg::air::keccak_sponge::eval_unit<uint64_t>(u, a.T, ctl, row, out);
+      else if constexpr (AIR == bpg::air::ARITHMETIC_MUL) bpg::air::arithmetic_mul::eval_unit<uint64_t>(u, row, out);
+      else if constexpr (AIR == bpg::air::PLONK) bpg::air::plonk::eval_chunk_unit<uint64_t>(u, a.T, ctl, row, out);
+      else bpg::air::synthetic::eval_unit<uint64_t>(shape, u, row, out);
+    }
+    r0 = out.result(0);
+    r1 = out.result(1);
+  }
+  if (a.partial) {
+    if (pos < n) {
+      a.partial[((uint64_t)blockIdx.y * 2) * n + pos] = r0;
+      a.partial[((uint64_t)blockIdx.y * 2 + 1) * n + pos] = r1;
+    }
+    return;
+  }
+  flag_rows(a, pos, (r0 | r1) != 0);
+}
+// AIR 8's Poseidon gate (K5 keeps it in a kernel of its own for the register budget, and so does the checker): the bare
+// differences folded, times q_hash, into partial row `wg_row`.   grid = (ceil(n / 256))
+__global__ void __launch_bounds__(256) air_check_plonk_hash_kernel(CheckArgs a, uint32_t wg_row) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (pos >= n) return;
+  CheckEmit out = check_emit(a, pos);
+  const CheckRow row = check_row(a, pos, false);
+  bpg::air::plonk::eval_hash_unit<uint64_t, CheckRow, CheckEmit, false>(row, out);
+  const uint64_t qh = row.cst(bpg::air::plonk::CST_HASH);
+  a.partial[((uint64_t)wg_row * 2) * n + pos] = gl::mulc(out.result(0), qh);
+  a.partial[((uint64_t)wg_row * 2 + 1) * n + pos] = gl::mulc(out.result(1), qh);
+}
+// the sum of the partial folds, tested.   grid = (ceil(n / 256))
+__global__ void __launch_bounds__(256) air_check_reduce_kernel(CheckArgs a, uint32_t n_rows) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  uint64_t r0 = 0, r1 = 0;
+  if (pos < n)
+    for (uint32_t c = 0; c < n_rows; c++) {
+      r0 = gl::addc(r0, a.partial[((uint64_t)c * 2) * n + pos]);
+      r1 = gl::addc(r1, a.partial[((uint64_t)c * 2 + 1) * n + pos]);
+    }
+  flag_rows(a, pos, (r0 | r1) != 0);
+}
+// apow[j * T + e] = alpha_j^e.   grid = (ceil(T / 256), 2)
+__global__ void __launch_bounds__(256) air_check_alpha_kernel(uint64_t* apow, uint32_t T, uint64_t a0, uint64_t a1) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= T) return;
+  apow[(uint64_t)blockIdx.y * T + e] = gl::pow(blockIdx.y ? a1 : a0, e);
+}
+// out[j * n_cols + c] = trace[c * stride + rows[j]].   grid = (ceil(n_cols / 256), n_rows)
+__global__ void __launch_bounds__(256) air_check_gather_kernel(const uint64_t* trace, uint64_t stride, uint32_t n_cols,
+                                                               const uint32_t* rows, uint64_t* out) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_cols) return;
+  out[(uint64_t)blockIdx.y * n_cols + c] = trace[(uint64_t)c * stride + rows[blockIdx.y]];
+}
+
+// The witness pre-flight's lookup check (proofgen.cpp): per row the term 1 + f (gamma + v - 1) of product column `col`
+// of the table (air::ctl::product_term: the same filter and column selection; challenge set 0 = (beta, gamma)).  A row
+// the filter leaves out gives 1, a tuple v gives gamma + v.  Keccak-f's looked tuple carries its input in the auxiliary
+// column h; here it is compressed from the trace, 23 rows up (the permutation's first row).   grid = (ceil(n / 256))
+template <uint32_t AIR>
+__global__ void __launch_bounds__(256) lookup_terms_kernel(const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta,
+                                                           uint64_t gamma, uint64_t* out) {
+  const uint64_t n = (uint64_t)1 << log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (pos >= n) return;
+  const CheckRow row{trace, nullptr, n, 0, pos, (pos + 1) & (n - 1), 0, nullptr};
+  uint64_t t = 1;
+  if constexpr (AIR == bpg::air::KECCAK_F) {
+    namespace kk = bpg::air::keccak;
+    const uint64_t g = row.loc(kk::COL_G);
+    if (g && pos >= 23) {
+      const CheckRow first{trace, nullptr, n, 0, pos - 23, pos - 22, 0, nullptr};
+      const uint64_t in = bpg::air::ctl::compress<uint64_t>([&](uint32_t j) { return first.loc(kk::COL_A + j); },
+                                                           bpg::air::ctl::TUPLE_LIMBS, beta);
+      const uint64_t o = bpg::air::ctl::compress<uint64_t>(
+          [&](uint32_t j) { return j < 2 ? row.loc(kk::COL_APPP + j) : row.loc(kk::COL_APP + j); }, bpg::air::ctl::TUPLE_LIMBS, beta);
+      const uint64_t v = gl::addc(in, gl::mulc(gl::pow(beta, bpg::air::ctl::TUPLE_LIMBS), o));
+      t = gl::addc(1, gl::mulc(g, gl::subc(gl::addc(gamma, v), 1)));
+    }
+  } else {
+    const uint64_t ctl[4] = {beta, gamma, beta, gamma};
+    t = bpg::air::ctl::product_term<uint64_t>(bpg::air::Shape{AIR, 0, 0, 1}, col, ctl, row);
+  }
+  out[pos] = t;
+}
+
+}  // namespace
+
+namespace bpg {
+
+uint64_t air_check_partial_words(CheckArgs& a) {
+  const air::Shape shape{a.air_id, a.n_cols, a.n_const, a.deg_pow};
+  const bool plonk = a.air_id == air::PLONK;
+  a.n_units = plonk ? air::plonk::N_UNITS - 1 : air::n_units(shape);  // (AIR 8's unit 10: the hash kernel)
+  const uint64_t blocks = ceil_div((uint64_t)1 << a.log_n, 256);
+  // a table of 512 workgroups or more fills the chip's 256 CUs alone: one pass; a shorter one spreads its units
+  // over grid.y up to ~1024 workgroups, as K5 does
+  if (blocks >= 512 || a.n_units == 1) {
+    a.units_per_wg = a.n_units;
+  } else {
+    const uint32_t want = (uint32_t)std::min<uint64_t>(a.n_units, ceil_div(1024, blocks));
+    a.units_per_wg = ceil_div(a.n_units, want);
+  }
+  a.wg_rows = ceil_div(a.n_units, a.units_per_wg);
+  const uint32_t rows = a.wg_rows + (plonk ? 1 : 0);
+  return rows > 1 ? 2 * ((uint64_t)rows << a.log_n) : 0;
+}
+
+int launch_air_check(const CheckArgs& a, hipStream_t st) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  BPG_HIP(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), st));
+  air_check_alpha_kernel<<<dim3(ceil_div(a.T, 256), 2), 256, 0, st>>>(const_cast<uint64_t*>(a.apow), a.T, a.alpha0, a.alpha1);
+  BPG_LAUNCH_CHECK();
+  const dim3 g1(ceil_div(n, 256), a.wg_rows);
+  switch (a.air_id) {
+    case air::KECCAK_F: air_check_kernel<air::KECCAK_F><<<g1, 256, 0, st>>>(a); break;
+    case air::LOGIC: air_check_kernel<air::LOGIC><<<g1, 256, 0, st>>>(a); break;
+    case air::MEMORY: air_check_kernel<air::MEMORY><<<g1, 256, 0, st>>>(a); break;
+    case air::ARITHMETIC: air_check_kernel<air::ARITHMETIC><<<g1, 256, 0, st>>>(a); break;
+    case air::BYTE_PACKING: air_check_kernel<air::BYTE_PACKING><<<g1, 256, 0, st>>>(a); break;
+    case air::KECCAK_SPONGE: air_check_kernel<air::KECCAK_SPONGE><<<g1, 256, 0, st>>>(a); break;
+    case air::ARITHMETIC_MUL: air_check_kernel<air::ARITHMETIC_MUL><<<g1, 256, 0, st>>>(a); break;
+    case air::PLONK: air_check_kernel<air::PLONK><<<g1, 256, 0, st>>>(a); break;
+    default: air_check_kernel<air::SYNTHETIC><<<g1, 256, 0, st>>>(a); break;
+  }
+  BPG_LAUNCH_CHECK();
+  if (a.air_id == air::PLONK) {
+    air_check_plonk_hash_kernel<<<ceil_div(n, 256), 256, 0, st>>>(a, a.wg_rows);
+    BPG_LAUNCH_CHECK();
+  }
+  if (a.partial) {
+    air_check_reduce_kernel<<<ceil_div(n, 256), 256, 0, st>>>(a, a.wg_rows + (a.air_id == air::PLONK ? 1 : 0));
+    BPG_LAUNCH_CHECK();
+  }
+  return BP_OK;
+}
+
+int launch_lookup_terms(uint32_t air_id, const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta, uint64_t gamma,
+                        uint64_t* out, hipStream_t st) {
+  const unsigned g = ceil_div((uint64_t)1 << log_n, 256);
+  switch (air_id) {
+    case air::KECCAK_F: lookup_terms_kernel<air::KECCAK_F><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
+    case air::LOGIC: lookup_terms_kernel<air::LOGIC><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
+    case air::MEMORY: lookup_terms_kernel<air::MEMORY><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
+    case air::BYTE_PACKING: lookup_terms_kernel<air::BYTE_PACKING><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
+    case air::KECCAK_SPONGE: lookup_terms_kernel<air::KECCAK_SPONGE><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
+    default: return fail(BP_ERR_INVALID_INPUT, "no lookup is built for AIR %u", air_id);
+  }
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+
+int launch_gather_rows(const uint64_t* trace, uint64_t stride, uint32_t n_cols, const uint32_t* d_rows, uint32_t n_rows,
+                       uint64_t* out, hipStream_t st) {
+  if (!n_rows || !n_cols) return BP_OK;
+  air_check_gather_kernel<<<dim3(ceil_div(n_cols, 256), n_rows), 256, 0, st>>>(trace, stride, n_cols, d_rows, out);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+
+}  // namespace bpg

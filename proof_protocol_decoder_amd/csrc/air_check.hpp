@@ -1,0 +1,34 @@
+// air_check.hpp -- the AIR trace checker (air_check.hip: device pass, air_check.cpp: host pass and C ABI).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace bpg {
+
+// One check of one trace on the trace domain (n = 2^log_n rows, x = w_n^i at row i).
+struct CheckArgs {
+  const uint64_t* trace;   // column-major, n_cols columns, column stride `stride`
+  const uint64_t* consts;  // column-major, n_const columns, column stride n (AIRs 0 and 8), else NULL
+  const uint64_t* apow;    // [2][T]: alpha_j^e, filled by launch_air_check
+  uint64_t* partial;       // [wg_rows][2][n] when the units are spread over grid.y (or AIR 8), else NULL
+  uint64_t* bitmap;        // [ceil(n / 64)]: bit i % 64 of word i / 64 = row i violates a constraint
+  unsigned long long* count;  // violated rows (zeroed by launch_air_check)
+  uint64_t stride, alpha0, alpha1;
+  uint64_t pub[4];         // AIR 8's public inputs
+  uint32_t air_id, log_n, n_cols, n_const, deg_pow;
+  uint32_t T;              // the AIR's own constraints (the lookup part of the list is not checked)
+  uint32_t n_units, units_per_wg, wg_rows;
+};
+// partial words (0: none) and the grid.y spreading for a check of `a` (fills n_units, units_per_wg, wg_rows)
+uint64_t air_check_partial_words(CheckArgs& a);
+int launch_air_check(const CheckArgs& a, hipStream_t st);
+// out[j * n_cols + c] = trace[c * stride + rows[j]], j < n_rows (d_rows on the device)
+int launch_gather_rows(const uint64_t* trace, uint64_t stride, uint32_t n_cols, const uint32_t* d_rows, uint32_t n_rows,
+                       uint64_t* out, hipStream_t st);
+
+// out[i] = the term of product column `col` (air::ctl::product_term, challenge set (beta, gamma)) at row i of a trace of
+// air_id (stride 2^log_n): 1 where the lookup's filter leaves the row out, gamma + the compressed tuple where it does not
+int launch_lookup_terms(uint32_t air_id, const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta, uint64_t gamma,
+                        uint64_t* out, hipStream_t st);
+
+}  // namespace bpg

@@ -13,7 +13,10 @@
 #include <system_error>
 #include <thread>
 #include <deque>
+#include <random>
 #include <set>
+#include <unordered_map>
+#include "air_check.hpp"
 #include "mpt.hpp"
 #include "prover.hpp"
 
@@ -817,15 +820,16 @@ static int check_lookups(const StarkCfg tcfg[BP_NUM_TABLES], const std::vector<u
   return BP_OK;
 }
 
-// generate_traces + the seven table proofs on one transcript (plonky2_evm `prove`), on the leased worker
-static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const TxnWitness* wit, TableProofs* tp) {
-  StarkCfg* tcfg = tp->tcfg;
+// whether table t is made from the caller's data (its AIR flag set and data given)
+static bool given_table(const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES], int t) {
+  return wit && wit->in[t] && (tcfg[t].air_id == WITNESS_AIR[t] || (t == 0 && tcfg[t].air_id == air::ARITHMETIC_MUL));
+}
+// generate_traces: the seven witnesses of a transaction in the worker's arena (d_trace[t]: n_cols x 2^log_n, column-major),
+// with the refusals of data that cannot form one statement.  Shared by the prover and the witness pre-flight.
+static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES],
+                        uint64_t* d_trace[BP_NUM_TABLES]) {
   int r;
-  // generate_traces + trace commitments for all tables, then the shared transcript prologue
-  uint64_t* d_trace[BP_NUM_TABLES];
-  Committed trace[BP_NUM_TABLES];
-  Challenger ch;
-  auto given = [&](int t) { return wit && wit->in[t] && (tcfg[t].air_id == WITNESS_AIR[t] || (t == 0 && tcfg[t].air_id == air::ARITHMETIC_MUL)); };
+  auto given = [&](int t) { return given_table(wit, tcfg, t); };
   // Two seeded tables that a lookup ties together are ONE statement: the seeded sponge table asks for no more
   // permutations than the Keccak-f table holds in full, and the seeded Keccak-f table's first permutations are the
   // ones the sponge rows ask for (air::ctl, keccak_sponge -> keccak_f).  Tables given by the caller are taken as they are.
@@ -937,6 +941,19 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
       w.arena.release(mark);
     }
   }
+  return BP_OK;
+}
+
+// generate_traces + the seven table proofs on one transcript (plonky2_evm `prove`), on the leased worker
+static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const TxnWitness* wit, TableProofs* tp) {
+  StarkCfg* tcfg = tp->tcfg;
+  int r;
+  // generate_traces + trace commitments for all tables, then the shared transcript prologue
+  uint64_t* d_trace[BP_NUM_TABLES];
+  Committed trace[BP_NUM_TABLES];
+  Challenger ch;
+  auto given = [&](int t) { return given_table(wit, tcfg, t); };
+  if ((r = build_traces(w, I, wit, tcfg, d_trace))) return r;
   // The seven trace commitments do not depend on each other.  Under load they queue on this prover's stream like
   // everything else (the chip is full); a prover that is ALONE on the device -- a lone transaction, the last one of a
   // shard -- borrows the streams of up to three idle workers and the commitments overlap: the wide Keccak table's long
@@ -1142,6 +1159,134 @@ int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t i
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_witness")
+
+// ---- the transaction witness pre-flight (bp_check_txn_witness) ----------------------------------------------------
+namespace {
+// the terms of one side of a lookup on the device (launch_lookup_terms), downloaded: tuples = the terms other than 1
+int lookup_side_terms(Worker& w, uint32_t air_id, const uint64_t* d_trace, uint32_t log_n, uint32_t col0, uint32_t n_cols,
+                      uint32_t stride, uint64_t beta, uint64_t gamma, std::vector<uint64_t>* out) {
+  const uint64_t N = (uint64_t)1 << log_n;
+  uint64_t* d = nullptr;
+  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n_cols * N * 8));
+  struct Free { void* p; ~Free() { (void)hipFree(p); } } guard{d};
+  for (uint32_t m = 0; m < n_cols; m++)
+    if (int r = launch_lookup_terms(air_id, d_trace, log_n, col0 + stride * m, beta, gamma, d + (size_t)m * N, w.stream)) return r;
+  out->resize((size_t)n_cols * N);
+  BPG_HIP(hipMemcpyAsync(out->data(), d, out->size() * 8, hipMemcpyDeviceToHost, w.stream));
+  BPG_HIP(hipStreamSynchronize(w.stream));
+  return BP_OK;
+}
+// the first row of side `a` (terms [n_cols][N], row-major over rows, then columns) whose tuple `b` does not have left
+int64_t first_unmatched(const std::vector<uint64_t>& a, uint32_t na, uint64_t Na, const std::vector<uint64_t>& b, uint64_t* n_tuples) {
+  std::unordered_map<uint64_t, int64_t> left;
+  for (uint64_t v : b)
+    if (v != 1) left[v]++;
+  int64_t first = -1;
+  uint64_t n = 0;
+  for (uint64_t i = 0; i < Na; i++)
+    for (uint32_t m = 0; m < na; m++) {
+      const uint64_t v = a[(size_t)m * Na + i];
+      if (v == 1) continue;
+      n++;
+      auto it = left.find(v);
+      if (it != left.end() && it->second > 0) it->second--;
+      else if (first < 0) first = (int64_t)i;
+    }
+  *n_tuples = n;
+  return first;
+}
+}  // namespace
+
+static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const TxnWitness* wit, bp_witness_report* out) {
+  if (!s || !ir || !out) return fail(BP_ERR_INVALID_INPUT, "bp_check_txn_witness: null argument");
+  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
+  std::memset(out, 0, sizeof(*out));
+  const uint64_t* I = reinterpret_cast<const uint64_t*>(ir);
+  StarkCfg tcfg[BP_NUM_TABLES];
+  std::vector<uint64_t> pv;
+  int r = parse_ir(s->cfg, I, wit, tcfg, &pv);
+  if (r) return r;
+  (void)hipSetDevice(s->cfg.device);
+  WorkerLease lease(s);
+  Worker& w = *lease.w;
+  w.abort_flag = nullptr;
+  w.abort_flag_u8 = nullptr;
+  uint64_t* d_trace[BP_NUM_TABLES];
+  struct Release { Worker& w; size_t mark; ~Release() { (void)w.wait(); w.arena.release(mark); } } rel{w, lease.mark};
+  if ((r = build_traces(w, I, wit, tcfg, d_trace))) return r;
+  if ((r = w.wait())) return r;
+  // the AIRs, table by table (a seeded or derived table satisfies its AIR by construction; the prover checks the given ones)
+  int status = BP_OK;
+  std::string why;
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    bp_witness_table& o = out->table[t];
+    if (tcfg[t].air_id == air::SYNTHETIC) continue;
+    o.checked = 1;
+    o.given = given_table(wit, tcfg, t);
+    const bp_stark_cfg c{tcfg[t].log_n, tcfg[t].n_cols, tcfg[t].n_const, tcfg[t].deg_pow, tcfg[t].rate_bits, tcfg[t].cap_height,
+                         tcfg[t].num_queries, tcfg[t].pow_bits, tcfg[t].arity_bits, tcfg[t].final_poly_bits};
+    uint32_t rows[8], nv = 0;
+    if ((r = bp_air_check_trace(tcfg[t].air_id, &c, d_trace[t], (uint64_t)1 << tcfg[t].log_n, nullptr, nullptr, 8, &o.n_violated_rows,
+                                rows, o.viol, 8, &nv, w.stream))) return r;
+    o.n_viol = std::min<uint32_t>(nv, 8);
+    if (status == BP_OK && o.given && o.n_violated_rows) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "the witness data given for table %s does not satisfy its AIR: row %u violates constraint %u "
+                    "(family %u), %llu rows in all", TABLE_NAMES[t], o.viol[0].row, o.viol[0].constraint, o.viol[0].family,
+                    (unsigned long long)o.n_violated_rows);
+      status = BP_ERR_VERIFY;
+      why = buf;
+    }
+  }
+  // the lookups, as multisets of compressed tuples under fresh challenges
+  std::random_device rd;
+  std::mt19937_64 g(((uint64_t)rd() << 32) ^ rd());
+  const air::ctl::Pair* P = air::ctl::pairs();
+  for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
+    const air::ctl::Pair& p = P[i];
+    bp_witness_lookup& o = out->lookup[i];
+    o.first_looking_row = o.first_looked_row = -1;
+    if (tcfg[p.looking_table].air_id != p.looking_air || tcfg[p.looked_table].air_id != p.looked_air) continue;
+    o.checked = 1;
+    uint64_t beta, gamma;
+    do beta = g() % gl::P; while (beta < 2);
+    do gamma = g() % gl::P; while (gamma < 2);
+    std::vector<uint64_t> a, b;
+    const uint32_t la = tcfg[p.looking_table].log_n, lb = tcfg[p.looked_table].log_n;
+    if ((r = lookup_side_terms(w, p.looking_air, d_trace[p.looking_table], la, p.looking_col, p.n_looking, p.stride, beta, gamma, &a))) return r;
+    if ((r = lookup_side_terms(w, p.looked_air, d_trace[p.looked_table], lb, p.looked_col, 1, 0, beta, gamma, &b))) return r;
+    o.first_looking_row = first_unmatched(a, p.n_looking, (uint64_t)1 << la, b, &o.n_looking);
+    o.first_looked_row = first_unmatched(b, 1, (uint64_t)1 << lb, a, &o.n_looked);
+    o.holds = o.first_looking_row < 0 && o.first_looked_row < 0;
+    if (status == BP_OK && !o.holds) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "cross-table lookup %s does not hold: first unmatched looking row %lld (table %s), looked row "
+                    "%lld (table %s)", p.name, (long long)o.first_looking_row, TABLE_NAMES[p.looking_table], (long long)o.first_looked_row,
+                    TABLE_NAMES[p.looked_table]);
+      status = BP_ERR_VERIFY;
+      why = buf;
+    }
+  }
+  return status == BP_OK ? BP_OK : fail(status, "%s", why.c_str());
+}
+int bp_check_txn_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data, bp_witness_report* out) try {
+  if (!data) return check_txn_impl(s, ir, ir_len, nullptr, out);
+  TxnWitness wit;
+  int r = witness_of(data, &wit);
+  if (r) return r;
+  return check_txn_impl(s, ir, ir_len, &wit, out);
+}
+BPG_ABI_CATCH("bp_check_txn_witness")
+int bp_check_txn_witness_keccak(const bp_state* s, const uint8_t* ir, size_t ir_len, const uint64_t* keccak_inputs, size_t n_perms,
+                                bp_witness_report* out) try {
+  if (!keccak_inputs && n_perms) return fail(BP_ERR_INVALID_INPUT, "bp_check_txn_witness_keccak: null inputs");
+  static const uint64_t none = 0;
+  TxnWitness wit;
+  wit.in[3] = keccak_inputs ? keccak_inputs : &none;
+  wit.n[3] = n_perms;
+  return check_txn_impl(s, ir, ir_len, &wit, out);
+}
+BPG_ABI_CATCH("bp_check_txn_witness_keccak")
 
 // What upstream's `prove` yields before the recursion (AllProof): the seven table proofs of a transaction on their one
 // transcript, with the public values and the lookup challenges.  data as for bp_generate_txn_proof_witness (nullable).

@@ -184,6 +184,88 @@ def quotient_eval(cfg, trace_lde, aux_lde, const_lde, ctl, alphas, air_id=AIR_SY
     return out
 
 
+class AirCheck:
+    """What bp_air_check_trace found: how many rows violate the AIR, the first of them (row order) and the constraints
+    those rows break (bp_air_violation: row, constraint index, family index into air_describe's families, kind, value
+    before the row selector).  `n_violations` counts all of them; at most `max_viol` are in `violations`."""
+
+    def __init__(self, air_id, n_violated_rows, rows, violations, n_violations):
+        self.air_id = air_id
+        self.n_violated_rows = n_violated_rows
+        self.rows = rows
+        self.violations = violations
+        self.n_violations = n_violations
+
+    @property
+    def ok(self):
+        return self.n_violated_rows == 0
+
+    def __repr__(self):
+        return "AirCheck(air %d: %d violated rows, first %s)" % (self.air_id, self.n_violated_rows, self.rows[:8])
+
+
+def _check_cfg(air_id, n_cols, n_const, log_n, deg_pow):
+    d = air_describe(air_id, n_cols, n_const, deg_pow)
+    if d.fixed_n_cols:
+        deg_pow = 3 if d.degree > 3 else 1
+    return stark_cfg(log_n, n_cols, n_const=n_const, deg_pow=deg_pow, rate_bits=1 if deg_pow == 1 else 3)
+
+
+def _check_shapes(n, consts, pub):
+    """the trace's height is a power of two, the constants are [n_const, n] (read with column stride n), four public inputs"""
+    if n < 1 or n & (n - 1):
+        raise ValueError("a trace has 2^log_n rows: got %d" % n)
+    if consts is not None and (len(consts.shape) != 2 or consts.shape[1] != n):
+        raise ValueError("constants must be [n_const, %d]: got %s" % (n, tuple(consts.shape)))
+    if pub is not None and len(pub) != 4:
+        raise ValueError("four public inputs: got %d" % len(pub))
+
+
+def _check_call(fn, air_id, cfg, trace_ptr, stride, consts_ptr, pub, max_rows, max_viol, *stream):
+    from ._lib import AirViolation
+    n_rows, n_viol = C.c_uint64(), C.c_uint32()
+    rows = (C.c_uint32 * max(1, max_rows))()
+    viol = (AirViolation * max(1, max_viol))()
+    pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
+    check(fn(air_id, C.byref(cfg), trace_ptr, stride, consts_ptr, pub_arr, max_rows, C.byref(n_rows), rows, viol, max_viol,
+             C.byref(n_viol), *stream))
+    got_rows = min(n_rows.value, max_rows)
+    return AirCheck(air_id, n_rows.value, [int(rows[i]) for i in range(got_rows)],
+                    [viol[i] for i in range(min(n_viol.value, max_viol))], n_viol.value)
+
+
+def check_air_trace(air_id, trace, consts=None, pub=None, max_rows=16, max_viol=None, deg_pow=1):
+    """bp_air_check_trace: which rows of `trace` ([n_cols, 2^log_n] on the device; a column slice of a wider buffer
+    keeps its stride) violate AIR `air_id`'s own constraints, and which constraints the first `max_rows` of them break.
+    consts: [n_const, 2^log_n] (AIR 0 with constants, AIR 8); pub: AIR 8's four public inputs; deg_pow: the synthetic
+    AIR's.  Nothing is raised for a bad trace: the result says what is wrong (AirCheck)."""
+    if not trace.is_cuda or trace.dtype != torch.int64 or trace.stride(1) != 1:
+        raise ValueError("check_air_trace needs an int64 device tensor with contiguous columns")
+    n_cols, n = trace.shape
+    if consts is not None:
+        _require_cuda(consts)
+    _check_shapes(n, consts, pub)
+    cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, deg_pow)
+    return _check_call(lib().bp_air_check_trace, air_id, cfg, trace.data_ptr(), trace.stride(0),
+                       consts.data_ptr() if consts is not None else None, pub, max_rows,
+                       4 * max_rows + 64 if max_viol is None else max_viol, _stream())
+
+
+def check_air_trace_host(air_id, trace, consts=None, pub=None, max_rows=16, max_viol=None, deg_pow=1):
+    """bp_air_check_trace_host: the same on the CPU, for a numpy uint64 trace [n_cols, 2^log_n] (rows may be strided)."""
+    trace = np.asarray(trace)
+    if trace.dtype != np.uint64 or trace.strides[1] != 8:
+        raise ValueError("check_air_trace_host needs a uint64 array with contiguous columns")
+    n_cols, n = trace.shape
+    if consts is not None:
+        consts = np.ascontiguousarray(consts, dtype=np.uint64)
+    _check_shapes(n, consts, pub)
+    cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, deg_pow)
+    return _check_call(lib().bp_air_check_trace_host, air_id, cfg, trace.ctypes.data, trace.strides[0] // 8,
+                       consts.ctypes.data if consts is not None else None, pub, max_rows,
+                       4 * max_rows + 64 if max_viol is None else max_viol)
+
+
 def fri_fold(values, log_nl, rate_bits, shift, beta, arity_bits=4):
     """bp_fri_fold: values [n_l << rate_bits, 2] (coset-major ext elements) -> next layer [(n_l >> 4) << rate_bits, 2]."""
     _require_cuda(values)

@@ -409,6 +409,61 @@ def generate_txn_table_proofs(p_state, gen_inputs, keccak_inputs=None, witness=N
     return take_buffer(out, n)
 
 
+class WitnessTable(C.Structure):
+    """bp_witness_table (include/bpg.h)"""
+    from ._lib import AirViolation as _V
+    _fields_ = [("checked", C.c_uint32), ("given", C.c_uint32), ("n_violated_rows", C.c_uint64), ("n_viol", C.c_uint32),
+                ("viol", _V * 8)]
+
+
+class WitnessLookup(C.Structure):
+    """bp_witness_lookup (include/bpg.h)"""
+    _fields_ = [("checked", C.c_uint32), ("holds", C.c_uint32), ("n_looking", C.c_uint64), ("n_looked", C.c_uint64),
+                ("first_looking_row", C.c_int64), ("first_looked_row", C.c_int64)]
+
+
+class WitnessReport(C.Structure):
+    """bp_witness_report (include/bpg.h), with the call's status and message: `ok` when the prover would accept the data"""
+    _fields_ = [("table", WitnessTable * 7), ("lookup", WitnessLookup * 3)]
+    LOOKUPS = ("keccak_sponge -> keccak_f", "byte_packing -> memory", "keccak_sponge -> logic")
+    status = 0
+    message = ""
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def violations(self, t):
+        return list(self.table[t].viol[:self.table[t].n_viol])
+
+
+def check_txn_witness(p_state, gen_inputs, keccak_inputs=None, witness=None):
+    """The witness pre-flight (bp_check_txn_witness): what generate_txn_proof would say about the same inputs, without
+    proving -- the tables' AIRs row by row and the three lookups as multisets.  Arguments as for generate_txn_proof.
+    Returns a WitnessReport (status 0 = ok, or BP_ERR_VERIFY with the table / row / constraint or the lookup and its
+    first unmatched rows in `message`); raises ProofGenError only where the prover would refuse the input."""
+    L = _bind()
+    ir = gen_inputs.to_bytes() if isinstance(gen_inputs, TxnProofGenIR) else bytes(gen_inputs)
+    rep = WitnessReport()
+    if keccak_inputs is None:
+        keccak_inputs = getattr(gen_inputs, "keccak_inputs", None)
+    if witness is None and getattr(gen_inputs, "witness", None) is None and keccak_inputs is not None:
+        flat = [int(x) for st in keccak_inputs for x in st]
+        arr = (C.c_uint64 * max(len(flat), 1))(*flat)
+        L.bp_check_txn_witness_keccak.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = L.bp_check_txn_witness_keccak(p_state._h, ir, len(ir), arr, len(flat) // 25, C.byref(rep))
+    else:
+        w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
+        L.bp_check_txn_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        rc = L.bp_check_txn_witness(p_state._h, ir, len(ir), C.byref(w) if w is not None else None, C.byref(rep))
+        del keep
+    if rc not in (0, -5):   # BP_OK, BP_ERR_VERIFY: a report; anything else is the prover's refusal
+        check(rc)
+    rep.status = rc
+    rep.message = L.bp_last_error().decode("utf-8", "replace") if rc else ""
+    return rep
+
+
 def verify_txn_table_proofs(cfg, table_proofs, gen_inputs=None):
     """upstream's verify_proof(all_stark, all_proof, config) on the CPU: every table proof against the shared transcript
     and the cross-table lookups between the tables proven with their AIRs.  cfg: a BpConfig (ProverState.cfg).

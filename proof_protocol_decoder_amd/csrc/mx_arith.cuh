@@ -35,6 +35,16 @@ __device__ __forceinline__ void reduce_rows(const uint64_t (&L)[N], const uint64
   for (int i = 0; i < N; i++) out[i] = gl::cc::mk64(l0[i], l1[i]);
 }
 
+// reduce_rows for one pair (the recombined S-box input of a grouped partial round, poseidon_mx.cuh): the same four
+// instructions, with the wait states a carry read right after its VALU write needs (gl.hpp, namespace cc)
+__device__ __forceinline__ uint64_t reduce_row(uint64_t L, uint64_t H) {
+  uint64_t T;
+  asm("v_mad_u64_u32 %0, vcc, %1, -1, %2" : "=v"(T) : "v"((uint32_t)(H >> 32)), "v"(L) : "vcc");
+  gl::cc::mask c1, b, unused;
+  const uint32_t l1 = gl::cc::add_co((uint32_t)(T >> 32), (uint32_t)H, c1);
+  const uint32_t l0 = gl::cc::subb0_co((uint32_t)T, c1, b);
+  return gl::cc::mk64(l0, gl::cc::addc0_co(l1, c1 & ~b, unused));
+}
 
 // four non-negative plane sums (each < 2^23) -> a0 + a1*2^8 + a2*2^16 + a3*2^24 < 2^48: two shift-adds and one
 // multiply-add (the compiler's own rendering of the 64-bit shift and add is five to six instructions)

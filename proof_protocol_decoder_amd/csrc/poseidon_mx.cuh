@@ -190,14 +190,21 @@ __device__ __forceinline__ void sbox_full(uint64_t (&e)[NS][3]) {
 // Up to K = 8 partial rounds at a time (poseidon_group.hpp; integer model tools/poseidon_group_model.py): within a
 // group only ONE word per state and round -- the next S-box input, an affine form of the eleven untouched words and the
 // earlier S-box outputs -- comes out of the matrix cores and is recombined; the twelve words are recombined once per
-// group.  228 -> ~140 VALU instructions per round and 64 states, 6 -> 5 MFMAs per set and round.  The 22 partial
-// rounds are 8 + 8 + 6: the third group runs steps 0..5 on the same form operands.
-//   operands (1 KiB each, shared by the four sets): W = forms over the bytes of w, D = one more sigma into the
-//   forms still to come, MAIN = the new state over (w, sigma_0..7) -- 40 operands in LDS, identical for the two long
-//   groups --, and 18 MAIN operands of the short group in global memory; C tables per group hold the round constants.
-//   B operands: blo / bhi = the state's byte planes as in mds(); bsig: lane group g holds sigma_g and sigma_{g+4}.
-//   Form f of a pair comes out in lane group f % 4 (rows 4(f%4)..+3 of the tile), so the gather into the dense
-//   S-box register and the way back come in four variants of the same three permlane swaps.
+// group.  6 -> 5 MFMAs per set and round.  The 22 partial rounds are 8 + 8 + 6: the third group runs steps 0..5 on the
+// same form operands.
+//   operands (1 KiB each): W = forms over the bytes of w, D = one more sigma into the forms still to come, MAIN = the
+//   new state over (w, sigma_0..7) -- 40 operands in LDS, identical for the two long groups --, and 18 MAIN operands of
+//   the short group in global memory; C tables per group hold the round constants.
+//   B operands: blo / bhi = the state's byte planes as in mds(); bsig[m]: lane group g holds sigma_j and sigma_{j+4}
+//   of set m with j = (g - m) % 4.
+//   ROTATED forms: set m reads every form operand (W, D) with its rows rotated by 4m, so form f of a pair comes out in
+//   lane group (f + m) % 4 of set m's tiles, and the four sets' copies of form J fill the four lane groups: one merge
+//   by lane group (3 selects per dword), ONE recombination and the S-box on a dense register, and sigma_J goes back
+//   into bsig[m] in the lane group it was computed in -- no lane ever moves data after step 0.  Since bsig[m] is
+//   rotated by m lane groups, every operand that multiplies it (the sigma chunks of W, D and MAIN) is read with its
+//   k-blocks rotated by m; MAIN keeps its rows, so the new state's words come out in their home lanes.  The rotations
+//   are only in which lane of the LDS image each lane reads (still conflict-free: a row rotation keeps the 16 lanes of
+//   an LDS cycle on 16 different banks); the images are the unrotated ones.
 namespace grp {
 constexpr int K = 8;
 constexpr poseidon::group::Layout LAY = poseidon::group::layout(K);
@@ -224,103 +231,138 @@ __device__ __forceinline__ void load_tables(uint32_t* __restrict__ lds, const ui
   for (uint32_t i = threadIdx.x; i < (uint32_t)TABLE_WORDS<NG> / 4; i += blockDim.x) dst[i] = src[i];
 }
 
-// gather<F>: x[m] holds set m's value in lane group F; afterwards x[F] holds set j's value in lane group j.
-// The same instructions in reverse order undo it (each swap is an involution).  Operands come from / go to asm
-// statements the hazard recogniser does not see: 2 wait states around every swap by hand.
-template <int F>
-__device__ __forceinline__ void gather(uint32_t (&l)[4], uint32_t (&h)[4]) {
-  if constexpr ((F & 1) == 0)
-    asm("s_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
-        "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\t"
-        "s_nop 0\n\t"
-        "v_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %4, %6\n\ts_nop 1"
-        : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
-  else
-    asm("s_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
-        "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\t"
-        "s_nop 0\n\t"
-        "v_permlane32_swap_b32 %1, %3\n\tv_permlane32_swap_b32 %5, %7\n\ts_nop 1"
-        : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
-}
-template <int F>
-__device__ __forceinline__ void scatter(uint32_t (&l)[4], uint32_t (&h)[4]) {
-  if constexpr ((F & 1) == 0)
-    asm("s_nop 1\n\t"
-        "v_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %4, %6\n\t"
-        "s_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
-        "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\ts_nop 1"
-        : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
-  else
-    asm("s_nop 1\n\t"
-        "v_permlane32_swap_b32 %1, %3\n\tv_permlane32_swap_b32 %5, %7\n\t"
-        "s_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
-        "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\ts_nop 1"
-        : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
+// step 0: x[m] holds set m's word 0 in lane group 0; afterwards x[0] holds set j's in lane group j -- set j's form 0
+// where the rotated layout wants it.  Operands come from / go to asm statements the hazard recogniser does not see:
+// 2 wait states around every swap by hand.
+__device__ __forceinline__ void gather0(uint32_t (&l)[4], uint32_t (&h)[4]) {
+  asm("s_nop 1\n\t"
+      "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
+      "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\t"
+      "s_nop 0\n\t"
+      "v_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %4, %6\n\ts_nop 1"
+      : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
 }
 
+// the lane of an operand image that lane `lane` of set m reads: rows rotated by 4m (ROWS), k-blocks by m (KBS)
+template <bool ROWS, bool KBS>
+__device__ __forceinline__ uint32_t rot_lane(uint32_t lane, int m) {
+  const uint32_t r = ROWS ? ((lane - 4u * (uint32_t)m) & 15u) : (lane & 15u);
+  const uint32_t kb = KBS ? (((lane >> 4) - (uint32_t)m) & 3u) : (lane >> 4);
+  return r | kb << 4;
+}
+
+// byte offsets, within an operand image, of the lane each set reads: W = rows rotated, D = rows and k-blocks (also the
+// sigma chunk of W), S = k-blocks (the sigma chunk of MAIN); set 0 reads its own lane everywhere (w[0]).
+struct Lanes {
+  uint32_t w[4], d[4], s[4];
+};
+__device__ __forceinline__ Lanes lanes_of(uint32_t lane) {
+  Lanes o;
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    o.w[m] = rot_lane<true, false>(lane, m) * 16;
+    o.d[m] = rot_lane<true, true>(lane, m) * 16;
+    o.s[m] = rot_lane<false, true>(lane, m) * 16;
+  }
+  return o;
+}
+// The offsets are the same in every group.  Called at the top of each group on the loop-carried values, the empty asm
+// statement makes them look new to the compiler, which would otherwise hoist the ~100 loop-invariant operand reads of a
+// group out of the group loop and spill them.  No instruction.
+__device__ __forceinline__ void renew(Lanes& o) {
+  asm volatile("" : "+v"(o.w[0]), "+v"(o.w[1]), "+v"(o.w[2]), "+v"(o.w[3]), "+v"(o.d[1]), "+v"(o.d[2]), "+v"(o.d[3]),
+               "+v"(o.s[1]), "+v"(o.s[2]), "+v"(o.s[3]));
+  o.d[0] = o.s[0] = o.w[0];
+}
+
+// operand at byte offset off of an image in LDS (at) or in global memory (at_global).  The address space is spelled
+// out: the two reads of MAIN's operands (LDS for the long groups, global for the short one) are otherwise merged into
+// one flat read through a selected 64-bit pointer per set.
+__device__ __forceinline__ v4i at(const v4i* image, uint32_t off) {
+  return *(__attribute__((address_space(3))) const v4i*)((__attribute__((address_space(3))) const char*)image + off);
+}
+__device__ __forceinline__ v4i at_global(const v4i* image, uint32_t off) {
+  return *(__attribute__((address_space(1))) const v4i*)((__attribute__((address_space(1))) const char*)image + off);
+}
+
+// row ROW (one lane group) of dwords SLOT, SLOT + 1 of a B operand := y
+template <int ROW, int SLOT>
+__device__ __forceinline__ void put_sigma(v4i& b, uint64_t y) {
+  b[SLOT] = __builtin_amdgcn_update_dpp(b[SLOT], (int)(uint32_t)y, 0xE4, 1 << ROW, 0xF, false);
+  b[SLOT + 1] = __builtin_amdgcn_update_dpp(b[SLOT + 1], (int)(uint32_t)(y >> 32), 0xE4, 1 << ROW, 0xF, false);
+}
+
+// Carried from group to group (made once per permutation by init_state): dword 3 of blo / bhi and the sigma slots not
+// yet written in bsig meet only zero operand bytes, so whatever the previous group left there is as good as the zeros
+// they start with, and nothing is re-zeroed per group.
 struct State {
   v4i blo[4], bhi[4], bsig[4];  // B operands of the four sets (bytes ^ 0x80)
-  v4i acc[4][2];                // the live form pair: tile L / H of every set
+  v4i acc[4][2];                // the live form pair: tile L / H of every set (rows rotated by 4m)
 };
+__device__ __forceinline__ void init_state(State& s) {
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    s.blo[m] = v4i{0, 0, 0, 0};
+    s.bhi[m] = v4i{0, 0, 0, 0};
+    s.bsig[m] = v4i{0, 0, 0, 0};
+  }
+}
 
 // step J of a group: S-box input J -> sigma_J into bsig and into the forms still to come
 // (full = false: the short group, whose last step is 5: no later form takes sigma_5)
 template <int J>
-__device__ __forceinline__ void step(State& s, uint64_t (&e)[4][3], const v4i* ops, const int* cform, uint32_t lane,
-                                     bool full = true) {
+__device__ __forceinline__ void step(State& s, uint64_t (&e)[4][3], const v4i* ops, const int* cform, const Lanes& o,
+                                     uint32_t kb, bool full = true) {
   constexpr int P = J / 4, F = J % 4;
-  const uint32_t kb = lane >> 4;
   if constexpr (F == 0) {  // start pair P: constants + the forms over w (+ the sigmas known so far)
     constexpr int nw = LAY.w_per_half[P];
 #pragma unroll
     for (int half = 0; half < 2; half++) {
-      const v4i c0 = ((const v4i*)(cform + (P * 2 + half) * 16))[kb];
-      const v4i a_lo = ops[(LAY.w_base[P] + half * nw) * 64 + lane], a_hi = ops[(LAY.w_base[P] + half * nw + 1) * 64 + lane];
+      const v4i* cf = (const v4i*)(cform + (P * 2 + half) * 16);
+      const v4i* w = ops + (LAY.w_base[P] + half * nw) * 64;
 #pragma unroll
       for (int m = 0; m < 4; m++) {
-        s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, s.blo[m], c0, 0, 0, 0);
-        s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, s.bhi[m], s.acc[m][half], 0, 0, 0);
-      }
-      if constexpr (P > 0) {
-        const v4i a_sg = ops[(LAY.w_base[P] + half * nw + 2) * 64 + lane];
-#pragma unroll
-        for (int m = 0; m < 4; m++) s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_sg, s.bsig[m], s.acc[m][half], 0, 0, 0);
+        s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(at(w, o.w[m]), s.blo[m], cf[(kb - m) & 3], 0, 0, 0);
+        s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(at(w + 64, o.w[m]), s.bhi[m], s.acc[m][half], 0, 0, 0);
+        if constexpr (P > 0)
+          s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(at(w + 128, o.d[m]), s.bsig[m], s.acc[m][half], 0, 0, 0);
       }
     }
   }
   uint32_t l[4], h[4];
-  if constexpr (J == 0) {  // F_0 is the state's own word 0 (lane group 0)
+  if constexpr (J == 0) {  // F_0 is the state's own word 0 (lane group 0 of every set)
 #pragma unroll
     for (int m = 0; m < 4; m++) { l[m] = (uint32_t)e[m][0]; h[m] = (uint32_t)(e[m][0] >> 32); }
-  } else {                 // form J: planes 0..3 / 4..7 in this lane's registers of tile L / H (lane group F)
-    uint64_t L[4], H[4], x[4];
+    gather0(l, h);
+  } else {                 // form J of set m is in lane group (F + m) % 4: merge the four sets, recombine once
+    v4i dl = s.acc[(4 - F) & 3][0], dh = s.acc[(4 - F) & 3][1];
 #pragma unroll
-    for (int m = 0; m < 4; m++) { L[m] = planes(s.acc[m][0]); H[m] = planes(s.acc[m][1]); }
-    reduce_rows<4>(L, H, x);
+    for (int g = 1; g < 4; g++) {
+      const bool here = kb == (uint32_t)g;
 #pragma unroll
-    for (int m = 0; m < 4; m++) { l[m] = (uint32_t)x[m]; h[m] = (uint32_t)(x[m] >> 32); }
+      for (int q = 0; q < 4; q++) {
+        dl[q] = here ? s.acc[(g - F + 4) & 3][0][q] : dl[q];
+        dh[q] = here ? s.acc[(g - F + 4) & 3][1][q] : dh[q];
+      }
+    }
+    const uint64_t x = mxa::reduce_row(planes(dl), planes(dh));
+    l[0] = (uint32_t)x;
+    h[0] = (uint32_t)(x >> 32);
   }
-  gather<F>(l, h);
-  const uint64_t y = sbox(gl::cc::mk64(l[F], h[F])) ^ 0x8080808080808080ULL;  // sigma_J of all 64 states, as a B operand
-  l[F] = (uint32_t)y;
-  h[F] = (uint32_t)(y >> 32);
-  scatter<F>(l, h);        // set m's sigma_J in lane group F of (l[m], h[m])
-#pragma unroll
-  for (int m = 0; m < 4; m++) {  // ... into its slot of bsig: only row F of the wave is written
-    s.bsig[m][2 * (J / 4)] = __builtin_amdgcn_update_dpp(s.bsig[m][2 * (J / 4)], (int)l[m], 0xE4, 1 << F, 0xF, false);
-    s.bsig[m][2 * (J / 4) + 1] = __builtin_amdgcn_update_dpp(s.bsig[m][2 * (J / 4) + 1], (int)h[m], 0xE4, 1 << F, 0xF, false);
-  }
+  const uint64_t y = sbox(gl::cc::mk64(l[0], h[0])) ^ 0x8080808080808080ULL;  // sigma_J of all 64 states, as a B operand
+  // set m's sigma_J is in lane group (F + m) % 4: only that row of bsig[m] is written
+  put_sigma<(F + 0) & 3, 2 * P>(s.bsig[0], y);
+  put_sigma<(F + 1) & 3, 2 * P>(s.bsig[1], y);
+  put_sigma<(F + 2) & 3, 2 * P>(s.bsig[2], y);
+  put_sigma<(F + 3) & 3, 2 * P>(s.bsig[3], y);
   if constexpr (J >= LAY.d_first[P] && J < LAY.d_first[P] + LAY.d_count[P]) {  // a later form of the pair needs sigma_J
     if (J == SHORT_K - 1 && !full) return;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
-      const v4i a = ops[(LAY.d_base[P] + 2 * (J - LAY.d_first[P]) + half) * 64 + lane];
+      const v4i* a = ops + (LAY.d_base[P] + 2 * (J - LAY.d_first[P]) + half) * 64;
 #pragma unroll
-      for (int m = 0; m < 4; m++) s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, s.bsig[m], s.acc[m][half], 0, 0, 0);
+      for (int m = 0; m < 4; m++)
+        s.acc[m][half] = __builtin_amdgcn_mfma_i32_16x16x64_i8(at(a, o.d[m]), s.bsig[m], s.acc[m][half], 0, 0, 0);
     }
   }
 }
@@ -328,13 +370,14 @@ __device__ __forceinline__ void step(State& s, uint64_t (&e)[4][3], const v4i* o
 // rounds r0 .. r0 + 7 of the partial rounds: e = t(r0) in, t(r0 + 8) out (S-box-input form, constants included);
 // the third group of NG = 3 is short: rounds 20..25, t(26) out
 template <int NG>
-__device__ __forceinline__ void partial_group(uint64_t (&e)[4][3], const uint32_t* tab, const uint32_t* __restrict__ gtab, int grp) {
+__device__ __forceinline__ void partial_group(State& s, Lanes& o, uint64_t (&e)[4][3], const uint32_t* tab,
+                                              const uint32_t* __restrict__ gtab, int grp) {
   const uint32_t lane = threadIdx.x & 63, kb = lane >> 4;
   const bool full = NG == 2 || grp < 2;   // wave-uniform
   const v4i* ops = (const v4i*)tab;
   const int* cform = (const int*)(tab + OPS_WORDS + grp * C_WORDS);
   const int* cmain = cform + poseidon::group::CFORM_WORDS;
-  State s;
+  renew(o);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
 #pragma unroll
@@ -342,45 +385,45 @@ __device__ __forceinline__ void partial_group(uint64_t (&e)[4][3], const uint32_
       s.blo[m][a] = (int)((uint32_t)e[m][a] ^ 0x80808080u);
       s.bhi[m][a] = (int)((uint32_t)(e[m][a] >> 32) ^ 0x80808080u);
     }
-    s.blo[m][3] = 0;
-    s.bhi[m][3] = 0;
-    s.bsig[m] = v4i{0, 0, 0, 0};
   }
-  step<0>(s, e, ops, cform, lane);
-  step<1>(s, e, ops, cform, lane);
-  step<2>(s, e, ops, cform, lane);
-  step<3>(s, e, ops, cform, lane);
-  step<4>(s, e, ops, cform, lane);
-  step<5>(s, e, ops, cform, lane, full);
+  step<0>(s, e, ops, cform, o, kb);
+  step<1>(s, e, ops, cform, o, kb);
+  step<2>(s, e, ops, cform, o, kb);
+  step<3>(s, e, ops, cform, o, kb);
+  step<4>(s, e, ops, cform, o, kb);
+  step<5>(s, e, ops, cform, o, kb, full);
   if (full) {
-    step<6>(s, e, ops, cform, lane);
-    step<7>(s, e, ops, cform, lane);
+    step<6>(s, e, ops, cform, o, kb);
+    step<7>(s, e, ops, cform, o, kb);
   }
-  // the new state: twelve words over (w, sigma_0 .. sigma_7 / sigma_5), recombined as in mds()
-  const v4i* lops = ops + LAY.main_base * 64 + lane;
-  const v4i* gops = (const v4i*)(gtab + TABLE_WORDS<NG>) + lane;
+  // the new state: twelve words over (w, sigma_0 .. sigma_7 / sigma_5), recombined as in mds(); the sigma chunk is
+  // read with its k-blocks rotated by m (bsig[m] is)
+  const v4i* lops = ops + LAY.main_base * 64;
+  const v4i* gops = (const v4i*)(gtab + TABLE_WORDS<NG>);
 #pragma unroll
   for (int g = 0; g < 3; g++) {
-    v4i d[4][2], A[2][3];
-    if (full) {
-#pragma unroll
-      for (int h = 0; h < 2; h++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[h][c] = lops[((g * 2 + h) * 3 + c) * 64];
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; h++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[h][c] = gops[((g * 2 + h) * 3 + c) * 64];
-    }
+    v4i d[4][2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
+      const int t = (g * 2 + h) * 3 * 64;
+      v4i a_lo, a_hi, a_sg[4];
+      if (full) {
+        a_lo = at(lops + t, o.s[0]);
+        a_hi = at(lops + t + 64, o.s[0]);
+#pragma unroll
+        for (int m = 0; m < 4; m++) a_sg[m] = at(lops + t + 128, o.s[m]);
+      } else {
+        a_lo = at_global(gops + t, o.s[0]);
+        a_hi = at_global(gops + t + 64, o.s[0]);
+#pragma unroll
+        for (int m = 0; m < 4; m++) a_sg[m] = at_global(gops + t + 128, o.s[m]);
+      }
       const v4i c0 = ((const v4i*)(cmain + (g * 2 + h) * 16))[kb];
 #pragma unroll
       for (int m = 0; m < 4; m++) {
-        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[h][0], s.blo[m], c0, 0, 0, 0);
-        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[h][1], s.bhi[m], d[m][h], 0, 0, 0);
-        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[h][2], s.bsig[m], d[m][h], 0, 0, 0);
+        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, s.blo[m], c0, 0, 0, 0);
+        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, s.bhi[m], d[m][h], 0, 0, 0);
+        d[m][h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_sg[m], s.bsig[m], d[m][h], 0, 0, 0);
       }
     }
     uint64_t L[4], H[4], x[4];
@@ -452,8 +495,11 @@ __device__ __forceinline__ void permute_grouped(uint64_t (&e)[4][3], const Ctx& 
     sbox_full<4>(e);
     mds4_lds<NG>(e, c, rnd, tab);
   }
+  grp::State s;
+  grp::init_state(s);
+  grp::Lanes o = grp::lanes_of(threadIdx.x & 63);
 #pragma unroll 1
-  for (int g = 0; g < NG; g++) grp::partial_group<NG>(e, tab, gtab, g);
+  for (int g = 0; g < NG; g++) grp::partial_group<NG>(s, o, e, tab, gtab, g);
   rnd = NG == 3 ? 26 : 20;
   if constexpr (NG == 2) {
 #pragma unroll 1

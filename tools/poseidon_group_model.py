@@ -482,6 +482,166 @@ def check(K, r0, n=6, seed=1):
     return G
 
 
+
+# ---- ROTATED forms, lane by lane (poseidon_mx.cuh, grp::step since round 6) -----------------------------------
+# A wave holds four sets of 16 states.  Set m reads every form operand (W, D) with its rows rotated by 4m, so form f
+# of a pair comes out in lane group (f + m) % 4 of set m's tiles; the four copies of form J are merged by lane group,
+# recombined once and put through one dense S-box; sigma_J goes back into bsig[m] in the lane group it was computed
+# in, so bsig[m] is rotated by m lane groups and every operand over it (sigma chunks of W, D, MAIN) is read with its
+# k-blocks rotated by m.  The model below keeps the device's lanes: operands are 64 lanes x 16 signed bytes,
+# accumulators 64 lanes x 4 i32, and the MFMA is v_mfma_i32_16x16x64_i8's operand map.
+
+def lanes_of_image(ops, idx):
+    """operand idx of an image as 64 lanes x 16 signed bytes"""
+    raw = ops[idx * 1024:(idx + 1) * 1024]
+    return [[b - 256 if b >= 128 else b for b in raw[16 * l:16 * l + 16]] for l in range(64)]
+
+
+def rot_lane(lane, m, rows, kbs):
+    """the image lane that lane `lane` of set m reads: rows rotated by 4m, k-blocks by m"""
+    r, kb = lane & 15, lane >> 4
+    if rows:
+        r = (r - 4 * m) & 15
+    if kbs:
+        kb = (kb - m) & 3
+    return r | kb << 4
+
+
+def read_rotated(ops, idx, m, rows, kbs):
+    img = lanes_of_image(ops, idx)
+    return [img[rot_lane(l, m, rows, kbs)] for l in range(64)]
+
+
+def mfma_lanes(A, B, C):
+    """v_mfma_i32_16x16x64_i8 on lanes: A lane (row, kb) and B lane (col, kb) supply k = 16 kb .. + 15; C and the result
+    hold D[row][col] in lane (col, row >> 2), register row & 3"""
+    D = [[0] * 4 for _ in range(64)]
+    for l in range(64):
+        col, rb = l & 15, l >> 4
+        for reg in range(4):
+            row = 4 * rb + reg
+            acc = C[l][reg]
+            for kb in range(4):
+                a, b = A[row + 16 * kb], B[col + 16 * kb]
+                acc += sum(x * y for x, y in zip(a, b) if x)
+            D[l][reg] = acc
+    return D
+
+
+def b_operand(dwords):
+    """four u32 dwords of one lane (bytes already ^ 0x80) -> 16 signed bytes as the MFMA reads them"""
+    out = []
+    for d in dwords:
+        for q in range(4):
+            b = (d >> (8 * q)) & 0xFF
+            out.append(b - 256 if b >= 128 else b)
+    return out
+
+
+def c_lanes(table, base, rot):
+    """C operand from a 16-entry row table: lane group kb reads rows 4 * ((kb - rot) % 4) .. + 3"""
+    return [table[base + 4 * (((l >> 4) - rot) & 3):base + 4 * (((l >> 4) - rot) & 3) + 4] for l in range(64)]
+
+
+def run_group_rotated(ops_f, cform, ops_m, cmain, e, bound, K, ops_f_K=8):
+    """One group on a whole wave, the kernel's rotated sequence.  e[m][lane] = the three words kb, kb + 4, kb + 8 of
+    state 16m + (lane & 15) held by that lane.  ops_f: the image holding the W / D operands (an eight-round group's for
+    the short group), ops_m + cmain: the MAIN operands (offset 0 = MAIN chunk 0) and their C table.  -> new e."""
+    L = layout(ops_f_K)
+    X = 0x80808080
+    blo = [[b_operand([(e[m][l][a] & 0xFFFFFFFF) ^ X for a in range(3)] + [0]) for l in range(64)] for m in range(4)]
+    bhi = [[b_operand([(e[m][l][a] >> 32) ^ X for a in range(3)] + [0]) for l in range(64)] for m in range(4)]
+    # dwords, bytes ^ 0x80.  The kernel carries bsig from group to group and never clears it: slots not yet written
+    # in this group hold the previous group's sigmas, which only zero operand bytes meet.  Garbage here says so.
+    rng = random.Random(K * 1000 + len(ops_m))
+    bsig = [[[rng.getrandbits(32) for _ in range(4)] for _ in range(64)] for m in range(4)]
+    acc = [[None, None] for _ in range(4)]
+    for J in range(K):
+        P, F = J // 4, J % 4
+        if F == 0:
+            nw = L["w_per_half"][P]
+            for half in range(2):
+                base = L["w_base"][P] + half * nw
+                for m in range(4):
+                    d = mfma_lanes(read_rotated(ops_f, base, m, True, False), blo[m],
+                                   c_lanes(cform, (P * 2 + half) * 16, m))
+                    d = mfma_lanes(read_rotated(ops_f, base + 1, m, True, False), bhi[m], d)
+                    if P:
+                        d = mfma_lanes(read_rotated(ops_f, base + 2, m, True, True),
+                                       [b_operand(x) for x in bsig[m]], d)
+                    acc[m][half] = d
+        if J == 0:
+            # gather: lane group g takes set g's word 0 (lane group 0 of set g)
+            dense = [e[l >> 4][l & 15][0] for l in range(64)]
+        else:
+            # merge: lane group g holds form J of set (g - F) % 4; then one recombination per lane
+            dense = []
+            for l in range(64):
+                m = ((l >> 4) - F) & 3
+                dense.append(recombine(acc[m][0][l], acc[m][1][l], bound))
+        y = [sbox(x) for x in dense]
+        for m in range(4):                                          # sigma_J of set m: lane group (F + m) % 4
+            g = (F + m) & 3
+            for l in range(16 * g, 16 * g + 16):
+                bsig[m][l][2 * P] = (y[l] & 0xFFFFFFFF) ^ X
+                bsig[m][l][2 * P + 1] = (y[l] >> 32) ^ X
+        if L["d_first"][P] <= J < L["d_first"][P] + L["d_count"][P] and J < K - 1:
+            for half in range(2):
+                idx = L["d_base"][P] + 2 * (J - L["d_first"][P]) + half
+                for m in range(4):
+                    acc[m][half] = mfma_lanes(read_rotated(ops_f, idx, m, True, True),
+                                              [b_operand(x) for x in bsig[m]], acc[m][half])
+    out = [[[0, 0, 0] for _ in range(64)] for m in range(4)]
+    for m in range(4):
+        bs = [b_operand(x) for x in bsig[m]]
+        for g in range(3):
+            res = []
+            for h in range(2):
+                base = (g * 2 + h) * 3
+                d = mfma_lanes(read_rotated(ops_m, base, 0, False, False), blo[m], c_lanes(cmain, (g * 2 + h) * 16, 0))
+                d = mfma_lanes(read_rotated(ops_m, base + 1, 0, False, False), bhi[m], d)
+                d = mfma_lanes(read_rotated(ops_m, base + 2, m, False, True), bs, d)
+                res.append(d)
+            for l in range(64):
+                out[m][l][g] = recombine(res[0][l], res[1][l], bound)
+    return out
+
+
+def wave_of_states(states):
+    """64 states (12 words each) -> e[m][lane][a] = word kb + 4a of state 16m + n"""
+    return [[[states[16 * m + (l & 15)][(l >> 4) + 4 * a] for a in range(3)] for l in range(64)] for m in range(4)]
+
+
+def states_of_wave(e):
+    st = [[None] * 12 for _ in range(64)]
+    for m in range(4):
+        for l in range(64):
+            for a in range(3):
+                w = e[m][l][a]
+                n, word = 16 * m + (l & 15), (l >> 4) + 4 * a
+                assert st[n][word] is None or st[n][word] == w
+                st[n][word] = w
+    return st
+
+
+def check_rotated(seed=3):
+    """the three groups of the kernel (rounds 4..11, 12..19 on the eight-round images, 20..25 as the short group) on a
+    wave of 64 random states, through the rotated operands and the merge, against the plain rounds"""
+    rng = random.Random(seed)
+    states = [[rng.randrange(P) for _ in range(12)] for _ in range(60)]
+    states += [[0] * 12, [P - 1] * 12, [0xFFFFFFFF00000000] * 12, [0x00000000FFFFFFFF] * 12]
+    for r0 in (4, 12):
+        G = build_group(8, r0)
+        ops, cform, cmain = device_images(G)
+        mb = layout(8)["main_base"]
+        got = states_of_wave(run_group_rotated(ops, cform, ops[mb * 1024:], cmain, wave_of_states(states), G["bound"], 8))
+        assert got == [plain_rounds(list(t), r0, 8)[0] for t in states], ("rotated", r0)
+    ops8, main6, cform6, cmain6, bound = short_group_images(20)
+    got = states_of_wave(run_group_rotated(ops8, cform6, main6, cmain6, wave_of_states(states), bound, 6))
+    assert got == [plain_rounds(list(t), 20, 6)[0] for t in states], ("rotated", 20)
+    return True
+
+
 if __name__ == "__main__":
     for K, r0 in ((8, 4), (8, 12), (6, 20), (4, 4)):
         G = check(K, r0)
@@ -489,3 +649,5 @@ if __name__ == "__main__":
               "largest plane sum %d (< 2^23 = %d)" % (K, r0, layout(K)["n_ops"], G["bound"], 1 << 23))
     check_short()
     print("rounds 20..25 on the eight-round group's form operands + a six-round group's MAIN operands == plain rounds")
+    check_rotated()
+    print("rotated forms (a wave of four sets, lane by lane: rounds 4..11, 12..19, 20..25) == plain rounds")

@@ -253,8 +253,49 @@ typedef struct bp_air_desc {
   uint32_t n_families;
   bp_air_family families[24]; /* interleaved families (synthetic AIR, CTL) list the index of their first member */
 } bp_air_desc;
-uint32_t bp_air_count(void);
+uint32_t bp_air_count(void); /* the BUILT-IN AIRs (9); registered programs, below, are not counted */
 int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t deg_pow, bp_air_desc* out);
+
+/* Run-time AIRs.  A table's constraints can also be given as DATA: a straight-line program of field operations, which
+ * the library validates, registers under an air_id of its own and interprets with one routine (csrc/air_program.hpp)
+ * in the three places a built-in AIR is compiled into: the quotient kernel, the CPU verifier and the trace checker.
+ * A host that has a constraint system as code traces its evaluation once into such a program.
+ *
+ * The program: little-endian u64 words.
+ *   word 0      magic "BPGAIRP1" (0x3150524941475042)
+ *   1 .. 9      n_cols (8 .. 65536), n_const (preprocessed constant columns, 0 .. 4096), n_public (0 .. 4), degree (1 .. 9:
+ *               the declared constraint degree; deg_pow of the table's bp_stark_cfg is 1 up to degree 3, else 3),
+ *               n_constraints (1 .. 65536), n_families (1 .. 24), n_regs (1 .. 64), n_units (1 .. 256), n_code (1 .. 2^20)
+ *   then        n_families x (first_index, count, kind, degree), bp_air_family's fields: the families cover the index
+ *               range [0, n_constraints) in order, exactly once; the kind of a constraint is its family's
+ *   then        n_units + 1 code offsets: unit u is code words [off[u], off[u + 1]); off[0] = 0, off[n_units] = n_code.
+ *               Units are what the kernels spread over grid.y; registers do not live across units.
+ *   then        n_code code words:  op | dst << 8 | a << 16 | b << 40  (8 / 8 / 24 / 24 bits)
+ *                 0 loc dst, a = column      1 nxt dst, a = column (next row)      2 cst dst, a = constant column
+ *                 3 pub dst, a = j           4 x dst (the evaluation point)        5 imm dst, the NEXT word = a constant < p
+ *                 6 add dst, a, b            7 sub dst, a, b  (a - b)              8 mul dst, a, b     (a, b: registers)
+ *                 9 emit: dst = the kind of constraint a's family, a = constraint index, b = register: adds the
+ *                   register to constraint a.  An index may be emitted several times (partial sums add), in any order.
+ * n_regs is bounded by where the device keeps the registers: LDS, 2 KiB a register per 256-lane workgroup, sized from
+ * the program's n_regs (64 registers = 128 KiB of the CU's 160 always fit; fewer registers = more workgroups per CU).
+ * bp_air_register refuses, with BP_ERR_INVALID_INPUT and a message "word <offset>: ...": bad magic or sizes, a register
+ * read before its unit writes it, column / register / constraint indices out of range, a non-canonical immediate, a
+ * constraint never emitted, families that do not tile the list, an emit whose kind is not its family's, and a DEGREE
+ * violation: degrees are propagated (loc / nxt / cst / x = 1, pub / imm = 0, add / sub = max, mul = sum), every emit
+ * must stay within its family's degree and every family within the program's.
+ *
+ * The id: 0x80000000 | (the first four bytes of Keccak-256 of the program's bytes, little-endian) & 0x7fffffff -- the
+ * same in every process, so header word 14 of a proof names the program to a verifier elsewhere.  Registering the same
+ * program again returns the same id; a different program whose id is taken is refused, never aliased.
+ * bp_air_describe answers for a registered id from the program's own tables (n_cols / n_const / deg_pow are ignored).
+ * Every entry that takes an air_id takes a registered one: bp_quotient_scratch_words, bp_quotient_eval,
+ * bp_air_check_trace(_host), bp_stark_verify_air(_pub), bp_stark_prove_trace.  A registered AIR has the auxiliary
+ * column of a table no lookup is built for (one constant running product, as AIR 4 and AIR 7); pub = four words when
+ * n_public > 0.  Not built: a registered AIR as one of a transaction's seven tables or in a cross-table lookup, and
+ * compiling a program to a native kernel at run time.  The program goes to a device once, at its first use there. */
+int bp_air_register(const uint64_t* program, size_t n_words, uint32_t* air_id_out);
+int bp_air_unregister(uint32_t air_id);
+int bp_air_program_digest(uint32_t air_id, uint8_t out[32]); /* Keccak-256 of the registered bytes */
 
 /* K5.  Constraint / quotient evaluation on the extended domain: what compute_quotient_polys does for one table.
  * shape: log_n, n_cols, n_const, deg_pow, rate_bits of the table (the other fields must make a valid
@@ -398,6 +439,14 @@ int bp_stark_prove_synthetic(const bp_stark_cfg* cfg, uint64_t seed, uint64_t co
  * n_const = 0, deg_pow = 1, rate_bits = 1; const_seed is ignored.  The air_id is header word 14 of the proof. */
 int bp_stark_prove_air(uint32_t air_id, const bp_stark_cfg* cfg, uint64_t seed, uint64_t const_seed, int device,
                        uint8_t** out, size_t* out_len);
+/* The same table proof from the CALLER's trace on device `device`: canonical words, column-major, n_cols columns x
+ * 2^log_n rows, column stride `stride` (>= 2^log_n) -- for a built-in air_id (the bytes are bp_stark_prove_air's when
+ * the trace is bp_*_trace(seed)'s) and for a registered one (bp_air_register), which bp_stark_prove_air refuses: there
+ * is no witness generator to draw from a seed.  d_consts: n_const columns, stride 2^log_n, or NULL; pub: the four
+ * public inputs (AIR 8, programs with n_public > 0), or NULL.  The trace must be complete when the call is made (the
+ * library proves on a stream of its own) and is not modified. */
+int bp_stark_prove_trace(uint32_t air_id, const bp_stark_cfg* cfg, const uint64_t* d_trace, uint64_t stride,
+                         const uint64_t* d_consts, const uint64_t* pub, int device, uint8_t** out, size_t* out_len);
 /* The CPU verifier (csrc/verifier.cpp, what VerifierState::verify runs per proof, verifier_state.rs:56-71) on one
  * table proof of bp_stark_prove_air: same transcript prologue.  const_cap: the 2^cap_height x 4 words of the
  * constants commitment when n_const > 0, else NULL.  Host only; BP_ERR_VERIFY + bp_last_error() on rejection. */

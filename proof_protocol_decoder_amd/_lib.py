@@ -95,6 +95,12 @@ def lib():
     L.bp_stark_verify_air.argtypes = [u32, C.POINTER(StarkCfg), C.POINTER(u64), C.c_char_p, C.c_size_t]
     L.bp_stark_prove_air.argtypes = [u32, C.POINTER(StarkCfg), u64, u64, i, C.POINTER(C.POINTER(C.c_uint8)),
                                      C.POINTER(C.c_size_t)]
+    L.bp_stark_verify_air_pub.argtypes = [u32, C.POINTER(StarkCfg), C.POINTER(u64), C.POINTER(u64), C.c_char_p, C.c_size_t]
+    L.bp_stark_prove_trace.argtypes = [u32, C.POINTER(StarkCfg), vp, u64, vp, C.POINTER(u64), i, C.POINTER(C.POINTER(C.c_uint8)),
+                                       C.POINTER(C.c_size_t)]
+    L.bp_air_register.argtypes = [vp, C.c_size_t, C.POINTER(u32)]
+    L.bp_air_unregister.argtypes = [u32]
+    L.bp_air_program_digest.argtypes = [u32, C.c_char_p]
     L.bp_fri_fold.argtypes = [vp, u32, u32, u32, u64, C.POINTER(u64), vp, vp]
     L.bp_openings.argtypes = [vp, u64, u32, u32, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]
     L.bp_pow_grind.argtypes = [C.POINTER(u64), u32, u32, C.POINTER(u64), vp]

@@ -1,0 +1,272 @@
+"""A builder for run-time AIRs: constraint programs for bp_air_register (include/bpg.h, csrc/air_program.hpp).
+
+    b = Builder(n_cols=8, n_const=1, n_public=2)
+    first = b.family(1, kind=FIRST_ROW, degree=1)       # the constraint list, family by family, in index order
+    step = b.family(2, kind=TRANSITION, degree=1)
+    b.unit()                                            # units: what the kernel spreads over grid.y
+    b.emit(first, b.loc(0) - b.pub(0))
+    b.emit(step, b.nxt(0) - b.loc(1))
+    b.emit(step + 1, b.nxt(1) - (b.loc(0) + b.loc(1)))
+    words = b.assemble()                                # numpy uint64: the program bytes
+    values = b.evaluate(row, next_row)                  # the same constraints over Python integers
+
+Expressions are built from loc(c), nxt(c), cst(c), pub(j), x and integers with + - *; equal subexpressions are one node
+(hash-consing), so a value used twice in a unit is computed once.  assemble() schedules every unit's emits in order,
+allocates registers by last use (a leaf -- a load or a constant -- is re-issued for each emit instead of being kept, which
+keeps n_regs, and with it the kernel's LDS footprint, small) and writes the words.  evaluate() walks the same expression
+graph over Python integers mod p: it shares nothing with the library's interpreter, which is what makes it a check of it.
+"""
+import numpy as np
+
+P = 2 ** 64 - 2 ** 32 + 1
+MAGIC = int.from_bytes(b"BPGAIRP1", "little")
+ALL_ROWS, TRANSITION, FIRST_ROW, LAST_ROW = 0, 1, 2, 3
+OP_LOC, OP_NXT, OP_CST, OP_PUB, OP_X, OP_IMM, OP_ADD, OP_SUB, OP_MUL, OP_EMIT = range(10)
+MAX_REGS = 64
+_LEAVES = (OP_LOC, OP_NXT, OP_CST, OP_PUB, OP_X, OP_IMM)
+
+
+class Expr:
+    """One node of a builder's expression graph (make them with the builder's loc / nxt / cst / pub / x / const)."""
+    __slots__ = ("b", "op", "a", "c", "degree", "n")
+
+    def __init__(self, b, op, a, c, degree, n):
+        self.b, self.op, self.a, self.c, self.degree, self.n = b, op, a, c, degree, n
+
+    def __add__(self, o):
+        return self.b._bin(OP_ADD, self, o)
+
+    def __radd__(self, o):
+        return self.b._bin(OP_ADD, o, self)
+
+    def __sub__(self, o):
+        return self.b._bin(OP_SUB, self, o)
+
+    def __rsub__(self, o):
+        return self.b._bin(OP_SUB, o, self)
+
+    def __mul__(self, o):
+        return self.b._bin(OP_MUL, self, o)
+
+    def __rmul__(self, o):
+        return self.b._bin(OP_MUL, o, self)
+
+    def __neg__(self):
+        return self.b._bin(OP_SUB, 0, self)
+
+
+class Builder:
+    def __init__(self, n_cols, n_const=0, n_public=0, degree=None):
+        self.n_cols, self.n_const, self.n_public, self.degree = n_cols, n_const, n_public, degree
+        self.families = []   # (first_index, count, kind, degree)
+        self.units = []      # lists of (index, Expr)
+        self._nodes = {}     # key -> Expr
+        self._order = []     # every node, operands before users
+
+    # ---- expressions
+    def _node(self, op, a, c, degree):
+        key = (op, a.n if isinstance(a, Expr) else a, c.n if isinstance(c, Expr) else c)
+        e = self._nodes.get(key)
+        if e is None:
+            e = self._nodes[key] = Expr(self, op, a, c, degree, len(self._order))
+            self._order.append(e)
+        return e
+
+    def loc(self, c):
+        assert 0 <= c < self.n_cols, "column %d of %d" % (c, self.n_cols)
+        return self._node(OP_LOC, c, None, 1)
+
+    def nxt(self, c):
+        assert 0 <= c < self.n_cols, "column %d of %d" % (c, self.n_cols)
+        return self._node(OP_NXT, c, None, 1)
+
+    def cst(self, c):
+        assert 0 <= c < self.n_const, "constant column %d of %d" % (c, self.n_const)
+        return self._node(OP_CST, c, None, 1)
+
+    def pub(self, j):
+        assert 0 <= j < self.n_public, "public input %d of %d" % (j, self.n_public)
+        return self._node(OP_PUB, j, None, 0)
+
+    @property
+    def x(self):
+        return self._node(OP_X, None, None, 1)
+
+    def const(self, v):
+        return self._node(OP_IMM, int(v) % P, None, 0)
+
+    def _bin(self, op, a, c):
+        a = a if isinstance(a, Expr) else self.const(a)
+        c = c if isinstance(c, Expr) else self.const(c)
+        assert a.b is self and c.b is self, "expressions of another builder"
+        if a.op == OP_IMM and c.op == OP_IMM:
+            return self.const({OP_ADD: a.a + c.a, OP_SUB: a.a - c.a, OP_MUL: a.a * c.a}[op])
+        if op == OP_ADD and a.op == OP_IMM and a.a == 0:
+            return c
+        if op in (OP_ADD, OP_SUB) and c.op == OP_IMM and c.a == 0:
+            return a
+        if op == OP_MUL and a.op == OP_IMM and a.a == 1:
+            return c
+        if op == OP_MUL and c.op == OP_IMM and c.a == 1:
+            return a
+        return self._node(op, a, c, a.degree + c.degree if op == OP_MUL else max(a.degree, c.degree))
+
+    # ---- the constraint list and the units
+    @property
+    def n_constraints(self):
+        return sum(f[1] for f in self.families)
+
+    def family(self, count, kind=ALL_ROWS, degree=2):
+        """The next `count` constraint indices, of one kind and degree bound; returns the first of them."""
+        first = self.n_constraints
+        self.families.append((first, count, kind, degree))
+        return first
+
+    def unit(self):
+        """Starts the next unit; the emits that follow belong to it.  Returns its number."""
+        self.units.append([])
+        return len(self.units) - 1
+
+    def _family_of(self, index):
+        for f in self.families:
+            if f[0] <= index < f[0] + f[1]:
+                return f
+        raise ValueError("constraint %d is in no family" % index)
+
+    def emit(self, index, e):
+        """Adds `e` to constraint `index` (several emits of one index add up)."""
+        e = e if isinstance(e, Expr) else self.const(e)
+        f = self._family_of(index)
+        if e.degree > f[3]:
+            raise ValueError("constraint %d: degree %d, its family allows %d" % (index, e.degree, f[3]))
+        if not self.units:
+            self.unit()
+        self.units[-1].append((index, e))
+
+    # ---- the independent statement: the constraints over Python integers
+    def evaluate(self, row, next_row, consts=(), pub=(), x=0):
+        """[n_constraints] values mod p at one row: row / next_row / consts / pub are sequences of integers."""
+        val = [None] * len(self._order)
+        for e in self._order:
+            if e.op == OP_LOC:
+                v = int(row[e.a])
+            elif e.op == OP_NXT:
+                v = int(next_row[e.a])
+            elif e.op == OP_CST:
+                v = int(consts[e.a])
+            elif e.op == OP_PUB:
+                v = int(pub[e.a])
+            elif e.op == OP_X:
+                v = int(x)
+            elif e.op == OP_IMM:
+                v = e.a
+            elif e.op == OP_ADD:
+                v = val[e.a.n] + val[e.c.n]
+            elif e.op == OP_SUB:
+                v = val[e.a.n] - val[e.c.n]
+            else:
+                v = val[e.a.n] * val[e.c.n]
+            val[e.n] = v % P
+        out = [0] * self.n_constraints
+        for u in self.units:
+            for index, e in u:
+                out[index] = (out[index] + val[e.n]) % P
+        return out
+
+    # ---- the words
+    def _schedule(self, emits):
+        """The unit as a list of steps ('node', Expr) / ('emit', index, Expr) / ('drop', leaves): every operand before
+        its user, a non-leaf node once per unit, a leaf once per emit."""
+        steps, done = [], set()
+        for index, root in emits:
+            leaves = set()
+            stack = [(root, False)]
+            while stack:
+                e, expanded = stack.pop()
+                if e.n in done or e.n in leaves:
+                    continue
+                if e.op in _LEAVES:
+                    leaves.add(e.n)
+                    steps.append(("node", e))
+                elif expanded:
+                    done.add(e.n)
+                    steps.append(("node", e))
+                else:
+                    stack.append((e, True))
+                    stack.append((e.c, False))
+                    stack.append((e.a, False))
+            steps.append(("emit", index, root))
+            # a leaf scheduled for this emit lives until its last use in it: later emits load it again
+            steps.append(("drop", leaves))
+        return steps
+
+    def _assemble_unit(self, emits):
+        steps = self._schedule(emits)
+        # last use of every value instance; a dropped leaf's next load is a new instance
+        inst, cur = [], {}   # step number -> instance id of the node it defines; node -> live instance
+        last_use = {}
+        uses = []            # per step: instance ids it reads
+        n_inst = 0
+        for i, s in enumerate(steps):
+            if s[0] == "node":
+                e = s[1]
+                reads = [] if e.op in _LEAVES else [cur[e.a.n], cur[e.c.n]]
+                cur[e.n] = n_inst
+                inst.append(n_inst)
+                n_inst += 1
+            elif s[0] == "emit":
+                reads = [cur[s[2].n]]
+                inst.append(None)
+            else:
+                for n in s[1]:
+                    cur.pop(n, None)
+                reads = []
+                inst.append(None)
+            for r in reads:
+                last_use[r] = i
+            uses.append(reads)
+        free, reg, words, top = [], {}, [], 0
+        for i, s in enumerate(steps):
+            if s[0] == "drop":
+                continue
+            regs = [reg[r] for r in uses[i]]
+            for r in set(uses[i]):
+                if last_use[r] == i:
+                    free.append(reg.pop(r))
+            if s[0] == "emit":
+                words.append(OP_EMIT | self._family_of(s[1])[2] << 8 | s[1] << 16 | regs[0] << 40)
+                continue
+            e, me = s[1], inst[i]
+            if me not in last_use:
+                raise AssertionError("a value nobody reads was scheduled")
+            free.sort()
+            d = free.pop(0) if free else top
+            top = max(top, d + 1)
+            reg[me] = d
+            if e.op == OP_IMM:
+                words += [OP_IMM | d << 8, e.a]
+            elif e.op == OP_X:
+                words.append(OP_X | d << 8)
+            elif e.op in _LEAVES:
+                words.append(e.op | d << 8 | e.a << 16)
+            else:
+                words.append(e.op | d << 8 | regs[0] << 16 | regs[1] << 40)
+        return words, top
+
+    def assemble(self):
+        """The program as numpy uint64 words (bp_air_register's input)."""
+        if not self.families or not self.units:
+            raise ValueError("a program has at least one family and one unit")
+        code, offsets, n_regs = [], [0], 1
+        for u in self.units:
+            words, top = self._assemble_unit(u)
+            code += words
+            offsets.append(len(code))
+            n_regs = max(n_regs, top)
+        if n_regs > MAX_REGS:
+            raise ValueError("the program needs %d registers, the library takes %d: split the unit" % (n_regs, MAX_REGS))
+        degree = self.degree if self.degree is not None else max(f[3] for f in self.families)
+        hdr = [MAGIC, self.n_cols, self.n_const, self.n_public, degree, self.n_constraints, len(self.families), n_regs,
+               len(self.units), len(code)]
+        fam = [w for f in self.families for w in f]
+        return np.array(hdr + fam + offsets + code, dtype=np.uint64)

@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 #include "air_check.hpp"
+#include "air_program.hpp"
 #include "prover.hpp"
 
 using namespace bpg;
@@ -40,6 +41,9 @@ struct IndexEmit {  // per-index sums of the AIR's own constraints, the trace do
   void transition(uint32_t idx, Ext c) { if (tr) all(idx, c); }
   void first(uint32_t idx, Ext c) { if (fi) all(idx, c); }
   void last(uint32_t idx, Ext c) { if (la) all(idx, c); }
+  void emit(uint32_t kind, uint32_t idx, Ext c) {  // the four by a run-time kind (air_program.hpp)
+    kind == 0 ? all(idx, c) : kind == 1 ? transition(idx, c) : kind == 2 ? first(idx, c) : last(idx, c);
+  }
 };
 
 struct Checker {
@@ -47,14 +51,18 @@ struct Checker {
   uint32_t log_n, T, n_units;
   uint64_t pub[4] = {0, 0, 0, 0};
   bp_air_desc desc;
+  std::shared_ptr<const air::prog::Program> program;  // a registered id: its program, interpreted (air_program.hpp)
   // v[idx] = the value of constraint idx at row i (loc = row i, nxt = row i + 1, cst = constants of row i)
   void eval_row(uint32_t i, const uint64_t* loc, const uint64_t* nxt, const uint64_t* cst, std::vector<Ext>& v) const {
     const uint32_t last = (1u << log_n) - 1;
     v.assign(T, gl::ext(0));
     IndexEmit e{v, T, i != last, i == 0, i == last};
-    const HostRow row{loc, nxt, cst, shape.air_id == air::PLONK ? gl::pow(gl::root(log_n), i) : 0, pub};
+    const HostRow row{loc, nxt, cst, shape.air_id == air::PLONK || program ? gl::pow(gl::root(log_n), i) : 0, pub};
     const uint64_t ctl[4] = {0, 0, 0, 0};
-    for (uint32_t u = 0; u < n_units; u++) air::eval_unit<Ext>(shape, u, T, ctl, row, e);
+    if (program)
+      for (uint32_t u = 0; u < n_units; u++) program->eval_unit<Ext>(u, row, e);
+    else
+      for (uint32_t u = 0; u < n_units; u++) air::eval_unit<Ext>(shape, u, T, ctl, row, e);
   }
   void family_of(uint32_t idx, uint32_t* family, uint32_t* kind) const {
     if (shape.air_id == air::SYNTHETIC) {  // interleaved: 3g all rows, 3g + 1 transition, 3g + 2 first row
@@ -105,8 +113,10 @@ int make_checker(const char* who, uint32_t air_id, const bp_stark_cfg* shape, co
   if (stride < ((uint64_t)1 << c.log_n)) return fail(BP_ERR_INVALID_INPUT, "%s: column stride %llu is shorter than the %u-row trace",
                                                      who, (unsigned long long)stride, 1u << c.log_n);
   if (c.n_const && !consts) return fail(BP_ERR_INVALID_INPUT, "%s: the AIR reads %u constant columns: pass them", who, c.n_const);
-  if (air_id == air::PLONK) {
-    if (!pub) return fail(BP_ERR_INVALID_INPUT, "%s: AIR 8 binds its first row to four public inputs: pass them", who);
+  k->program = air::prog::find(air_id);
+  if (air::prog::is_registered(air_id) && !k->program) return fail(BP_ERR_INVALID_INPUT, "%s: AIR program 0x%08x was unregistered", who, air_id);
+  if (air_id == air::PLONK || (k->program && k->program->n_public)) {
+    if (!pub) return fail(BP_ERR_INVALID_INPUT, "%s: the AIR reads public inputs (AIR 8: four, bound to its first row): pass four words", who);
     for (int j = 0; j < 4; j++) {
       if (pub[j] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "%s: non-canonical public input", who);
       k->pub[j] = pub[j];
@@ -114,8 +124,8 @@ int make_checker(const char* who, uint32_t air_id, const bp_stark_cfg* shape, co
   }
   k->shape = air::Shape{air_id, c.n_cols, c.n_const, c.deg_pow};
   k->log_n = c.log_n;
-  k->T = air::n_constraints(k->shape);
-  k->n_units = air::n_units(k->shape);
+  k->T = air::any_n_constraints(k->shape);
+  k->n_units = air::any_n_units(k->shape);
   if ((rc = bp_air_describe(air_id, c.n_cols, c.n_const, c.deg_pow, &k->desc))) return rc;
   return BP_OK;
 }

@@ -15,77 +15,13 @@
 #include "common.hpp"
 #include "gl.hpp"
 #include "air.hpp"
+#include "air_check_dev.cuh"
+#include "air_program.hpp"
 
 namespace {
 
 using bpg::CheckArgs;
-
-struct CheckRow {  // row i of the trace (lanes = consecutive rows: coalesced), no auxiliary columns
-  const uint64_t *trace, *cst_;
-  uint64_t ts, cs, pos, pos_next;
-  uint64_t xv;
-  const uint64_t* pub_;
-  __device__ __forceinline__ uint64_t x() const { return xv; }
-  __device__ __forceinline__ uint64_t pub(uint32_t j) const { return pub_[j]; }
-  __device__ __forceinline__ uint64_t loc(uint32_t c) const { return trace[(uint64_t)c * ts + pos]; }
-  __device__ __forceinline__ uint64_t nxt(uint32_t c) const { return trace[(uint64_t)c * ts + pos_next]; }
-  __device__ __forceinline__ uint64_t cst(uint32_t k) const { return cst_[(uint64_t)k * cs + pos]; }
-  __device__ __forceinline__ uint64_t aux(uint32_t) const { return 0; }
-  __device__ __forceinline__ uint64_t aux_nxt(uint32_t) const { return 0; }
-};
-struct CheckEmit {  // K5's consumer (stark_kernels.hip, DevEmit) with the trace domain's selectors as masks
-  const uint64_t* apow;  // [2][T]
-  uint32_t T;
-  uint64_t m_tr, m_first, m_last;  // all ones where the selector is 1, else zero
-  gl::DotAcc acc[4];
-  uint64_t pend_v;
-  uint32_t pend_e;
-  bool has;
-  __device__ __forceinline__ void push(uint32_t idx, uint64_t v) {
-    if (idx >= T) return;  // a lookup share: not the AIR's own constraint
-    const uint32_t e = T - 1 - idx;
-    if (!has) {
-      pend_v = v; pend_e = e; has = true;
-      return;
-    }
-    const uint64_t a[4] = {pend_v, pend_v, v, v};
-    const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], apow[e], apow[T + e]};
-    gl::dot_mad4(acc, a, w);
-    has = false;
-  }
-  __device__ __forceinline__ void all(uint32_t idx, uint64_t v) { push(idx, v); }
-  __device__ __forceinline__ void transition(uint32_t idx, uint64_t v) { push(idx, v & m_tr); }
-  __device__ __forceinline__ void first(uint32_t idx, uint64_t v) { push(idx, v & m_first); }
-  __device__ __forceinline__ void last(uint32_t idx, uint64_t v) { push(idx, v & m_last); }
-  __device__ __forceinline__ uint64_t result(int j) {
-    if (has) {
-      const uint64_t a[4] = {pend_v, pend_v, 0, 0};
-      const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], 0, 0};
-      gl::dot_mad4(acc, a, w);
-      has = false;
-    }
-    return gl::addc(gl::dot_reduce(acc[j]), gl::dot_reduce(acc[2 + j]));
-  }
-};
-__device__ __forceinline__ CheckEmit check_emit(const CheckArgs& a, uint64_t pos) {
-  const uint64_t last = ((uint64_t)1 << a.log_n) - 1;
-  return CheckEmit{a.apow, a.T, pos != last ? ~0ull : 0ull, pos == 0 ? ~0ull : 0ull, pos == last ? ~0ull : 0ull,
-                   {gl::dot_zero(), gl::dot_zero(), gl::dot_zero(), gl::dot_zero()}, 0, 0, false};
-}
-__device__ __forceinline__ CheckRow check_row(const CheckArgs& a, uint64_t pos, bool with_x) {
-  const uint64_t n = (uint64_t)1 << a.log_n;
-  return CheckRow{a.trace, a.consts, a.stride, n, pos, (pos + 1) & (n - 1),
-                  with_x ? gl::pow(gl::root(a.log_n), pos) : 0, a.pub};
-}
-// bit `pos % 64` of word `pos / 64` = bad; lane 0 of each wave (its row is a multiple of 64) writes the wave's word.
-// Every lane of the wave must get here (no early return before it).
-__device__ __forceinline__ void flag_rows(const CheckArgs& a, uint64_t pos, bool bad) {
-  const unsigned long long b = __ballot(bad);
-  if ((threadIdx.x & 63) == 0 && pos < ((uint64_t)1 << a.log_n)) {
-    a.bitmap[pos >> 6] = b;
-    if (b) atomicAdd(a.count, (unsigned long long)__popcll(b));
-  }
-}
+using namespace bpg::chk;
 
 // grid = (ceil(n / 256), wg_rows): workgroup row y evaluates units [y * units_per_wg, ...) of the AIR's list (AIR 8:
 // its ten chunk units; the Poseidon gate is air_check_plonk_hash_kernel's).  One workgroup row: the row's fold is
@@ -202,7 +138,7 @@ namespace bpg {
 uint64_t air_check_partial_words(CheckArgs& a) {
   const air::Shape shape{a.air_id, a.n_cols, a.n_const, a.deg_pow};
   const bool plonk = a.air_id == air::PLONK;
-  a.n_units = plonk ? air::plonk::N_UNITS - 1 : air::n_units(shape);  // (AIR 8's unit 10: the hash kernel)
+  a.n_units = plonk ? air::plonk::N_UNITS - 1 : air::any_n_units(shape);  // (AIR 8's unit 10: the hash kernel)
   const uint64_t blocks = ceil_div((uint64_t)1 << a.log_n, 256);
   // a table of 512 workgroups or more fills the chip's 256 CUs alone: one pass; a shorter one spreads its units
   // over grid.y up to ~1024 workgroups, as K5 does
@@ -223,7 +159,9 @@ int launch_air_check(const CheckArgs& a, hipStream_t st) {
   air_check_alpha_kernel<<<dim3(ceil_div(a.T, 256), 2), 256, 0, st>>>(const_cast<uint64_t*>(a.apow), a.T, a.alpha0, a.alpha1);
   BPG_LAUNCH_CHECK();
   const dim3 g1(ceil_div(n, 256), a.wg_rows);
-  switch (a.air_id) {
+  if (air::prog::is_registered(a.air_id)) {
+    if (int rc = launch_air_check_program(a, g1, st)) return rc;
+  } else switch (a.air_id) {
     case air::KECCAK_F: air_check_kernel<air::KECCAK_F><<<g1, 256, 0, st>>>(a); break;
     case air::LOGIC: air_check_kernel<air::LOGIC><<<g1, 256, 0, st>>>(a); break;
     case air::MEMORY: air_check_kernel<air::MEMORY><<<g1, 256, 0, st>>>(a); break;

@@ -22,6 +22,8 @@ struct CheckArgs {
 // partial words (0: none) and the grid.y spreading for a check of `a` (fills n_units, units_per_wg, wg_rows)
 uint64_t air_check_partial_words(CheckArgs& a);
 int launch_air_check(const CheckArgs& a, hipStream_t st);
+// air_program.hip: launch_air_check's row pass when a.air_id is a registered program (air_program.hpp)
+int launch_air_check_program(const CheckArgs& a, dim3 grid, hipStream_t st);
 // out[j * n_cols + c] = trace[c * stride + rows[j]], j < n_rows (d_rows on the device)
 int launch_gather_rows(const uint64_t* trace, uint64_t stride, uint32_t n_cols, const uint32_t* d_rows, uint32_t n_rows,
                        uint64_t* out, hipStream_t st);

@@ -1,0 +1,157 @@
+// air_program.hip -- the device instantiation of the program interpreter (air_program.hpp): K5 on the LDE coset and the
+// trace checker's row pass for REGISTERED AIRs, beside quotient_air_kernel (stark_kernels.hip) and air_check_kernel
+// (air_check.hip), with their row accessors, consumers, alpha-power tables and partial-sum paths (quotient_dev.cuh,
+// air_check_dev.cuh): the fold of a program is the built-in kernels' fold.
+//
+// A lane owns one point; the code is read wave-uniformly (scalar loads: pc never depends on the lane, nothing is
+// decoded per lane) and every branch of the interpreter is a scalar branch.
+//
+// The register file.  A register numbered at run time cannot be a VGPR (the compiler would put the array in scratch), so
+// the program's registers live in LDS as [reg][lane]: register r of lane l at word r * 256 + l -- consecutive lanes,
+// 8 bytes each, conflict-free ds_read_b64 / ds_write_b64, and no barrier anywhere: a lane only ever touches its own
+// column.  A register is 2 KiB of the workgroup's LDS; the dynamic allocation is sized from the program's n_regs, so
+// a program of 10 registers (20 KiB) keeps seven workgroups on a CU and one of 64 (128 KiB, the validator's limit) one.
+// The value an instruction has just written also stays in a VGPR (`acc`): an operand that names the register written
+// last is read from there, which takes half the LDS reads out of the chains  v = v + v, v = v + b, e = e - c  these
+// programs mostly are.
+#include <mutex>
+#include "air_check_dev.cuh"
+#include "air_program.hpp"
+#include "common.hpp"
+#include "quotient_dev.cuh"
+
+namespace {
+
+using namespace bpg::k5;
+using namespace bpg::chk;
+namespace prog = bpg::air::prog;
+
+extern __shared__ uint64_t lds_regs[];  // [n_regs][256]
+
+struct LdsRegs {
+  uint64_t* lane;  // register 0 of this lane
+  uint64_t acc;    // the value of register `last`
+  uint32_t last;   // wave-uniform
+  __device__ __forceinline__ uint64_t get(uint32_t r) const { return r == last ? acc : lane[r * 256]; }
+  __device__ __forceinline__ void set(uint32_t r, uint64_t v) {
+    lane[r * 256] = v;
+    acc = v;
+    last = r;
+  }
+};
+__device__ __forceinline__ LdsRegs lds_regs_of_lane() { return LdsRegs{lds_regs + threadIdx.x, 0, ~0u}; }
+
+// image: the program's unit offsets (n_air_units + 1 words), then its code (prog::Program::image).
+// grid = (rows / 256, workgroup rows, proofs) as quotient_air_kernel's; dynamic LDS = n_regs * 2 KiB.
+__global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg::QuotArgs> batch, const uint64_t* __restrict__ image) {
+  if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
+  const bpg::QuotArgs& q = batch.a[blockIdx.z];
+  const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (pos >= rows) return;
+  const uint32_t n = 1u << q.log_n;
+  const uint32_t t = (uint32_t)(pos >> q.log_n), m = (uint32_t)(pos & (n - 1));
+  DevEmit out{q.apow, q.n_constraints, row_point(q, t, m),
+              {gl::dot_zero(), gl::dot_zero(), gl::dot_zero(), gl::dot_zero()}, 0, 0, false};
+  DevRow row{q.trace_lde, q.aux_lde, q.const_lde, q.trace_stride, q.aux_stride, q.const_stride, pos,
+             ((uint64_t)t << q.log_n) | ((m + 1) & (n - 1)), out.rp.x, q.ctl.pub};
+  LdsRegs regs = lds_regs_of_lane();
+  const uint64_t* __restrict__ code = image + q.n_air_units + 1;
+  const uint32_t n_units = q.n_air_units + q.n_ctl_units;
+  const uint32_t u0 = blockIdx.y * q.units_per_wg, u1 = min(u0 + q.units_per_wg, n_units);
+#pragma unroll 1
+  for (uint32_t u = u0; u < u1; u++) {
+    if (u < q.n_air_units) {
+      prog::run<uint64_t>(code, (uint32_t)image[u], (uint32_t)image[u + 1], regs, row, out);
+    } else {
+      // "a table no lookup is built for": the one constant running product AIR 4 and AIR 7 have
+      const bpg::air::Shape cs{bpg::air::ARITHMETIC, q.n_cols, q.n_const, q.deg_pow};
+      bpg::air::ctl::eval<uint64_t>(cs, q.n_air_constraints, 0, q.n_aux, q.ctl.v, row, out);
+    }
+  }
+  const uint64_t r0 = out.result(0), r1 = out.result(1);
+  if (gridDim.y == 1) {
+    const uint64_t zh_inv = q.apow[2 * (size_t)q.n_constraints + 32 + t];
+    q.qvals[pos] = gl::mulc(r0, zh_inv);
+    q.qvals[rows + pos] = gl::mulc(r1, zh_inv);
+  } else {
+    q.partial[((uint64_t)blockIdx.y * 2) * rows + pos] = r0;
+    q.partial[((uint64_t)blockIdx.y * 2 + 1) * rows + pos] = r1;
+  }
+}
+
+// grid = (ceil(n / 256), wg_rows) as air_check_kernel's; dynamic LDS = n_regs * 2 KiB.
+__global__ void __launch_bounds__(256) air_check_program_kernel(bpg::CheckArgs a, const uint64_t* __restrict__ image) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  uint64_t r0 = 0, r1 = 0;
+  if (pos < n) {
+    CheckEmit out = check_emit(a, pos);
+    const CheckRow row = check_row(a, pos, true);
+    LdsRegs regs = lds_regs_of_lane();
+    const uint64_t* __restrict__ code = image + a.n_units + 1;
+    const uint32_t u0 = blockIdx.y * a.units_per_wg, u1 = min(u0 + a.units_per_wg, a.n_units);
+#pragma unroll 1
+    for (uint32_t u = u0; u < u1; u++) prog::run<uint64_t>(code, (uint32_t)image[u], (uint32_t)image[u + 1], regs, row, out);
+    r0 = out.result(0);
+    r1 = out.result(1);
+  }
+  if (a.partial) {
+    if (pos < n) {
+      a.partial[((uint64_t)blockIdx.y * 2) * n + pos] = r0;
+      a.partial[((uint64_t)blockIdx.y * 2 + 1) * n + pos] = r1;
+    }
+    return;
+  }
+  flag_rows(a, pos, (r0 | r1) != 0);
+}
+
+// A dynamic LDS allocation above 64 KiB has to be asked for before the launch: once per device and kernel, for the
+// validator's limit (prog::MAX_REGS registers), so every registered program fits.
+int allow_large_lds() {
+  static std::mutex mu;
+  static std::vector<int> done;
+  int dev = 0;
+  BPG_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  for (int d : done)
+    if (d == dev) return BP_OK;
+  const int bytes = (int)(prog::MAX_REGS * 256 * 8);
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&air_check_program_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.push_back(dev);
+  return BP_OK;
+}
+
+int program_of(uint32_t air_id, uint32_t n_units, std::shared_ptr<const prog::Program>* p, const uint64_t** d_image) {
+  *p = prog::find(air_id);
+  if (!*p) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x was unregistered", air_id);
+  if ((*p)->n_units != n_units) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x: the launch was sized for another program", air_id);
+  if (int rc = allow_large_lds()) return rc;
+  return prog::device_image(*p, d_image);
+}
+
+}  // namespace
+
+namespace bpg {
+
+// The evaluation launch of launch_quotient (stark_kernels.hip) for a registered id: same grid, same argument blocks.
+int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer& kt, hipStream_t st) {
+  const QuotArgs& q = qb.a[0];
+  std::shared_ptr<const prog::Program> p;
+  const uint64_t* d_image = nullptr;
+  if (int rc = program_of(q.air_id, q.n_air_units, &p, &d_image)) return rc;
+  BPG_LAUNCH_TIMED(kt, quotient_program_kernel, grid, 256, p->n_regs * 256 * 8, st, qb, d_image);
+  return BP_OK;
+}
+
+// The row pass of launch_air_check (air_check.hip) for a registered id.
+int launch_air_check_program(const CheckArgs& a, dim3 grid, hipStream_t st) {
+  std::shared_ptr<const prog::Program> p;
+  const uint64_t* d_image = nullptr;
+  if (int rc = program_of(a.air_id, a.n_units, &p, &d_image)) return rc;
+  air_check_program_kernel<<<grid, 256, p->n_regs * 256 * 8, st>>>(a, d_image);
+  return BP_OK;
+}
+
+}  // namespace bpg

@@ -219,8 +219,14 @@ static uint32_t n_fri_layers(const StarkCfg& c) {  // FriReductionStrategy::Cons
 std::atomic<int> g_k5_spread_all{0};  // measurement knob (bp_tune_k5_spread): the loaded-device spreading rule for the synthetic AIR too
 int check_cfg(const StarkCfg& c) {
   const air::Info* ai = air::info(c.air_id);
-  if (!ai) return fail(BP_ERR_INVALID_INPUT, "unknown air_id %u (bp_air_count() AIRs are built in)", c.air_id);
-  if (ai->n_cols && (c.n_cols != ai->n_cols || c.n_const != ai->n_const_max || c.deg_pow != (ai->degree > 3 ? 3u : 1u)))
+  const auto program = ai ? nullptr : air::prog::find(c.air_id);
+  if (!ai && !program)
+    return fail(BP_ERR_INVALID_INPUT, "unknown air_id %u (bp_air_count() AIRs are built in; a program gets its id from bp_air_register)", c.air_id);
+  if (program && (c.n_cols != program->n_cols || c.n_const != program->n_const || c.deg_pow != program->deg_pow()))
+    return fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x has %u columns, %u constant columns and degree %u (deg_pow %u): got n_cols=%u "
+                "n_const=%u deg_pow=%u", c.air_id, program->n_cols, program->n_const, program->degree, program->deg_pow(), c.n_cols,
+                c.n_const, c.deg_pow);
+  if (ai && ai->n_cols && (c.n_cols != ai->n_cols || c.n_const != ai->n_const_max || c.deg_pow != (ai->degree > 3 ? 3u : 1u)))
     return fail(BP_ERR_INVALID_INPUT, "AIR %u (%s) has %u columns, %u constant columns and degree %u (deg_pow %u): got n_cols=%u "
                 "n_const=%u deg_pow=%u", c.air_id, ai->name, ai->n_cols, ai->n_const_max, ai->degree, ai->degree > 3 ? 3u : 1u,
                 c.n_cols, c.n_const, c.deg_pow);
@@ -485,10 +491,10 @@ int quotient_args(const StarkCfg& cfg, const Ctl& ctl, uint64_t alpha0, uint64_t
   qa.log_n = log_n; qa.rate_bits = r; qa.n_cols = C; qa.n_const = K; qa.n_aux = A; qa.deg_pow = cfg.deg_pow;
   // the constraint list and its units (air.hpp): the AIR's, then the table's lookups (air::ctl).  The synthetic
   // table's many product columns are sliced into units; a real table's few lookup columns are one unit.
-  qa.n_air_constraints = air::n_constraints(shape);
+  qa.n_air_constraints = air::any_n_constraints(shape);
   qa.n_constraints = qa.n_air_constraints + air::ctl::n_constraints(shape);
   qa.side_rows = cfg.air_id == air::PLONK ? 1 : 0;
-  qa.n_air_units = air::n_units(shape) - qa.side_rows;
+  qa.n_air_units = air::any_n_units(shape) - qa.side_rows;
   qa.aux_per_unit = cfg.air_id == air::SYNTHETIC ? std::max<uint32_t>(16, (A + 15) / 16) : A;
   // (AIR 8's copy constraints ride in its own ten units, next to the gates that read the same wires: no lookup unit)
   qa.n_ctl_units = cfg.air_id == air::PLONK ? 0 : (A + qa.aux_per_unit - 1) / qa.aux_per_unit;

@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "gl.hpp"
 #include "stark_kernels.hpp"
+#include "air_program.hpp"
 
 namespace bpg {
 

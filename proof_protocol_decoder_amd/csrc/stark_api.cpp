@@ -108,6 +108,9 @@ void bp_release_cached_memory(void) {
 int bp_stark_prove_air(uint32_t air_id, const bp_stark_cfg* cfg, uint64_t seed, uint64_t const_seed, int device,
                        uint8_t** out, size_t* out_len) try {
   if (!cfg || !out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_air: null argument");
+  if (air::prog::is_registered(air_id))
+    return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_air: a registered AIR has no witness generator to draw from a seed: prove its trace "
+                "with bp_stark_prove_trace");
   StarkCfg c{cfg->log_n, cfg->n_cols, cfg->n_const, cfg->deg_pow, cfg->rate_bits, cfg->cap_height,
              cfg->num_queries, cfg->pow_bits, cfg->arity_bits, cfg->final_poly_bits, air_id};
   int rc = check_cfg(c);
@@ -178,6 +181,72 @@ int bp_stark_prove_air(uint32_t air_id, const bp_stark_cfg* cfg, uint64_t seed, 
 }
 BPG_ABI_CATCH("bp_stark_prove_air")
 
+// The same proof from the caller's trace: what bp_stark_prove_air does after its witness generator has run.
+int bp_stark_prove_trace(uint32_t air_id, const bp_stark_cfg* cfg, const uint64_t* d_trace, uint64_t stride, const uint64_t* d_consts,
+                         const uint64_t* pub, int device, uint8_t** out, size_t* out_len) try {
+  if (!cfg || !d_trace || !out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_trace: null argument");
+  StarkCfg c{cfg->log_n, cfg->n_cols, cfg->n_const, cfg->deg_pow, cfg->rate_bits, cfg->cap_height,
+             cfg->num_queries, cfg->pow_bits, cfg->arity_bits, cfg->final_poly_bits, air_id};
+  int rc = check_cfg(c);
+  if (rc) return rc;
+  const uint64_t N = (uint64_t)1 << c.log_n, M = N << c.rate_bits;
+  if (stride < N) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_trace: column stride %llu is shorter than the %llu-row trace",
+                              (unsigned long long)stride, (unsigned long long)N);
+  if (c.n_const && !d_consts) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_trace: the AIR reads %u constant columns: pass them", c.n_const);
+  const auto program = air::prog::find(air_id);
+  Ctl ctl;
+  if (air_id == air::PLONK || (program && program->n_public)) {
+    if (!pub) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_trace: the AIR reads public inputs: pass four words");
+    for (int j = 0; j < 4; j++) {
+      if (pub[j] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_trace: non-canonical public input");
+      ctl.pub[j] = pub[j];
+    }
+  }
+  // the arena of bp_stark_prove_air, plus the trace itself when it has to be packed to stride n
+  const size_t cols = (size_t)c.n_cols + c.n_const + c.n_cols / 8 + (2u << c.rate_bits) + 64;
+  size_t bytes = cols * (2 * N + M) * 8 + (size_t)80 * M * 8 + ((size_t)c.n_cols / 32 + 64) * 8 * N * 8 + (64u << 20);
+  if (stride != N) bytes += (size_t)c.n_cols * N * 8;
+  Worker* wp = take_worker(device, bytes, &rc);
+  if (!wp) return rc;
+  Worker& w = *wp;
+  struct Parker {
+    Worker* w;
+    ~Parker() { park_worker(w); }
+  } parker{wp};
+  auto body = [&]() -> int {
+    Challenger ch;
+    Committed consts, trace;
+    if (c.n_const) {
+      int r2 = commit(w, d_consts, c.n_const, c.log_n, c.rate_bits, c.cap_height, false, &consts);
+      if (r2) return r2;
+      ch.observe(consts.cap.data(), consts.cap.size());
+    }
+    const uint64_t* d_tv = d_trace;
+    if (stride != N) {
+      uint64_t* packed = w.arena.alloc_words((size_t)c.n_cols * N);
+      if (!packed) return fail(BP_ERR_DEVICE, "arena exhausted");
+      BPG_HIP(hipMemcpy2DAsync(packed, N * 8, d_trace, stride * 8, N * 8, c.n_cols, hipMemcpyDeviceToDevice, w.stream));
+      d_tv = packed;
+    }
+    int r2 = commit(w, d_tv, c.n_cols, c.log_n, c.rate_bits, c.cap_height, false, &trace);
+    if (r2) return r2;
+    ch.observe(trace.cap.data(), trace.cap.size());
+    for (int i = 0; i < 4; i++) ctl.v[i] = ch.challenge();
+    std::vector<uint64_t> proof;
+    if ((r2 = stark_prove(w, c, c.n_const ? &consts : nullptr, trace, d_tv, ctl, ch, proof))) return r2;
+    *out_len = proof.size() * 8;
+    *out = static_cast<uint8_t*>(std::malloc(*out_len));
+    if (!*out) return fail(BP_ERR_DEVICE, "host allocation failed");
+    std::memcpy(*out, proof.data(), *out_len);
+    return BP_OK;
+  };
+  rc = body();
+  if (rc) (void)hipStreamSynchronize(w.stream);
+  else rc = w.wait();
+  return rc;
+}
+BPG_ABI_CATCH("bp_stark_prove_trace")
+
 int bp_stark_prove_synthetic(const bp_stark_cfg* cfg, uint64_t seed, uint64_t const_seed, int device,
                              uint8_t** out, size_t* out_len) {
   return bp_stark_prove_air(air::SYNTHETIC, cfg, seed, const_seed, device, out, out_len);
@@ -227,9 +296,30 @@ BPG_ABI_CATCH("bp_stark_verify_air_pub")
 
 // ---- the AIR registry (air.hpp) --------------------------------------------------------------------------
 
+// the BUILT-IN AIRs only: registered programs (air_program.cpp) live beside them under ids with the top bit set
 uint32_t bp_air_count(void) { return air::COUNT; }
 
 int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t deg_pow, bp_air_desc* out) try {
+  if (const auto p = air::prog::find(air_id)) {  // a registered program answers from its own tables; the width asked about is ignored
+    if (!out) return fail(BP_ERR_INVALID_INPUT, "bp_air_describe: null output");
+    std::memset(out, 0, sizeof(*out));
+    out->air_id = air_id;
+    std::strncpy(out->name, "program", sizeof(out->name) - 1);
+    out->fixed_n_cols = out->n_cols = p->n_cols;
+    out->n_const_max = p->n_const;
+    out->degree = p->degree;
+    out->n_aux = 1;  // "a table no lookup is built for": the constant running product AIR 4 and AIR 7 have
+    out->n_air_constraints = p->n_constraints;
+    out->n_ctl_constraints = 2;
+    out->n_units = p->n_units;
+    uint32_t n = 0;
+    for (uint32_t f = 0; f < p->n_families; f++)
+      out->families[n++] = bp_air_family{p->families[f].first_index, p->families[f].count, p->families[f].kind, p->families[f].degree};
+    if (n < 24) out->families[n++] = bp_air_family{p->n_constraints, 1, 1, 3};
+    if (n < 24) out->families[n++] = bp_air_family{p->n_constraints + 1, 1, 3, 2};
+    out->n_families = n;
+    return BP_OK;
+  }
   const air::Info* ai = air::info(air_id);
   if (!ai || !out) return fail(BP_ERR_INVALID_INPUT, "bp_air_describe: unknown air_id %u or null output", air_id);
   std::memset(out, 0, sizeof(*out));

@@ -16,10 +16,13 @@
 #include "poseidon.cuh"
 #include "poseidon_mx.cuh"
 #include "stark_kernels.hpp"
+#include "quotient_dev.cuh"
+#include "air_program.hpp"
 
 namespace {
 
 using gl::Ext;
+using namespace bpg::k5;
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ULL;
@@ -33,14 +36,6 @@ __device__ __forceinline__ uint64_t rnd(uint64_t seed, uint64_t col, uint64_t ro
 __device__ __forceinline__ uint64_t pow_e(uint64_t t, uint32_t e) {
   return e == 3 ? gl::mulc(gl::mulc(t, t), t) : t;
 }
-// w_n^m from the half-size table tw[e] = w_n^e, e < n/2
-__device__ __forceinline__ uint64_t root_pow(const uint64_t* __restrict__ tw, uint32_t log_n, uint32_t m) {
-  if (log_n == 0) return 1;
-  const uint32_t half = 1u << (log_n - 1);
-  uint64_t w = tw[m & (half - 1)];
-  return (m & half) ? gl::negc(w) : w;
-}
-
 // ---------------------------------------------------------------- synthetic witness
 __global__ void __launch_bounds__(256)
 synth_const_kernel(uint64_t* out, uint32_t log_n, uint32_t n_const, uint64_t seed) {
@@ -791,72 +786,6 @@ __global__ void __launch_bounds__(256) plonk_partial_products_kernel(bpg::BatchO
 // tall enough to fill the chip takes ONE pass (grid.y = 1): the quotient value is written straight away and no
 // partial sums ever reach HBM.  Short tables spread their units over grid.y workgroup rows; the partial sums of
 // the rows simply add (every term carries its absolute power), which quotient_sum_kernel does.
-struct RowPoint {
-  uint64_t z_last, l_first, l_last, x;
-};
-__device__ __forceinline__ RowPoint row_point(const bpg::QuotArgs& q, uint32_t t, uint32_t m) {
-  // per-coset constants from the table alpha_table_kernel left behind the alpha powers (t is a per-lane value:
-  // indexing the kernel-argument arrays with it would pull all 48 words into SGPRs)
-  const uint64_t* coset = q.apow + 2 * (size_t)q.n_constraints;
-  const uint64_t x = gl::mulc(coset[t], root_pow(q.tw_n, q.log_n, m));
-  const uint64_t zh = coset[16 + t];
-  RowPoint p;
-  p.x = x;
-  p.z_last = gl::subc(x, q.g_inv);
-  const uint64_t zn = gl::mulc(zh, q.n_inv);
-  // both Lagrange denominators with one inversion (x is off the subgroup: neither is zero)
-  const uint64_t df = gl::subc(x, 1), dl = gl::subc(gl::mulc(q.g, x), 1);
-  const uint64_t both = gl::mulc(zn, gl::inv(gl::mulc(df, dl)));
-  p.l_first = gl::mulc(both, dl);
-  p.l_last = gl::mulc(both, df);
-  return p;
-}
-struct DevRow {  // one point of the coset: column-major matrices, lanes = consecutive rows (coalesced)
-  const uint64_t *trace, *aux_, *cst_;
-  uint64_t ts, as, cs, pos, pos_next;
-  uint64_t xv;          // the point itself
-  const uint64_t* pub_;  // the table's public inputs (kernel arguments)
-  __device__ __forceinline__ uint64_t x() const { return xv; }
-  __device__ __forceinline__ uint64_t pub(uint32_t j) const { return pub_[j]; }
-  __device__ __forceinline__ uint64_t loc(uint32_t c) const { return trace[(uint64_t)c * ts + pos]; }
-  __device__ __forceinline__ uint64_t nxt(uint32_t c) const { return trace[(uint64_t)c * ts + pos_next]; }
-  __device__ __forceinline__ uint64_t cst(uint32_t k) const { return cst_[(uint64_t)k * cs + pos]; }
-  __device__ __forceinline__ uint64_t aux(uint32_t k) const { return aux_[(uint64_t)k * as + pos]; }
-  __device__ __forceinline__ uint64_t aux_nxt(uint32_t k) const { return aux_[(uint64_t)k * as + pos_next]; }
-};
-struct DevEmit {  // the constraint consumer: two constraints (x two challenges) per dot_mad4
-  const uint64_t* apow;  // [2][T]: alpha_j^e (wave-uniform reads)
-  uint32_t T;
-  RowPoint rp;
-  gl::DotAcc acc[4];  // 0, 1: challenge 0 / 1 of the first constraint of a pair; 2, 3: of the second
-  uint64_t pend_v;
-  uint32_t pend_e;
-  bool has;
-  __device__ __forceinline__ void push(uint32_t idx, uint64_t v) {
-    const uint32_t e = T - 1 - idx;
-    if (!has) {
-      pend_v = v; pend_e = e; has = true;
-      return;
-    }
-    const uint64_t a[4] = {pend_v, pend_v, v, v};
-    const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], apow[e], apow[T + e]};
-    gl::dot_mad4(acc, a, w);
-    has = false;
-  }
-  __device__ __forceinline__ void all(uint32_t idx, uint64_t v) { push(idx, v); }
-  __device__ __forceinline__ void transition(uint32_t idx, uint64_t v) { push(idx, gl::mulc(v, rp.z_last)); }
-  __device__ __forceinline__ void first(uint32_t idx, uint64_t v) { push(idx, gl::mulc(v, rp.l_first)); }
-  __device__ __forceinline__ void last(uint32_t idx, uint64_t v) { push(idx, gl::mulc(v, rp.l_last)); }
-  __device__ __forceinline__ uint64_t result(int j) {
-    if (has) {
-      const uint64_t a[4] = {pend_v, pend_v, 0, 0};
-      const uint64_t w[4] = {apow[pend_e], apow[T + pend_e], 0, 0};
-      gl::dot_mad4(acc, a, w);
-      has = false;
-    }
-    return gl::addc(gl::dot_reduce(acc[j]), gl::dot_reduce(acc[2 + j]));
-  }
-};
 // grid = (rows / 256, workgroup rows); workgroup row y evaluates units [y * units_per_wg, ...) of the list
 // "AIR units, then CTL units".
 // The Keccak-f evaluator wants 193 VGPRs (two waves per SIMD); held to 168 (three waves, 26 registers in scratch) it is
@@ -1652,7 +1581,10 @@ int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, 
   // algorithmic bytes: every element of the three LDE matrices read once, the two quotient columns written
   // (AIR 8 is counted with the synthetic recursion-shaped proofs it replaces)
   KernelTimer kt(PROF_K5 + (q.air_id < air::COUNT ? q.air_id : 0), st, 8.0 * (double)rows * ((double)q.n_cols + q.n_aux + q.n_const + 2) * batch, true);
-  if (q.air_id == bpg::air::KECCAK_F) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::KECCAK_F>, g1, 256, 0, st, qb);
+  if (bpg::air::prog::is_registered(q.air_id)) {
+    if (int rc = launch_quotient_program(qb, g1, kt, st)) return rc;
+  }
+  else if (q.air_id == bpg::air::KECCAK_F) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::KECCAK_F>, g1, 256, 0, st, qb);
   else if (q.air_id == bpg::air::LOGIC) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::LOGIC>, g1, 256, 0, st, qb);
   else if (q.air_id == bpg::air::MEMORY) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::MEMORY>, g1, 256, 0, st, qb);
   else if (q.air_id == bpg::air::ARITHMETIC) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::ARITHMETIC>, g1, 256, 0, st, qb);

@@ -213,6 +213,9 @@ int launch_plonk_trace(const PlonkTraceArgs* a, uint32_t batch, uint32_t log_n, 
 // every proof of the batch has the shape and the unit spreading of q[0]
 int launch_quotient(const QuotArgs* q, uint32_t batch, const QuotCoset& coset, hipStream_t st);
 inline int launch_quotient(const QuotArgs& q, const QuotCoset& coset, hipStream_t st) { return launch_quotient(&q, 1, coset, st); }
+// air_program.hip: launch_quotient's evaluation launch when q.air_id is a registered program (air_program.hpp)
+struct KernelTimer;
+int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer& kt, hipStream_t st);
 int launch_quotient_chunks(const ChunkArgs* c, uint32_t batch, hipStream_t st);
 int launch_power_vectors(const PowerVecArgs* a, uint32_t batch, uint32_t log_n, uint32_t n_points, hipStream_t st);
 // d_out: n_points (<= 3) vectors of 2n words each: point y at d_out + y * 2n

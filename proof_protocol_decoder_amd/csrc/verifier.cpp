@@ -78,6 +78,9 @@ struct Consumer {
   void transition(uint32_t idx, Ext c) { all(idx, gl::mul(c, z_last)); }
   void first(uint32_t idx, Ext c) { all(idx, gl::mul(c, l_first)); }
   void last(uint32_t idx, Ext c) { all(idx, gl::mul(c, l_last)); }
+  void emit(uint32_t kind, uint32_t idx, Ext c) {  // the four by a run-time kind (air_program.hpp)
+    kind == 0 ? all(idx, c) : kind == 1 ? transition(idx, c) : kind == 2 ? first(idx, c) : last(idx, c);
+  }
 };
 
 // fri::verifier::compute_evaluation: interpolate the arity coset values, evaluate at beta.
@@ -135,13 +138,18 @@ int stark_verify(const StarkCfg& cfg, const uint64_t* const_cap, const Ctl& ctl,
     if (gl::eq(zh, gl::ext(0))) REJECT("Opening point is in the subgroup.");
     const Ext zhn = gl::scale(zh, gl::inv(N));
     const air::Shape shape{cfg.air_id, C, K, cfg.deg_pow};
-    const uint32_t n_air = air::n_constraints(shape);
+    const auto program = air::prog::find(cfg.air_id);  // a registered id: its program, interpreted (air_program.hpp)
+    if (air::prog::is_registered(cfg.air_id) && !program) return fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x was unregistered", cfg.air_id);
+    const uint32_t n_air = program ? program->n_constraints : air::n_constraints(shape);
     Consumer k(n_air + air::ctl::n_constraints(shape), alpha0, alpha1);
     k.z_last = gl::sub(zeta, gl::ext(gl::inv(g)));
     k.l_first = gl::mul(zhn, gl::inv(gl::sub(zeta, gl::ext(1))));
     k.l_last = gl::mul(zhn, gl::inv(gl::sub(gl::scale(zeta, g), gl::ext(1))));
     const OpenedRow row{oz, oz + 2 * (size_t)K, on, oz + 2 * (size_t)(K + C), on + 2 * (size_t)C, zeta, ctl.pub};
-    for (uint32_t u = 0; u < air::n_units(shape); u++) air::eval_unit<Ext>(shape, u, n_air, ctl.v, row, k);
+    if (program)
+      for (uint32_t u = 0; u < program->n_units; u++) program->eval_unit<Ext>(u, row, k);
+    else
+      for (uint32_t u = 0; u < air::n_units(shape); u++) air::eval_unit<Ext>(shape, u, n_air, ctl.v, row, k);
     air::ctl::eval<Ext>(shape, n_air, 0, A, ctl.v, row, k);
     const uint64_t* oq = oz + 2 * (size_t)(K + C + A);
     for (int j = 0; j < 2; j++) {

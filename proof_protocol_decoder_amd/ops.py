@@ -90,6 +90,28 @@ def air_describe(air_id, n_cols=0, n_const=0, deg_pow=1):
     return d
 
 
+def air_register(words):
+    """bp_air_register: registers a constraint program (air_program.Builder.assemble(), or any uint64 words of the format in
+    include/bpg.h) and returns its air_id, 0x80000000 | 31 bits of the Keccak-256 of its bytes: the same in every process.
+    Every entry that takes an air_id takes it.  Registering the same words again returns the same id."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    air_id = C.c_uint32()
+    check(lib().bp_air_register(words.ctypes.data, words.size, C.byref(air_id)))
+    return air_id.value
+
+
+def air_unregister(air_id):
+    """bp_air_unregister: forgets a registered program (and frees its device images)."""
+    check(lib().bp_air_unregister(air_id))
+
+
+def air_program_digest(air_id):
+    """bp_air_program_digest: the Keccak-256 of a registered program's bytes."""
+    out = C.create_string_buffer(32)
+    check(lib().bp_air_program_digest(air_id, out))
+    return out.raw
+
+
 def logic_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_logic_trace: the AIR-2 witness [524, 2^log_n]; inputs [2^log_n, 9] int64 on the device (operation code, the
     four words of operand 0, of operand 1), or drawn from `seed`."""
@@ -319,6 +341,39 @@ def stark_prove_air(air_id, cfg, seed, const_seed=0, device=0):
     n = C.c_size_t()
     check(lib().bp_stark_prove_air(air_id, C.byref(cfg), seed, const_seed, device, C.byref(out), C.byref(n)))
     return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+
+
+def stark_prove_trace(air_id, cfg, trace, consts=None, pub=None, device=None):
+    """bp_stark_prove_trace: the table proof of stark_prove_air from the caller's trace ([n_cols, 2^log_n] int64 on the
+    device, canonical words; a column slice of a wider buffer keeps its stride), for a built-in or a registered air_id.
+    consts: [n_const, 2^log_n]; pub: four public inputs (AIR 8, programs that read some).  Returns proof words (u64)."""
+    if not trace.is_cuda or trace.dtype != torch.int64 or trace.stride(1) != 1:
+        raise ValueError("stark_prove_trace needs an int64 device tensor with contiguous columns")
+    if consts is not None:
+        _require_cuda(consts)
+    _check_shapes(trace.shape[1], consts, pub)
+    if trace.shape[0] != cfg.n_cols or trace.shape[1] != 1 << cfg.log_n:
+        raise ValueError("the trace is %s, the configuration says [%d, %d]" % (tuple(trace.shape), cfg.n_cols, 1 << cfg.log_n))
+    torch.cuda.synchronize(trace.device)  # the library proves on a stream of its own
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t()
+    pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
+    dev = trace.device.index if device is None else device
+    check(lib().bp_stark_prove_trace(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
+                                     consts.data_ptr() if consts is not None else None, pub_arr, dev or 0, C.byref(out), C.byref(n)))
+    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+
+
+def stark_verify_air(air_id, cfg, proof, const_cap=None, pub=None):
+    """bp_stark_verify_air_pub: the CPU verifier on one table proof (uint64 words); raises BpgError(BP_ERR_VERIFY) on
+    rejection.  const_cap: the constants commitment's cap words when the table has constant columns."""
+    proof = np.ascontiguousarray(proof, dtype=np.uint64)
+    cap = None
+    if const_cap is not None:
+        const_cap = np.ascontiguousarray(const_cap, dtype=np.uint64)
+        cap = const_cap.ctypes.data_as(C.POINTER(C.c_uint64))
+    pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
+    check(lib().bp_stark_verify_air_pub(air_id, C.byref(cfg), cap, pub_arr, proof.tobytes(), proof.size * 8))
 
 
 def stark_prove_synthetic(cfg, seed, const_seed=0, device=0):

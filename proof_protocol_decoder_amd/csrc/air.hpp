@@ -4,7 +4,9 @@
 // plonky_block_proof_gen/src/proof_gen.rs:44-52 through prove_single_table / compute_quotient_polys) is here an
 // `air_id` plus ONE templated evaluation routine: the same source is instantiated over canonical base-field words on
 // the device (every point of the LDE coset) and over the quadratic extension on the host (the verifier's check at
-// zeta).  An AIR is described by
+// zeta).  In the source an AIR is three things: its row of the descriptor table (DESC, "registry" below: every fact
+// about it that is data), its branch of the unit evaluator eval_unit_of<AIR> (the routine in its namespace) and its
+// witness generator (launch_air_trace, stark_kernels.hip).  An AIR is described by
 //   * its shape (columns, preprocessed constant columns, constraint degree),
 //   * its constraint list: every constraint has a fixed INDEX i in [0, n_constraints), a kind
 //     (all rows / transition = times (x - g^(n-1)) / first row = times L_0 / last row = times L_(n-1)) and a degree,
@@ -42,10 +44,13 @@
 // AIR 7  arithmetic_mul  the multiplicative half of the arithmetic table: x * y = z + 2^256 w on 256-bit words, a 32-column
 //                      schoolbook product over sixteen 16-bit limbs with 21-bit carries, 1217 columns, degree 3.  A
 //                      table of its own here: merged into AIR 4's rows it would add 900 columns to every addition.
+// AIR 8  plonk         the proof system of the recursion layer on a fixed PLONK-shaped circuit: 135 wires, 85 preprocessed
+//                      constants, degree 9; its copy constraints ride in its own units (section "AIR 8" below).
 // The auxiliary columns of a table are its cross-table lookups (namespace ctl below; upstream's CTL checks sit beside
 // Stark::eval the same way): their constraints follow the AIR's in the list.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 #include "gl.hpp"
 #if defined(__HIP__)
 #include "poseidon.cuh"  // the device form of the Poseidon gate's round function (PoseidonOps<uint64_t>)
@@ -1362,41 +1367,151 @@ GL_HD void eval_unit(uint32_t u, uint32_t ctl_base, const uint64_t ctl[4], const
 }  // namespace plonk
 
 // ------------------------------------------------------------------------------------------ registry
-GL_HD uint32_t n_constraints(const Shape& s) {
-  return s.air_id == KECCAK_F ? keccak::N_CONSTRAINTS
-         : s.air_id == LOGIC  ? logic::N_CONSTRAINTS
-         : s.air_id == MEMORY ? memory::N_CONSTRAINTS
-         : s.air_id == ARITHMETIC ? arithmetic::N_CONSTRAINTS
-         : s.air_id == BYTE_PACKING ? byte_packing::N_CONSTRAINTS
-         : s.air_id == KECCAK_SPONGE ? keccak_sponge::N_CONSTRAINTS
-         : s.air_id == ARITHMETIC_MUL ? arithmetic_mul::N_CONSTRAINTS
-         : s.air_id == PLONK ? plonk::N_CONSTRAINTS
-                              : synthetic::n_constraints(s);
+namespace ctl {  // the layout of the tables' auxiliary columns (what they hold: "cross-table lookups" below)
+// The FILTER columns of the three looked tables (which rows are exposed) are TRACE columns (keccak::COL_G, memory::COL_G, logic::COL_G):
+// they are committed before the lookup challenges (beta, gamma) are drawn.  (Round 4 kept them among the auxiliary
+// columns, committed AFTER the challenges: a prover could then pick the exposed subset knowing the challenges -- a
+// subset-product search over a smooth multiplicative group, ADVICE r4.)  Upstream keeps its filters in the trace too.
+constexpr uint32_t KECCAK_H = 0, KECCAK_Z = 2, KECCAK_N_AUX = 4, KECCAK_N_CONSTRAINTS = 10;
+// sponge: z_0 z_1 (-> keccak_f), then per block-of-eight-limbs m < 5 and challenge set c the product 2 + 2 m + c (-> logic)
+constexpr uint32_t SPONGE_Z = 0, SPONGE_LZ = 2, SPONGE_LOGIC_OPS = 5, SPONGE_N_AUX = 2 + 2 * SPONGE_LOGIC_OPS, SPONGE_N_CONSTRAINTS = 2 * SPONGE_N_AUX;
+constexpr uint32_t LOGIC_Z = 0, LOGIC_N_AUX = 2, LOGIC_N_CONSTRAINTS = 5;
+constexpr uint32_t LOGIC_TUPLE = 27;  // is_and, is_or, is_xor, eight limbs of each input, eight of the result
+constexpr uint32_t TUPLE_LIMBS = 50;  // a Keccak state as 32-bit limbs
+constexpr uint32_t PACK_Z = 0, PACK_N_AUX = 2, PACK_N_CONSTRAINTS = 4;
+constexpr uint32_t MEM_Z = 0, MEM_N_AUX = 2, MEM_N_CONSTRAINTS = 5;
+constexpr uint32_t WORD_TUPLE = 11;  // is_read, address, timestamp, eight value limbs
+// AIR 8 (plonk): per challenge set c, column 10 c = Z_c and 10 c + k = the k-th partial product, k = 1..9
+constexpr uint32_t PLONK_N_AUX = 20, PLONK_N_CONSTRAINTS = 22, PLONK_CHUNK = 8, PLONK_CHUNKS = 10;
+}  // namespace ctl
+
+// The descriptor of a built-in AIR: everything about it that is data, once.  n_constraints, n_units, ctl::n_aux,
+// ctl::n_constraints, ctl::first_product and info() below, bp_air_describe and the launchers read it; it is a constant
+// expression, so with a compile-time AIR (the kernels) every read folds away.
+struct Family {
+  uint32_t first, count, kind, degree;  // constraints first, first + 1, ...; kinds: 0 all rows, 1 transition, 2 first row, 3 last row
+};
+struct Desc {
+  const char* name;
+  uint32_t n_cols;       // 0: any width (multiple of 4 not required; groups of four columns are constrained)
+  uint32_t n_const_max;  // preprocessed constant columns the AIR can use
+  uint32_t degree;       // constraint degree (x deg_pow for the synthetic AIR); rate_bits must give 2^r >= degree - 1
+  uint32_t n_constraints, n_units;  // the AIR's own list (AIR 0: functions of the Shape, namespace synthetic)
+  // the auxiliary columns, their constraints (AIR 0: functions of the Shape, namespace ctl) and the first column that is
+  // a running product (the columns before it are helpers); products run to the last column (AIR 8 keeps its two
+  // running products, columns 0 and 10, in its own kernels: stark_kernels.hip)
+  uint32_t n_aux, n_ctl_constraints, first_product;
+  uint32_t aux_reads;  // columns one product column reads (launch_aux's algorithmic bytes); 0: no lookup is built, z = 1
+  bool in_pair;        // a side of a lookup between tables (ctl::pairs)
+  Family families[12];      // the AIR's constraints in list order, closed by a count of 0
+  Family ctl_families[10];  // the lookup constraints that follow them, `first` counted from n_constraints
+};
+// (a filtered running product is a pair of families: transition z - z' term {i, 1, 1, 3}, last row z - term {i + 1, 1, 3, 2})
+constexpr Desc DESC[COUNT] = {
+    // the families of a synthetic table follow from its width: bp_air_describe (stark_api.cpp)
+    {"synthetic", 0, 4096, 3, 0, 0, 0, 0, 0, 2, false, {}, {}},
+    {"keccak_f", keccak::N_COLS, 0, 3, keccak::N_CONSTRAINTS, keccak::N_UNITS, ctl::KECCAK_N_AUX, ctl::KECCAK_N_CONSTRAINTS, ctl::KECCAK_Z, 53, true,
+     {{keccak::F0, 24, 2, 1}, {keccak::F1, 24, 1, 1}, {keccak::F2, 1984, 0, 2}, {keccak::F3, 320, 0, 3}, {keccak::F4, 320, 0, 3},
+      {keccak::F5, 50, 0, 3}, {keccak::F6, 50, 0, 3}, {keccak::F7, 2, 0, 1}, {keccak::F8, 2, 0, 2}, {keccak::F9, 50, 1, 2}},
+     {{0, 2, 0, 2},                                              // the filter g: a bit, set on last-round rows only
+      {2, 1, 0, 2}, {3, 1, 1, 2}, {4, 1, 0, 2}, {5, 1, 1, 2},  // h_c: the compressed input, fixed on first-round rows, carried along
+      {6, 1, 1, 3}, {7, 1, 3, 2}, {8, 1, 1, 3}, {9, 1, 3, 2}}},
+    {"logic", logic::N_COLS, 0, 3, logic::N_CONSTRAINTS, logic::N_UNITS, ctl::LOGIC_N_AUX, ctl::LOGIC_N_CONSTRAINTS, ctl::LOGIC_Z, 524, true,
+     {{logic::L0, 3, 0, 2}, {logic::L1, 1, 0, 2}, {logic::L2, 512, 0, 2}, {logic::L3, 8, 0, 3}},
+     {{0, 1, 0, 2},  // the filter g of the looked table: a bit
+      {1, 1, 1, 3}, {2, 1, 3, 2}, {3, 1, 1, 3}, {4, 1, 3, 2}}},
+    {"memory", memory::N_COLS, 0, 3, memory::N_CONSTRAINTS, memory::N_UNITS, ctl::MEM_N_AUX, ctl::MEM_N_CONSTRAINTS, ctl::MEM_Z, 12, true,
+     {{memory::M0, 1, 0, 2}, {memory::M1, 1, 0, 2}, {memory::M2, 32, 0, 2}, {memory::M3, 1, 1, 2}, {memory::M4, 1, 1, 2},
+      {memory::M5, 8, 1, 3}, {memory::M6, 8, 1, 3}, {memory::M7, 8, 2, 2}},
+     {{0, 1, 0, 2},  // the filter g of the looked table: a bit
+      {1, 1, 1, 3}, {2, 1, 3, 2}, {3, 1, 1, 3}, {4, 1, 3, 2}}},
+    // AIR 4, AIR 7: no lookup is built, one constant running product (section "cross-table lookups")
+    {"arithmetic", arithmetic::N_COLS, 0, 2, arithmetic::N_CONSTRAINTS, arithmetic::N_UNITS, 1, 2, 0, 0, false,
+     {{arithmetic::A0, 4, 0, 2}, {arithmetic::A1, 1, 0, 2}, {arithmetic::A2, 256, 0, 2}, {arithmetic::A3, 16, 0, 2},
+      {arithmetic::A4, 16, 0, 2}, {arithmetic::A5, 1, 0, 2}},
+     {{0, 1, 1, 3}, {1, 1, 3, 2}}},
+    {"byte_packing", byte_packing::N_COLS, 0, 2, byte_packing::N_CONSTRAINTS, byte_packing::N_UNITS, ctl::PACK_N_AUX, ctl::PACK_N_CONSTRAINTS, ctl::PACK_Z, 43, true,
+     {{byte_packing::P0, 1, 0, 2}, {byte_packing::P1, 32, 0, 2}, {byte_packing::P2, 1, 0, 2}, {byte_packing::P3, 256, 0, 2},
+      {byte_packing::P4, 32, 0, 2}, {byte_packing::P5, 8, 0, 2}},
+     {{0, 1, 1, 3}, {1, 1, 3, 2}, {2, 1, 1, 3}, {3, 1, 3, 2}}},
+    {"keccak_sponge", keccak_sponge::N_COLS, 0, 2, keccak_sponge::N_CONSTRAINTS, keccak_sponge::N_UNITS, ctl::SPONGE_N_AUX, ctl::SPONGE_N_CONSTRAINTS, ctl::SPONGE_Z, 102, true,
+     {{keccak_sponge::K0, 2, 0, 2}, {keccak_sponge::K1, 1, 0, 2}, {keccak_sponge::K2, 136, 0, 2}, {keccak_sponge::K3, 1, 0, 1},
+      {keccak_sponge::K4, 1088, 0, 2}, {keccak_sponge::K5, 1088, 0, 2}, {keccak_sponge::K6, 136, 0, 2}, {keccak_sponge::K7, 34, 0, 2},
+      {keccak_sponge::K8, 50, 1, 2}, {keccak_sponge::K9, 50, 2, 1}, {keccak_sponge::K10, 1, 1, 2}},
+     // the twelve products, interleaved like the synthetic tables': 2k transition, 2k + 1 last row
+     {{0, ctl::SPONGE_N_AUX, 1, 3}, {1, ctl::SPONGE_N_AUX, 3, 2}}},
+    {"arithmetic_mul", arithmetic_mul::N_COLS, 0, 3, arithmetic_mul::N_CONSTRAINTS, arithmetic_mul::N_UNITS, 1, 2, 0, 0, false,
+     {{arithmetic_mul::U0, 1, 0, 2}, {arithmetic_mul::U1, 256, 0, 2}, {arithmetic_mul::U2, 256, 0, 2}, {arithmetic_mul::U3, 672, 0, 2},
+      {arithmetic_mul::U4, 32, 0, 3}, {arithmetic_mul::U5, 1, 0, 1}},
+     {{0, 1, 1, 3}, {1, 1, 3, 2}}},
+    {"plonk", plonk::N_COLS, plonk::N_CONST, 9, plonk::N_CONSTRAINTS, plonk::N_UNITS, ctl::PLONK_N_AUX, ctl::PLONK_N_CONSTRAINTS, 0, 0, false,
+     {{plonk::G0, 20, 0, 4}, {plonk::G1, 44, 0, 3}, {plonk::G2, 22, 0, 2}, {plonk::G3, 4, 2, 1}, {plonk::G4, 118, 0, 8}, {plonk::G5, 5, 0, 3}},
+     // the copy constraints: per challenge set ten chunk relations and Z(first) = 1
+     {{0, 10, 0, 9}, {10, 1, 2, 1}, {11, 10, 0, 9}, {21, 1, 2, 1}}},
+};
+// the families of every fixed table cover its two counts
+constexpr bool families_cover(const Family* f, uint32_t max, uint32_t total) {
+  uint32_t sum = 0;
+  for (uint32_t i = 0; i < max && f[i].count; i++) sum += f[i].count;
+  return sum == total;
 }
-GL_HD uint32_t n_units(const Shape& s) {
-  return s.air_id == KECCAK_F ? keccak::N_UNITS
-         : s.air_id == LOGIC  ? logic::N_UNITS
-         : s.air_id == MEMORY ? memory::N_UNITS
-         : s.air_id == ARITHMETIC ? arithmetic::N_UNITS
-         : s.air_id == BYTE_PACKING ? byte_packing::N_UNITS
-         : s.air_id == KECCAK_SPONGE ? keccak_sponge::N_UNITS
-         : s.air_id == ARITHMETIC_MUL ? arithmetic_mul::N_UNITS
-         : s.air_id == PLONK ? plonk::N_UNITS
-                              : synthetic::n_units(s);
+constexpr bool descriptors_consistent() {
+  for (uint32_t a = 1; a < COUNT; a++)
+    if (!families_cover(DESC[a].families, 12, DESC[a].n_constraints) || !families_cover(DESC[a].ctl_families, 10, DESC[a].n_ctl_constraints))
+      return false;
+  return true;
 }
-// ctl_base / ctl: the index of the table's first lookup constraint and the lookup challenges -- AIR 8's units carry its
-// copy constraints (the other tables' lookup constraints are ctl::eval's)
+static_assert(descriptors_consistent(), "an AIR's families do not add up to its constraint count");
+
+inline const Desc* info(uint32_t air_id) { return air_id < COUNT ? &DESC[air_id] : nullptr; }
+// a built-in table of fixed shape: its descriptor row is the whole answer (a synthetic table's follows from its Shape)
+GL_HD bool fixed_shape(uint32_t air_id) { return air_id != SYNTHETIC && air_id < COUNT; }
+GL_HD uint32_t n_constraints(const Shape& s) { return fixed_shape(s.air_id) ? DESC[s.air_id].n_constraints : synthetic::n_constraints(s); }
+GL_HD uint32_t n_units(const Shape& s) { return fixed_shape(s.air_id) ? DESC[s.air_id].n_units : synthetic::n_units(s); }
+
+// Unit `unit` of AIR `AIR`, the AIR a compile-time constant (the kernels are instantiated per AIR) and the argument list
+// the same for all.  ctl_base / ctl: the index of the table's first lookup constraint and the lookup challenges -- AIR
+// 8's units carry its copy constraints (the other tables' lookup constraints are ctl::eval's).
+// AIR 8 differs between device and host: its unit 10, the Poseidon gate, needs another register budget than the chunk
+// units, so on the device it is a kernel of its own (quotient_plonk_hash_kernel, air_check_plonk_hash_kernel) and the
+// kernels that call this routine run units 0..9 only; the host evaluates all eleven here.
+template <uint32_t AIR, class T, class Row, class Emit>
+GL_HD void eval_unit_of(const Shape& s, uint32_t unit, uint32_t ctl_base, const uint64_t ctl[4], const Row& row, Emit& out) {
+  if constexpr (AIR == KECCAK_F) keccak::eval_unit<T>(unit, row, out);
+  else if constexpr (AIR == LOGIC) logic::eval_unit<T>(unit, ctl_base, ctl, row, out);
+  else if constexpr (AIR == MEMORY) memory::eval_unit<T>(row, out);
+  else if constexpr (AIR == ARITHMETIC) arithmetic::eval_unit<T>(unit, row, out);
+  else if constexpr (AIR == BYTE_PACKING) byte_packing::eval_unit<T>(unit, row, out);
+  else if constexpr (AIR == KECCAK_SPONGE) keccak_sponge::eval_unit<T>(unit, ctl_base, ctl, row, out);
+  else if constexpr (AIR == ARITHMETIC_MUL) arithmetic_mul::eval_unit<T>(unit, row, out);
+  else if constexpr (AIR == PLONK) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    plonk::eval_chunk_unit<T>(unit, ctl_base, ctl, row, out);
+#else
+    plonk::eval_unit<T>(unit, ctl_base, ctl, row, out);
+#endif
+  } else synthetic::eval_unit<T>(s, unit, row, out);
+}
+// A run-time air_id as a compile-time constant: f(std::integral_constant<uint32_t, AIR>{}).  The one switch over the
+// built-in AIRs; an id that is none of them counts as AIR 0 (check_cfg has refused it before anything is launched).
+template <class Fn>
+GL_HD void dispatch(uint32_t air_id, Fn&& f) {
+  switch (air_id) {
+    case KECCAK_F: f(std::integral_constant<uint32_t, KECCAK_F>{}); break;
+    case LOGIC: f(std::integral_constant<uint32_t, LOGIC>{}); break;
+    case MEMORY: f(std::integral_constant<uint32_t, MEMORY>{}); break;
+    case ARITHMETIC: f(std::integral_constant<uint32_t, ARITHMETIC>{}); break;
+    case BYTE_PACKING: f(std::integral_constant<uint32_t, BYTE_PACKING>{}); break;
+    case KECCAK_SPONGE: f(std::integral_constant<uint32_t, KECCAK_SPONGE>{}); break;
+    case ARITHMETIC_MUL: f(std::integral_constant<uint32_t, ARITHMETIC_MUL>{}); break;
+    case PLONK: f(std::integral_constant<uint32_t, PLONK>{}); break;
+    default: f(std::integral_constant<uint32_t, SYNTHETIC>{}); break;
+  }
+}
+// the same unit of a table whose AIR is known at run time (the verifier, the host side of the trace checker)
 template <class T, class Row, class Emit>
 GL_HD void eval_unit(const Shape& s, uint32_t unit, uint32_t ctl_base, const uint64_t ctl[4], const Row& row, Emit& out) {
-  if (s.air_id == KECCAK_F) keccak::eval_unit<T>(unit, row, out);
-  else if (s.air_id == LOGIC) logic::eval_unit<T>(unit, ctl_base, ctl, row, out);
-  else if (s.air_id == MEMORY) memory::eval_unit<T>(row, out);
-  else if (s.air_id == ARITHMETIC) arithmetic::eval_unit<T>(unit, row, out);
-  else if (s.air_id == BYTE_PACKING) byte_packing::eval_unit<T>(unit, row, out);
-  else if (s.air_id == KECCAK_SPONGE) keccak_sponge::eval_unit<T>(unit, ctl_base, ctl, row, out);
-  else if (s.air_id == ARITHMETIC_MUL) arithmetic_mul::eval_unit<T>(unit, row, out);
-  else if (s.air_id == PLONK) plonk::eval_unit<T>(unit, ctl_base, ctl, row, out);
-  else synthetic::eval_unit<T>(s, unit, row, out);
+  dispatch(s.air_id, [&](auto A) { eval_unit_of<decltype(A)::value, T>(s, unit, ctl_base, ctl, row, out); });
 }
 
 // ------------------------------------------------------------------------------------------ cross-table lookups
@@ -1446,45 +1561,12 @@ GL_HD void eval_unit(const Shape& s, uint32_t unit, uint32_t ctl_base, const uin
 // AIR 4, 7           1 column: no lookup is built for these tables (upstream's go through the CPU table, which needs
 //                    the EVM interpreter): a constant running product z = 1 keeps the oracle set of every table the same.
 namespace ctl {
-// The FILTER columns of the three looked tables (which rows are exposed) are TRACE columns (keccak::COL_G, memory::COL_G, logic::COL_G):
-// they are committed before the lookup challenges (beta, gamma) are drawn.  (Round 4 kept them among the auxiliary
-// columns, committed AFTER the challenges: a prover could then pick the exposed subset knowing the challenges -- a
-// subset-product search over a smooth multiplicative group, ADVICE r4.)  Upstream keeps its filters in the trace too.
-constexpr uint32_t KECCAK_H = 0, KECCAK_Z = 2, KECCAK_N_AUX = 4, KECCAK_N_CONSTRAINTS = 10;
-// sponge: z_0 z_1 (-> keccak_f), then per block-of-eight-limbs m < 5 and challenge set c the product 2 + 2 m + c (-> logic)
-constexpr uint32_t SPONGE_Z = 0, SPONGE_LZ = 2, SPONGE_LOGIC_OPS = 5, SPONGE_N_AUX = 2 + 2 * SPONGE_LOGIC_OPS, SPONGE_N_CONSTRAINTS = 2 * SPONGE_N_AUX;
-constexpr uint32_t LOGIC_Z = 0, LOGIC_N_AUX = 2, LOGIC_N_CONSTRAINTS = 5;
-constexpr uint32_t LOGIC_TUPLE = 27;  // is_and, is_or, is_xor, eight limbs of each input, eight of the result
-constexpr uint32_t TUPLE_LIMBS = 50;  // a Keccak state as 32-bit limbs
-constexpr uint32_t PACK_Z = 0, PACK_N_AUX = 2, PACK_N_CONSTRAINTS = 4;
-constexpr uint32_t MEM_Z = 0, MEM_N_AUX = 2, MEM_N_CONSTRAINTS = 5;
-constexpr uint32_t WORD_TUPLE = 11;  // is_read, address, timestamp, eight value limbs
-// AIR 8 (plonk): per challenge set c, column 10 c = Z_c and 10 c + k = the k-th partial product, k = 1..9
-constexpr uint32_t PLONK_N_AUX = 20, PLONK_N_CONSTRAINTS = 22, PLONK_CHUNK = 8, PLONK_CHUNKS = 10;
-
-GL_HD uint32_t n_aux(const Shape& s) {
-  return s.air_id == SYNTHETIC ? s.n_cols / 8
-         : s.air_id == KECCAK_F ? KECCAK_N_AUX
-         : s.air_id == KECCAK_SPONGE ? SPONGE_N_AUX
-         : s.air_id == BYTE_PACKING ? PACK_N_AUX
-         : s.air_id == MEMORY ? MEM_N_AUX
-         : s.air_id == LOGIC ? LOGIC_N_AUX
-         : s.air_id == PLONK ? PLONK_N_AUX
-                             : 1;
-}
+// a table that is none of the built-in ones (a registered program) has no lookup: one constant product, as AIR 4 and 7
+GL_HD uint32_t n_aux(const Shape& s) { return s.air_id == SYNTHETIC ? s.n_cols / 8 : s.air_id < COUNT ? DESC[s.air_id].n_aux : 1; }
 GL_HD uint32_t n_constraints(const Shape& s) {
-  return s.air_id == SYNTHETIC ? 2 * (s.n_cols / 8)
-         : s.air_id == KECCAK_F ? KECCAK_N_CONSTRAINTS
-         : s.air_id == KECCAK_SPONGE ? SPONGE_N_CONSTRAINTS
-         : s.air_id == BYTE_PACKING ? PACK_N_CONSTRAINTS
-         : s.air_id == MEMORY ? MEM_N_CONSTRAINTS
-         : s.air_id == LOGIC ? LOGIC_N_CONSTRAINTS
-         : s.air_id == PLONK ? PLONK_N_CONSTRAINTS
-                                     : 2;
+  return s.air_id == SYNTHETIC ? 2 * (s.n_cols / 8) : s.air_id < COUNT ? DESC[s.air_id].n_ctl_constraints : 2;
 }
-// the first aux column that is a running product (the columns before it are helpers); products run to the last column
-// (AIR 8 keeps its two running products, columns 0 and 10, in its own kernels: stark_kernels.hip)
-GL_HD uint32_t first_product(uint32_t air_id) { return air_id == KECCAK_F ? KECCAK_Z : air_id == MEMORY ? MEM_Z : 0; }
+GL_HD uint32_t first_product(uint32_t air_id) { return air_id < COUNT ? DESC[air_id].first_product : 0; }
 
 // sum_{j < n} beta^j col(j) by Horner from the top
 template <class T, class Col>
@@ -1712,28 +1794,6 @@ inline const Pair* pairs() {
   return P;
 }
 }  // namespace ctl
-
-struct Info {
-  uint32_t air_id;
-  const char* name;
-  uint32_t n_cols;       // 0: any width (multiple of 4 not required; groups of four columns are constrained)
-  uint32_t n_const_max;  // preprocessed constant columns the AIR can use
-  uint32_t degree;       // constraint degree (x deg_pow for the synthetic AIR); rate_bits must give 2^r >= degree - 1
-};
-inline const Info* info(uint32_t air_id) {
-  static const Info table[COUNT] = {
-      {SYNTHETIC, "synthetic", 0, 4096, 3},
-      {KECCAK_F, "keccak_f", keccak::N_COLS, 0, 3},
-      {LOGIC, "logic", logic::N_COLS, 0, 3},
-      {MEMORY, "memory", memory::N_COLS, 0, 3},
-      {ARITHMETIC, "arithmetic", arithmetic::N_COLS, 0, 2},
-      {BYTE_PACKING, "byte_packing", byte_packing::N_COLS, 0, 2},
-      {KECCAK_SPONGE, "keccak_sponge", keccak_sponge::N_COLS, 0, 2},
-      {ARITHMETIC_MUL, "arithmetic_mul", arithmetic_mul::N_COLS, 0, 3},
-      {PLONK, "plonk", plonk::N_COLS, plonk::N_CONST, 9},
-  };
-  return air_id < COUNT ? &table[air_id] : nullptr;
-}
 
 }  // namespace air
 }  // namespace bpg

@@ -39,15 +39,7 @@ __global__ void __launch_bounds__(256) air_check_kernel(CheckArgs a) {
     const uint32_t u0 = blockIdx.y * a.units_per_wg, u1 = min(u0 + a.units_per_wg, a.n_units);
 #pragma unroll 1
     for (uint32_t u = u0; u < u1; u++) {
-      if constexpr (AIR == bpg::air::KECCAK_F) bpg::air::keccak::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::LOGIC) bpg::air::logic::eval_unit<uint64_t>(u, a.T, ctl, row, out);
-      else if constexpr (AIR == bpg::air::MEMORY) bpg::air::memory::eval_unit<uint64_t>(row, out);
-      else if constexpr (AIR == bpg::air::ARITHMETIC) bpg::air::arithmetic::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::BYTE_PACKING) bpg::air::byte_packing::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::KECCAK_SPONGE) bpg::air::keccak_sponge::eval_unit<uint64_t>(u, a.T, ctl, row, out);
-      else if constexpr (AIR == bpg::air::ARITHMETIC_MUL) bpg::air::arithmetic_mul::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::PLONK) bpg::air::plonk::eval_chunk_unit<uint64_t>(u, a.T, ctl, row, out);
-      else bpg::air::synthetic::eval_unit<uint64_t>(shape, u, row, out);
+      bpg::air::eval_unit_of<AIR, uint64_t>(shape, u, a.T, ctl, row, out);
     }
     r0 = out.result(0);
     r1 = out.result(1);
@@ -161,17 +153,7 @@ int launch_air_check(const CheckArgs& a, hipStream_t st) {
   const dim3 g1(ceil_div(n, 256), a.wg_rows);
   if (air::prog::is_registered(a.air_id)) {
     if (int rc = launch_air_check_program(a, g1, st)) return rc;
-  } else switch (a.air_id) {
-    case air::KECCAK_F: air_check_kernel<air::KECCAK_F><<<g1, 256, 0, st>>>(a); break;
-    case air::LOGIC: air_check_kernel<air::LOGIC><<<g1, 256, 0, st>>>(a); break;
-    case air::MEMORY: air_check_kernel<air::MEMORY><<<g1, 256, 0, st>>>(a); break;
-    case air::ARITHMETIC: air_check_kernel<air::ARITHMETIC><<<g1, 256, 0, st>>>(a); break;
-    case air::BYTE_PACKING: air_check_kernel<air::BYTE_PACKING><<<g1, 256, 0, st>>>(a); break;
-    case air::KECCAK_SPONGE: air_check_kernel<air::KECCAK_SPONGE><<<g1, 256, 0, st>>>(a); break;
-    case air::ARITHMETIC_MUL: air_check_kernel<air::ARITHMETIC_MUL><<<g1, 256, 0, st>>>(a); break;
-    case air::PLONK: air_check_kernel<air::PLONK><<<g1, 256, 0, st>>>(a); break;
-    default: air_check_kernel<air::SYNTHETIC><<<g1, 256, 0, st>>>(a); break;
-  }
+  } else air::dispatch(a.air_id, [&](auto A) { air_check_kernel<A.value><<<g1, 256, 0, st>>>(a); });
   BPG_LAUNCH_CHECK();
   if (a.air_id == air::PLONK) {
     air_check_plonk_hash_kernel<<<ceil_div(n, 256), 256, 0, st>>>(a, a.wg_rows);
@@ -187,14 +169,10 @@ int launch_air_check(const CheckArgs& a, hipStream_t st) {
 int launch_lookup_terms(uint32_t air_id, const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta, uint64_t gamma,
                         uint64_t* out, hipStream_t st) {
   const unsigned g = ceil_div((uint64_t)1 << log_n, 256);
-  switch (air_id) {
-    case air::KECCAK_F: lookup_terms_kernel<air::KECCAK_F><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
-    case air::LOGIC: lookup_terms_kernel<air::LOGIC><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
-    case air::MEMORY: lookup_terms_kernel<air::MEMORY><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
-    case air::BYTE_PACKING: lookup_terms_kernel<air::BYTE_PACKING><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
-    case air::KECCAK_SPONGE: lookup_terms_kernel<air::KECCAK_SPONGE><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out); break;
-    default: return fail(BP_ERR_INVALID_INPUT, "no lookup is built for AIR %u", air_id);
-  }
+  if (air_id >= air::COUNT || !air::DESC[air_id].in_pair) return fail(BP_ERR_INVALID_INPUT, "no lookup is built for AIR %u", air_id);
+  air::dispatch(air_id, [&](auto A) {
+    if constexpr (air::DESC[A.value].in_pair) lookup_terms_kernel<A.value><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out);
+  });
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

@@ -909,18 +909,9 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the memory table's log");
       if ((r = launch_memory_inputs_from_byte_packing(d_trace[1], tcfg[1].log_n, d_in, (uint32_t)N, w.stream))) return r;
     }
-    switch (tcfg[t].air_id) {
-      case air::KECCAK_F: r = launch_keccak_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::LOGIC: r = launch_logic_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::MEMORY: r = launch_memory_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::ARITHMETIC: r = launch_arithmetic_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::ARITHMETIC_MUL: r = launch_arithmetic_mul_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::BYTE_PACKING: r = launch_byte_packing_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream); break;
-      case air::KECCAK_SPONGE:
-        r = launch_keccak_sponge_trace(d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream, sponge_row_limit);
-        break;
-      default: r = launch_synth_trace(d_trace[t], nullptr, tcfg[t].log_n, tcfg[t].n_cols, 0, 1, seed, w.stream); break;
-    }
+    r = tcfg[t].air_id == air::SYNTHETIC
+            ? launch_synth_trace(d_trace[t], nullptr, tcfg[t].log_n, tcfg[t].n_cols, 0, 1, seed, w.stream)
+            : launch_air_trace(tcfg[t].air_id, d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream, sponge_row_limit);
     if (r) return r;
     // the filter column of a looked table (air::ctl) is part of its TRACE: written here, committed with the trace, i.e.
     // before the lookup challenges are drawn.  The looking table's trace is there already (GEN_ORDER).

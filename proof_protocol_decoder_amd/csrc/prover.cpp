@@ -218,7 +218,7 @@ static uint32_t n_fri_layers(const StarkCfg& c) {  // FriReductionStrategy::Cons
 }
 std::atomic<int> g_k5_spread_all{0};  // measurement knob (bp_tune_k5_spread): the loaded-device spreading rule for the synthetic AIR too
 int check_cfg(const StarkCfg& c) {
-  const air::Info* ai = air::info(c.air_id);
+  const air::Desc* ai = air::info(c.air_id);
   const auto program = ai ? nullptr : air::prog::find(c.air_id);
   if (!ai && !program)
     return fail(BP_ERR_INVALID_INPUT, "unknown air_id %u (bp_air_count() AIRs are built in; a program gets its id from bp_air_register)", c.air_id);

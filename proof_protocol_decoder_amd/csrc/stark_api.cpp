@@ -142,15 +142,9 @@ int bp_stark_prove_air(uint32_t air_id, const bp_stark_cfg* cfg, uint64_t seed, 
     }
     uint64_t* d_trace = w.arena.alloc_words((size_t)c.n_cols * N);
     if (!d_trace) return fail(BP_ERR_DEVICE, "arena exhausted");
-    int r2 = c.air_id == air::KECCAK_F ? launch_keccak_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::LOGIC  ? launch_logic_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::MEMORY ? launch_memory_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::ARITHMETIC ? launch_arithmetic_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::BYTE_PACKING ? launch_byte_packing_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::KECCAK_SPONGE ? launch_keccak_sponge_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::ARITHMETIC_MUL ? launch_arithmetic_mul_trace(d_trace, nullptr, c.log_n, seed, w.stream)
-             : c.air_id == air::PLONK ? BP_OK
-                                       : launch_synth_trace(d_trace, d_consts, c.log_n, c.n_cols, c.n_const, c.deg_pow, seed, w.stream);
+    int r2 = c.air_id == air::PLONK ? BP_OK  // (its witness needs the public inputs: below)
+             : c.air_id == air::SYNTHETIC ? launch_synth_trace(d_trace, d_consts, c.log_n, c.n_cols, c.n_const, c.deg_pow, seed, w.stream)
+                                          : launch_air_trace(c.air_id, d_trace, nullptr, c.log_n, seed, w.stream);
     Ctl ctl;
     if (c.air_id == air::PLONK) {  // the public-input list of a lone table proof follows from the seed (lone_public_input_list)
       uint64_t pi[LONE_PI_LEN];
@@ -320,7 +314,7 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
     out->n_families = n;
     return BP_OK;
   }
-  const air::Info* ai = air::info(air_id);
+  const air::Desc* ai = air::info(air_id);
   if (!ai || !out) return fail(BP_ERR_INVALID_INPUT, "bp_air_describe: unknown air_id %u or null output", air_id);
   std::memset(out, 0, sizeof(*out));
   out->air_id = air_id;
@@ -340,116 +334,54 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
   auto fam = [&](uint32_t first, uint32_t count, uint32_t kind, uint32_t degree) {
     if (n < 24) out->families[n++] = bp_air_family{first, count, kind, degree};
   };
-  if (air_id == air::KECCAK_F) {
-    namespace kk = air::keccak;
-    fam(kk::F0, 24, 2, 1); fam(kk::F1, 24, 1, 1); fam(kk::F2, 1984, 0, 2); fam(kk::F3, 320, 0, 3); fam(kk::F4, 320, 0, 3);
-    fam(kk::F5, 50, 0, 3); fam(kk::F6, 50, 0, 3); fam(kk::F7, 2, 0, 1); fam(kk::F8, 2, 0, 2); fam(kk::F9, 50, 1, 2);
-  } else if (air_id == air::LOGIC) {
-    namespace lg = air::logic;
-    fam(lg::L0, 3, 0, 2); fam(lg::L1, 1, 0, 2); fam(lg::L2, 512, 0, 2); fam(lg::L3, 8, 0, 3);
-  } else if (air_id == air::MEMORY) {
-    namespace mm = air::memory;
-    fam(mm::M0, 1, 0, 2); fam(mm::M1, 1, 0, 2); fam(mm::M2, 32, 0, 2); fam(mm::M3, 1, 1, 2); fam(mm::M4, 1, 1, 2);
-    fam(mm::M5, 8, 1, 3); fam(mm::M6, 8, 1, 3); fam(mm::M7, 8, 2, 2);
-  } else if (air_id == air::ARITHMETIC) {
-    namespace ar = air::arithmetic;
-    fam(ar::A0, 4, 0, 2); fam(ar::A1, 1, 0, 2); fam(ar::A2, 256, 0, 2); fam(ar::A3, 16, 0, 2); fam(ar::A4, 16, 0, 2);
-    fam(ar::A5, 1, 0, 2);
-  } else if (air_id == air::BYTE_PACKING) {
-    namespace bk = air::byte_packing;
-    fam(bk::P0, 1, 0, 2); fam(bk::P1, 32, 0, 2); fam(bk::P2, 1, 0, 2); fam(bk::P3, 256, 0, 2); fam(bk::P4, 32, 0, 2);
-    fam(bk::P5, 8, 0, 2);
-  } else if (air_id == air::KECCAK_SPONGE) {
-    namespace sp = air::keccak_sponge;
-    fam(sp::K0, 2, 0, 2); fam(sp::K1, 1, 0, 2); fam(sp::K2, 136, 0, 2); fam(sp::K3, 1, 0, 1); fam(sp::K4, 1088, 0, 2);
-    fam(sp::K5, 1088, 0, 2); fam(sp::K6, 136, 0, 2); fam(sp::K7, 34, 0, 2); fam(sp::K8, 50, 1, 2); fam(sp::K9, 50, 2, 1);
-    fam(sp::K10, 1, 1, 2);
-  } else if (air_id == air::PLONK) {
-    namespace pk = air::plonk;
-    fam(pk::G0, 20, 0, 4); fam(pk::G1, 44, 0, 3); fam(pk::G2, 22, 0, 2); fam(pk::G3, 4, 2, 1); fam(pk::G4, 118, 0, 8); fam(pk::G5, 5, 0, 3);
-  } else if (air_id == air::ARITHMETIC_MUL) {
-    namespace am = air::arithmetic_mul;
-    fam(am::U0, 1, 0, 2); fam(am::U1, 256, 0, 2); fam(am::U2, 256, 0, 2); fam(am::U3, 672, 0, 2); fam(am::U4, 32, 0, 3);
-    fam(am::U5, 1, 0, 1);
-  } else {
-    // interleaved per group of four columns: 3g all rows, 3g + 1 transition, 3g + 2 first row
-    fam(0, C / 4, 0, 2); fam(1, C / 4, 1, 3 * dp); fam(2, C / 4, 2, 1);
-  }
-  // the table's lookups (air::ctl), in list order after the AIR's own constraints
+  // the AIR's own constraints, then the table's lookups (air::ctl) in list order after them
   const uint32_t b = out->n_air_constraints;
   if (air_id == air::SYNTHETIC) {
+    // interleaved per group of four columns: 3g all rows, 3g + 1 transition, 3g + 2 first row
+    fam(0, C / 4, 0, 2); fam(1, C / 4, 1, 3 * dp); fam(2, C / 4, 2, 1);
     fam(b, C / 8, 1, 2); fam(b + 1, C / 8, 3, 1);  // running products, interleaved 2k (transition), 2k + 1 (last row)
-  } else if (air_id == air::PLONK) {  // the copy constraints: per challenge set ten chunk relations and Z(first) = 1
-    for (uint32_t c = 0; c < 2; c++) { fam(b + 11 * c, 10, 0, 9); fam(b + 11 * c + 10, 1, 2, 1); }
   } else {
-    uint32_t i = b;
-    if (air_id == air::KECCAK_F) {
-      fam(i, 2, 0, 2); i += 2;           // the filter g: a bit, set on last-round rows only
-      for (int c = 0; c < 2; c++) {      // h_c: the compressed input, fixed on first-round rows, carried along
-        fam(i, 1, 0, 2); fam(i + 1, 1, 1, 2); i += 2;
-      }
-    }
-    if (air_id == air::MEMORY || air_id == air::LOGIC) { fam(i, 1, 0, 2); i += 1; }  // the filter g of the looked table: a bit
-    const uint32_t n_products = out->n_aux - air::ctl::first_product(air_id);
-    if (n_products > 4) {  // (the sponge table's twelve) interleaved like the synthetic tables': 2k transition, 2k + 1 last row
-      fam(i, n_products, 1, 3); fam(i + 1, n_products, 3, 2);
-    } else {
-      for (uint32_t k = 0; k < n_products; k++) {  // filtered running products
-        fam(i, 1, 1, 3); fam(i + 1, 1, 3, 2); i += 2;
-      }
-    }
+    for (const air::Family& f : ai->families) if (f.count) fam(f.first, f.count, f.kind, f.degree);
+    for (const air::Family& f : ai->ctl_families) if (f.count) fam(b + f.first, f.count, f.kind, f.degree);
   }
   out->n_families = n;
   return BP_OK;
 }
 BPG_ABI_CATCH("bp_air_describe")
 
+// the seven bp_<table>_trace entries: one body, the table's name in the messages
+static int table_trace(const char* entry, uint32_t air_id, const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out,
+                       void* stream) {
+  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "%s: null output", entry);
+  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "%s: log_n out of range", entry);
+  return launch_air_trace(air_id, d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+}
 int bp_keccak_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_keccak_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_keccak_trace: log_n out of range");
-  return launch_keccak_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_keccak_trace", air::KECCAK_F, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_keccak_trace")
-
 int bp_logic_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_logic_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_logic_trace: log_n out of range");
-  return launch_logic_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_logic_trace", air::LOGIC, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_logic_trace")
-
 int bp_memory_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_memory_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_memory_trace: log_n out of range");
-  return launch_memory_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_memory_trace", air::MEMORY, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_memory_trace")
-
 int bp_arithmetic_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_trace: log_n out of range");
-  return launch_arithmetic_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_arithmetic_trace", air::ARITHMETIC, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_arithmetic_trace")
-
 int bp_byte_packing_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_byte_packing_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_byte_packing_trace: log_n out of range");
-  return launch_byte_packing_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_byte_packing_trace", air::BYTE_PACKING, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_byte_packing_trace")
-
 int bp_keccak_sponge_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_keccak_sponge_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_keccak_sponge_trace: log_n out of range");
-  return launch_keccak_sponge_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_keccak_sponge_trace", air::KECCAK_SPONGE, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_keccak_sponge_trace")
-
 int bp_arithmetic_mul_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_trace_out) return fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mul_trace: null output");
-  if (log_n < 4 || log_n > 26) return fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mul_trace: log_n out of range");
-  return launch_arithmetic_mul_trace(d_trace_out, d_inputs, log_n, seed, as_stream(stream));
+  return table_trace("bp_arithmetic_mul_trace", air::ARITHMETIC_MUL, d_inputs, seed, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_arithmetic_mul_trace")
 

@@ -813,15 +813,7 @@ quotient_air_kernel(bpg::BatchOf<bpg::QuotArgs> batch) {
 #pragma unroll 1
   for (uint32_t u = u0; u < u1; u++) {
     if (u < q.n_air_units) {
-      if constexpr (AIR == bpg::air::KECCAK_F) bpg::air::keccak::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::LOGIC) bpg::air::logic::eval_unit<uint64_t>(u, q.n_air_constraints, q.ctl.v, row, out);
-      else if constexpr (AIR == bpg::air::MEMORY) bpg::air::memory::eval_unit<uint64_t>(row, out);
-      else if constexpr (AIR == bpg::air::ARITHMETIC) bpg::air::arithmetic::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::BYTE_PACKING) bpg::air::byte_packing::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::KECCAK_SPONGE) bpg::air::keccak_sponge::eval_unit<uint64_t>(u, q.n_air_constraints, q.ctl.v, row, out);
-      else if constexpr (AIR == bpg::air::ARITHMETIC_MUL) bpg::air::arithmetic_mul::eval_unit<uint64_t>(u, row, out);
-      else if constexpr (AIR == bpg::air::PLONK) bpg::air::plonk::eval_chunk_unit<uint64_t>(u, q.n_air_constraints, q.ctl.v, row, out);  // (unit 10: quotient_plonk_hash_kernel)
-      else bpg::air::synthetic::eval_unit<uint64_t>(shape, u, row, out);
+      bpg::air::eval_unit_of<AIR, uint64_t>(shape, u, q.n_air_constraints, q.ctl.v, row, out);  // (AIR 8: units 0..9; unit 10 is quotient_plonk_hash_kernel)
     } else {
       const uint32_t k0 = (u - q.n_air_units) * q.aux_per_unit, k1 = min(k0 + q.aux_per_unit, q.n_aux);
       const bpg::air::Shape cs{AIR, q.n_cols, q.n_const, q.deg_pow};  // AIR as a constant: the other tables' lookups fold away
@@ -1410,37 +1402,19 @@ int launch_synth_trace(const SynthTraceArgs* a, uint32_t batch, uint32_t log_n, 
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
-int launch_keccak_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  dim3 grid(ceil_div((uint64_t)1 << log_n, 256), 6);
-  keccak_trace_kernel<<<grid, 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_logic_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  dim3 grid(ceil_div((uint64_t)1 << log_n, 256), 2);
-  logic_trace_kernel<<<grid, 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_memory_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  memory_trace_kernel<<<ceil_div((uint64_t)1 << log_n, 256), 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_arithmetic_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  arithmetic_trace_kernel<<<ceil_div((uint64_t)1 << log_n, 256), 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_byte_packing_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  byte_packing_trace_kernel<<<ceil_div((uint64_t)1 << log_n, 256), 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_keccak_sponge_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st,
-                               uint32_t row_limit) {
-  dim3 grid(ceil_div((uint64_t)1 << log_n, 256), 3);
-  keccak_sponge_trace_kernel<<<grid, 256, 0, st>>>(d_trace, d_inputs, log_n, seed, row_limit);
+int launch_air_trace(uint32_t air_id, uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st,
+                     uint32_t sponge_row_limit) {
+  const unsigned gx = ceil_div((uint64_t)1 << log_n, 256);
+  switch (air_id) {  // the witness kernel of each table (grid.y: the kernel's own split of a row's columns)
+    case air::KECCAK_F: keccak_trace_kernel<<<dim3(gx, 6), 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    case air::LOGIC: logic_trace_kernel<<<dim3(gx, 2), 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    case air::MEMORY: memory_trace_kernel<<<gx, 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    case air::ARITHMETIC: arithmetic_trace_kernel<<<gx, 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    case air::BYTE_PACKING: byte_packing_trace_kernel<<<gx, 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    case air::KECCAK_SPONGE: keccak_sponge_trace_kernel<<<dim3(gx, 3), 256, 0, st>>>(d_trace, d_inputs, log_n, seed, sponge_row_limit); break;
+    case air::ARITHMETIC_MUL: arithmetic_mul_trace_kernel<<<gx, 256, 0, st>>>(d_trace, d_inputs, log_n, seed); break;
+    default: return fail(BP_ERR_INVALID_INPUT, "launch_air_trace: AIR %u has a witness entry of its own (launch_synth_trace, launch_plonk_trace) or none", air_id);
+  }
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1480,11 +1454,6 @@ int launch_lookup_filter(uint32_t air_id, uint64_t* d_trace, uint32_t log_n, con
   } else {
     return fail(BP_ERR_INVALID_INPUT, "launch_lookup_filter: AIR %u is not a looked table", air_id);
   }
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
-}
-int launch_arithmetic_mul_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st) {
-  arithmetic_mul_trace_kernel<<<ceil_div((uint64_t)1 << log_n, 256), 256, 0, st>>>(d_trace, d_inputs, log_n, seed);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1549,18 +1518,14 @@ int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_col
   const dim3 grid(n_aux - p0, 1, batch);
   // algorithmic bytes: every column a product reads, once, and the product column written (SURVEY.md section 8(d):
   // 24 n per column of a synthetic table)
-  const double reads = air_id == air::SYNTHETIC ? 2 : air_id == air::KECCAK_F ? 53 : air_id == air::KECCAK_SPONGE ? 102
-                       : air_id == air::BYTE_PACKING ? 43 : air_id == air::MEMORY ? 12 : air_id == air::LOGIC ? 524 : 0;
+  // A table no lookup is built for (its products read nothing: AIR 4, AIR 7, a registered program) keeps the constant
+  // product z = 1, and AIR 4's instantiation serves them all.
+  const uint32_t reads = air_id < air::COUNT ? air::DESC[air_id].aux_reads : 0;
   KernelTimer kt(PROF_AUX, st, 8.0 * (double)((uint64_t)1 << log_n) * (reads + 1) * (n_aux - p0) * batch, true);
-  switch (air_id) {
-    case air::SYNTHETIC: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::SYNTHETIC>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    case air::KECCAK_F: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::KECCAK_F>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    case air::KECCAK_SPONGE: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::KECCAK_SPONGE>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    case air::BYTE_PACKING: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::BYTE_PACKING>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    case air::MEMORY: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::MEMORY>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    case air::LOGIC: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::LOGIC>, grid, threads, 0, st, ab, log_n, n_cols); break;
-    default: BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ARITHMETIC>, grid, threads, 0, st, ab, log_n, n_cols); break;  // no lookup: z = 1
-  }
+  air::dispatch(reads ? air_id : air::ARITHMETIC, [&](auto A) {
+    if constexpr (air::DESC[A.value].aux_reads || A.value == air::ARITHMETIC)
+      BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<A.value>, grid, threads, 0, st, ab, log_n, n_cols);
+  });
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1583,16 +1548,7 @@ int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, 
   KernelTimer kt(PROF_K5 + (q.air_id < air::COUNT ? q.air_id : 0), st, 8.0 * (double)rows * ((double)q.n_cols + q.n_aux + q.n_const + 2) * batch, true);
   if (bpg::air::prog::is_registered(q.air_id)) {
     if (int rc = launch_quotient_program(qb, g1, kt, st)) return rc;
-  }
-  else if (q.air_id == bpg::air::KECCAK_F) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::KECCAK_F>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::LOGIC) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::LOGIC>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::MEMORY) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::MEMORY>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::ARITHMETIC) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::ARITHMETIC>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::BYTE_PACKING) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::BYTE_PACKING>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::KECCAK_SPONGE) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::KECCAK_SPONGE>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::ARITHMETIC_MUL) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::ARITHMETIC_MUL>, g1, 256, 0, st, qb);
-  else if (q.air_id == bpg::air::PLONK) BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::PLONK>, g1, 256, 0, st, qb);
-  else BPG_LAUNCH_TIMED(kt, quotient_air_kernel<bpg::air::SYNTHETIC>, g1, 256, 0, st, qb);
+  } else air::dispatch(q.air_id, [&](auto A) { BPG_LAUNCH_TIMED(kt, quotient_air_kernel<A.value>, g1, 256, 0, st, qb); });
   kt.stop();
   if (q.side_rows) {
     BPG_LAUNCH_CHECK();

@@ -168,19 +168,16 @@ inline int launch_synth_trace(uint64_t* d_trace, const uint64_t* d_consts, uint3
   const SynthTraceArgs a{d_trace, d_consts, seed};
   return launch_synth_trace(&a, 1, log_n, n_cols, n_const, deg_pow, st);
 }
-// AIR 1 witness: n rows x 2430 columns; d_inputs [ceil(n / 24)][25] lanes or null (then drawn from seed)
-int launch_keccak_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
-int launch_logic_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
-int launch_memory_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
-int launch_arithmetic_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
-int launch_byte_packing_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
-// row_limit: rows of a SEEDED table from this one on are padding rows (a table given by the caller is taken as it is)
-int launch_keccak_sponge_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st,
-                               uint32_t row_limit = ~0u);
+// The witness of AIR 1..7: n rows of the table's columns (air::info) from d_inputs -- the table's items, e.g. AIR 1:
+// [ceil(n / 24)][25] lanes -- or, d_inputs null, drawn from seed.  sponge_row_limit (AIR 6 only): rows of a SEEDED table
+// from this one on are padding rows (a table given by the caller is taken as it is).  AIR 0 and AIR 8 take other
+// arguments: launch_synth_trace, launch_plonk_trace.
+int launch_air_trace(uint32_t air_id, uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st,
+                     uint32_t sponge_row_limit = ~0u);
 // [n_perms][25] input lanes for a seeded Keccak-f table whose sponge table (trace on the device) is real
 int launch_keccak_inputs_from_sponge(const uint64_t* d_sponge_trace, uint32_t sponge_log_n, uint64_t* d_inputs, uint32_t n_perms,
                                      uint64_t seed, hipStream_t st);
-// the memory log ([n_mem][11], for launch_memory_trace) that goes with a byte-packing trace: two operations per packing row
+// the memory log ([n_mem][11], for AIR 3's launch_air_trace) that goes with a byte-packing trace: two operations per packing row
 // the logic table's operations when the sponge table is proven by its AIR too (keccak_sponge -> logic): five per covered sponge row,
 // then the caller's (d_given, may be null) or seeded ones
 int launch_logic_inputs_from_sponge(const uint64_t* d_sponge_trace, uint32_t sponge_log_n, uint32_t covered, const uint64_t* d_given,
@@ -193,7 +190,6 @@ int launch_memory_inputs_from_byte_packing(const uint64_t* d_pack_trace, uint32_
 // (its address and timestamp columns name the operations it looks up), flag_b unused.  flag_a null: nothing is exposed.
 int launch_lookup_filter(uint32_t air_id, uint64_t* d_trace, uint32_t log_n, const uint64_t* flag_a, const uint64_t* flag_b,
                          uint32_t n_flags, hipStream_t st);
-int launch_arithmetic_mul_trace(uint64_t* d_trace, const uint64_t* d_inputs, uint32_t log_n, uint64_t seed, hipStream_t st);
 int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_cols, uint32_t log_n, hipStream_t st);
 // AIR 8 (plonk): the constants (selectors, gate constants, sigmas of the fixed circuit) and the witness
 // lay: the public-input list the circuit hashes in its hash rows and the Merkle paths it walks (air::plonk::Layout)

@@ -267,22 +267,31 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
  *               the declared constraint degree; deg_pow of the table's bp_stark_cfg is 1 up to degree 3, else 3),
  *               n_constraints (1 .. 65536), n_families (1 .. 24), n_regs (1 .. 64), n_units (1 .. 256), n_code (1 .. 2^20)
  *   then        n_families x (first_index, count, kind, degree), bp_air_family's fields: the families cover the index
- *               range [0, n_constraints) in order, exactly once; the kind of a constraint is its family's
- *   then        n_units + 1 code offsets: unit u is code words [off[u], off[u + 1]); off[0] = 0, off[n_units] = n_code.
+ *               range [0, n_constraints) in order, exactly once (first_index = where the family before ends, count >= 1);
+ *               kind 0 .. 3, degree 1 .. the program's; the kind of a constraint is its family's
+ *   then        n_units + 1 code offsets: unit u is code words [off[u], off[u + 1]); off[0] = 0, off[n_units] = n_code,
+ *               off[u] < off[u + 1]: no unit is empty.
  *               Units are what the kernels spread over grid.y; registers do not live across units.
+ *   The program is exactly these 10 + 4 n_families + n_units + 1 + n_code words.
  *   then        n_code code words:  op | dst << 8 | a << 16 | b << 40  (8 / 8 / 24 / 24 bits)
  *                 0 loc dst, a = column      1 nxt dst, a = column (next row)      2 cst dst, a = constant column
  *                 3 pub dst, a = j           4 x dst (the evaluation point)        5 imm dst, the NEXT word = a constant < p
  *                 6 add dst, a, b            7 sub dst, a, b  (a - b)              8 mul dst, a, b     (a, b: registers)
  *                 9 emit: dst = the kind of constraint a's family, a = constraint index, b = register: adds the
  *                   register to constraint a.  An index may be emitted several times (partial sums add), in any order.
+ *               dst is a register below n_regs for every operation but emit; an operation above 9 is refused, and so
+ *               is an imm whose constant word is not inside its unit; a field an operation does not use (b of a load,
+ *               a and b of x and imm) is not looked at.
  * n_regs is bounded by where the device keeps the registers: LDS, 2 KiB a register per 256-lane workgroup, sized from
  * the program's n_regs (64 registers = 128 KiB of the CU's 160 always fit; fewer registers = more workgroups per CU).
  * bp_air_register refuses, with BP_ERR_INVALID_INPUT and a message "word <offset>: ...": bad magic or sizes, a register
  * read before its unit writes it, column / register / constraint indices out of range, a non-canonical immediate, a
  * constraint never emitted, families that do not tile the list, an emit whose kind is not its family's, and a DEGREE
  * violation: degrees are propagated (loc / nxt / cst / x = 1, pub / imm = 0, add / sub = max, mul = sum), every emit
- * must stay within its family's degree and every family within the program's.
+ * must stay within its family's degree and every family within the program's.  A FIRST-ROW or LAST-ROW family is held
+ * to less: degree <= 2 in a program of degree <= 3, <= 8 otherwise.  Those constraints are multiplied by L_0 / L_(n-1), of
+ * degree n - 1, so a family of degree d leaves a quotient of degree (d + 1)(n - 1) - n, and the 2^rate_bits n quotient
+ * coefficients (rate_bits 1 / 3) hold that only for d <= 2^rate_bits: above it an honest proof is rejected.
  *
  * The id: 0x80000000 | (the first four bytes of Keccak-256 of the program's bytes, little-endian) & 0x7fffffff -- the
  * same in every process, so header word 14 of a proof names the program to a verifier elsewhere.  Registering the same
@@ -303,7 +312,13 @@ int bp_air_program_digest(uint32_t air_id, uint8_t out[32]); /* Keccak-256 of th
  * column-major and coset-major with column stride n << rate_bits (d_aux_lde: bp_air_desc.n_aux columns; d_const_lde may
  * be NULL when n_const == 0).  ctl = beta0, gamma0, beta1, gamma1; alphas = the two constraint challenges.
  * d_scratch: bp_quotient_scratch_words(air_id, shape) words.  d_qvals_out: [2][n << rate_bits], coset-major:
- * position t*n + m = quotient value at 7 * w_{n 2^r}^(t + 2^r m), already divided by Z_H.
+ * position t*n + m = quotient value at x = 7 * w_{n 2^r}^(t + 2^r m), already divided by Z_H.  Row j of the output is
+ *   ( sum_i alphas[j]^(T - 1 - i) * sel_i(x) * c_i(x) ) / Z_H(x),   Z_H(x) = x^n - 1,
+ * over the T = n_air_constraints + n_ctl_constraints constraints of bp_air_describe's list in index order (what
+ * starky's consumer acc = acc * alpha + c leaves), c_i evaluated on the row at t*n + m with the NEXT row at
+ * t*n + ((m + 1) mod n) -- the same coset -- and sel_i by the kind of i's family: 1 (all rows), x - g^-1 (transition),
+ * L_0(x) = Z_H(x) / (n (x - 1)) (first row), L_(n-1)(x) = Z_H(x) / (n (g x - 1)) (last row), g = w_n.  The entry takes no
+ * public inputs: pub(j) reads zero here (bp_stark_prove_trace and the verifier pass a table's own).
  * One kernel serves every AIR; the random linear combination stays in registers, and a table tall enough to fill
  * the chip is evaluated in one pass without partial sums in HBM. */
 uint64_t bp_quotient_scratch_words(uint32_t air_id, const struct bp_stark_cfg* shape);

@@ -26,6 +26,13 @@ MAX_REGS = 64
 _LEAVES = (OP_LOC, OP_NXT, OP_CST, OP_PUB, OP_X, OP_IMM)
 
 
+def boundary_degree(degree):
+    """The degree a first-row or last-row family may have in a program of `degree`.  Those rows' selectors are Lagrange
+    polynomials of degree n - 1, so a family of degree d leaves a quotient of degree (d + 1)(n - 1) - n, and the
+    2^rate_bits n quotient coefficients (rate_bits 1 up to degree 3, else 3) hold that only for d <= 2^rate_bits."""
+    return 2 if degree <= 3 else 8
+
+
 class Expr:
     """One node of a builder's expression graph (make them with the builder's loc / nxt / cst / pub / x / const)."""
     __slots__ = ("b", "op", "a", "c", "degree", "n")
@@ -118,9 +125,17 @@ class Builder:
 
     def family(self, count, kind=ALL_ROWS, degree=2):
         """The next `count` constraint indices, of one kind and degree bound; returns the first of them."""
+        if self.degree is not None:
+            self._check_boundary(kind, degree, self.degree)
         first = self.n_constraints
         self.families.append((first, count, kind, degree))
         return first
+
+    def _check_boundary(self, kind, degree, program_degree):
+        """bp_air_register's rule for first-row and last-row families (boundary_degree)"""
+        if kind in (FIRST_ROW, LAST_ROW) and degree > boundary_degree(program_degree):
+            raise ValueError("a first-row or last-row family of degree %d: a program of degree %d takes them up to degree %d"
+                             % (degree, program_degree, boundary_degree(program_degree)))
 
     def unit(self):
         """Starts the next unit; the emits that follow belong to it.  Returns its number."""
@@ -266,6 +281,8 @@ class Builder:
         if n_regs > MAX_REGS:
             raise ValueError("the program needs %d registers, the library takes %d: split the unit" % (n_regs, MAX_REGS))
         degree = self.degree if self.degree is not None else max(f[3] for f in self.families)
+        for f in self.families:
+            self._check_boundary(f[2], f[3], degree)
         hdr = [MAGIC, self.n_cols, self.n_const, self.n_public, degree, self.n_constraints, len(self.families), n_regs,
                len(self.units), len(code)]
         fam = [w for f in self.families for w in f]

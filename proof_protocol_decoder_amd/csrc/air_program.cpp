@@ -63,6 +63,13 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
     if (q[2] > 3) REFUSE(fam0 + 4 * f + 2, "family %u: kind %llu (0 all rows, 1 transition, 2 first row, 3 last row)", f, (unsigned long long)q[2]);
     if (q[3] == 0 || q[3] > p->degree)
       REFUSE(fam0 + 4 * f + 3, "family %u: degree %llu is outside 1 .. the program's degree %u", f, (unsigned long long)q[3], p->degree);
+    // A first-row or last-row constraint is multiplied by a Lagrange polynomial of degree n - 1, not by a linear factor:
+    // a family of degree d leaves a quotient of degree (d + 1)(n - 1) - n, which the 2^rate_bits n quotient
+    // coefficients hold only for d <= 2^rate_bits (rate_bits 1 up to degree 3, else 3).  Above that an honest proof
+    // fails the constraint check at zeta, so the program is refused here.
+    if (q[2] >= 2 && q[3] > boundary_degree(p->degree))
+      REFUSE(fam0 + 4 * f + 3, "family %u: a %s family of degree %llu; a program of degree %u takes them up to degree %u (the row's "
+             "selector has degree n - 1)", f, q[2] == 2 ? "first-row" : "last-row", (unsigned long long)q[3], p->degree, boundary_degree(p->degree));
     p->families[f] = Family{(uint32_t)q[0], (uint32_t)q[1], (uint32_t)q[2], (uint32_t)q[3]};
     for (uint64_t i = 0; i < q[1]; i++) fam_of[next + i] = (uint8_t)f;
     next += q[1];

@@ -46,6 +46,8 @@ constexpr uint32_t MIN_COLS = 8, MAX_COLS = 65536, MAX_CONST = 4096, MAX_PUBLIC 
                    MAX_FAMILIES = 24, MAX_REGS = 64, MAX_UNITS = 256, MAX_CODE = 1u << 20;
 constexpr uint32_t OP_LOC = 0, OP_NXT = 1, OP_CST = 2, OP_PUB = 3, OP_X = 4, OP_IMM = 5, OP_ADD = 6, OP_SUB = 7, OP_MUL = 8,
                    OP_EMIT = 9, OP_COUNT = 10;
+// the degree a first-row or last-row family may have in a program of `degree`: 2^rate_bits of the table's configuration
+constexpr uint32_t boundary_degree(uint32_t degree) { return degree > 3 ? 8 : 2; }
 constexpr uint32_t REGISTERED_BIT = 0x80000000u;
 GL_HD bool is_registered(uint32_t air_id) { return (air_id & REGISTERED_BIT) != 0; }
 

@@ -9,8 +9,10 @@ import numpy as np
 import pytest
 
 import air_program_cases as cases
+import air_program_random as rnd
 from air_program_cases import P
-from proof_protocol_decoder_amd.air_program import ALL_ROWS, OP_EMIT, OP_IMM, OP_LOC, OP_MUL, TRANSITION, Builder
+from proof_protocol_decoder_amd.air_program import (ALL_ROWS, FIRST_ROW, LAST_ROW, OP_EMIT, OP_IMM, OP_LOC, OP_MUL, TRANSITION,
+                                                    Builder)
 from util import rand_field
 
 
@@ -172,7 +174,13 @@ def _unit_table(w):
     return OFF0 + 1
 
 
-RULES = [_bad_magic, _too_many_regs, _wrong_length, _read_before_write, _column_out_of_range, _register_out_of_range,
+def _boundary_family_degree(w):
+    w[4] = 3                                    # a degree-3 program whose family 1 is a first-row family of degree 3
+    w[FAM0 + 4 + 2], w[FAM0 + 4 + 3] = 2, 3
+    return FAM0 + 4 + 3
+
+
+RULES = [_boundary_family_degree, _bad_magic, _too_many_regs, _wrong_length, _read_before_write, _column_out_of_range, _register_out_of_range,
          _constraint_out_of_range, _non_canonical_immediate, _never_emitted, _families_do_not_tile, _families_end_short,
          _emit_degree, _family_degree, _emit_kind, _unit_table]
 
@@ -293,6 +301,256 @@ def test_host_interpreter_gives_the_values_of_python_integers(name):
     r = ops().check_air_trace_host(air, trace, consts=consts, pub=pub, max_rows=n, max_viol=len(want) + 8)
     assert r.n_violated_rows == n and r.rows == list(range(n)) and r.n_violations == len(want)
     assert reported(r) == want
+
+
+# ---------------------------------------------------------------------------------------------- 3b. random programs
+
+
+@pytest.mark.parametrize("name", rnd.CASES + rnd.PROBES)
+def test_a_random_program_is_what_its_case_says(name):
+    """the generator's own assertions (air_program_random.check_program and case): degree, units, registers, every
+    operation, kind, input and edge immediate, an index fed from two units"""
+    c = rnd.case(name)
+    assert c.n_constraints == c.b.n_constraints and c.b.n_cols == c.n_free + c.n_constraints
+
+
+@pytest.mark.parametrize("name", rnd.CASES)
+def test_host_checker_on_random_rows_of_a_random_program(name):
+    """32 random rows (nothing is satisfied): the host checker reports evaluate()'s values, tuple for tuple"""
+    c = rnd.case(name)
+    air = ops().air_register(c.words)
+    rng = np.random.default_rng([7, c.kw["seed"]])
+    n = 32
+    trace = rand_field(rng, (c.b.n_cols, n))
+    consts = rand_field(rng, (c.b.n_const, n))
+    pub = [int(v) for v in rand_field(rng, (4,), edge=False)]
+    want = expected_violations(c.b, trace, consts, pub)
+    assert len(want) > c.n_constraints                       # (first-row and last-row families count once)
+    r = ops().check_air_trace_host(air, trace, consts=consts, pub=pub, max_rows=n, max_viol=len(want) + 8)
+    assert r.n_violated_rows == n and r.rows == list(range(n)) and r.n_violations == len(want)
+    assert reported(r) == want
+
+
+@pytest.mark.parametrize("log_n", [5, 8])
+@pytest.mark.parametrize("name", rnd.CASES)
+def test_host_checker_accepts_the_constructed_witness(name, log_n):
+    """the witness is valid although every slack cell is wrong where its constraint's kind is switched off: a selector
+    that masked nothing would report those rows"""
+    c = rnd.case(name)
+    air = ops().air_register(c.words)
+    trace, consts, pub = rnd.witness(name, log_n)
+    r = ops().check_air_trace_host(air, trace, consts=consts, pub=pub)
+    assert r.ok and r.rows == [] and r.violations == [] and r.n_violations == 0, r
+
+
+@pytest.mark.parametrize("name", rnd.CASES)
+def test_a_corrupted_cell_of_a_random_program_is_reported_as_python_computes_it(name):
+    """one slack cell per kind on a row where the kind is on, and one free cell that a nxt reads (the violation lands
+    on the row before as well): (row, constraint, family, kind, value) are evaluate()'s"""
+    c = rnd.case(name)
+    air = ops().air_register(c.words)
+    clean, consts, pub = rnd.witness(name, 5)
+    n = clean.shape[1]
+    rng = np.random.default_rng([11, c.kw["seed"]])
+    bump = lambda t, col, row: (int(t[col, row]) + 1 + int(rng.integers(0, 1 << 40))) % P
+    for kind in rnd.KINDS:                                   # the slack cell's own constraint, on its own row, only
+        row, col = rnd.active_cell(c, kind, n, rng)
+        t = clean.copy()
+        t[col, row] = bump(t, col, row)
+        want = expected_violations(c.b, t, consts, pub)
+        assert [(v[0], v[1], v[3]) for v in want] == [(row, col - c.n_free, kind)], want
+        _same_report(air, t, consts, pub, want)
+    for row in (9, 0):                                       # a free cell some nxt reads: row 0's readers sit on row n - 1
+        for col in range(c.n_free):
+            t = clean.copy()
+            t[col, row] = bump(t, col, row)
+            want = expected_violations(c.b, t, consts, pub)
+            if (row - 1) % n in {v[0] for v in want}:
+                break
+        else:
+            raise AssertionError("no free column of row %d is read as a next row" % row)
+        _same_report(air, t, consts, pub, want)
+
+
+def _same_report(air, t, consts, pub, want):
+    n = t.shape[1]
+    r = ops().check_air_trace_host(air, t, consts=consts, pub=pub, max_rows=n, max_viol=len(want) + 8)
+    assert reported(r) == want and r.n_violations == len(want)
+    assert r.rows == sorted({v[0] for v in want}) and r.n_violated_rows == len(r.rows)
+
+
+@pytest.mark.parametrize("name", rnd.PROBES)
+def test_a_first_row_or_last_row_family_above_its_degree_cap_is_refused(name):
+    """A program of degree 3 whose first-row and last-row families are cubic, and one of degree 9 with families of degree
+    9.  The validator used to register both.  The selector of such a row is a Lagrange polynomial of degree n - 1: a
+    family of degree d leaves a quotient of degree (d + 1)(n - 1) - n, and the 2^rate_bits n quotient coefficients hold
+    that only for d <= 2^rate_bits (the test below computes 92 against 64 and 278 against 256 at 2^5 rows), so an honest
+    proof cannot pass the constraint check at zeta; with those families at degree 2 / 8 the generator's programs prove
+    and verify (tests/test_gpu_air_program.py).  So the validator refuses the program and names the family's degree
+    word, and the builder raises on the same condition."""
+    from proof_protocol_decoder_amd._lib import BpgError
+    c = rnd.case(name)
+    above = [(k, f) for k, f in enumerate(c.b.families) if f[2] >= 2]
+    assert above and all(f[3] == c.degree > rnd.boundary_degree_cap(c.degree) for _, f in above)
+    with pytest.raises(BpgError) as e:
+        ops().air_register(c.words)
+    assert e.value.code == -2 and re.search(r"word %d: family %d: a (first|last)-row family of degree %d" % (
+        10 + 4 * above[0][0] + 3, above[0][0], c.degree), e.value.message), e.value.message
+    w = c.words.copy()                                       # at the cap the same words register
+    for k, _ in above:
+        w[10 + 4 * k + 3] = rnd.boundary_degree_cap(c.degree)
+    with pytest.raises(BpgError, match="degree violation"):  # (the emits are still cubic)
+        ops().air_register(w)
+    for kind in (FIRST_ROW, LAST_ROW):
+        with pytest.raises(ValueError, match="first-row or last-row"):
+            Builder(8, degree=c.degree).family(1, kind, c.degree)
+        assert Builder(8, degree=c.degree).family(1, kind, rnd.boundary_degree_cap(c.degree)) == 0
+    late = Builder(8)                                        # no declared degree: the families' maximum, known at assemble()
+    late.emit(late.family(1, FIRST_ROW, 3), late.loc(0) * late.loc(1) * late.loc(2))
+    with pytest.raises(ValueError, match="first-row or last-row"):
+        late.assemble()
+
+
+@pytest.mark.parametrize("above,at_cap", [("first-row-deg3", "deg3-u5"), ("first-row-deg9", "deg9-u5")])
+def test_the_honest_quotient_of_a_boundary_family_above_its_cap_does_not_fit_the_proof(above, at_cap):
+    """why the rule: over Python integers at 2^5 rows, the quotient of a valid witness has degree (d + 1)(n - 1) - n for
+    first-row and last-row families of degree d -- past the n << rate_bits coefficients a proof holds when d is the
+    program's degree, within them at the cap"""
+    n = 32
+    for name, fits in ((above, False), (at_cap, True)):
+        c = rnd.case(name)
+        d = max(f[3] for f in c.b.families if f[2] >= 2)
+        assert d == (rnd.boundary_degree_cap(c.degree) if fits else c.degree)
+        degree = rnd.honest_quotient_degree(name)
+        assert degree == (d + 1) * (n - 1) - n and (degree < n << c.rate_bits) == fits, (name, degree)
+
+
+# ---------------------------------------------------------------------------------------------- 3c. the validator, restated
+
+MAGIC = int.from_bytes(b"BPGAIRP1", "little")
+
+
+def restated_accepts(words):
+    """include/bpg.h's "Run-time AIRs" comment as code, written from that text (not from csrc/air_program.cpp): True
+    where the comment says bp_air_register takes the words"""
+    w = [int(v) for v in words]
+    if len(w) < 10 or w[0] != MAGIC:
+        return False
+    limits = [(8, 65536), (0, 4096), (0, 4), (1, 9), (1, 65536), (1, 24), (1, 64), (1, 256), (1, 1 << 20)]
+    if any(not lo <= v <= hi for v, (lo, hi) in zip(w[1:10], limits)):
+        return False
+    n_cols, n_const, n_public, degree, n_constraints, n_families, n_regs, n_units, n_code = w[1:10]
+    off0 = 10 + 4 * n_families
+    code0 = off0 + n_units + 1
+    if len(w) != code0 + n_code:
+        return False
+    family_of, covered = [], 0
+    for f in range(n_families):
+        first, count, kind, deg = w[10 + 4 * f:14 + 4 * f]
+        if first != covered or count < 1 or covered + count > n_constraints:        # in order, exactly once
+            return False
+        if kind > 3 or not 1 <= deg <= degree:
+            return False
+        if kind >= 2 and deg > (2 if degree <= 3 else 8):                            # first row, last row
+            return False
+        family_of += [(kind, deg)] * count
+        covered += count
+    if covered != n_constraints:
+        return False
+    off = w[off0:code0]
+    if off[0] != 0 or off[n_units] != n_code or any(off[u + 1] <= off[u] for u in range(n_units)):
+        return False
+    emitted = set()
+    for u in range(n_units):
+        deg_of = {}                                                                  # registers do not live across units
+        pc, end = code0 + off[u], code0 + off[u + 1]
+        while pc < end:
+            op, dst, a, b = w[pc] & 0xFF, (w[pc] >> 8) & 0xFF, (w[pc] >> 16) & 0xFFFFFF, w[pc] >> 40
+            pc += 1
+            if op > 9:
+                return False
+            if op == 9:
+                if a >= n_constraints or b not in deg_of or dst != family_of[a][0] or deg_of[b] > family_of[a][1]:
+                    return False
+                emitted.add(a)
+                continue
+            if dst >= n_regs:
+                return False
+            if op in (0, 1):
+                ok, d = a < n_cols, 1
+            elif op == 2:
+                ok, d = a < n_const, 1
+            elif op == 3:
+                ok, d = a < n_public, 0
+            elif op == 4:
+                ok, d = True, 1
+            elif op == 5:
+                ok, d = pc < end and w[pc] < P, 0
+                pc += 1
+            else:
+                ok = a in deg_of and b in deg_of                                     # (a register >= n_regs is never written)
+                d = ok and (deg_of[a] + deg_of[b] if op == 8 else max(deg_of[a], deg_of[b]))
+            if not ok:
+                return False
+            deg_of[dst] = d
+    return len(emitted) == n_constraints
+
+
+def mutants(words, rng, count):
+    """`count` single-word mutations of a program: (offset, value), the value another than the word's"""
+    h = rnd.header(words)
+    off0 = 10 + 4 * h["n_families"]
+    code0 = off0 + h["n_units"] + 1
+    regions = [(0, 10), (10, off0), (off0, code0), (code0, len(words))]
+    edges = [0, 1, P - 1, P, P + 1, (1 << 32) - 1, 1 << 32, (1 << 64) - 1, 1 << 63]
+    out = []
+    while len(out) < count:
+        lo, hi = regions[int(rng.choice(4, p=[0.1, 0.15, 0.05, 0.7]))]
+        at = int(rng.integers(lo, hi))
+        old = int(words[at])
+        how = int(rng.integers(0, 8))
+        if how == 0:
+            new = int(rng.integers(0, 70))
+        elif how == 1:
+            new = edges[int(rng.integers(0, len(edges)))]
+        elif how == 2:
+            new = int(words[int(rng.integers(0, len(words)))])
+        elif how == 3:                                       # a word of the same region: a family field, another instruction
+            new = int(words[int(rng.integers(lo, hi))])
+        elif how == 4:                                       # a small step: the next column, register, count
+            new = (old + int(rng.choice([-1, 1])) * (1 << int(rng.choice([0, 8, 16, 40])))) % (1 << 64)
+        else:
+            new = old ^ (1 << int(rng.integers(0, 64)))
+        if new != old:
+            out.append((at, new))
+    return out
+
+
+def test_validator_accepts_exactly_what_the_header_comment_says():
+    """2100 seeded single-word mutations of three random programs (header, family, offset and code words; small
+    integers, the field's edges, bit flips, other words of the program): bp_air_register takes exactly the mutants the
+    restatement of include/bpg.h takes.  At least a quarter are taken and a quarter refused, by the restatement alone."""
+    from proof_protocol_decoder_amd._lib import BpgError
+    o = ops()
+    taken = refused = 0
+    for name in ("deg3-u5", "inputs", "regs-mid"):
+        words = rnd.case(name).words
+        assert restated_accepts(words)
+        rng = np.random.default_rng([13, rnd.case(name).kw["seed"]])
+        for at, new in mutants(words, rng, 700):
+            w = words.copy()
+            w[at] = np.uint64(new)
+            want = restated_accepts(w)
+            taken, refused = taken + want, refused + (not want)
+            try:
+                air = o.air_register(w)
+            except BpgError as e:
+                assert e.code == -2 and re.search(r"word \d+: ", e.message), e.message
+                assert not want, "%s: word %d = 0x%x is refused (%s); include/bpg.h takes it" % (name, at, new, e.message)
+            else:
+                o.air_unregister(air)
+                assert want, "%s: word %d = 0x%x is registered; include/bpg.h refuses it" % (name, at, new)
+    assert taken + refused == 2100 and 4 * taken >= 2100 and 4 * refused >= 2100, (taken, refused)
 
 
 # ---------------------------------------------------------------------------------------------- 4. against the built-ins

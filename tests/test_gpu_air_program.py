@@ -1,12 +1,15 @@
 """Run-time AIRs on the GPU (csrc/air_program.hip: the interpreter's K5 and trace-checker kernels; bp_stark_prove_trace):
 K5 of a registered transcription against the built-in kernel word for word, bp_stark_prove_trace against
 bp_stark_prove_air byte for byte, whole proofs under a registered id, AIR 3's transcription through the device checker
-and the verifier, and a Fibonacci-style table that is nobody's built-in.  Everything is exact.  CPU side:
-tests/test_air_program.py."""
+and the verifier, a Fibonacci-style table that is nobody's built-in, and seeded random programs (tests/air_program_random.py: degrees 1 to
+9, up to 64 registers, 40 units, every operation and kind) whose only reference is the builder's evaluate() over Python
+integers: the device checker, bp_quotient_eval against a fold written here, whole proofs.  Everything is exact.  CPU
+side: tests/test_air_program.py."""
 import numpy as np
 import pytest
 
 import air_program_cases as cases
+import air_program_random as rnd
 from air_program_cases import P
 from util import to_dev, to_host
 
@@ -240,3 +243,176 @@ def test_a_fibonacci_table_with_constants_and_public_inputs(bpg, log_n, nq, pb):
         assert not r.ok and r.rows == want.rows and {v.kind for v in r.violations} == kinds
         assert [(v.row, v.constraint, v.value) for v in r.violations] == [(v.row, v.constraint, v.value) for v in want.violations]
         assert cases.verify(fib, cfg, bpg.ops.stark_prove_trace(fib, cfg, bad, consts=consts, pub=pub), cap, pub) == -5
+
+
+# ---------------------------------------------------------------------------------------------- 12. random programs
+
+HEIGHTS = [(name, log_n) for name in rnd.CASES for log_n in (5, 8, 12)] + [(name, 15) for name in rnd.CASES if rnd.case(name).tall]
+HEIGHT_IDS = ["%s@%d" % h for h in HEIGHTS]
+assert sorted(rnd.case(name).deg_pow for name, log_n in HEIGHTS if log_n == 15) == [1, 3]   # one tall case of each deg_pow
+
+
+def reported(r):
+    return [(v.row, v.constraint, v.family, v.kind, v.value) for v in r.violations]
+
+
+def device_witness(name, log_n):
+    trace, consts, pub = rnd.witness(name, log_n)
+    return trace, consts, pub, to_dev(trace.copy()), to_dev(consts.copy())      # (the cached arrays are read-only)
+
+
+@pytest.mark.parametrize("name,log_n", HEIGHTS, ids=HEIGHT_IDS)
+def test_device_checker_on_a_random_program(bpg, name, log_n):
+    """The constructed witness (wrong slack cells wherever a kind is switched off) is clean; with five random cells, a
+    first-row slack cell in row 0 and a last-row one in row n - 1 changed, the device reports what the host pass
+    reports, and its first 16 violations are evaluate()'s.  Spread over grid.y and in one pass."""
+    c = rnd.case(name)
+    reg = bpg.ops.air_register(c.words)
+    trace, consts, pub, t, cd = device_witness(name, log_n)
+    n = 1 << log_n
+    rng = np.random.default_rng([0x900, c.kw["seed"], log_n])
+    bad = trace.copy()
+    cells = [(int(rng.integers(0, n)), int(rng.integers(0, c.b.n_cols))) for _ in range(5)]
+    cells += [rnd.active_cell(c, rnd.FIRST_ROW, n, rng), rnd.active_cell(c, rnd.LAST_ROW, n, rng)]
+    for row, col in cells:
+        bad[col, row] = (int(bad[col, row]) + 1 + int(rng.integers(0, 3))) % P
+    host = bpg.ops.check_air_trace_host(reg, bad, consts=consts, pub=pub, max_rows=64, max_viol=4096)
+    key = lambda r: (r.n_violated_rows, r.rows, r.n_violations, reported(r))
+    assert host.n_violated_rows >= 2 and host.rows[0] == 0 and host.rows[-1] == n - 1
+    assert reported(host)[:16] == rnd.violations(c.b, bad, consts, pub, host.rows)[:16]
+    for loaded in (0, 1):
+        bpg.lib().bp_tune_assume_loaded(loaded)
+        try:
+            r = bpg.ops.check_air_trace(reg, t, consts=cd, pub=pub)
+            dev = bpg.ops.check_air_trace(reg, to_dev(bad), consts=cd, pub=pub, max_rows=64, max_viol=4096)
+        finally:
+            bpg.lib().bp_tune_assume_loaded(-1)
+        assert r.ok and r.rows == [] and r.violations == [], (loaded, r)
+        assert key(dev) == key(host), loaded
+
+
+def python_quotient(c, log_n, loc, nxt, cst, aux, aux_nxt, alphas, pos):
+    """Both quotient words at coset-major position pos = t n + m, over Python integers: the point
+    x = 7 w_{n 2^r}^(t + 2^r m); constraint i of kind k times its selector -- 1, x - g^-1, L_0(x) = Z_H(x) / (n (x - 1)),
+    L_{n-1}(x) = Z_H(x) / (n (g x - 1)), g = w_n -- weighed with alpha_j^(T - 1 - i), T = the program's constraints + the
+    two of the constant running product z (transition z - z', last row z - 1: AIRS.md section 3 with no filter, term = 1),
+    the sum divided by Z_H(x) = x^n - 1.  bp_quotient_eval takes no public inputs: pub(j) reads zero there."""
+    n, r = 1 << log_n, c.rate_bits
+    t, m = pos >> log_n, pos & (n - 1)
+    inv = lambda v: pow(v % P, P - 2, P)
+    x = 7 * pow(pow(7, (P - 1) >> (log_n + r), P), t + (m << r), P) % P
+    g = pow(7, (P - 1) >> log_n, P)
+    zh = (pow(x, n, P) - 1) % P
+    sel = [1, (x - inv(g)) % P, zh * inv(n * (x - 1)) % P, zh * inv(n * (g * x - 1)) % P]
+    vals = c.b.evaluate(loc, nxt, cst, (0, 0, 0, 0), x)
+    terms = [(i, f[2], vals[i]) for f in c.b.families for i in range(f[0], f[0] + f[1])]
+    T = c.n_constraints + 2
+    terms += [(T - 2, rnd.TRANSITION, (aux - aux_nxt) % P), (T - 1, rnd.LAST_ROW, (aux - 1) % P)]
+    return [sum(pow(a, T - 1 - i, P) * sel[kind] * v for i, kind, v in terms) * inv(zh) % P for a in alphas]
+
+
+@pytest.mark.parametrize("name,log_n", HEIGHTS, ids=HEIGHT_IDS)
+def test_quotient_eval_of_a_random_program_equals_the_fold_over_python_integers(bpg, name, log_n):
+    """K5 without the verifier: the LDE of the witness and the constants (ops.lde_batch, pinned to the oracle elsewhere),
+    an auxiliary LDE of all ones (the constant running product: its two constraints vanish identically), and both
+    quotient words recomputed by python_quotient at 48 positions: every coset, m in {0, 1, n - 2, n - 1} (the next row
+    wraps inside the coset) and random m.  On the coset a kind that is 'switched off' is not: the wrong slack cells of
+    the witness enter through the selectors, and the quotient of a valid witness is still a polynomial -- which is why
+    the values are compared with a fold and not with zero.  Spread and one-pass launches give the same words."""
+    import torch
+    c = rnd.case(name)
+    reg = bpg.ops.air_register(c.words)
+    trace, consts, pub, t, cd = device_witness(name, log_n)
+    n, r = 1 << log_n, c.rate_bits
+    rows = n << r
+    _, lde = bpg.ops.lde_batch(t, r)
+    _, clde = bpg.ops.lde_batch(cd, r)
+    aux = torch.ones((1, rows), dtype=torch.int64, device="cuda")
+    rng = np.random.default_rng([0x901, c.kw["seed"], log_n])
+    ctl = [int(v) for v in rng.integers(2, P, size=4, dtype=np.uint64)]
+    alphas = [int(v) for v in rng.integers(2, P, size=2, dtype=np.uint64)]
+    cfg = bpg.ops.stark_cfg(log_n, c.b.n_cols, n_const=c.b.n_const, deg_pow=c.deg_pow, rate_bits=r)
+    got = []
+    for loaded in (0, 1):
+        bpg.lib().bp_tune_assume_loaded(loaded)
+        try:
+            got.append(bpg.ops.quotient_eval(cfg, lde, aux, clde, ctl, alphas, air_id=reg))
+        finally:
+            bpg.lib().bp_tune_assume_loaded(-1)
+    assert got[0].shape == got[1].shape == (2, rows) and bool((got[0] == got[1]).all()), "spread != one-pass"
+    assert bool((got[0] != 0).any())
+    ms = [0, 1, n - 2, n - 1]
+    pos = [tt * n + m for tt in range(1 << r) for m in ms]
+    pos += [int(v) for v in rng.integers(0, rows, size=48 - len(pos))]
+    assert len(pos) == 48 and {p >> log_n for p in pos} == set(range(1 << r))
+    nxt = [(p >> log_n) * n + ((p & (n - 1)) + 1) % n for p in pos]
+    idx = torch.tensor(pos + nxt, dtype=torch.int64, device="cuda")
+    L, CL, Q = to_host(lde[:, idx].contiguous()), to_host(clde[:, idx].contiguous()), to_host(got[0][:, idx[:48]].contiguous())
+    for k, p in enumerate(pos):
+        want = python_quotient(c, log_n, L[:, k], L[:, 48 + k], CL[:, k], 1, 1, alphas, p)
+        assert [int(Q[0, k]), int(Q[1, k])] == want, (name, log_n, "position", p, "coset", p >> log_n, "m", p & (n - 1))
+
+
+PROOF_COST = {5: (6, 6), 8: (20, 10), 12: (84, 16), 15: (84, 16)}
+
+
+@pytest.mark.parametrize("name,log_n", HEIGHTS, ids=HEIGHT_IDS)
+def test_a_random_program_proves_and_verifies(bpg, name, log_n):
+    """bp_stark_prove_trace of the constructed witness verifies; a flipped bit, each public input the program reads
+    changed, a wrong constants commitment and a proof made from a witness with one ACTIVE slack cell changed are each
+    rejected, the last at the constraint check at zeta."""
+    c = rnd.case(name)
+    reg = bpg.ops.air_register(c.words)
+    trace, consts, pub, t, cd = device_witness(name, log_n)
+    n = 1 << log_n
+    nq, pb = PROOF_COST[log_n]
+    cfg = cases.cfg_for(reg, log_n, num_queries=nq, pow_bits=pb)
+    assert (cfg.n_cols, cfg.n_const, cfg.deg_pow, cfg.rate_bits) == (c.b.n_cols, c.b.n_const, c.deg_pow, c.rate_bits)
+    cap = constants_cap(bpg, cd, log_n, rate_bits=c.rate_bits)
+    rng = np.random.default_rng([0x902, c.kw["seed"], log_n])
+    for loaded in ((0, 1) if log_n <= 8 else ((rnd.CASES.index(name) + log_n) % 2,)):
+        bpg.lib().bp_tune_assume_loaded(loaded)
+        try:
+            proof = bpg.ops.stark_prove_trace(reg, cfg, t, consts=cd, pub=pub)
+        finally:
+            bpg.lib().bp_tune_assume_loaded(-1)
+        assert int(proof[14]) == reg
+        assert cases.verify(reg, cfg, proof, cap, pub) == 0, (loaded, bpg.lib().bp_last_error())
+    flipped = proof.copy()
+    flipped[proof.size // 2 + int(rng.integers(0, 8))] ^= np.uint64(1 << int(rng.integers(0, 32)))
+    assert cases.verify(reg, cfg, flipped, cap, pub) == -5
+    for j in range(c.b.n_public):
+        wrong = list(pub)
+        wrong[j] = (wrong[j] + 1) % P
+        assert cases.verify(reg, cfg, proof, cap, wrong) == -5, j
+    other = consts.copy()
+    other[c.b.n_const - 1, int(rng.integers(0, n))] ^= np.uint64(1)
+    assert cases.verify(reg, cfg, proof, constants_cap(bpg, to_dev(other), log_n, rate_bits=c.rate_bits), pub) == -5
+    kind = rnd.KINDS[int(rng.integers(0, 4))]
+    row, col = rnd.active_cell(c, kind, n, rng)
+    bad = trace.copy()
+    bad[col, row] = (int(bad[col, row]) + 1) % P
+    assert not bpg.ops.check_air_trace_host(reg, bad, consts=consts, pub=pub).ok
+    assert cases.verify(reg, cfg, bpg.ops.stark_prove_trace(reg, cfg, to_dev(bad), consts=cd, pub=pub), cap, pub) == -5, (kind, row, col)
+    assert b"constraint check at zeta" in bpg.lib().bp_last_error()
+
+
+@pytest.mark.parametrize("at_cap,above", [("deg3-u5", "first-row-deg3"), ("deg9-u5", "first-row-deg9")])
+def test_first_row_and_last_row_families_at_their_degree_cap_verify_and_above_it_are_refused(bpg, at_cap, above):
+    """The degree rule of first-row and last-row families (include/bpg.h, AIRS.md section 1).  The programs `above`
+    (degree 3 with cubic first-row and last-row families; degree 9 with families of degree 9) used to register; the
+    quotient of such a family has degree (d + 1)(n - 1) - n and does not fit the 2^rate_bits n coefficients of a proof
+    (tests/test_air_program.py computes it over Python integers: 92 against 64, 278 against 256 at 2^5 rows), so the
+    rule refuses them at registration.  Here: families AT the cap, degree 2 in a degree-3 program and 8 in a degree-9
+    one, prove and verify at 2^5 rows, where (d + 1)(n - 1) - n is closest to the bound relative to n."""
+    from proof_protocol_decoder_amd._lib import BpgError
+    with pytest.raises(BpgError, match="-row family of degree"):
+        bpg.ops.air_register(rnd.case(above).words)
+    c = rnd.case(at_cap)
+    cap = rnd.boundary_degree_cap(c.degree)
+    assert {f[2] for f in c.b.families if f[2] >= 2 and f[3] == cap} == {rnd.FIRST_ROW, rnd.LAST_ROW}
+    reg = bpg.ops.air_register(c.words)
+    trace, consts, pub, t, cd = device_witness(at_cap, 5)
+    cfg = cases.cfg_for(reg, 5, num_queries=6, pow_bits=6)
+    proof = bpg.ops.stark_prove_trace(reg, cfg, t, consts=cd, pub=pub)
+    assert cases.verify(reg, cfg, proof, constants_cap(bpg, cd, 5, rate_bits=c.rate_bits), pub) == 0

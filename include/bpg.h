@@ -110,6 +110,10 @@ int bp_debug_copy_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, void* s
  * (a, b) * (b, a^b); then the interleaved group forms the NTT butterflies use: a + canon(b), a - canon(b),
  * canon(a), canon(b). */
 int bp_debug_field_ops(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
+/* The multiplications by 2^(12k), k = 1..7, of the NTT's shift-only 16-point DFTs (gl::mul_pow2_n) on n words
+ * (any u64).  d_out: 21 planes of n canonical words, plane 3(k-1) + f: a * 2^(12k) by the groups of four (f = 0), the
+ * groups of three (f = 1) and the one-element form (f = 2). */
+int bp_debug_mul_pow2(const uint64_t* d_a, uint64_t* d_out, uint64_t n, void* stream);
 
 /* Tuning knob: the size (rows / nodes / candidates of one launch) from which the hashing kernels put 64 Poseidon
  * states on a wave.  Matrix-core form (default): four sets of 16 states per wave from this size up, two from half of

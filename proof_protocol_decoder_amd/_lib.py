@@ -76,6 +76,7 @@ def lib():
     L.bp_lde_batch.argtypes = [vp, u64, vp, u64, vp, u64, u32, u32, u32, i, vp]
     L.bp_poseidon_perm_batch.argtypes = [vp, u64, vp]
     L.bp_debug_field_ops.argtypes = [vp, vp, vp, u64, vp]
+    L.bp_debug_mul_pow2.argtypes = [vp, vp, u64, vp]
     L.bp_quotient_scratch_words.argtypes = [u32, C.POINTER(StarkCfg)]
     L.bp_quotient_scratch_words.restype = u64
     L.bp_quotient_eval.argtypes = [u32, C.POINTER(StarkCfg), vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, vp]

@@ -49,6 +49,11 @@ __device__ __forceinline__ uint64_t mad_eps_co(uint32_t a, uint64_t c, mask& co)
   asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(d), "=s"(co) : "v"(a), "v"(c));
   return d;
 }
+__device__ __forceinline__ uint64_t mul_eps(uint32_t a) {  // a*(2^32-1): never carries
+  uint64_t d;
+  asm("v_mad_u64_u32 %0, vcc, %1, -1, 0" : "=v"(d) : "v"(a) : "vcc");
+  return d;
+}
 __device__ __forceinline__ uint32_t add_co(uint32_t a, uint32_t b, mask& co) {
   uint32_t d;
   asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(d), "=s"(co) : "v"(a), "v"(b));
@@ -280,6 +285,146 @@ __device__ __forceinline__ void canon_n(uint64_t (&a)[N]) {
   for (int i = 0; i < N; i++) a[i] = cc::mk64(lo[i], hi[i]);
 }
 #endif
+// ---- multiplication by 2^S, 0 < S < 96: the twiddles of a 16-point DFT are such powers (root(4) = 2^12 up to
+// sign, 2^96 = -1), and a shift plus one or two folds costs 6 / 10 / 8 instructions where mul() costs 15 and a table
+// load.  Any u64 in, reduced u64 out, like mul().  With x * 2^s (0 < s < 32) = (l0, l1, l2) in 32-bit limbs:
+//   S = s:       (l0, l1) + l2*EPS                       one multiply-add, carry: + EPS
+//   S = 32 + s:  the above, then y * 2^32 = (0, y0) + y1*EPS   (y1*EPS as a fresh product, y0 added to its high word)
+//   S = 64 + s:  l0*EPS - (l1, l2)                       2^64 = EPS, 2^96 = -1, 2^128 = -2^32; borrow: - EPS
+// None of the +-EPS corrections can wrap again (the bounds are those of mul_n), so each is two instructions.
+GL_HD uint64_t mul_pow2_portable(uint64_t x, unsigned S) {
+  if (S < 64) return reduce128(x << S, S ? x >> (64 - S) : 0);
+  const unsigned s = S - 64;                 // x * 2^s = lo + hi*2^64 with hi < 2^31, times 2^64: lo*2^64 - hi*2^32
+  const uint64_t lo = x << s, hi = s ? x >> (64 - s) : 0;
+  return sub(reduce128(0, lo), hi << 32);
+}
+#if defined(__HIP__)
+__device__ __forceinline__ void shl96(uint64_t x, int s, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
+  const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
+  l0 = x0 << s;
+  l1 = (x1 << s) | (x0 >> (32 - s));
+  l2 = x1 >> (32 - s);
+}
+// one-element forms (every carry consumer carries its s_nop, as in mul()): for what is left over beside the groups
+__device__ __forceinline__ uint64_t mul_pow2_lo(uint64_t x, int s) {  // x * 2^s, 0 < s < 32
+  uint32_t l0, l1, l2;
+  shl96(x, s, l0, l1, l2);
+  cc::mask c3, b3, cx;
+  const uint64_t V = cc::mad_eps_co(l2, cc::mk64(l0, l1), c3);
+  const uint32_t t0 = cc::subb0_co((uint32_t)V, c3, b3);
+  const uint32_t t1 = cc::addc0_co((uint32_t)(V >> 32), c3 & ~b3, cx);
+  return cc::mk64(t0, t1);
+}
+__device__ __forceinline__ uint64_t mul_2p32(uint64_t y) {  // y * 2^32
+  cc::mask c3, b3, cx;
+  const uint64_t V = cc::mul_eps((uint32_t)(y >> 32));
+  const uint32_t h = cc::add_co((uint32_t)(V >> 32), (uint32_t)y, c3);
+  const uint32_t t0 = cc::subb0_co((uint32_t)V, c3, b3);
+  const uint32_t t1 = cc::addc0_co(h, c3 & ~b3, cx);
+  return cc::mk64(t0, t1);
+}
+__device__ __forceinline__ uint64_t mul_pow2_hi(uint64_t x, int s) {  // x * 2^(64 + s), 0 < s < 32
+  uint32_t l0, l1, l2;
+  shl96(x, s, l0, l1, l2);
+  cc::mask bw, bw2, b3, cx;
+  const uint64_t D = cc::mul_eps(l0);
+  const uint32_t t0 = cc::sub_co((uint32_t)D, l1, bw);
+  const uint32_t t1 = cc::subb_co((uint32_t)(D >> 32), l2, bw, bw2);
+  const uint32_t r0 = cc::addc0_co(t0, bw2, b3);
+  const uint32_t r1 = cc::subb0_co(t1, bw2 & ~b3, cx);
+  return cc::mk64(r0, r1);
+}
+// groups of N = 3 or 4, instruction-interleaved like mul_n (no s_nop).  The shifts may differ from element to element:
+// they are ordinary instructions, only the carry chains are shared.
+template <int N>
+__device__ __forceinline__ void mul_pow2_lo_n(const uint64_t (&a)[N], const int (&s)[N], uint64_t (&r)[N]) {
+  static_assert(N == 3 || N == 4, "groups of 3 or 4");
+  uint32_t l2[N], t0[N], t1[N];
+  uint64_t P[N];
+  cc::mask c3[N], b3[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    uint32_t l0, l1;
+    shl96(a[i], s[i], l0, l1, l2[i]);
+    P[i] = cc::mk64(l0, l1);
+  }
+  cc::mad_eps_co(P, c3, l2);     // V = (l0, l1) + l2*EPS mod 2^64, carry c3 (weight 2^64 = EPS)
+#pragma unroll
+  for (int i = 0; i < N; i++) { t0[i] = (uint32_t)P[i]; t1[i] = (uint32_t)(P[i] >> 32); }
+  cc::subb0_co(t0, b3, c3);      // + c3*EPS in two instructions (mul_n)
+#pragma unroll
+  for (int i = 0; i < N; i++) c3[i] &= ~b3[i];
+  cc::addc0_cv(t1, c3);
+#pragma unroll
+  for (int i = 0; i < N; i++) r[i] = cc::mk64(t0[i], t1[i]);
+}
+template <int N>
+__device__ __forceinline__ void mul_2p32_n(const uint64_t (&a)[N], uint64_t (&r)[N]) {
+  static_assert(N == 3 || N == 4, "groups of 3 or 4");
+  uint32_t y0[N], y1[N], t0[N], t1[N];
+  uint64_t V[N];
+  cc::mask c3[N], b3[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) { y0[i] = (uint32_t)a[i]; y1[i] = (uint32_t)(a[i] >> 32); }
+  cc::mul_eps_o(V, y1);          // y1*EPS <= 2^64 - 2^33 + 1
+#pragma unroll
+  for (int i = 0; i < N; i++) { t0[i] = (uint32_t)V[i]; t1[i] = (uint32_t)(V[i] >> 32); }
+  cc::add_co(t1, c3, y0);        // + y0*2^32 mod 2^64, carry c3
+  cc::subb0_co(t0, b3, c3);      // + c3*EPS
+#pragma unroll
+  for (int i = 0; i < N; i++) c3[i] &= ~b3[i];
+  cc::addc0_cv(t1, c3);
+#pragma unroll
+  for (int i = 0; i < N; i++) r[i] = cc::mk64(t0[i], t1[i]);
+}
+template <int N>
+__device__ __forceinline__ void mul_pow2_hi_n(const uint64_t (&a)[N], const int (&s)[N], uint64_t (&r)[N]) {
+  static_assert(N == 3 || N == 4, "groups of 3 or 4");
+  uint32_t l0[N], l1[N], l2[N], t0[N], t1[N];
+  uint64_t D[N];
+  cc::mask bw[N], bw2[N], b3[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) shl96(a[i], s[i], l0[i], l1[i], l2[i]);
+  cc::mul_eps_o(D, l0);          // l0*2^64
+#pragma unroll
+  for (int i = 0; i < N; i++) { t0[i] = (uint32_t)D[i]; t1[i] = (uint32_t)(D[i] >> 32); }
+  cc::sub_co(t0, bw, l1);        // - (l1, l2), borrow bw2
+  cc::subb_co(t1, bw2, l2, bw);
+  cc::addc0_co(t0, b3, bw2);     // - bw2*EPS (cannot borrow: then the difference is >= 2^64 - 2^63)
+#pragma unroll
+  for (int i = 0; i < N; i++) bw2[i] &= ~b3[i];
+  cc::subb0_cv(t1, bw2);
+#pragma unroll
+  for (int i = 0; i < N; i++) r[i] = cc::mk64(t0[i], t1[i]);
+}
+// x * 2^S for one compile-time S
+template <int S, int N>
+__device__ __forceinline__ void mul_pow2_n(const uint64_t (&a)[N], uint64_t (&r)[N]) {
+  static_assert(0 < S && S < 96 && S % 32 != 0, "2^S with 0 < S < 96, S no multiple of 32");
+  int s[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) s[i] = S % 32;
+  if constexpr (S < 32) {
+    mul_pow2_lo_n<N>(a, s, r);
+  } else if constexpr (S < 64) {
+    uint64_t y[N];
+    mul_pow2_lo_n<N>(a, s, y);
+    mul_2p32_n<N>(y, r);
+  } else {
+    mul_pow2_hi_n<N>(a, s, r);
+  }
+}
+#endif
+// x * 2^S, 0 < S < 96 and S no multiple of 32 on the device (all the NTT needs: S = 12 k)
+GL_HD uint64_t mul_pow2(uint64_t x, unsigned S) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (S < 32) return mul_pow2_lo(x, (int)S);
+  if (S < 64) return mul_2p32(mul_pow2_lo(x, (int)S - 32));
+  return mul_pow2_hi(x, (int)S - 64);
+#else
+  return mul_pow2_portable(x, S);
+#endif
+}
 #if defined(__HIP__)
 // Unreduced dot-product accumulator: sum of 64x64-bit products kept as three 64-bit columns
 // (a0*b0 | a0*b1 + a1*b0 | a1*b1) plus a wrap counter per column; 4 multiply-adds and 4 carry counts

@@ -476,6 +476,34 @@ merkle_subtree_wide_kernel(const uint64_t* __restrict__ child, uint64_t* __restr
   }
 }
 
+// Check kernel for gl::mul_pow2_n / gl::mul_pow2: out[3(k-1) + f][i] = a[i] * 2^(12k), k = 1..7 (bpg.h).
+template <int K>
+__device__ __forceinline__ void mul_pow2_planes(const uint64_t (&x)[4], uint64_t* __restrict__ out, uint64_t n, uint64_t i0) {
+  uint64_t r4[4], r3[3];
+  const uint64_t x3[3] = {x[1], x[2], x[3]};
+  gl::mul_pow2_n<12 * K, 4>(x, r4);
+  __builtin_amdgcn_sched_barrier(0);
+  gl::mul_pow2_n<12 * K, 3>(x3, r3);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint64_t i = i0 + k;
+    if (i >= n) break;
+    out[(3 * (K - 1) + 0) * n + i] = gl::canon(r4[k]);
+    out[(3 * (K - 1) + 1) * n + i] = k ? gl::canon(r3[k - 1]) : gl::canon(r4[0]);
+    out[(3 * (K - 1) + 2) * n + i] = gl::canon(gl::mul_pow2(x[k], 12 * K));
+  }
+  if constexpr (K < 7) mul_pow2_planes<K + 1>(x, out, n, i0);
+}
+__global__ void __launch_bounds__(256) mul_pow2_kernel(const uint64_t* __restrict__ a, uint64_t* __restrict__ out, uint64_t n) {
+  const uint64_t i0 = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  uint64_t x[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) x[k] = a[i0 + k < n ? i0 + k : n - 1];
+  mul_pow2_planes<1>(x, out, n, i0);
+}
+
 // 8-byte-per-lane streaming copy: calibrates the rocprofv3 FETCH_SIZE / WRITE_SIZE counters for the
 // access width every field kernel here uses (MI355X_MICROARCH.md, HBM section).
 __global__ void __launch_bounds__(256)
@@ -793,6 +821,14 @@ int bp_debug_field_ops(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out
   if (!n) return BP_OK;
   if (!d_a || !d_b || !d_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_field_ops: null buffer");
   field_ops_kernel<<<bpg::ceil_div(bpg::ceil_div(n, 4), 256), 256, 0, bpg::as_stream(stream)>>>(d_a, d_b, d_out, n);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+
+int bp_debug_mul_pow2(const uint64_t* d_a, uint64_t* d_out, uint64_t n, void* stream) {
+  if (!n) return BP_OK;
+  if (!d_a || !d_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_mul_pow2: null buffer");
+  mul_pow2_kernel<<<bpg::ceil_div(bpg::ceil_div(n, 4), 256), 256, 0, bpg::as_stream(stream)>>>(d_a, d_out, n);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

@@ -33,29 +33,8 @@ constexpr uint32_t LOG_BLK_MAX = 14;  // 2^14 * 8 B = 128 KiB of the 160 KiB LDS
 // The R/2 twiddle multiplies of a stage are independent: they go through gl::mul_n in groups of four
 // (instruction-interleaved carry chains, gl.hpp), falling back to the one-at-a-time form for R < 8.
 // J0: the caller guarantees j == 0 and log_sub == 0 (the innermost pass: 2^LOGR consecutive elements of a block
-// that starts at a multiple of 2^LOGR).  The twiddle of a butterfly is then a compile-time power w^(m mod half),
-// and a third to all of them are w^0 = 1: those multiplies are skipped (15 of the 32 of a radix-16 pass).
-// The remaining ones are gathered into groups of four / three for gl::mul_n; after full unrolling every index
-// below is a constant.
-template <int N>
-__device__ __forceinline__ void mul_group(uint64_t (&x)[16], const int (&idx)[4], const uint64_t (&d)[4], const uint64_t (&w)[4]) {
-  if constexpr (N == 4) {
-    uint64_t r[4];
-    gl::mul_n<4>(d, w, r);
-#pragma unroll
-    for (int i = 0; i < 4; i++) x[idx[i]] = r[i];
-  } else if constexpr (N == 3) {
-    const uint64_t d3[3] = {d[0], d[1], d[2]}, w3[3] = {w[0], w[1], w[2]};
-    uint64_t r[3];
-    gl::mul_n<3>(d3, w3, r);
-#pragma unroll
-    for (int i = 0; i < 3; i++) x[idx[i]] = r[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; i++) x[idx[i]] = gl::mul(d[i], w[i]);
-  }
-}
-
+// that starts at a multiple of 2^LOGR); the butterflies whose twiddle is w^0 = 1 then skip the multiply.
+// The radix-16 passes of the 2^12..2^14-point block kernels do not come through here: see dit16 / dif16 below.
 template <int LOGR, bool J0 = false>
 __device__ __forceinline__ void dif_butterflies(uint64_t (&x)[1 << LOGR], const uint64_t* __restrict__ tw,
                                                 uint32_t j, uint32_t log_sub, uint32_t tw_shift) {
@@ -64,56 +43,7 @@ __device__ __forceinline__ void dif_butterflies(uint64_t (&x)[1 << LOGR], const 
   for (int s = 0; s < LOGR; s++) {
     const int half = R >> (s + 1);
     // butterfly k of the stage pairs x[m], x[m + half], m = (k / half) * 2 * half + k % half
-    if constexpr (NB % 4 == 0 && J0 && LOGR == 4) {
-      uint64_t dd[NB];
-#pragma unroll
-      for (int k0 = 0; k0 < NB; k0 += 4) {
-        uint64_t a[4], b[4], d[4], r[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int k = k0 + i, m = (k / half) * 2 * half + (k % half);
-          a[i] = x[m];
-          b[i] = x[m + half];
-        }
-        gl::canon_n<4>(b);
-        gl::add_n<4>(a, b, r);
-        gl::sub_n<4>(a, b, d);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int k = k0 + i, m = (k / half) * 2 * half + (k % half);
-          x[m] = r[i];
-          dd[k] = d[i];
-        }
-      }
-      // multiply only where the twiddle is not 1
-      int cnt = 0;
-      int idx[4] = {0, 0, 0, 0};
-      uint64_t dv[4] = {0, 0, 0, 0}, wv[4] = {0, 0, 0, 0};
-      uint64_t xx[16];
-#pragma unroll
-      for (int i = 0; i < 16; i++) xx[i] = x[i];
-#pragma unroll
-      for (int k = 0; k < NB; k++) {
-        const int m = (k / half) * 2 * half + (k % half), e = m & (half - 1);
-        if (e == 0) {
-          xx[m + half] = dd[k];
-        } else {
-          idx[cnt] = m + half;
-          dv[cnt] = dd[k];
-          wv[cnt] = tw[(uint32_t)e << (tw_shift + s)];
-          cnt++;
-          if (cnt == 4) {
-            mul_group<4>(xx, idx, dv, wv);
-            cnt = 0;
-          }
-        }
-      }
-      if (cnt == 3) mul_group<3>(xx, idx, dv, wv);
-      else if (cnt == 2) mul_group<2>(xx, idx, dv, wv);
-      else if (cnt == 1) mul_group<1>(xx, idx, dv, wv);
-#pragma unroll
-      for (int i = 0; i < 16; i++) x[i] = xx[i];
-    } else if constexpr (NB % 4 == 0) {
+    if constexpr (NB % 4 == 0) {
 #pragma unroll
       for (int k0 = 0; k0 < NB; k0 += 4) {
         uint64_t a[4], b[4], d[4], w[4], r[4];
@@ -168,51 +98,7 @@ __device__ __forceinline__ void dit_butterflies(uint64_t (&x)[1 << LOGR], const 
 #pragma unroll
   for (int s = 0; s < LOGR; s++) {
     const int step = 1 << s;  // stage block size = sub << (s+1); tw_shift is for S = sub << LOGR
-    if constexpr (NB % 4 == 0 && J0 && LOGR == 4) {
-      // products first (only where the twiddle is not 1), then the additions of the whole stage
-      uint64_t xx[16];
-#pragma unroll
-      for (int i = 0; i < 16; i++) xx[i] = x[i];
-      int cnt = 0;
-      int idx[4] = {0, 0, 0, 0};
-      uint64_t dv[4] = {0, 0, 0, 0}, wv[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < NB; k++) {
-        const int m = (k / step) * 2 * step + (k % step), e = m & (step - 1);
-        if (e != 0) {
-          idx[cnt] = m + step;
-          dv[cnt] = x[m + step];
-          wv[cnt] = tw[(uint32_t)e << (tw_shift + (LOGR - 1 - s))];
-          cnt++;
-          if (cnt == 4) {
-            mul_group<4>(xx, idx, dv, wv);
-            cnt = 0;
-          }
-        }
-      }
-      if (cnt == 3) mul_group<3>(xx, idx, dv, wv);
-      else if (cnt == 2) mul_group<2>(xx, idx, dv, wv);
-      else if (cnt == 1) mul_group<1>(xx, idx, dv, wv);
-#pragma unroll
-      for (int k0 = 0; k0 < NB; k0 += 4) {
-        uint64_t a[4], r[4], hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int k = k0 + i, m = (k / step) * 2 * step + (k % step);
-          a[i] = xx[m];
-          r[i] = xx[m + step];
-        }
-        gl::canon_n<4>(r);
-        gl::add_n<4>(a, r, hi);
-        gl::sub_n<4>(a, r, lo);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int k = k0 + i, m = (k / step) * 2 * step + (k % step);
-          x[m] = hi[i];
-          x[m + step] = lo[i];
-        }
-      }
-    } else if constexpr (NB % 4 == 0) {
+    if constexpr (NB % 4 == 0) {
 #pragma unroll
       for (int k0 = 0; k0 < NB; k0 += 4) {
         uint64_t a[4], v[4], w[4], r[4], hi[4], lo[4];
@@ -249,6 +135,172 @@ __device__ __forceinline__ void dit_butterflies(uint64_t (&x)[1 << LOGR], const 
       }
     }
   }
+}
+
+// ---- radix-16 passes of the block kernels (ntt16_*): ONE twiddle layer and a 16-point DFT that only shifts.
+// The four radix-2 stages of a pass at sub-block size sub = 2^log_sub compute, for lane offset j < sub,
+//   DIT:  x'[q]  = sum_m  x[m] * w_S^(j*brev4(m)) * w_16^(q*brev4(m))          (S = 16 sub)
+//   DIF:  x'[m]  = w_S^(j*brev4(m)) * sum_q x[q] * w_16^(q*brev4(m))
+// i.e. a layer of 15 general multiplies (register 0 has w^0) and a DFT whose twiddles are powers of w_16 = root(4).
+// In Goldilocks every 16th root of unity is +-2^(12k) (2^96 = -1): with g = 2^12, root(4) = -2^60 = g^13 and its inverse
+// is g^3.  The DFT under g^c is the DFT under g with its outputs renamed (frequency f sits where g's has c*f), and g^e,
+// e < 8, carries no sign: so both directions run the SAME DFT under g, whose 17 non-trivial twiddles are gl::mul_pow2
+// shifts (6..10 instructions) instead of 15-instruction multiplies with a table load each, and rename their registers
+// afterwards (free: after unrolling every index is a constant).  A pass has 15 general multiplies instead of 32 (17 in
+// the innermost pass, which now has none: its layer is all ones).  The DIT kernels are built for the forward root, the
+// DIF kernels for the inverse root.  The layer's factors come from a table of their own (get_table kinds 4 / 5):
+// lay[((16 + r) << log_sub) + j] = w_S^(j*r), consecutive lanes read consecutive words.
+constexpr int brev4(int m) { return ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3); }
+
+// Which registers a DFT stage multiplies by which power of two.  `lo`: those with a factor 2^s or 2^(32 + s)
+// (the first step of both), `mid`: the ones that go on with * 2^32, `hi`: factors 2^(64 + s).
+struct Pow2Plan {
+  int n_lo, n_mid, n_hi;
+  int lo_idx[8], lo_sh[8], mid_idx[8], hi_idx[8], hi_sh[8];
+};
+constexpr Pow2Plan pow2_plan(int s, bool dif) {
+  Pow2Plan p{};
+  for (int k = 0; k < 8; k++) {
+    const int h = dif ? (8 >> s) : (1 << s);                 // distance of the pair
+    const int m = (k / h) * 2 * h + (k % h);
+    const int e = (m & (h - 1)) << (dif ? s : 3 - s);        // twiddle w_16^e, e < 8
+    if (e == 0) continue;
+    const int S = 12 * e;
+    if (S < 64) {
+      p.lo_idx[p.n_lo] = m + h; p.lo_sh[p.n_lo] = S % 32; p.n_lo++;
+      if (S >= 32) p.mid_idx[p.n_mid++] = m + h;
+    } else {
+      p.hi_idx[p.n_hi] = m + h; p.hi_sh[p.n_hi] = S - 64; p.n_hi++;
+    }
+  }
+  return p;
+}
+// STEP 0: x *= 2^sh, 1: x *= 2^32, 2: x *= 2^(64 + sh), on CNT registers: groups of four / three, what is left over
+// one by one
+template <int STEP, int CNT, int I0 = 0>
+__device__ __forceinline__ void apply_pow2(uint64_t (&x)[16], const int (&idx)[8], const int (&sh)[8]) {
+  constexpr int LEFT = CNT - I0, N = LEFT >= 4 ? 4 : LEFT;
+  if constexpr (N >= 3) {
+    uint64_t v[N], r[N];
+    int s[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) { v[i] = x[idx[I0 + i]]; s[i] = sh[I0 + i]; }
+    if constexpr (STEP == 0) gl::mul_pow2_lo_n<N>(v, s, r);
+    else if constexpr (STEP == 1) gl::mul_2p32_n<N>(v, r);
+    else gl::mul_pow2_hi_n<N>(v, s, r);
+#pragma unroll
+    for (int i = 0; i < N; i++) x[idx[I0 + i]] = r[i];
+    __builtin_amdgcn_sched_barrier(0);  // one group of carry masks at a time (see dif_butterflies)
+    apply_pow2<STEP, CNT, I0 + N>(x, idx, sh);
+  } else {
+#pragma unroll
+    for (int i = I0; i < CNT; i++) {
+      if constexpr (STEP == 0) x[idx[i]] = gl::mul_pow2_lo(x[idx[i]], sh[i]);
+      else if constexpr (STEP == 1) x[idx[i]] = gl::mul_2p32(x[idx[i]]);
+      else x[idx[i]] = gl::mul_pow2_hi(x[idx[i]], sh[i]);
+    }
+  }
+}
+template <int S, bool DIF>
+__device__ __forceinline__ void dft16_twiddles(uint64_t (&x)[16]) {
+  constexpr Pow2Plan p = pow2_plan(S, DIF);
+  apply_pow2<0, p.n_lo>(x, p.lo_idx, p.lo_sh);
+  apply_pow2<1, p.n_mid>(x, p.mid_idx, p.lo_sh);
+  apply_pow2<2, p.n_hi>(x, p.hi_idx, p.hi_sh);
+}
+// the eight pairs x[m], x[m + H] of a stage -> sum, difference (lazily reduced, as in the generic stages)
+template <int H>
+__device__ __forceinline__ void dft16_addsub(uint64_t (&x)[16]) {
+#pragma unroll
+  for (int k0 = 0; k0 < 8; k0 += 4) {
+    uint64_t a[4], b[4], hi[4], lo[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int k = k0 + i, m = (k / H) * 2 * H + (k % H);
+      a[i] = x[m];
+      b[i] = x[m + H];
+    }
+    gl::canon_n<4>(b);
+    gl::add_n<4>(a, b, hi);
+    gl::sub_n<4>(a, b, lo);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int k = k0 + i, m = (k / H) * 2 * H + (k % H);
+      x[m] = hi[i];
+      x[m + H] = lo[i];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// x[m] *= w_S^(j * brev4(m)), m = 1..15, in groups {1..4}, {5..8}, {9..12}, {13..15}.  The factors of a group are
+// loaded while the group before it multiplies: all fifteen at once are 30 more live registers than the kernels have.
+template <int M0>
+__device__ __forceinline__ void layer16_load(uint64_t (&w)[4], const uint64_t* __restrict__ lay, uint32_t j, uint32_t log_sub) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if (M0 + i < 16) w[i] = lay[((uint32_t)(16 + brev4(M0 + i)) << log_sub) + j];
+}
+template <int M0 = 1>
+__device__ __forceinline__ void layer16(uint64_t (&x)[16], const uint64_t* __restrict__ lay, uint32_t j, uint32_t log_sub,
+                                        const uint64_t (&w)[4]) {
+  uint64_t wn[4] = {0, 0, 0, 0};
+  if constexpr (M0 + 4 < 16) layer16_load<M0 + 4>(wn, lay, j, log_sub);
+  if constexpr (M0 + 4 <= 16) {
+    const uint64_t v[4] = {x[M0], x[M0 + 1], x[M0 + 2], x[M0 + 3]};
+    uint64_t r[4];
+    gl::mul_n<4>(v, w, r);
+#pragma unroll
+    for (int i = 0; i < 4; i++) x[M0 + i] = r[i];
+  } else {
+    const uint64_t v[3] = {x[13], x[14], x[15]}, w3[3] = {w[0], w[1], w[2]};
+    uint64_t r[3];
+    gl::mul_n<3>(v, w3, r);
+#pragma unroll
+    for (int i = 0; i < 3; i++) x[13 + i] = r[i];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (M0 + 4 < 16) layer16<M0 + 4>(x, lay, j, log_sub, wn);
+}
+__device__ __forceinline__ void layer16(uint64_t (&x)[16], const uint64_t* __restrict__ lay, uint32_t j, uint32_t log_sub) {
+  uint64_t w[4];
+  layer16_load<1>(w, lay, j, log_sub);
+  layer16<1>(x, lay, j, log_sub, w);
+}
+// forward root.  J0: the innermost pass (j = 0: the layer is all ones)
+template <bool J0 = false>
+__device__ __forceinline__ void dit16(uint64_t (&x)[16], const uint64_t* __restrict__ lay, uint32_t j, uint32_t log_sub) {
+  if constexpr (!J0) layer16(x, lay, j, log_sub);
+  dft16_addsub<1>(x);
+  dft16_twiddles<1, false>(x);
+  dft16_addsub<2>(x);
+  dft16_twiddles<2, false>(x);
+  dft16_addsub<4>(x);
+  dft16_twiddles<3, false>(x);
+  dft16_addsub<8>(x);
+  // output q of the DFT under root(4) = g^13 is output 13 q of the one under g
+  uint64_t y[16];
+#pragma unroll
+  for (int q = 0; q < 16; q++) y[q] = x[(13 * q) & 15];
+#pragma unroll
+  for (int q = 0; q < 16; q++) x[q] = y[q];
+}
+// inverse root
+template <bool J0 = false>
+__device__ __forceinline__ void dif16(uint64_t (&x)[16], const uint64_t* __restrict__ lay, uint32_t j, uint32_t log_sub) {
+  dft16_addsub<8>(x);
+  dft16_twiddles<0, true>(x);
+  dft16_addsub<4>(x);
+  dft16_twiddles<1, true>(x);
+  dft16_addsub<2>(x);
+  dft16_twiddles<2, true>(x);
+  dft16_addsub<1>(x);
+  // register m holds frequency brev4(m) of the DFT under g; the one under root(4)^-1 = g^3 has 3 f there
+  uint64_t y[16];
+#pragma unroll
+  for (int m = 0; m < 16; m++) y[m] = x[brev4((3 * brev4(m)) & 15)];
+#pragma unroll
+  for (int m = 0; m < 16; m++) x[m] = y[m];
+  if constexpr (!J0) layer16(x, lay, j, log_sub);
 }
 
 // One pass over a block of 2^log_blk elements held in `buf` (LDS).  span_log = log2(S).
@@ -350,7 +402,13 @@ __device__ __forceinline__ uint32_t insert4(uint32_t t, uint32_t m, uint32_t b) 
 // or on x[(g << R) + u] when CONTIG.
 template <int R, int SH, bool CONTIG, bool DIF>
 __device__ __forceinline__ void sub_butterflies(uint64_t (&x)[16], const uint64_t* __restrict__ tw, uint32_t j,
-                                                uint32_t j_step_log, uint32_t log_sub, uint32_t tw_shift) {
+                                                uint32_t j_step_log, uint32_t log_sub, uint32_t tw_shift,
+                                                const uint64_t* __restrict__ lay) {
+  if constexpr (R == 4) {  // a whole radix-16 pass (2^12-point blocks): layer + shift-only DFT
+    if (DIF) dif16<CONTIG>(x, lay, j, log_sub);
+    else dit16<CONTIG>(x, lay, j, log_sub);
+    return;
+  }
   constexpr int G = 16 >> R;
 #pragma unroll
   for (int g = 0; g < G; g++) {
@@ -378,6 +436,7 @@ struct Ntt16Args {
   uint64_t out_scalar;    // DIF: 1/n (1 = none)
   uint32_t log_n_total, n_cosets, n_units;  // n_units = columns * blocks per column (1-D grid mapping)
   const uint64_t* tw_top; // split kernels (F = 1): w_{2B}^e, e < B: the stage that joins the two halves
+  const uint64_t* lay;    // twiddle layers of the radix-16 passes (get_table kind 4 / 5 for B): see dit16 / dif16
 };
 
 // ---- "split" forms (template parameter F = 1): a block of 2^(L+1) elements is transformed by TWO workgroups of
@@ -440,7 +499,7 @@ __global__ void __launch_bounds__((1 << L) / 16) ntt16_dif_kernel(Ntt16Args a) {
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = src[m * T + t];
   }
-  dif_butterflies<4>(x, a.tw, t, L - 4, 0);
+  dif16(x, a.lay, t, L - 4);
 #pragma unroll
   for (int m = 0; m < 16; m++) buf[swz<L>(m * T + t)] = x[m];
   __syncthreads();
@@ -448,7 +507,7 @@ __global__ void __launch_bounds__((1 << L) / 16) ntt16_dif_kernel(Ntt16Args a) {
   for (int b = L - 8; b > 0; b -= 4) {
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(insert4(t, m, b))];
-    dif_butterflies<4>(x, a.tw, t & ((1u << b) - 1), b, L - (b + 4));
+    dif16(x, a.lay, t & ((1u << b) - 1), b);
 #pragma unroll
     for (int m = 0; m < 16; m++) buf[swz<L>(insert4(t, m, b))] = x[m];
     __syncthreads();
@@ -456,7 +515,7 @@ __global__ void __launch_bounds__((1 << L) / 16) ntt16_dif_kernel(Ntt16Args a) {
   const uint32_t base = gl::bitrev(t, L - 4) << 4;
 #pragma unroll
   for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(base | m)];
-  sub_butterflies<RT, 0, true, true>(x, a.tw, 0, 0, 0, L - RT);
+  sub_butterflies<RT, 0, true, true>(x, a.tw, 0, 0, 0, L - RT, a.lay);
   // In-place DIF leaves position i holding coefficient bitrev(i): exactly the bit-reversed storage
   // order.  One more (conflict-free) LDS exchange turns "16 consecutive words per lane" into
   // coalesced 8-byte lanes for the global store.
@@ -581,7 +640,7 @@ __global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per
   // innermost field [3:0]
 #pragma unroll
   for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(base | m)];
-  dit_butterflies<4, true>(x, tw, 0, 0, L - 4);
+  dit16<true>(x, a.lay, 0, 0);
 #pragma unroll
   for (int m = 0; m < 16; m++) buf[swz<L>(base | m)] = x[m];
   __syncthreads();
@@ -589,7 +648,7 @@ __global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per
   for (int b = 4; b + 4 <= L - RT; b += 4) {
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(insert4(t, m, b))];
-    dit_butterflies<4>(x, tw, t & ((1u << b) - 1), b, L - (b + 4));
+    dit16(x, a.lay, t & ((1u << b) - 1), b);
 #pragma unroll
     for (int m = 0; m < 16; m++) buf[swz<L>(insert4(t, m, b))] = x[m];
     __syncthreads();
@@ -601,7 +660,7 @@ __global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per
   asm volatile("" : "+v"(t2));
 #pragma unroll
   for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(m * T + t2)];
-  sub_butterflies<RT, 4 - RT, false, false>(x, tw, t2, L - 4, L - RT, 0);
+  sub_butterflies<RT, 4 - RT, false, false>(x, tw, t2, L - 4, L - RT, 0, a.lay);
   uint64_t* dst = a.out + col * a.out_stride + coset * a.out_coset_stride + off;
 #pragma unroll
   for (int m0 = 0; m0 < 16; m0 += 4) {
@@ -687,7 +746,7 @@ ntt16_dit_persist_kernel(Ntt16Args a, uint32_t n_items) {
     uint64_t x[16];
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(base | m)];
-    dit_butterflies<4, true>(x, tw, 0, 0, L - 4);
+    dit16<true>(x, a.lay, 0, 0);
 #pragma unroll
     for (int m = 0; m < 16; m++) buf[swz<L>(base | m)] = x[m];
     __syncthreads();
@@ -696,7 +755,7 @@ ntt16_dit_persist_kernel(Ntt16Args a, uint32_t n_items) {
       asm volatile("" : "+v"(tc));
 #pragma unroll
       for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(insert4(tc, m, b))];
-      dit_butterflies<4>(x, tw, tc & ((1u << b) - 1), b, L - (b + 4));
+      dit16(x, a.lay, tc & ((1u << b) - 1), b);
 #pragma unroll
       for (int m = 0; m < 16; m++) buf[swz<L>(insert4(tc, m, b))] = x[m];
       __syncthreads();
@@ -710,7 +769,7 @@ ntt16_dit_persist_kernel(Ntt16Args a, uint32_t n_items) {
     }
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(m * T + t2)];
-    sub_butterflies<RT, 4 - RT, false, false>(x, tw, t2, L - 4, L - RT, 0);
+    sub_butterflies<RT, 4 - RT, false, false>(x, tw, t2, L - 4, L - RT, 0, a.lay);
     uint64_t* dst = a.out + col * a.out_stride + coset * a.out_coset_stride + off;
 #pragma unroll
     for (int m0 = 0; m0 < 16; m0 += 4) {
@@ -842,6 +901,15 @@ __global__ void twiddle_table_kernel(uint64_t* out, uint32_t count, uint64_t w) 
   uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < count) out[e] = gl::pow(w, e);
 }
+// Twiddle layers of the radix-16 passes (dit16 / dif16), all sub-block sizes 2^b, b <= log_n - 4, in one table of
+// 2^(log_n + 1) words: out[((16 + r) << b) + j] = w_(2^(b+4))^(j*r), r < 16, j < 2^b.  w = root of order 2^log_n.
+__global__ void layer_table_kernel(uint64_t* out, uint32_t log_n, uint64_t w) {
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (2u << log_n)) return;
+  if (idx < 16) { out[idx] = 1; return; }  // below the b = 0 rows: not read
+  const uint32_t b = 31 - __clz(idx) - 4, r = (idx >> b) - 16, j = idx & ((1u << b) - 1);
+  out[idx] = gl::pow(w, (uint64_t)(j * r) << (log_n - b - 4));
+}
 // scale[t][pos] = (7 * w_M^t)^(+-bitrev_n(pos)),  M = n << rate_bits
 __global__ void coset_scale_table_kernel(uint64_t* out, uint32_t log_n, uint32_t rate_bits, uint64_t w_m,
                                          int inverse) {
@@ -866,7 +934,7 @@ __global__ void bitrev_permute_kernel(uint64_t* cols, uint64_t stride, uint32_t 
 
 // ---- per-device table cache ----------------------------------------------------------------
 struct TableKey {
-  int dev, kind;  // kind 0: fwd twiddles, 1: inv twiddles, 2: coset scales, 3: inverse coset scales
+  int dev, kind;  // kind 0: fwd twiddles, 1: inv twiddles, 2: coset scales, 3: inverse coset scales, 4 / 5: fwd / inv radix-16 layers
   uint32_t log_n, rate_bits;
   bool operator<(const TableKey& o) const {
     return std::tie(dev, kind, log_n, rate_bits) < std::tie(o.dev, o.kind, o.log_n, o.rate_bits);
@@ -884,14 +952,21 @@ int get_table(int kind, uint32_t log_n, uint32_t rate_bits, const uint64_t** out
   int dev = 0;
   BPG_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_table_mu);
-  TableKey key{dev, kind, log_n, kind >= 2 ? rate_bits : 0};
+  TableKey key{dev, kind, log_n, (kind == 2 || kind == 3) ? rate_bits : 0};
   auto it = g_tables.find(key);
   if (it != g_tables.end()) {
     *out = it->second;
     return BP_OK;
   }
   uint64_t* d = nullptr;
-  if (kind >= 2) {
+  if (kind >= 4) {
+    if (log_n < 4 || log_n > LOG_BLK_MAX) return fail(BP_ERR_DEVICE, "radix-16 layer table for 2^%u points", log_n);
+    const uint32_t count = 2u << log_n;
+    BPG_HIP(hipMalloc(&d, (uint64_t)count * 8));
+    uint64_t w = gl::root(log_n);
+    if (kind == 5) w = gl::inv(w);
+    layer_table_kernel<<<ceil_div(count, 256), 256, 0, 0>>>(d, log_n, w);
+  } else if (kind >= 2) {
     uint64_t count = (uint64_t)1 << (log_n + rate_bits);
     BPG_HIP(hipMalloc(&d, count * 8));
     dim3 grid(ceil_div((uint64_t)1 << log_n, 256), 1u << rate_bits);
@@ -1082,10 +1157,13 @@ int intt_nat2br(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t 
     src = out;
     src_stride = out_stride;
   }
-  if (log_blk >= 12) {
+  // the 16-elements-per-lane kernels are built for the direction they are used in (dif16: inverse root); a forward
+  // DIF transform of such a block takes the generic LDS kernel
+  if (log_blk >= 12 && inverse) {
     Ntt16Args b{};
     b.in = src; b.in_stride = src_stride; b.out = out; b.out_stride = out_stride; b.out_coset_stride = 0;
     b.tw = tw_b; b.scale = nullptr; b.out_scalar = inverse ? gl::inv((uint64_t)1 << log_n) : 1;
+    if ((rc = get_table(5, log_blk, 0, &b.lay))) return rc;
     b.log_n_total = log_n; b.n_cosets = 1; b.n_units = 0;
     KernelTimer kt(PROF_INTT_DIF, st, 16.0 * (double)n_cols * (double)((uint64_t)1 << log_n));
     if (use_ntt_mx(log_blk, false)) {
@@ -1138,8 +1216,9 @@ int ntt_br2nat(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t o
   const uint64_t *tw_n = nullptr, *tw_b = nullptr;
   int rc;
   if ((rc = get_table(inverse ? 1 : 0, log_blk, 0, &tw_b))) return rc;
-  if (log_blk >= 12) {
+  if (log_blk >= 12 && !inverse) {  // dit16: forward root (see intt_nat2br)
     Ntt16Args b{};
+    if ((rc = get_table(4, log_blk, 0, &b.lay))) return rc;
     b.in = in; b.in_stride = in_stride; b.out = out; b.out_stride = out_stride; b.out_coset_stride = coset_stride;
     b.tw = tw_b; b.scale = scale; b.out_scalar = 1; b.log_n_total = log_n; b.n_cosets = n_cosets;
     b.n_units = n_cols << (log_n - log_blk);

@@ -1273,7 +1273,9 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(bpg::BatchOf<bpg::FriLaye
 __global__ void __launch_bounds__(256) pow_grind_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result) {
   const bpg::PowArgs& a = batch.a[blockIdx.z];
   result += blockIdx.z;
-  if (__hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base) return;  // see pow_grind_mx_kernel
+  // a witness below this workgroup's first candidate is already known: see pow_grind_mx_kernel (here every lane works
+  // for itself, so lanes may leave one by one)
+  if (__hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base + blockIdx.x * (uint64_t)blockDim.x) return;
   const uint64_t cand = a.base + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   uint64_t s[12];
 #pragma unroll
@@ -1293,8 +1295,15 @@ pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result
   result += blockIdx.z;  // one witness word per proof of the batch
   // A witness below this batch is already known (an earlier batch of the same speculative group found it: batches
   // run one after the other on the stream, so the value is stable and the same for every thread): nothing here can
-  // be smaller, the whole grid leaves before it loads a table.
-  if (__hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base) return;
+  // be smaller, the whole grid leaves before it loads a table.  The same holds per workgroup WITHIN a batch: under load
+  // a 2^15-candidate batch is dispatched progressively, and a workgroup that starts after a smaller witness has been
+  // found holds only larger candidates.  The minimum is unchanged.  That value moves while the grid runs, so one lane
+  // reads it for the workgroup (the tables below are built by all of its lanes together).
+  __shared__ uint32_t beaten;
+  if (threadIdx.x == 0)
+    beaten = __hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base + (uint64_t)blockIdx.x * 256;
+  __syncthreads();
+  if (beaten) return;
   constexpr int NG = GR ? GR : 2;
   __shared__ __attribute__((aligned(16))) uint32_t cin[GR ? poseidon::mx::CIN_GROUPED_WORDS<NG> : poseidon::mx::CIN_WORDS];
   __shared__ __attribute__((aligned(16))) uint32_t gt[GR ? poseidon::mx::grp::TABLE_WORDS<NG> : 4];

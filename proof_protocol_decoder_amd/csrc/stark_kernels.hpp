@@ -241,7 +241,7 @@ int launch_query_layers(const QueryLayerArgs& a, uint32_t batch, uint32_t n_laye
 
 // ntt.hip
 int init_ntt_kernels();
-int get_table(int kind, uint32_t log_n, uint32_t rate_bits, const uint64_t** out);  // 0 fwd, 1 inv, 2 coset, 3 inv coset
+int get_table(int kind, uint32_t log_n, uint32_t rate_bits, const uint64_t** out);  // 0 fwd, 1 inv, 2 coset, 3 inv coset, 4 / 5 fwd / inv radix-16 layers (ntt.hip)
 int intt_nat2br(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t out_stride, uint32_t log_n,
                 uint32_t n_cols, bool inverse, hipStream_t st);
 int ntt_br2nat(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t out_stride, uint64_t coset_stride,

@@ -72,6 +72,16 @@ def field_ops(a, b):
     return out
 
 
+def mul_pow2(a):
+    """bp_debug_mul_pow2: [21, n] planes, plane 3(k-1) + f = a * 2^(12k) mod p (canonical), k = 1..7, by the groups of
+    four (f = 0), of three (f = 1) and the one-element form (f = 2); a: any u64 patterns."""
+    _require_cuda(a)
+    n = a.numel()
+    out = torch.empty((21, n), dtype=torch.int64, device=a.device)
+    check(lib().bp_debug_mul_pow2(a.data_ptr(), out.data_ptr(), n, _stream()))
+    return out
+
+
 AIR_SYNTHETIC, AIR_KECCAK_F = 0, 1
 KECCAK_COLS = 2431
 LOGIC_COLS = 524

@@ -35,6 +35,8 @@ OPS = {
     "subb_co_o":  ("v_subb_co_u32_e64 {x}, {co}, {a}, {b}, {ci}", ("uint32_t", "x"), True, [("uint32_t", "v", "a"), ("uint32_t", "v", "b"), ("mask", "s", "ci")]),
     "add_m1_co_o": ("v_add_co_u32_e64 {x}, {co}, {a}, -1", ("uint32_t", "x"), True, [("uint32_t", "v", "a")]),                                   # x = a + 2^32-1
     "addc0_co_o": ("v_addc_co_u32_e64 {x}, {co}, {a}, 0, {ci}", ("uint32_t", "x"), True, [("uint32_t", "v", "a"), ("mask", "s", "ci")]),          # x = a + ci
+    # a*(2^32-1) as a fresh 64-bit value: the 2^64 = EPS step of the multiplications by 2^S (gl::mul_pow2_n); never carries
+    "mul_eps_o":  ("v_mad_u64_u32 {x}, vcc, {a}, -1, 0", ("uint64_t", "x"), False, [("uint32_t", "v", "a")]),                                    # x = a*(2^32-1)
 }
 
 
@@ -42,7 +44,7 @@ def emit(n):
     out = []
     for name, (line, (xt, xa), has_co, ins) in OPS.items():
         write_only = name == "sel_eps" or name.endswith("_o")
-        clobber = ' : "vcc"' if name.endswith("_cv") else ""
+        clobber = ' : "vcc"' if " vcc," in line else ""
         params = [f"{xt} (&{xa})[{n}]"] + ([f"mask (&co)[{n}]"] if has_co else []) + [f"const {t} (&{a})[{n}]" for t, _, a in ins]
         out.append(f"__device__ __forceinline__ void {name}(" + ", ".join(params) + ") {")
         idx, slots = 0, {}

@@ -302,10 +302,43 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
  * program again returns the same id; a different program whose id is taken is refused, never aliased.
  * bp_air_describe answers for a registered id from the program's own tables (n_cols / n_const / deg_pow are ignored).
  * Every entry that takes an air_id takes a registered one: bp_quotient_scratch_words, bp_quotient_eval,
- * bp_air_check_trace(_host), bp_stark_verify_air(_pub), bp_stark_prove_trace.  A registered AIR has the auxiliary
- * column of a table no lookup is built for (one constant running product, as AIR 4 and AIR 7); pub = four words when
- * n_public > 0.  Not built: a registered AIR as one of a transaction's seven tables or in a cross-table lookup, and
- * compiling a program to a native kernel at run time.  The program goes to a device once, at its first use there. */
+ * bp_air_check_trace(_host), bp_stark_verify_air(_pub), bp_stark_prove_trace.  A registered AIR without ports has the
+ * auxiliary column of a table no lookup is built for (one constant running product, as AIR 4 and AIR 7); pub = four
+ * words when n_public > 0.  Not built: a registered AIR as one of a transaction's seven tables, and compiling a program
+ * to a native kernel at run time.  The program goes to a device once, at its first use there.
+ *
+ * Lookup ports: the format "BPGAIRP2" (0x3250524941475042).  "BPGAIRP1" stays valid and untouched.  A PORT is a filter f
+ * and a tuple t_0 .. t_(n_tuple - 1) of expressions over the row: the rows where f = 1 send (a looking port) or expose
+ * (a looked port) their tuple to another table, which bp_stark_prove_table_set links it to.  "BPGAIRP2" is "BPGAIRP1" with
+ *   word 10     n_ports (0 .. 8), after the nine header words above (n_units counts the constraint units only; n_regs
+ *               covers both kinds of unit)
+ *   then        the family table, as above
+ *   then        n_ports words: n_tuple of port l (1 .. 128)
+ *   then        n_units + n_ports + 1 code offsets: the constraint units, then PORT UNIT l = unit n_units + l
+ *   then        n_code code words, with one more operation:
+ *                 10 port: dst = slot, a = port index, b = register.  Slot 0 adds the register to the port's filter f,
+ *                    slot 1 + j to tuple element t_j.  Partial sums add, in any order, as with emit.
+ *   The program is exactly these 11 + 4 n_families + n_ports + n_units + n_ports + 1 + n_code words.
+ * Port units may load and compute but not emit; constraint units may not port; port unit l names port l only; every
+ * slot 0 .. n_tuple of a port is written at least once and none beyond.
+ * What follows from a port is derived by the library, so a program cannot get the product argument wrong.  With the
+ * challenge set c = (beta_c, gamma_c), v_c = sum_j beta_c^j t_j and term_c = 1 + f (gamma_c + v_c - 1):
+ *   auxiliary columns: 2 n_ports; port l has z_(l,0), z_(l,1) at columns 2l, 2l + 1, z_c[i] = prod_(i' >= i) term_c[i']
+ *               (backwards, as every running product here).  n_ports = 0 keeps the single constant product.
+ *   constraints: 5 per port after the program's own, at n_constraints + 5l, in AIR 3's order:
+ *               all rows f f - f; then for c = 0, 1: transition z_c - z_c' term_c, last row z_c - term_c.
+ *               bp_air_describe reports them (n_aux, n_ctl_constraints, five families per port with the degrees
+ *               max(1, 2 deg f), 1 + deg f + deg t, max(1, deg f + deg t); where n_families + 5 n_ports > 24 three
+ *               interleaved families stand for all ports instead -- (n_constraints, n_ports, all rows),
+ *               (n_constraints + 1, 2 n_ports, transition), (n_constraints + 2, 2 n_ports, last row), members of port l
+ *               at + 5l and, the second of a port's two, 2 further -- with the largest degree among the ports).
+ *   refused:    2 deg f > degree; 1 + deg f + max_j deg t_j > degree; deg f + max_j deg t_j above the first-row / last-row
+ *               bound stated above (z - term is a last-row constraint); more than 21 families in a program with ports
+ *               (bp_air_desc.families holds both lists); a slot never written or beyond n_tuple; port outside a port unit, or for another port;
+ *               emit in a port unit; n_ports > 8; n_tuple outside 1 .. 128.  Each with the word offset, as above.
+ * The trace checker is unchanged: it checks the AIR's own constraints only, ports dropped, as for the built-in tables.
+ * bp_stark_prove_trace on a program with ports proves it alone: its ports are linked to nothing, their constraints are
+ * checked; bp_quotient_eval (d_aux_lde: 2 n_ports columns) and bp_stark_verify_air(_pub) take the id as any other. */
 int bp_air_register(const uint64_t* program, size_t n_words, uint32_t* air_id_out);
 int bp_air_unregister(uint32_t air_id);
 int bp_air_program_digest(uint32_t air_id, uint8_t out[32]); /* Keccak-256 of the registered bytes */
@@ -329,6 +362,19 @@ uint64_t bp_quotient_scratch_words(uint32_t air_id, const struct bp_stark_cfg* s
 int bp_quotient_eval(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* d_trace_lde,
                      const uint64_t* d_aux_lde, const uint64_t* d_const_lde, const uint64_t ctl[4],
                      const uint64_t alphas[2], uint64_t* d_scratch, uint64_t* d_qvals_out, void* stream);
+
+/* The running products of a registered program's ports on the trace domain, without a proof around them: what the prover
+ * commits as the table's auxiliary columns.  air_id: a registered program with ports (anything else: BP_ERR_INVALID_INPUT).
+ * shape, d_trace, stride, d_consts, pub: as bp_air_check_trace's.  ctl = beta0, gamma0, beta1, gamma1.
+ * d_aux_out: 2 n_ports columns x 2^log_n words, column stride 2^log_n: port l's z_0 at column 2l, z_1 at 2l + 1. */
+int bp_air_port_products(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* d_trace, uint64_t stride,
+                         const uint64_t* d_consts, const uint64_t pub[4], const uint64_t ctl[4], uint64_t* d_aux_out, void* stream);
+
+/* Test entry: the auxiliary columns (bp_air_desc.n_aux of them: helper columns, then the running products; column
+ * stride 2^log_n) the prover commits for a BUILT-IN table with a lookup side (AIR 1, 2, 3, 5, 6), from a trace of column
+ * stride 2^log_n.  What bp_air_port_products is compared with. */
+int bp_debug_air_aux(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* d_trace, const uint64_t ctl[4],
+                     uint64_t* d_aux_out, void* stream);
 
 /* The AIR trace checker: which rows of a witness violate which constraints of its AIR, without proving it (upstream's
  * debugging aid check_constraints).  The AIR is evaluated on the TRACE domain: row i with the next row (i + 1) mod n and
@@ -479,6 +525,60 @@ void bp_stark_public_inputs(uint64_t seed, uint64_t out[4]);
 void bp_stark_public_input_list(uint64_t seed, uint64_t out[4]);
 int bp_stark_verify_air_pub(uint32_t air_id, const bp_stark_cfg* cfg, const uint64_t* const_cap, const uint64_t* pub,
                             const uint8_t* proof, size_t len);
+/* Table sets: several caller traces, linked port to port, proven on ONE transcript and verified as ONE statement.
+ * A member is a registered program with ports, or a built-in AIR with a lookup side, whose ports are its product
+ * columns in order (port l = auxiliary columns first_product + 2l + c); filters and tuples as AIRS.md section 3 states:
+ *   AIR 1 keccak_f       port 0 (looked): filter g (column 2430); tuple = 50 input limbs, 50 output limbs of the permutation
+ *   AIR 2 logic          port 0 (looked): filter g (column 523); tuple = is_and, is_or, is_xor, 8 limbs of input 0, of
+ *                        input 1, of the result (27)
+ *   AIR 3 memory         port 0 (looked): filter g (column 44); tuple = is_read, address, timestamp, 8 value limbs (11)
+ *   AIR 5 byte_packing   port 0 (looking): filter = the row has a length; tuple = is_read, address, timestamp, 8 value limbs
+ *   AIR 6 keccak_sponge  port 0 (looking): filter is_full + is_final; tuple = 34 xored rate limbs, 16 capacity limbs, 50
+ *                        updated state limbs.  Ports 1 .. 5 (looking, limb group m = port - 1): the same filter; tuple =
+ *                        0, 0, 1, limbs 8m .. 8m + 7 of the rate before, of the block, of the xored rate (limbs past the
+ *                        34th are zero)
+ * The filter column g of a built-in member is whatever the caller's trace holds.  "Looking" and "looked" only say which
+ * side of a link a port is on: the identity is symmetric.  A link states, for both challenge sets,
+ *   prod over its looking ports of z(first row) = z_looked(first row):
+ * the multiset of tuples the looking ports send on their filtered rows is the multiset the looked port exposes.
+ * At most 8 tables and 16 links; every port of every member is in exactly one link (an unlinked port or a port named
+ * twice is refused, before a device is touched).
+ * Transcript: a fresh challenger observes the statement -- "BPGTSET1", n_tables, n_links; per table air_id, log_n,
+ * n_cols, n_const, rate_bits and, for a registered id, the eight 32-bit little-endian words of the program's Keccak-256
+ * digest; per link n_looking, its looking (table, port) pairs, the looked pair -- then per table the constants cap (if
+ * any), the trace cap and four public inputs (zeros without), draws the four lookup challenges, and is threaded through
+ * the table proofs in order.  Every trace is committed before the challenges exist.
+ * After the proofs every link is checked on the first-row openings: an unbalanced link fails with BP_ERR_VERIFY and a
+ * message naming the link's index and both ends, unless flags has BP_SET_SKIP_LINK_CHECK (the container is returned
+ * anyway: for showing a verifier an unbalanced set).
+ * The container (u64 words): "BPGTSET1" (0x3154455354475042), n_tables, n_links, beta0, gamma0, beta1, gamma1; per link
+ * n_looking, its (table, port) pairs, the looked pair; per table air_id, log_n, n_cols, n_words and the proof words.
+ * bp_stark_verify_table_set: the statement is the VERIFIER's -- tables (d_trace, stride, d_consts are ignored; pub is
+ * read), const_caps (n_tables pointers, NULL where a table has no constant columns; the array may be NULL when none
+ * has) and links are the caller's own, never read from the container, whose shape must agree with them.  It re-derives
+ * the transcript, compares the challenges, verifies each table from the transcript state it was proven at and checks
+ * every link.  Registered members must be registered in the verifying process.  Host only. */
+typedef struct bp_set_table {
+  uint32_t air_id;
+  bp_stark_cfg cfg;
+  const uint64_t* d_trace;
+  uint64_t stride;
+  const uint64_t* d_consts;
+  const uint64_t* pub;
+} bp_set_table;
+typedef struct bp_set_port {
+  uint32_t table, port;
+} bp_set_port;
+typedef struct bp_set_link {
+  uint32_t n_looking;
+  bp_set_port looking[8];
+  bp_set_port looked;
+} bp_set_link;
+#define BP_SET_SKIP_LINK_CHECK 1u
+int bp_stark_prove_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links,
+                             uint32_t flags, int device, uint8_t** out, size_t* out_len);
+int bp_stark_verify_table_set(const bp_set_table* statement, uint32_t n_tables, const uint64_t* const* const_caps,
+                              const bp_set_link* links, uint32_t n_links, const uint8_t* proof, size_t len);
 /* bp_stark_prove_synthetic keeps one worker (stream + device arena, up to ~100 GB for a 2^20 x 2432
  * table) parked per device between calls, because re-allocating it costs more than the proof.
  * This frees the parked workers. */

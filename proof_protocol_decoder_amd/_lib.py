@@ -39,6 +39,25 @@ class AirDesc(C.Structure):
                 + [("families", AirFamily * 24)])
 
 
+class SetTable(C.Structure):
+    """bp_set_table: a member of a table set."""
+    _fields_ = [("air_id", C.c_uint32), ("cfg", StarkCfg), ("d_trace", C.c_void_p), ("stride", C.c_uint64),
+                ("d_consts", C.c_void_p), ("pub", C.POINTER(C.c_uint64))]
+
+
+class SetPort(C.Structure):
+    """bp_set_port: port `port` of table `table` of a set."""
+    _fields_ = [("table", C.c_uint32), ("port", C.c_uint32)]
+
+
+class SetLink(C.Structure):
+    """bp_set_link: the looking ports' tuples are the looked port's."""
+    _fields_ = [("n_looking", C.c_uint32), ("looking", SetPort * 8), ("looked", SetPort)]
+
+
+BP_SET_SKIP_LINK_CHECK = 1
+
+
 class AirViolation(C.Structure):
     """bp_air_violation: one constraint a row of a trace breaks (bp_air_check_trace)."""
     _fields_ = [(n, C.c_uint32) for n in ("row", "constraint", "family", "kind")] + [("value", C.c_uint64)]
@@ -99,6 +118,12 @@ def lib():
     L.bp_stark_verify_air_pub.argtypes = [u32, C.POINTER(StarkCfg), C.POINTER(u64), C.POINTER(u64), C.c_char_p, C.c_size_t]
     L.bp_stark_prove_trace.argtypes = [u32, C.POINTER(StarkCfg), vp, u64, vp, C.POINTER(u64), i, C.POINTER(C.POINTER(C.c_uint8)),
                                        C.POINTER(C.c_size_t)]
+    L.bp_debug_air_aux.argtypes = [u32, C.POINTER(StarkCfg), vp, C.POINTER(u64), vp, vp]
+    L.bp_air_port_products.argtypes = [u32, C.POINTER(StarkCfg), vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp, vp]
+    L.bp_stark_prove_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(SetLink), u32, u32, i,
+                                           C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.bp_stark_verify_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(C.POINTER(u64)), C.POINTER(SetLink), u32,
+                                            C.c_char_p, C.c_size_t]
     L.bp_air_register.argtypes = [vp, C.c_size_t, C.POINTER(u32)]
     L.bp_air_unregister.argtypes = [u32]
     L.bp_air_program_digest.argtypes = [u32, C.c_char_p]

@@ -10,6 +10,15 @@
     words = b.assemble()                                # numpy uint64: the program bytes
     values = b.evaluate(row, next_row)                  # the same constraints over Python integers
 
+A lookup PORT makes the table a side of a cross-table lookup (AIRS.md section 3, "Run-time lookups"):
+
+    p = b.port(b.loc(7), [b.loc(0), b.loc(1) + b.nxt(1)])   # filter, tuple; returns the port's index
+    words = b.assemble()                                # a builder with a port assembles "BPGAIRP2"
+    (f, t), = b.evaluate_ports(row, next_row)           # the filter and the tuple over Python integers
+
+The program only states the filter and the tuple; the two running products of the port and their five constraints are
+the library's (include/bpg.h).  A builder without a port assembles the "BPGAIRP1" bytes it always did.
+
 Expressions are built from loc(c), nxt(c), cst(c), pub(j), x and integers with + - *; equal subexpressions are one node
 (hash-consing), so a value used twice in a unit is computed once.  assemble() schedules every unit's emits in order,
 allocates registers by last use (a leaf -- a load or a constant -- is re-issued for each emit instead of being kept, which
@@ -20,6 +29,9 @@ import numpy as np
 
 P = 2 ** 64 - 2 ** 32 + 1
 MAGIC = int.from_bytes(b"BPGAIRP1", "little")
+MAGIC2 = int.from_bytes(b"BPGAIRP2", "little")
+OP_PORT = 10
+MAX_PORTS, MAX_TUPLE, MAX_FAMILIES_WITH_PORTS = 8, 128, 21
 ALL_ROWS, TRANSITION, FIRST_ROW, LAST_ROW = 0, 1, 2, 3
 OP_LOC, OP_NXT, OP_CST, OP_PUB, OP_X, OP_IMM, OP_ADD, OP_SUB, OP_MUL, OP_EMIT = range(10)
 MAX_REGS = 64
@@ -67,6 +79,7 @@ class Builder:
         self.n_cols, self.n_const, self.n_public, self.degree = n_cols, n_const, n_public, degree
         self.families = []   # (first_index, count, kind, degree)
         self.units = []      # lists of (index, Expr)
+        self.ports = []      # (filter Expr, [tuple Exprs])
         self._nodes = {}     # key -> Expr
         self._order = []     # every node, operands before users
 
@@ -158,9 +171,30 @@ class Builder:
             self.unit()
         self.units[-1].append((index, e))
 
+    def port(self, filter_expr, tuple_exprs):
+        """A lookup port: the rows where `filter_expr` is 1 send (or expose) the tuple `tuple_exprs`.  Returns its index.
+        The degrees bp_air_register asks for -- 2 deg f <= degree, 1 + deg f + max deg t <= degree, deg f + max deg t <=
+        boundary_degree(degree) -- are checked by assemble(), when the program's degree is known."""
+        f = filter_expr if isinstance(filter_expr, Expr) else self.const(filter_expr)
+        t = [e if isinstance(e, Expr) else self.const(e) for e in tuple_exprs]
+        if not 1 <= len(t) <= MAX_TUPLE:
+            raise ValueError("a port's tuple has 1 .. %d elements: got %d" % (MAX_TUPLE, len(t)))
+        if len(self.ports) == MAX_PORTS:
+            raise ValueError("a program has at most %d ports" % MAX_PORTS)
+        self.ports.append((f, t))
+        return len(self.ports) - 1
+
+    def _check_ports(self, degree):
+        for l, (f, t) in enumerate(self.ports):
+            dt = max(e.degree for e in t)
+            if 2 * f.degree > degree or 1 + f.degree + dt > degree or f.degree + dt > boundary_degree(degree):
+                raise ValueError("port %d: a filter of degree %d and a tuple of degree %d do not fit a program of degree %d"
+                                 % (l, f.degree, dt, degree))
+        if len(self.families) > MAX_FAMILIES_WITH_PORTS:
+            raise ValueError("%d families: a program with ports has at most %d of its own" % (len(self.families), MAX_FAMILIES_WITH_PORTS))
+
     # ---- the independent statement: the constraints over Python integers
-    def evaluate(self, row, next_row, consts=(), pub=(), x=0):
-        """[n_constraints] values mod p at one row: row / next_row / consts / pub are sequences of integers."""
+    def _values(self, row, next_row, consts, pub, x):
         val = [None] * len(self._order)
         for e in self._order:
             if e.op == OP_LOC:
@@ -182,11 +216,21 @@ class Builder:
             else:
                 v = val[e.a.n] * val[e.c.n]
             val[e.n] = v % P
+        return val
+
+    def evaluate(self, row, next_row, consts=(), pub=(), x=0):
+        """[n_constraints] values mod p at one row: row / next_row / consts / pub are sequences of integers."""
+        val = self._values(row, next_row, consts, pub, x)
         out = [0] * self.n_constraints
         for u in self.units:
             for index, e in u:
                 out[index] = (out[index] + val[e.n]) % P
         return out
+
+    def evaluate_ports(self, row, next_row, consts=(), pub=(), x=0):
+        """Per port (f, [t_j]) mod p at one row, over Python integers."""
+        val = self._values(row, next_row, consts, pub, x)
+        return [(val[f.n], [val[e.n] for e in t]) for f, t in self.ports]
 
     # ---- the words
     def _schedule(self, emits):
@@ -215,7 +259,8 @@ class Builder:
             steps.append(("drop", leaves))
         return steps
 
-    def _assemble_unit(self, emits):
+    def _assemble_unit(self, emits, port=None):
+        """port: None for a constraint unit; else the unit of that port, whose `emits` are (slot, Expr)."""
         steps = self._schedule(emits)
         # last use of every value instance; a dropped leaf's next load is a new instance
         inst, cur = [], {}   # step number -> instance id of the node it defines; node -> live instance
@@ -249,7 +294,10 @@ class Builder:
                 if last_use[r] == i:
                     free.append(reg.pop(r))
             if s[0] == "emit":
-                words.append(OP_EMIT | self._family_of(s[1])[2] << 8 | s[1] << 16 | regs[0] << 40)
+                if port is None:
+                    words.append(OP_EMIT | self._family_of(s[1])[2] << 8 | s[1] << 16 | regs[0] << 40)
+                else:
+                    words.append(OP_PORT | s[1] << 8 | port << 16 | regs[0] << 40)
                 continue
             e, me = s[1], inst[i]
             if me not in last_use:
@@ -268,8 +316,9 @@ class Builder:
                 words.append(e.op | d << 8 | regs[0] << 16 | regs[1] << 40)
         return words, top
 
-    def assemble(self):
-        """The program as numpy uint64 words (bp_air_register's input)."""
+    def assemble(self, check_ports=True):
+        """The program as numpy uint64 words (bp_air_register's input): "BPGAIRP1", or "BPGAIRP2" when the builder has a
+        port.  check_ports=False leaves the ports' degree rules to bp_air_register (the tests of its refusals)."""
         if not self.families or not self.units:
             raise ValueError("a program has at least one family and one unit")
         code, offsets, n_regs = [], [0], 1
@@ -278,12 +327,24 @@ class Builder:
             code += words
             offsets.append(len(code))
             n_regs = max(n_regs, top)
+        for l, (f, t) in enumerate(self.ports):
+            words, top = self._assemble_unit([(0, f)] + [(1 + j, e) for j, e in enumerate(t)], port=l)
+            code += words
+            offsets.append(len(code))
+            n_regs = max(n_regs, top)
         if n_regs > MAX_REGS:
             raise ValueError("the program needs %d registers, the library takes %d: split the unit" % (n_regs, MAX_REGS))
-        degree = self.degree if self.degree is not None else max(f[3] for f in self.families)
+        # the declared degree, else what the families and the ports' derived constraints (f f - f, z - z' term) need
+        degree = self.degree if self.degree is not None else max(
+            [f[3] for f in self.families] + [max(2 * f.degree, 1 + f.degree + max(e.degree for e in t)) for f, t in self.ports])
         for f in self.families:
             self._check_boundary(f[2], f[3], degree)
         hdr = [MAGIC, self.n_cols, self.n_const, self.n_public, degree, self.n_constraints, len(self.families), n_regs,
                len(self.units), len(code)]
         fam = [w for f in self.families for w in f]
+        if self.ports:
+            if check_ports:
+                self._check_ports(degree)
+            hdr = [MAGIC2] + hdr[1:] + [len(self.ports)]
+            fam += [len(t) for _, t in self.ports]
         return np.array(hdr + fam + offsets + code, dtype=np.uint64)

@@ -1383,6 +1383,9 @@ constexpr uint32_t MEM_Z = 0, MEM_N_AUX = 2, MEM_N_CONSTRAINTS = 5;
 constexpr uint32_t WORD_TUPLE = 11;  // is_read, address, timestamp, eight value limbs
 // AIR 8 (plonk): per challenge set c, column 10 c = Z_c and 10 c + k = the k-th partial product, k = 1..9
 constexpr uint32_t PLONK_N_AUX = 20, PLONK_N_CONSTRAINTS = 22, PLONK_CHUNK = 8, PLONK_CHUNKS = 10;
+// Not an AIR: the id under which aux_suffix_product_kernel multiplies up terms that another kernel has left in the
+// product columns themselves, every column a product (a registered program's ports: air_program.hip), as AIR 8's are.
+constexpr uint32_t TERMS_IN_COLUMN = COUNT;
 }  // namespace ctl
 
 // The descriptor of a built-in AIR: everything about it that is data, once.  n_constraints, n_units, ctl::n_aux,
@@ -1582,6 +1585,7 @@ template <class T, class Row>
 GL_HD T product_term(const Shape& s, uint32_t col, const uint64_t ctl[4], const Row& row) {
   typedef Ops<T> F;
   if (s.air_id == PLONK) return row.aux(col);  // the row's total num / den, left in the column by plonk_chunk_ratios_kernel
+  if (s.air_id == TERMS_IN_COLUMN) return row.aux(col);  // a port's term, left in the column by program_port_terms_kernel
   if (s.air_id == SYNTHETIC) {
     const T beta = F::k(ctl[2 * (col & 1)]), gamma = F::k(ctl[2 * (col & 1) + 1]);
     return F::add(F::add(gamma, row.loc(8 * col)), F::mul(beta, row.loc(8 * col + 1)));

@@ -36,7 +36,10 @@ int refuse(size_t off, const char* fmt, ...) {
 // Fills *p from the words or refuses them, naming the offending word.
 int validate(const uint64_t* w, size_t n_words, Program* p) {
   if (!w || n_words < HDR_WORDS) REFUSE(0, "a program has at least the %u header words, got %zu", HDR_WORDS, n_words);
-  if (w[0] != MAGIC) REFUSE(0, "bad magic (expected \"BPGAIRP1\")");
+  if (w[0] != MAGIC && w[0] != MAGIC2) REFUSE(0, "bad magic (expected \"BPGAIRP1\" or \"BPGAIRP2\")");
+  const bool p2 = w[0] == MAGIC2;
+  const size_t hdr_words = p2 ? HDR_WORDS2 : HDR_WORDS;
+  if (n_words < hdr_words) REFUSE(0, "a \"BPGAIRP2\" program has at least the %u header words, got %zu", HDR_WORDS2, n_words);
   struct Range { uint32_t* out; uint64_t lo, hi; const char* name; };
   const Range hdr[9] = {{&p->n_cols, MIN_COLS, MAX_COLS, "n_cols"}, {&p->n_const, 0, MAX_CONST, "n_const"},
                         {&p->n_public, 0, MAX_PUBLIC, "n_public"}, {&p->degree, 1, MAX_DEGREE, "degree"},
@@ -48,8 +51,25 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
              (unsigned long long)hdr[i].hi);
     *hdr[i].out = (uint32_t)w[1 + i];
   }
-  const size_t fam0 = HDR_WORDS, off0 = fam0 + 4 * (size_t)p->n_families, code0 = off0 + p->n_units + 1, total = code0 + p->n_code;
+  if (p2) {
+    if (w[10] > MAX_PORTS) REFUSE(10, "n_ports = %llu is outside 0 .. %u", (unsigned long long)w[10], MAX_PORTS);
+    p->n_ports = (uint32_t)w[10];
+    // bp_air_describe lists the program's families and then the ports': five per port where they fit, else three
+    // interleaved ones for all ports, which always fit behind MAX_FAMILIES_WITH_PORTS of the program's own
+    if (p->n_ports && p->n_families > MAX_FAMILIES_WITH_PORTS)
+      REFUSE(6, "n_families = %u: a program with ports has at most %u families of its own (bp_air_describe lists the ports' behind them)",
+             p->n_families, MAX_FAMILIES_WITH_PORTS);
+  }
+  const size_t fam0 = hdr_words, port0 = fam0 + 4 * (size_t)p->n_families, off0 = port0 + p->n_ports,
+               code0 = off0 + p->n_units + p->n_ports + 1, total = code0 + p->n_code;
+  const uint32_t n_all_units = p->n_units + p->n_ports;
   if (n_words != total) REFUSE(9, "the header's sizes make a program of %zu words, got %zu", total, n_words);
+  p->off0 = off0;
+  for (uint32_t l = 0; l < p->n_ports; l++) {
+    if (w[port0 + l] < 1 || w[port0 + l] > MAX_TUPLE)
+      REFUSE(port0 + l, "port %u: n_tuple = %llu is outside 1 .. %u", l, (unsigned long long)w[port0 + l], MAX_TUPLE);
+    p->n_tuple[l] = (uint32_t)w[port0 + l];
+  }
   // the family table tiles [0, n_constraints)
   std::vector<uint8_t> fam_of(p->n_constraints);
   uint64_t next = 0;
@@ -79,21 +99,36 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
            (unsigned long long)next, p->n_constraints);
   // the unit table tiles the code
   if (w[off0] != 0) REFUSE(off0, "the first unit starts at code word %llu, not 0", (unsigned long long)w[off0]);
-  for (uint32_t u = 0; u < p->n_units; u++)
+  for (uint32_t u = 0; u < n_all_units; u++)
     if (w[off0 + u + 1] <= w[off0 + u] || w[off0 + u + 1] > p->n_code)
       REFUSE(off0 + u + 1, "unit %u ends at code word %llu: units are non-empty, in order, inside the %u code words", u,
              (unsigned long long)w[off0 + u + 1], p->n_code);
-  if (w[off0 + p->n_units] != p->n_code)
-    REFUSE(off0 + p->n_units, "the last unit ends at code word %llu of %u", (unsigned long long)w[off0 + p->n_units], p->n_code);
+  if (w[off0 + n_all_units] != p->n_code)
+    REFUSE(off0 + n_all_units, "the last unit ends at code word %llu of %u", (unsigned long long)w[off0 + n_all_units], p->n_code);
   // the code, unit by unit: operands in range, registers written before they are read, degrees
   std::vector<uint8_t> emitted(p->n_constraints, 0);
-  for (uint32_t u = 0; u < p->n_units; u++) {
+  for (uint32_t u = 0; u < n_all_units; u++) {
     int deg[MAX_REGS];  // -1: not written in this unit
     for (uint32_t r = 0; r < MAX_REGS; r++) deg[r] = -1;
+    // a port unit: the degree of every slot written so far (-1: never), slot 0 the filter
+    const bool port_unit = u >= p->n_units;
+    const uint32_t port = u - p->n_units;
+    int slot_deg[MAX_TUPLE + 1];
+    for (uint32_t j = 0; j <= MAX_TUPLE; j++) slot_deg[j] = -1;
     for (size_t pc = code0 + w[off0 + u], end = code0 + w[off0 + u + 1]; pc < end; pc++) {
       const uint64_t c = w[pc];
       const uint32_t op = (uint32_t)c & 0xff, d = (uint32_t)(c >> 8) & 0xff, a = (uint32_t)(c >> 16) & 0xffffff, b = (uint32_t)(c >> 40);
-      if (op >= OP_COUNT) REFUSE(pc, "unknown operation %u", op);
+      if (op >= (p2 ? OP_COUNT2 : OP_COUNT)) REFUSE(pc, "unknown operation %u", op);
+      if (op == OP_EMIT && port_unit) REFUSE(pc, "emit in port unit %u: a port's constraints are the library's", port);
+      if (op == OP_PORT) {
+        if (!port_unit) REFUSE(pc, "port in constraint unit %u: ports are fed by their own units", u);
+        if (a != port) REFUSE(pc, "the unit of port %u feeds port %u", port, a);
+        if (d > p->n_tuple[port]) REFUSE(pc, "slot %u of port %u, whose tuple has %u elements (slots 0 .. %u)", d, port, p->n_tuple[port], p->n_tuple[port]);
+        if (b >= p->n_regs) REFUSE(pc, "register %u of %u", b, p->n_regs);
+        if (deg[b] < 0) REFUSE(pc, "register %u is read before unit %u writes it", b, u);
+        if (deg[b] > slot_deg[d]) slot_deg[d] = deg[b];
+        continue;
+      }
       if (op != OP_EMIT && d >= p->n_regs) REFUSE(pc, "destination register %u of %u", d, p->n_regs);
       auto reads = [&](uint32_t r) -> int {
         if (r >= p->n_regs) return refuse(pc, "register %u of %u", r, p->n_regs);
@@ -138,6 +173,25 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
         }
       }
     }
+    if (port_unit) {
+      int deg_t = 0;
+      for (uint32_t j = 0; j <= p->n_tuple[port]; j++) {
+        if (slot_deg[j] < 0) REFUSE(off0 + u, "port %u: slot %u (%s) is never written", port, j, j ? "a tuple element" : "the filter");
+        if (j && slot_deg[j] > deg_t) deg_t = slot_deg[j];
+      }
+      const int deg_f = slot_deg[0];
+      p->port_deg_f[port] = (uint32_t)deg_f;
+      p->port_deg_t[port] = (uint32_t)deg_t;
+      // f f - f on all rows, z - z' term on transitions, z - term on the last row (term = 1 + f (gamma + v - 1))
+      if (2 * deg_f > (int)p->degree)
+        REFUSE(off0 + u, "degree violation: port %u has a filter of degree %d, f f - f must fit the program's degree %u", port, deg_f, p->degree);
+      if (1 + deg_f + deg_t > (int)p->degree)
+        REFUSE(off0 + u, "degree violation: port %u has a filter of degree %d and a tuple of degree %d, z - z' term must fit the program's "
+               "degree %u", port, deg_f, deg_t, p->degree);
+      if (deg_f + deg_t > (int)boundary_degree(p->degree))
+        REFUSE(off0 + u, "degree violation: port %u has a filter of degree %d and a tuple of degree %d, the last-row constraint z - term "
+               "takes degree %u in a program of degree %u", port, deg_f, deg_t, boundary_degree(p->degree), p->degree);
+    }
   }
   for (uint32_t i = 0; i < p->n_constraints; i++)
     if (!emitted[i]) REFUSE(fam0 + 4 * (size_t)fam_of[i], "constraint %u (family %u) is never emitted", i, fam_of[i]);
@@ -172,8 +226,9 @@ int device_image(const std::shared_ptr<const Program>& p, const uint64_t** d_ima
       return BP_OK;
     }
   uint64_t* d = nullptr;
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d), p->image_words() * 8));
-  if (hipMemcpy(d, p->image(), p->image_words() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+  const std::vector<uint64_t> image = p->image();
+  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d), image.size() * 8));
+  if (hipMemcpy(d, image.data(), image.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(d);
     return fail(BP_ERR_DEVICE, "upload of AIR program 0x%08x failed", p->air_id);
   }
@@ -193,6 +248,16 @@ uint32_t any_n_units(const Shape& s) {
   if (!prog::is_registered(s.air_id)) return n_units(s);
   const auto p = prog::find(s.air_id);
   return p ? p->n_units : 0;
+}
+uint32_t any_n_aux(const Shape& s) {
+  if (!prog::is_registered(s.air_id)) return ctl::n_aux(s);
+  const auto p = prog::find(s.air_id);
+  return p ? p->n_aux() : 1;
+}
+uint32_t any_n_ctl_constraints(const Shape& s) {
+  if (!prog::is_registered(s.air_id)) return ctl::n_constraints(s);
+  const auto p = prog::find(s.air_id);
+  return p ? p->n_ctl_constraints() : 2;
 }
 
 }  // namespace air

@@ -14,6 +14,12 @@
 // The value an instruction has just written also stays in a VGPR (`acc`): an operand that names the register written
 // last is read from there, which takes half the LDS reads out of the chains  v = v + v, v = v + b, e = e - c  these
 // programs mostly are.
+//
+// Lookup ports ("BPGAIRP2").  A port unit is one more unit of the same loop whose `port` words feed a PortAcc (the filter
+// and the tuple compressed by both challenge sets: 6 VGPRs) instead of the fold; the slot of a `port` word is wave-uniform,
+// so the beta-power table is read like the code, with scalar loads.  K5 then hands the port's five constraints to the
+// same DevEmit (prog::port_constraints).  The witness of a port's two product columns is program_port_terms_kernel (the
+// terms, a lane per trace row) followed by aux_suffix_product_kernel in the form AIR 8 uses (stark_kernels.hip).
 #include <mutex>
 #include "air_check_dev.cuh"
 #include "air_program.hpp"
@@ -43,7 +49,11 @@ __device__ __forceinline__ LdsRegs lds_regs_of_lane() { return LdsRegs{lds_regs 
 
 // image: the program's unit offsets (n_air_units + 1 words), then its code (prog::Program::image).
 // grid = (rows / 256, workgroup rows, proofs) as quotient_air_kernel's; dynamic LDS = n_regs * 2 KiB.
-__global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg::QuotArgs> batch, const uint64_t* __restrict__ image) {
+// n_code: the program's code words; the port units' offsets (n_ports + 1 words) follow them in the image.
+// PORTS: the program has lookup ports; without them the kernel is the one it was before ports existed.
+template <bool PORTS>
+__global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg::QuotArgs> batch, const uint64_t* __restrict__ image,
+                                                               uint32_t n_code) {
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
   const bpg::QuotArgs& q = batch.a[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
@@ -63,6 +73,12 @@ __global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg:
   for (uint32_t u = u0; u < u1; u++) {
     if (u < q.n_air_units) {
       prog::run<uint64_t>(code, (uint32_t)image[u], (uint32_t)image[u + 1], regs, row, out);
+    } else if constexpr (PORTS) {
+      const uint32_t l = u - q.n_air_units;
+      const uint64_t* __restrict__ port_off = code + n_code;
+      prog::PortAcc<uint64_t> acc{q.apow + 2 * (size_t)q.n_constraints + 48, 0, 0, 0};
+      prog::run_port<uint64_t>(code, (uint32_t)port_off[l], (uint32_t)port_off[l + 1], regs, row, acc);
+      prog::port_constraints<uint64_t>(q.n_air_constraints + prog::PORT_CONSTRAINTS * l, l, q.ctl.v, acc, row, out);
     } else {
       // "a table no lookup is built for": the one constant running product AIR 4 and AIR 7 have
       const bpg::air::Shape cs{bpg::air::ARITHMETIC, q.n_cols, q.n_const, q.deg_pow};
@@ -106,6 +122,43 @@ __global__ void __launch_bounds__(256) air_check_program_kernel(bpg::CheckArgs a
   flag_rows(a, pos, (r0 | r1) != 0);
 }
 
+// beta_c^j, j < 128, c < 2, behind the per-coset words of every proof's alpha-power table.  One workgroup of 256 lanes
+// per proof of the batch.
+__global__ void __launch_bounds__(256) beta_table_kernel(bpg::BatchOf<bpg::QuotArgs> batch) {
+  const bpg::QuotArgs& q = batch.a[blockIdx.x];
+  const uint32_t t = threadIdx.x;
+  const_cast<uint64_t*>(q.apow)[2 * (size_t)q.n_constraints + 48 + t] = gl::pow(q.ctl.v[t >> 7 ? 2 : 0], t & (prog::MAX_TUPLE - 1));
+}
+
+// The terms of a program's ports on the trace domain: a lane owns a trace row (the checker's row accessor: nxt wraps,
+// x = w^i), runs the port units of its workgroup row and writes term_0, term_1 of each into the port's two auxiliary
+// columns, where aux_suffix_product_kernel multiplies them up.  The beta powers travel as a kernel argument (2 KiB,
+// read wave-uniformly).  grid = (ceil(n / 256), n_ports); dynamic LDS = n_regs * 2 KiB.
+struct PortTermsArgs {
+  const uint64_t *trace, *consts;
+  uint64_t* aux;  // [2 * n_ports][n]
+  uint64_t stride;
+  uint32_t log_n, n_units, n_code;
+  uint64_t ctl[4], pub[4];
+};
+struct BetaTab {
+  uint64_t v[2 * prog::MAX_TUPLE];
+};
+__global__ void __launch_bounds__(256) program_port_terms_kernel(PortTermsArgs a, BetaTab bt, const uint64_t* __restrict__ image) {
+  const uint64_t n = (uint64_t)1 << a.log_n;
+  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (pos >= n) return;
+  const CheckRow row{a.trace, a.consts, a.stride, n, pos, (pos + 1) & (n - 1), gl::pow(gl::root(a.log_n), pos), a.pub};
+  LdsRegs regs = lds_regs_of_lane();
+  const uint64_t* __restrict__ code = image + a.n_units + 1;
+  const uint64_t* __restrict__ port_off = code + a.n_code;
+  const uint32_t l = blockIdx.y;
+  prog::PortAcc<uint64_t> acc{bt.v, 0, 0, 0};
+  prog::run_port<uint64_t>(code, (uint32_t)port_off[l], (uint32_t)port_off[l + 1], regs, row, acc);
+  a.aux[(uint64_t)(2 * l) * n + pos] = acc.term(0, a.ctl);
+  a.aux[(uint64_t)(2 * l + 1) * n + pos] = acc.term(1, a.ctl);
+}
+
 // A dynamic LDS allocation above 64 KiB has to be asked for before the launch: once per device and kernel, for the
 // validator's limit (prog::MAX_REGS registers), so every registered program fits.
 int allow_large_lds() {
@@ -117,8 +170,10 @@ int allow_large_lds() {
   for (int d : done)
     if (d == dev) return BP_OK;
   const int bytes = (int)(prog::MAX_REGS * 256 * 8);
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&air_check_program_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&program_port_terms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   done.push_back(dev);
   return BP_OK;
 }
@@ -141,7 +196,33 @@ int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer&
   std::shared_ptr<const prog::Program> p;
   const uint64_t* d_image = nullptr;
   if (int rc = program_of(q.air_id, q.n_air_units, &p, &d_image)) return rc;
-  BPG_LAUNCH_TIMED(kt, quotient_program_kernel, grid, 256, p->n_regs * 256 * 8, st, qb, d_image);
+  if (q.n_ports != p->n_ports) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x: the launch was sized for another program", q.air_id);
+  if (q.n_ports) BPG_LAUNCH_TIMED(kt, quotient_program_kernel<true>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
+  else BPG_LAUNCH_TIMED(kt, quotient_program_kernel<false>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
+  return BP_OK;
+}
+
+// The beta powers of every proof of a batch, beside its alpha powers: launch_quotient issues this with the alpha tables,
+// before the evaluation launch and its timer.
+int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t st) {
+  beta_table_kernel<<<batch, 256, 0, st>>>(qb);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+
+int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st) {
+  std::shared_ptr<const prog::Program> p = prog::find(air_id);
+  if (!p || !p->n_ports) return bpg::fail(BP_ERR_INVALID_INPUT, "air_id 0x%08x is no registered program with lookup ports", air_id);
+  const uint64_t* d_image = nullptr;
+  if (int rc = program_of(air_id, p->n_units, &p, &d_image)) return rc;
+  if (p->n_const && !a.consts) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x reads %u constant columns: pass them", air_id, p->n_const);
+  PortTermsArgs pa{a.trace, a.consts, a.aux, trace_stride, log_n, p->n_units, p->n_code, {}, {}};
+  for (int i = 0; i < 4; i++) { pa.ctl[i] = a.ctl.v[i]; pa.pub[i] = a.ctl.pub[i]; }
+  BetaTab bt;
+  prog::beta_powers(a.ctl.v, bt.v);
+  const dim3 grid((unsigned)((((uint64_t)1 << log_n) + 255) / 256), p->n_ports);
+  program_port_terms_kernel<<<grid, 256, p->n_regs * 256 * 8, st>>>(pa, bt, d_image);
+  BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 

@@ -247,7 +247,7 @@ int check_cfg(const StarkCfg& c) {
 }
 ProofLayout proof_layout(const StarkCfg& c) {
   ProofLayout L{};
-  L.n_aux = air::ctl::n_aux(air::Shape{c.air_id, c.n_cols, c.n_const, c.deg_pow});
+  L.n_aux = air::any_n_aux(air::Shape{c.air_id, c.n_cols, c.n_const, c.deg_pow});
   L.n_quot = 2u << c.rate_bits;
   L.n_layers = n_fri_layers(c);
   L.final_len = 1u << (c.log_n - L.n_layers * c.arity_bits);
@@ -482,7 +482,7 @@ int quotient_args(const StarkCfg& cfg, const Ctl& ctl, uint64_t alpha0, uint64_t
   QuotArgs& qa = *out;
   const uint32_t log_n = cfg.log_n, r = cfg.rate_bits, R = 1u << r, C = cfg.n_cols, K = cfg.n_const;
   const air::Shape shape{cfg.air_id, C, K, cfg.deg_pow};
-  const uint32_t A = air::ctl::n_aux(shape);
+  const uint32_t A = air::any_n_aux(shape);
   const uint64_t N = (uint64_t)1 << log_n, M = N << r;
   const uint64_t wM = gl::root(log_n + r), wN = gl::root(log_n);
   qa.trace_stride = qa.aux_stride = qa.const_stride = M;
@@ -492,12 +492,15 @@ int quotient_args(const StarkCfg& cfg, const Ctl& ctl, uint64_t alpha0, uint64_t
   // the constraint list and its units (air.hpp): the AIR's, then the table's lookups (air::ctl).  The synthetic
   // table's many product columns are sliced into units; a real table's few lookup columns are one unit.
   qa.n_air_constraints = air::any_n_constraints(shape);
-  qa.n_constraints = qa.n_air_constraints + air::ctl::n_constraints(shape);
+  qa.n_constraints = qa.n_air_constraints + air::any_n_ctl_constraints(shape);
   qa.side_rows = cfg.air_id == air::PLONK ? 1 : 0;
   qa.n_air_units = air::any_n_units(shape) - qa.side_rows;
   qa.aux_per_unit = cfg.air_id == air::SYNTHETIC ? std::max<uint32_t>(16, (A + 15) / 16) : A;
   // (AIR 8's copy constraints ride in its own ten units, next to the gates that read the same wires: no lookup unit)
   qa.n_ctl_units = cfg.air_id == air::PLONK ? 0 : (A + qa.aux_per_unit - 1) / qa.aux_per_unit;
+  // a registered program's ports are a unit each (air_program.hpp); without ports it has the one constant product
+  qa.n_ports = air::prog::is_registered(cfg.air_id) && A > 1 ? A / 2 : 0;
+  if (qa.n_ports) qa.n_ctl_units = qa.n_ports;
   // One pass (the alpha fold never leaves the registers) once the rows alone fill the chip: 2048 workgroups of
   // 256 lanes = 2 per SIMD.  Shorter tables spread their units over grid.y until the launch has that many.
   // While several provers share the device nothing needs filling: one pass, one launch fewer on the proof's
@@ -609,7 +612,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   ARENA_ALLOC(d_qc, (size_t)B * Q * N);  // chunk coefficients: live until the end (quotient oracle)
   const size_t mark_tmp = w.arena.mark();
   {
-    const size_t cpow_words = 2 * (size_t)qa[0].n_constraints + 48, part_words = quotient_partial_words(qa[0]) + 1;
+    const size_t cpow_words = quotient_table_words(qa[0]), part_words = quotient_partial_words(qa[0]) + 1;
     ARENA_ALLOC(d_cpow, B * cpow_words);
     ARENA_ALLOC(d_partial, B * part_words);
     ARENA_ALLOC(d_qvals, (size_t)B * 2 * M);

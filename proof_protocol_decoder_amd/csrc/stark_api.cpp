@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 #include "prover.hpp"
 
@@ -77,6 +78,309 @@ void park_worker(Worker* w) {
   delete w;
 }
 }  // namespace
+
+// ---- table sets: several caller traces linked port to port, proven on one transcript (include/bpg.h) ---------
+
+namespace {
+constexpr uint64_t SET_MAGIC = 0x3154455354475042ULL;  // "BPGTSET1"
+constexpr uint32_t SET_MAX_TABLES = 8, SET_MAX_LINKS = 16, SET_MAX_LOOKING = 8;
+
+// the lookup ports of a member: a registered program's own, a built-in's product columns in air::DESC order
+// (port l = columns first_product + 2l + c); 0: the id is no side of any lookup
+uint32_t set_ports_of(uint32_t air_id, uint32_t* first_product) {
+  *first_product = 0;
+  if (const auto p = air::prog::find(air_id)) return p->n_ports;
+  const air::Desc* d = air::info(air_id);
+  if (!d || !d->in_pair) return 0;
+  *first_product = d->first_product;
+  return (d->n_aux - d->first_product) / 2;
+}
+struct SetShape {
+  StarkCfg cfg[SET_MAX_TABLES];
+  uint32_t n_ports[SET_MAX_TABLES], first_product[SET_MAX_TABLES];
+};
+// the statement of a set, refused or accepted without touching a device
+int check_set(const char* who, const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, SetShape* out) {
+  if (!tables || !links) return fail(BP_ERR_INVALID_INPUT, "%s: null argument", who);
+  if (n_tables < 1 || n_tables > SET_MAX_TABLES) return fail(BP_ERR_INVALID_INPUT, "%s: a set has 1 .. %u tables, got %u", who, SET_MAX_TABLES, n_tables);
+  if (n_links < 1 || n_links > SET_MAX_LINKS) return fail(BP_ERR_INVALID_INPUT, "%s: a set has 1 .. %u links, got %u", who, SET_MAX_LINKS, n_links);
+  uint32_t used[SET_MAX_TABLES][16] = {};
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const bp_stark_cfg& c = tables[t].cfg;
+    out->cfg[t] = StarkCfg{c.log_n, c.n_cols, c.n_const, c.deg_pow, c.rate_bits, c.cap_height, c.num_queries, c.pow_bits, c.arity_bits,
+                           c.final_poly_bits, tables[t].air_id};
+    if (int rc = check_cfg(out->cfg[t])) {
+      const std::string why = bp_last_error();
+      return fail(rc, "%s: table %u: %s", who, t, why.c_str());
+    }
+    out->n_ports[t] = set_ports_of(tables[t].air_id, &out->first_product[t]);
+    if (!out->n_ports[t])
+      return fail(BP_ERR_INVALID_INPUT, "%s: table %u: air_id %u (0x%08x) has no lookup port: a member is a registered program with ports or "
+                  "one of the built-in AIRs 1, 2, 3, 5, 6", who, t, tables[t].air_id, tables[t].air_id);
+    if (tables[t].pub)
+      for (int j = 0; j < 4; j++)
+        if (tables[t].pub[j] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "%s: table %u: non-canonical public input", who, t);
+    const auto program = air::prog::find(tables[t].air_id);
+    if (!tables[t].pub && (tables[t].air_id == air::PLONK || (program && program->n_public)))
+      return fail(BP_ERR_INVALID_INPUT, "%s: table %u: the AIR reads public inputs: pass four words", who, t);
+  }
+  for (uint32_t k = 0; k < n_links; k++) {
+    const bp_set_link& l = links[k];
+    if (l.n_looking < 1 || l.n_looking > SET_MAX_LOOKING)
+      return fail(BP_ERR_INVALID_INPUT, "%s: link %u has %u looking ports (1 .. %u)", who, k, l.n_looking, SET_MAX_LOOKING);
+    for (uint32_t m = 0; m <= l.n_looking; m++) {
+      const bp_set_port& e = m < l.n_looking ? l.looking[m] : l.looked;
+      if (e.table >= n_tables) return fail(BP_ERR_INVALID_INPUT, "%s: link %u names table %u of %u", who, k, e.table, n_tables);
+      if (e.port >= out->n_ports[e.table])
+        return fail(BP_ERR_INVALID_INPUT, "%s: link %u names port %u of table %u, which has %u", who, k, e.port, e.table, out->n_ports[e.table]);
+      if (used[e.table][e.port]++)
+        return fail(BP_ERR_INVALID_INPUT, "%s: port %u of table %u is named twice (link %u): a port is in exactly one link", who, e.port, e.table, k);
+    }
+  }
+  for (uint32_t t = 0; t < n_tables; t++)
+    for (uint32_t l = 0; l < out->n_ports[t]; l++)
+      if (!used[t][l])
+        return fail(BP_ERR_INVALID_INPUT, "%s: port %u of table %u is in no link: an unlinked port proves nothing about the other tables (prove "
+                    "the table alone with bp_stark_prove_trace)", who, l, t);
+  return BP_OK;
+}
+// the statement, as both sides observe it before any commitment
+int observe_set(Challenger& ch, const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, const SetShape& sh) {
+  ch.observe(SET_MAGIC % gl::P);
+  ch.observe(n_tables);
+  ch.observe(n_links);
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const StarkCfg& c = sh.cfg[t];
+    const uint64_t w[5] = {c.air_id, c.log_n, c.n_cols, c.n_const, c.rate_bits};
+    ch.observe(w, 5);
+    if (air::prog::is_registered(c.air_id)) {  // the whole digest: a verifier does not trust 31 bits of id
+      const auto p = air::prog::find(c.air_id);
+      if (!p) return fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x was unregistered", c.air_id);
+      for (int j = 0; j < 8; j++) {
+        uint32_t d;
+        std::memcpy(&d, p->digest + 4 * j, 4);
+        ch.observe(d);
+      }
+    }
+  }
+  for (uint32_t k = 0; k < n_links; k++) {
+    ch.observe(links[k].n_looking);
+    for (uint32_t m = 0; m <= links[k].n_looking; m++) {
+      const bp_set_port& e = m < links[k].n_looking ? links[k].looking[m] : links[k].looked;
+      ch.observe(e.table);
+      ch.observe(e.port);
+    }
+  }
+  return BP_OK;
+}
+// Every link on the first-row openings: for both challenge sets the product of the looking ports' values is the looked
+// port's (check_lookups' identity, proofgen.cpp, with a looking count).
+int check_links(const SetShape& sh, const bp_set_link* links, uint32_t n_links, const std::vector<uint64_t>* proof) {
+  for (uint32_t k = 0; k < n_links; k++) {
+    const bp_set_link& l = links[k];
+    for (uint32_t c = 0; c < 2; c++) {
+      auto first_row = [&](const bp_set_port& e) {
+        const ProofLayout L = proof_layout(sh.cfg[e.table]);
+        const uint64_t* v = proof[e.table].data() + L.open_first + 2 * (size_t)(sh.first_product[e.table] + 2 * e.port + c);
+        return gl::Ext{v[0], v[1]};
+      };
+      gl::Ext a = gl::ext(1);
+      for (uint32_t m = 0; m < l.n_looking; m++) a = gl::mul(a, first_row(l.looking[m]));
+      const gl::Ext b = first_row(l.looked);
+      if (a.c0 != b.c0 || a.c1 != b.c1)
+        return fail(BP_ERR_VERIFY, "link %u does not hold (challenge set %u): port %u of table %u%s asks for tuples that port %u of table %u "
+                    "does not expose", k, c, l.looking[0].port, l.looking[0].table, l.n_looking > 1 ? " (and the link's other looking ports)" : "",
+                    l.looked.port, l.looked.table);
+    }
+  }
+  return BP_OK;
+}
+size_t table_arena_bytes(const StarkCfg& c, bool packed) {
+  const uint64_t N = (uint64_t)1 << c.log_n, M = N << c.rate_bits;
+  const size_t cols = (size_t)c.n_cols + c.n_const + c.n_cols / 8 + (2u << c.rate_bits) + 64;
+  return cols * (2 * N + M) * 8 + (size_t)80 * M * 8 + ((size_t)c.n_cols / 32 + 64) * 8 * N * 8 + (packed ? (size_t)c.n_cols * N * 8 : 0);
+}
+}  // namespace
+
+extern "C" {
+
+int bp_stark_prove_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, uint32_t flags,
+                             int device, uint8_t** out, size_t* out_len) try {
+  if (!out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_table_set: null argument");
+  if (flags & ~(uint32_t)BP_SET_SKIP_LINK_CHECK) return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_table_set: unknown flags 0x%x", flags);
+  SetShape sh;
+  int rc = check_set("bp_stark_prove_table_set", tables, n_tables, links, n_links, &sh);
+  if (rc) return rc;
+  size_t bytes = 64u << 20;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const uint64_t N = (uint64_t)1 << sh.cfg[t].log_n;
+    if (!tables[t].d_trace || (sh.cfg[t].n_const && !tables[t].d_consts))
+      return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_table_set: table %u: null trace, or the AIR reads %u constant columns and none are given", t,
+                  sh.cfg[t].n_const);
+    if (tables[t].stride < N)
+      return fail(BP_ERR_INVALID_INPUT, "bp_stark_prove_table_set: table %u: column stride %llu is shorter than the %llu-row trace", t,
+                  (unsigned long long)tables[t].stride, (unsigned long long)N);
+    bytes += table_arena_bytes(sh.cfg[t], tables[t].stride != N);
+  }
+  Worker* wp = take_worker(device, bytes, &rc);
+  if (!wp) return rc;
+  Worker& w = *wp;
+  struct Parker {
+    Worker* w;
+    ~Parker() { park_worker(w); }
+  } parker{wp};
+  auto body = [&]() -> int {
+    Challenger ch;
+    int r2 = observe_set(ch, tables, n_tables, links, n_links, sh);
+    if (r2) return r2;
+    // every commitment before the lookup challenges exist: per table the constants (if any), the trace, the public inputs
+    Committed consts[SET_MAX_TABLES], trace[SET_MAX_TABLES];
+    const uint64_t* d_tv[SET_MAX_TABLES];
+    Ctl ctl[SET_MAX_TABLES];
+    for (uint32_t t = 0; t < n_tables; t++) {
+      const StarkCfg& c = sh.cfg[t];
+      const uint64_t N = (uint64_t)1 << c.log_n;
+      if (c.n_const) {
+        if ((r2 = commit(w, tables[t].d_consts, c.n_const, c.log_n, c.rate_bits, c.cap_height, false, &consts[t]))) return r2;
+        ch.observe(consts[t].cap.data(), consts[t].cap.size());
+      }
+      d_tv[t] = tables[t].d_trace;
+      if (tables[t].stride != N) {
+        uint64_t* packed = w.arena.alloc_words((size_t)c.n_cols * N);
+        if (!packed) return fail(BP_ERR_DEVICE, "arena exhausted");
+        BPG_HIP(hipMemcpy2DAsync(packed, N * 8, tables[t].d_trace, tables[t].stride * 8, N * 8, c.n_cols, hipMemcpyDeviceToDevice, w.stream));
+        d_tv[t] = packed;
+      }
+      if ((r2 = commit(w, d_tv[t], c.n_cols, c.log_n, c.rate_bits, c.cap_height, false, &trace[t]))) return r2;
+      ch.observe(trace[t].cap.data(), trace[t].cap.size());
+      if (tables[t].pub)
+        for (int j = 0; j < 4; j++) ctl[t].pub[j] = tables[t].pub[j];
+      ch.observe(ctl[t].pub, 4);
+    }
+    uint64_t v[4];
+    for (int i = 0; i < 4; i++) v[i] = ch.challenge();
+    // the table proofs in order, one transcript threaded through all of them (prove_tables, proofgen.cpp)
+    std::vector<uint64_t> proof[SET_MAX_TABLES];
+    for (uint32_t t = 0; t < n_tables; t++) {
+      for (int i = 0; i < 4; i++) ctl[t].v[i] = v[i];
+      const size_t mark = w.arena.mark();
+      if ((r2 = stark_prove(w, sh.cfg[t], sh.cfg[t].n_const ? &consts[t] : nullptr, trace[t], d_tv[t], ctl[t], ch, proof[t]))) return r2;
+      w.arena.release(mark);
+    }
+    if (!(flags & BP_SET_SKIP_LINK_CHECK))
+      if ((r2 = check_links(sh, links, n_links, proof))) return r2;
+    std::vector<uint64_t> blob = {SET_MAGIC, n_tables, n_links, v[0], v[1], v[2], v[3]};
+    for (uint32_t k = 0; k < n_links; k++) {
+      blob.push_back(links[k].n_looking);
+      for (uint32_t m = 0; m <= links[k].n_looking; m++) {
+        const bp_set_port& e = m < links[k].n_looking ? links[k].looking[m] : links[k].looked;
+        blob.push_back(e.table);
+        blob.push_back(e.port);
+      }
+    }
+    for (uint32_t t = 0; t < n_tables; t++) {
+      const uint64_t hdr[4] = {sh.cfg[t].air_id, sh.cfg[t].log_n, sh.cfg[t].n_cols, proof[t].size()};
+      blob.insert(blob.end(), hdr, hdr + 4);
+      blob.insert(blob.end(), proof[t].begin(), proof[t].end());
+    }
+    *out_len = blob.size() * 8;
+    *out = static_cast<uint8_t*>(std::malloc(*out_len));
+    if (!*out) return fail(BP_ERR_DEVICE, "host allocation failed");
+    std::memcpy(*out, blob.data(), *out_len);
+    return BP_OK;
+  };
+  rc = body();
+  if (rc) {
+    const std::string why = bp_last_error();  // (the wait below must not lose the message)
+    (void)hipStreamSynchronize(w.stream);
+    return fail(rc, "%s", why.c_str());
+  }
+  if ((rc = w.wait())) {  // the caller gets no buffer with a failure
+    std::free(*out);
+    *out = nullptr;
+    *out_len = 0;
+  }
+  return rc;
+}
+BPG_ABI_CATCH("bp_stark_prove_table_set")
+
+// The statement is the VERIFIER's: tables (device pointers ignored), constants caps and links are the caller's own; the
+// container only supplies the proofs.  Host only.
+int bp_stark_verify_table_set(const bp_set_table* tables, uint32_t n_tables, const uint64_t* const* const_caps, const bp_set_link* links,
+                              uint32_t n_links, const uint8_t* bytes, size_t len) try {
+  if (!bytes) return fail(BP_ERR_INVALID_INPUT, "bp_stark_verify_table_set: null argument");
+  SetShape sh;
+  int rc = check_set("bp_stark_verify_table_set", tables, n_tables, links, n_links, &sh);
+  if (rc) return rc;
+  for (uint32_t t = 0; t < n_tables; t++)
+    if (sh.cfg[t].n_const && !(const_caps && const_caps[t]))
+      return fail(BP_ERR_INVALID_INPUT, "bp_stark_verify_table_set: table %u has constant columns: pass their cap", t);
+  if (len % 8 || len < 7 * 8) return fail(BP_ERR_VERIFY, "table set: truncated");
+  const size_t n_words = len / 8;
+  std::vector<uint64_t> Wv(n_words);
+  std::memcpy(Wv.data(), bytes, len);
+  const uint64_t* W = Wv.data();
+  if (W[0] != SET_MAGIC) return fail(BP_ERR_VERIFY, "table set: bad magic (expected \"BPGTSET1\")");
+  if (W[1] != n_tables || W[2] != n_links)
+    return fail(BP_ERR_VERIFY, "table set: the container holds %llu tables and %llu links, the statement %u and %u", (unsigned long long)W[1],
+                (unsigned long long)W[2], n_tables, n_links);
+  size_t off = 7;
+  for (uint32_t k = 0; k < n_links; k++) {
+    const bp_set_link& l = links[k];
+    if (off + 3 + 2 * (size_t)l.n_looking > n_words) return fail(BP_ERR_VERIFY, "table set: truncated at link %u", k);
+    bool same = W[off] == l.n_looking;
+    for (uint32_t m = 0; same && m <= l.n_looking; m++) {
+      const bp_set_port& e = m < l.n_looking ? l.looking[m] : l.looked;
+      same = W[off + 1 + 2 * m] == e.table && W[off + 2 + 2 * m] == e.port;
+    }
+    if (!same) return fail(BP_ERR_VERIFY, "table set: link %u of the container is not link %u of the statement", k, k);
+    off += 3 + 2 * (size_t)l.n_looking;
+  }
+  std::vector<uint64_t> proof[SET_MAX_TABLES];
+  ProofLayout L[SET_MAX_TABLES];
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const StarkCfg& c = sh.cfg[t];
+    L[t] = proof_layout(c);
+    if (off + 4 > n_words) return fail(BP_ERR_VERIFY, "table set: truncated at table %u", t);
+    if (W[off] != c.air_id || W[off + 1] != c.log_n || W[off + 2] != c.n_cols || W[off + 3] != L[t].total)
+      return fail(BP_ERR_VERIFY, "table set: table %u is proven as air_id 0x%llx, 2^%llu rows x %llu columns in %llu words; the statement is "
+                  "0x%x, 2^%u x %u in %zu", t, (unsigned long long)W[off], (unsigned long long)W[off + 1], (unsigned long long)W[off + 2],
+                  (unsigned long long)W[off + 3], c.air_id, c.log_n, c.n_cols, L[t].total);
+    off += 4;
+    if (off + L[t].total > n_words) return fail(BP_ERR_VERIFY, "table set: truncated in table %u", t);
+    proof[t].assign(W + off, W + off + L[t].total);
+    off += L[t].total;
+    // the header words stark_verify does not look at: the container must be exactly what the prover wrote
+    const uint64_t* P = proof[t].data();
+    if (P[4] != L[t].n_aux || P[5] != L[t].n_quot || P[7] != c.cap_height || P[11] != c.deg_pow || P[12] != c.pow_bits || P[13] != c.arity_bits || P[15] != 0)
+      return fail(BP_ERR_VERIFY, "table set: table %u: proof header does not match the statement", t);
+  }
+  if (off != n_words) return fail(BP_ERR_VERIFY, "table set: trailing words");
+  Challenger ch;
+  if ((rc = observe_set(ch, tables, n_tables, links, n_links, sh))) return rc;
+  Ctl ctl[SET_MAX_TABLES];
+  for (uint32_t t = 0; t < n_tables; t++) {
+    if (sh.cfg[t].n_const) ch.observe(const_caps[t], L[t].cap_words);
+    ch.observe(proof[t].data() + L[t].trace_cap, L[t].cap_words);
+    if (tables[t].pub)
+      for (int j = 0; j < 4; j++) ctl[t].pub[j] = tables[t].pub[j];
+    ch.observe(ctl[t].pub, 4);
+  }
+  for (int i = 0; i < 4; i++) {
+    const uint64_t v = ch.challenge();
+    if (v != W[3 + i]) return fail(BP_ERR_VERIFY, "table set: the lookup challenges do not follow from the statement and the commitments");
+    for (uint32_t t = 0; t < n_tables; t++) ctl[t].v[i] = v;
+  }
+  for (uint32_t t = 0; t < n_tables; t++)
+    if ((rc = stark_verify(sh.cfg[t], sh.cfg[t].n_const ? const_caps[t] : nullptr, ctl[t], ch, proof[t].data(), proof[t].size()))) {
+      const std::string why = bp_last_error();
+      return fail(rc, "table set: table %u: %s", t, why.c_str());
+    }
+  return check_links(sh, links, n_links, proof);
+}
+BPG_ABI_CATCH("bp_stark_verify_table_set")
+
+}  // extern "C"
 
 extern "C" {
 
@@ -236,7 +540,11 @@ int bp_stark_prove_trace(uint32_t air_id, const bp_stark_cfg* cfg, const uint64_
   };
   rc = body();
   if (rc) (void)hipStreamSynchronize(w.stream);
-  else rc = w.wait();
+  else if ((rc = w.wait())) {  // the caller gets no buffer with a failure
+    std::free(*out);
+    *out = nullptr;
+    *out_len = 0;
+  }
   return rc;
 }
 BPG_ABI_CATCH("bp_stark_prove_trace")
@@ -302,15 +610,41 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
     out->fixed_n_cols = out->n_cols = p->n_cols;
     out->n_const_max = p->n_const;
     out->degree = p->degree;
-    out->n_aux = 1;  // "a table no lookup is built for": the constant running product AIR 4 and AIR 7 have
+    // without ports "a table no lookup is built for": the constant running product AIR 4 and AIR 7 have
+    out->n_aux = p->n_aux();
     out->n_air_constraints = p->n_constraints;
-    out->n_ctl_constraints = 2;
+    out->n_ctl_constraints = p->n_ctl_constraints();
     out->n_units = p->n_units;
     uint32_t n = 0;
     for (uint32_t f = 0; f < p->n_families; f++)
       out->families[n++] = bp_air_family{p->families[f].first_index, p->families[f].count, p->families[f].kind, p->families[f].degree};
-    if (n < 24) out->families[n++] = bp_air_family{p->n_constraints, 1, 1, 3};
-    if (n < 24) out->families[n++] = bp_air_family{p->n_constraints + 1, 1, 3, 2};
+    if (!p->n_ports) {
+      if (n < 24) out->families[n++] = bp_air_family{p->n_constraints, 1, 1, 3};
+      if (n < 24) out->families[n++] = bp_air_family{p->n_constraints + 1, 1, 3, 2};
+    }
+    // per port: the filter bit, then per challenge set the product's transition and last-row constraint, with the
+    // degrees registration propagated (air_program.hpp).  Where five families per port do not fit the description, three
+    // interleaved ones stand for all ports (period 5: the bits at b + 5l, the transitions at b + 5l + 1 and + 3, the
+    // last-row ones at b + 5l + 2 and + 4), with the largest degree among the ports.
+    if (n + air::prog::PORT_CONSTRAINTS * p->n_ports > 24) {
+      uint32_t d0 = 1, d1 = 1, d2 = 1;
+      for (uint32_t l = 0; l < p->n_ports; l++) {
+        d0 = std::max(d0, 2 * p->port_deg_f[l]);
+        d1 = std::max(d1, 1 + p->port_deg_f[l] + p->port_deg_t[l]);
+        d2 = std::max(d2, p->port_deg_f[l] + p->port_deg_t[l]);
+      }
+      out->families[n++] = bp_air_family{p->n_constraints, p->n_ports, 0, d0};
+      out->families[n++] = bp_air_family{p->n_constraints + 1, 2 * p->n_ports, 1, d1};
+      out->families[n++] = bp_air_family{p->n_constraints + 2, 2 * p->n_ports, 3, d2};
+    } else
+    for (uint32_t l = 0; l < p->n_ports; l++) {
+      const uint32_t b = p->n_constraints + air::prog::PORT_CONSTRAINTS * l, df = p->port_deg_f[l], dt = p->port_deg_t[l];
+      out->families[n++] = bp_air_family{b, 1, 0, std::max(1u, 2 * df)};
+      for (uint32_t c = 0; c < 2; c++) {
+        out->families[n++] = bp_air_family{b + 1 + 2 * c, 1, 1, 1 + df + dt};
+        out->families[n++] = bp_air_family{b + 2 + 2 * c, 1, 3, std::max(1u, df + dt)};
+      }
+    }
     out->n_families = n;
     return BP_OK;
   }
@@ -470,7 +804,7 @@ uint64_t bp_quotient_scratch_words(uint32_t air_id, const bp_stark_cfg* shape) {
   uint64_t words = 0;
   for (int loaded = 0; loaded < 2; loaded++) {
     if (quotient_args(c, ctl, 1, 1, &qa, nullptr, loaded)) return 0;
-    words = std::max<uint64_t>(words, 2 * (uint64_t)qa.n_constraints + 48 + quotient_partial_words(qa));
+    words = std::max<uint64_t>(words, quotient_table_words(qa) + quotient_partial_words(qa));
   }
   return words;
 }
@@ -493,10 +827,54 @@ int bp_quotient_eval(uint32_t air_id, const bp_stark_cfg* shape, const uint64_t*
   QuotCoset coset{};
   qa.trace_lde = d_trace_lde; qa.aux_lde = d_aux_lde; qa.const_lde = c.n_const ? d_const_lde : nullptr;
   if ((rc = quotient_args(c, ctl, alphas[0], alphas[1], &qa, &coset))) return rc;
-  qa.apow = d_scratch; qa.partial = d_scratch + 2 * (size_t)qa.n_constraints + 48; qa.qvals = d_qvals_out;
+  qa.apow = d_scratch; qa.partial = d_scratch + quotient_table_words(qa); qa.qvals = d_qvals_out;
   return launch_quotient(qa, coset, as_stream(stream));
 }
 BPG_ABI_CATCH("bp_quotient_eval")
+
+// The running products of a registered program's ports on the trace domain: what stark_prove commits as the table's
+// auxiliary columns, without a proof around it.
+int bp_air_port_products(uint32_t air_id, const bp_stark_cfg* shape, const uint64_t* d_trace, uint64_t stride, const uint64_t* d_consts,
+                         const uint64_t pub[4], const uint64_t ctl_in[4], uint64_t* d_aux_out, void* stream) try {
+  const auto program = air::prog::find(air_id);
+  if (!program || !program->n_ports)
+    return fail(BP_ERR_INVALID_INPUT, "bp_air_port_products: air_id 0x%08x is no registered program with lookup ports", air_id);
+  StarkCfg c;
+  int rc = quot_cfg(air_id, shape, &c);
+  if (rc) return rc;
+  if (!d_trace || !ctl_in || !d_aux_out || (c.n_const && !d_consts)) return fail(BP_ERR_INVALID_INPUT, "bp_air_port_products: null argument");
+  if (stride < ((uint64_t)1 << c.log_n))
+    return fail(BP_ERR_INVALID_INPUT, "bp_air_port_products: column stride %llu is shorter than the 2^%u-row trace", (unsigned long long)stride, c.log_n);
+  AuxArgs a{d_trace, d_aux_out, Ctl{}};
+  a.consts = c.n_const ? d_consts : nullptr;
+  for (int i = 0; i < 4; i++) {
+    if (ctl_in[i] >= gl::P || (pub && pub[i] >= gl::P)) return fail(BP_ERR_INVALID_INPUT, "bp_air_port_products: non-canonical challenge or public input");
+    a.ctl.v[i] = ctl_in[i];
+    a.ctl.pub[i] = pub ? pub[i] : 0;
+  }
+  if (program->n_public && !pub) return fail(BP_ERR_INVALID_INPUT, "bp_air_port_products: the AIR reads public inputs: pass four words");
+  return launch_port_products(&a, 1, air_id, c.log_n, stride, as_stream(stream));
+}
+BPG_ABI_CATCH("bp_air_port_products")
+
+// Test entry: the auxiliary columns (helpers and running products, bp_air_desc.n_aux of them, column stride 2^log_n) the
+// prover commits for a BUILT-IN table with a lookup side, from a trace of column stride 2^log_n.
+int bp_debug_air_aux(uint32_t air_id, const bp_stark_cfg* shape, const uint64_t* d_trace, const uint64_t ctl_in[4], uint64_t* d_aux_out,
+                     void* stream) try {
+  const air::Desc* ai = air::info(air_id);
+  if (!ai || !ai->in_pair) return fail(BP_ERR_INVALID_INPUT, "bp_debug_air_aux: air_id %u is no built-in AIR with a lookup side", air_id);
+  StarkCfg c;
+  int rc = quot_cfg(air_id, shape, &c);
+  if (rc) return rc;
+  if (!d_trace || !ctl_in || !d_aux_out) return fail(BP_ERR_INVALID_INPUT, "bp_debug_air_aux: null argument");
+  AuxArgs a{d_trace, d_aux_out, Ctl{}};
+  for (int i = 0; i < 4; i++) {
+    if (ctl_in[i] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "bp_debug_air_aux: non-canonical challenge");
+    a.ctl.v[i] = ctl_in[i];
+  }
+  return launch_aux(&a, 1, air_id, c.n_cols, c.log_n, as_stream(stream));
+}
+BPG_ABI_CATCH("bp_debug_air_aux")
 
 int bp_fri_fold(const uint64_t* d_values, uint32_t log_nl, uint32_t rate_bits, uint32_t arity_bits, uint64_t shift,
                 const uint64_t beta[2], uint64_t* d_out, void* stream) try {

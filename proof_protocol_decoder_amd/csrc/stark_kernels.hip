@@ -1498,12 +1498,26 @@ int launch_plonk_trace(const PlonkTraceArgs* a, uint32_t batch, uint32_t log_n, 
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
+// A registered program's ports: the interpreter leaves every port's two terms in its columns (air_program.hip), the scan
+// multiplies them up in the form AIR 8 uses, the term read from the column itself.
+int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st) {
+  if (int rc = check_batch(batch)) return rc;
+  const uint32_t n_aux = air::any_n_aux(air::Shape{air_id, 0, 0, 1});
+  for (uint32_t b = 0; b < batch; b++)
+    if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, st)) return rc;
+  const uint32_t threads = std::max(64u, std::min(1024u, 1u << log_n));
+  KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
+  BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ctl::TERMS_IN_COLUMN>, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, 0u);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
 int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_cols, uint32_t log_n, hipStream_t st) {
   const air::Shape shape{air_id, n_cols, 0, 1};
-  const uint32_t n_aux = air::ctl::n_aux(shape), p0 = air::ctl::first_product(air_id);
+  const uint32_t n_aux = air::any_n_aux(shape), p0 = air::ctl::first_product(air_id);
   if (!n_aux) return BP_OK;
   if (int rc = check_batch(batch)) return rc;
   const BatchOf<AuxArgs> ab = batch_of(a, batch);
+  if (air::prog::is_registered(air_id) && n_aux > 1) return launch_port_products(a, batch, air_id, log_n, (uint64_t)1 << log_n, st);
   if (air_id == air::KECCAK_F) {  // the helper columns first: the products read them
     keccak_ctl_helpers_kernel<<<dim3(ceil_div((uint64_t)1 << log_n, 256), 1, batch), 256, 0, st>>>(ab, log_n);
     BPG_LAUNCH_CHECK();
@@ -1551,6 +1565,8 @@ int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, 
   BPG_LAUNCH_CHECK();
   const uint32_t n_units = q.n_air_units + q.n_ctl_units, wg_rows = ceil_div(n_units, q.units_per_wg);
   const BatchOf<QuotArgs> qb = batch_of(qs, batch);
+  if (q.n_ports)
+    if (int rc = launch_beta_tables(qb, batch, st)) return rc;
   dim3 g1(ceil_div(rows, 256), wg_rows, batch);
   // algorithmic bytes: every element of the three LDE matrices read once, the two quotient columns written
   // (AIR 8 is counted with the synthetic recursion-shaped proofs it replaces)

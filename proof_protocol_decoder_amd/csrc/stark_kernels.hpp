@@ -42,9 +42,14 @@ struct QuotArgs {
   // AIR 8: its Poseidon gate (unit 10) is a pass of its own (quotient_plonk_hash_kernel: another register budget), whose
   // sums are one more row of `partial`; n_air_units then counts the ten chunk units only
   uint32_t side_rows;
+  // a registered program with lookup ports (air_program.hpp): n_ctl_units = n_ports port units, and 2 * 128 words
+  // beta_c^j follow the 48 per-coset words of apow
+  uint32_t n_ports;
   uint64_t alpha0, alpha1, g, g_inv, n_inv;
   Ctl ctl;
 };
+// the words of QuotArgs::apow: the alpha powers, the per-coset constants, a port program's beta powers
+inline size_t quotient_table_words(const QuotArgs& q) { return 2 * (size_t)q.n_constraints + 48 + (q.n_ports ? 256 : 0); }
 struct QuotCoset {  // per coset: 7*w_M^t, g_t^n - 1 and its inverse (the same for every proof of a shape)
   uint64_t g_t[16], zh_t[16], zh_inv_t[16];
 };
@@ -212,6 +217,12 @@ inline int launch_quotient(const QuotArgs& q, const QuotCoset& coset, hipStream_
 // air_program.hip: launch_quotient's evaluation launch when q.air_id is a registered program (air_program.hpp)
 struct KernelTimer;
 int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer& kt, hipStream_t st);
+int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t st);  // a port program's beta powers, behind apow's 48 coset words
+// air_program.hip: launch_aux's first half for a registered program with ports: term_0, term_1 of every port into the
+// port's two auxiliary columns (launch_aux then multiplies them up, aux_suffix_product_kernel<TERMS_IN_COLUMN>)
+int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st);
+// stark_kernels.hip: both halves, the running products of every port in a.aux ([2 * n_ports][n])
+int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st);
 int launch_quotient_chunks(const ChunkArgs* c, uint32_t batch, hipStream_t st);
 int launch_power_vectors(const PowerVecArgs* a, uint32_t batch, uint32_t log_n, uint32_t n_points, hipStream_t st);
 // d_out: n_points (<= 3) vectors of 2n words each: point y at d_out + y * 2n

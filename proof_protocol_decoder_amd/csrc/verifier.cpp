@@ -141,7 +141,7 @@ int stark_verify(const StarkCfg& cfg, const uint64_t* const_cap, const Ctl& ctl,
     const auto program = air::prog::find(cfg.air_id);  // a registered id: its program, interpreted (air_program.hpp)
     if (air::prog::is_registered(cfg.air_id) && !program) return fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x was unregistered", cfg.air_id);
     const uint32_t n_air = program ? program->n_constraints : air::n_constraints(shape);
-    Consumer k(n_air + air::ctl::n_constraints(shape), alpha0, alpha1);
+    Consumer k(n_air + air::any_n_ctl_constraints(shape), alpha0, alpha1);
     k.z_last = gl::sub(zeta, gl::ext(gl::inv(g)));
     k.l_first = gl::mul(zhn, gl::inv(gl::sub(zeta, gl::ext(1))));
     k.l_last = gl::mul(zhn, gl::inv(gl::sub(gl::scale(zeta, g), gl::ext(1))));
@@ -150,7 +150,17 @@ int stark_verify(const StarkCfg& cfg, const uint64_t* const_cap, const Ctl& ctl,
       for (uint32_t u = 0; u < program->n_units; u++) program->eval_unit<Ext>(u, row, k);
     else
       for (uint32_t u = 0; u < air::n_units(shape); u++) air::eval_unit<Ext>(shape, u, n_air, ctl.v, row, k);
-    air::ctl::eval<Ext>(shape, n_air, 0, A, ctl.v, row, k);
+    if (program && program->n_ports) {  // a program's ports: the same routine, the five constraints of each from here
+      uint64_t bpow[2 * air::prog::MAX_TUPLE];
+      air::prog::beta_powers(ctl.v, bpow);
+      for (uint32_t l = 0; l < program->n_ports; l++) {
+        air::prog::PortAcc<Ext> acc{bpow, {}, {}, {}};
+        program->eval_port<Ext>(l, row, acc);
+        air::prog::port_constraints<Ext>(n_air + air::prog::PORT_CONSTRAINTS * l, l, ctl.v, acc, row, k);
+      }
+    } else {
+      air::ctl::eval<Ext>(shape, n_air, 0, A, ctl.v, row, k);
+    }
     const uint64_t* oq = oz + 2 * (size_t)(K + C + A);
     for (int j = 0; j < 2; j++) {
       Ext acc = gl::ext(0);

@@ -350,6 +350,100 @@ def stark_prove_trace(air_id, cfg, trace, consts=None, pub=None, device=None):
     return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
 
 
+def air_port_products(air_id, trace, ctl, consts=None, pub=None):
+    """bp_air_port_products: the running products [2 * n_ports, 2^log_n] of a registered program's lookup ports over
+    `trace` ([n_cols, 2^log_n] int64 on the device; a column slice of a wider buffer keeps its stride): port l's z_0 at
+    row 2l, z_1 at 2l + 1.  ctl = beta0, gamma0, beta1, gamma1."""
+    if not trace.is_cuda or trace.dtype != torch.int64 or trace.stride(1) != 1:
+        raise ValueError("air_port_products needs an int64 device tensor with contiguous columns")
+    n_cols, n = trace.shape
+    if consts is not None:
+        _require_cuda(consts)
+    _check_shapes(n, consts, pub)
+    d = air_describe(air_id)
+    cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, 1)
+    out = torch.empty((d.n_aux, n), dtype=torch.int64, device=trace.device)
+    pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
+    check(lib().bp_air_port_products(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
+                                     consts.data_ptr() if consts is not None else None, pub_arr,
+                                     (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
+    return out
+
+
+def debug_air_aux(air_id, trace, ctl):
+    """bp_debug_air_aux (a test entry): the auxiliary columns [n_aux, 2^log_n] the prover commits for a built-in table
+    with a lookup side, from a contiguous trace [n_cols, 2^log_n]."""
+    _require_cuda(trace)
+    n_cols, n = trace.shape
+    _check_shapes(n, None, None)
+    cfg = _check_cfg(air_id, n_cols, 0, n.bit_length() - 1, 1)
+    out = torch.empty((air_describe(air_id).n_aux, n), dtype=torch.int64, device=trace.device)
+    check(lib().bp_debug_air_aux(air_id, C.byref(cfg), trace.data_ptr(), (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
+    return out
+
+
+def _set_arguments(tables, links):
+    """(SetTable array, SetLink array, what they point to) from tables = dicts / tuples with air_id, cfg and optionally
+    trace, consts, pub, and links = (looking ports, looked port), a port = (table, port)."""
+    from ._lib import SetLink, SetPort, SetTable
+    keep = []
+    ta = (SetTable * max(1, len(tables)))()
+    for t, m in zip(ta, tables):
+        t.air_id, t.cfg = m["air_id"], m["cfg"]
+        trace, consts, pub = m.get("trace"), m.get("consts"), m.get("pub")
+        if trace is not None:
+            if not trace.is_cuda or trace.dtype != torch.int64 or trace.stride(1) != 1:
+                raise ValueError("a set's traces are int64 device tensors with contiguous columns")
+            t.d_trace, t.stride = trace.data_ptr(), trace.stride(0)
+        if consts is not None:
+            _require_cuda(consts)
+            t.d_consts = consts.data_ptr()
+        if pub is not None:
+            arr = (C.c_uint64 * 4)(*[int(x) for x in pub])
+            keep.append(arr)
+            t.pub = C.cast(arr, C.POINTER(C.c_uint64))
+    la = (SetLink * max(1, len(links)))()
+    for l, (looking, looked) in zip(la, links):
+        l.n_looking = len(looking)
+        for k, (table, port) in enumerate(looking[:8]):
+            l.looking[k] = SetPort(table, port)
+        l.looked = SetPort(*looked)
+    return ta, la, keep
+
+
+def stark_prove_table_set(tables, links, skip_link_check=False, device=0):
+    """bp_stark_prove_table_set: the traces of `tables` (dicts: air_id, cfg, trace, and consts / pub where the AIR has
+    them), linked port to port by `links` = [([(table, port), ...looking], (table, port) looked), ...], proven on one
+    transcript.  Returns the "BPGTSET1" container words (u64).  An unbalanced link raises BpgError(BP_ERR_VERIFY) naming
+    it, unless skip_link_check."""
+    from ._lib import BP_SET_SKIP_LINK_CHECK
+    ta, la, keep = _set_arguments(tables, links)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()  # the library proves on a stream of its own
+    out = C.POINTER(C.c_uint8)()
+    n = C.c_size_t()
+    check(lib().bp_stark_prove_table_set(ta, len(tables), la, len(links), BP_SET_SKIP_LINK_CHECK if skip_link_check else 0,
+                                         device, C.byref(out), C.byref(n)))
+    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+
+
+def stark_verify_table_set(tables, links, proof, const_caps=None):
+    """bp_stark_verify_table_set: the CPU verifier on a set's container.  The statement -- tables (air_id, cfg, pub; no
+    traces), links, const_caps (per table the constants cap words or None) -- is the caller's own.  Raises
+    BpgError(BP_ERR_VERIFY) on rejection."""
+    ta, la, keep = _set_arguments([{k: v for k, v in m.items() if k not in ("trace", "consts")} for m in tables], links)
+    caps = None
+    if const_caps is not None:
+        caps = (C.POINTER(C.c_uint64) * len(tables))()
+        for k, cap in enumerate(const_caps):
+            if cap is not None:
+                cap = np.ascontiguousarray(cap, dtype=np.uint64)
+                keep.append(cap)
+                caps[k] = cap.ctypes.data_as(C.POINTER(C.c_uint64))
+    proof = np.ascontiguousarray(proof, dtype=np.uint64)
+    check(lib().bp_stark_verify_table_set(ta, len(tables), caps, la, len(links), proof.tobytes(), proof.size * 8))
+
+
 def stark_verify_air(air_id, cfg, proof, const_cap=None, pub=None):
     """bp_stark_verify_air_pub: the CPU verifier on one table proof (uint64 words); raises BpgError(BP_ERR_VERIFY) on
     rejection.  const_cap: the constants commitment's cap words when the table has constant columns."""

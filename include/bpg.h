@@ -142,9 +142,9 @@ void bp_tune_poseidon_mx_sets(int sets);
 /* The four-set matrix-core kernels take the partial rounds in groups: within a group only the next S-box input (an
  * affine form of the untouched words and the earlier S-box outputs, evaluated by int8 MFMAs on their bytes) is
  * recombined per round, the twelve words once per group (csrc/poseidon_mx.cuh, grp; tools/poseidon_group_model.py).
- * 3 (default; any other non-zero value means 3): all 22 partial rounds, as 8 + 8 + 6; 2: rounds 4..19 as 8 + 8, rounds
- * 20..25 one by one; 0: every round by itself.  Results are identical in every mode. */
-void bp_tune_poseidon_grouped(int mode);
+ * Non-zero (default): all 22 partial rounds in three groups, 8 + 8 + 6; 0: every round by itself.  Results are
+ * identical either way. */
+void bp_tune_poseidon_grouped(int on);
 /* The load-dependent choices -- Poseidon sets per wave by launch size, K5 and the FRI alpha-combination in one pass
  * without partial sums -- follow the number of bp_generate_*_proof calls at work on the device (six or more =
  * loaded): -1 (default).  0 / 1: stated by a caller that drives the L0 / L0.5 entry points from its own threads (the
@@ -183,23 +183,22 @@ uint32_t bp_debug_poseidon_group_ops(uint32_t K);
 int bp_debug_poseidon_group_tables(uint32_t K, uint32_t r0, uint8_t* out_ops, int32_t* out_cform, int32_t* out_cmain,
                                    int32_t* out_max_plane_sum);
 
-/* Tuning knob for K2: 0 (default) = automatic, 1 = never, 2 = wherever possible: transform a 2^13 / 2^14-point
- * block with TWO workgroups that each do half of the stage coupling its halves while loading (csrc/ntt.hip).
- * Results are identical either way. */
+/* Tuning knob for K2: 0 (default; also any other value) = automatic, 1 = never, 2 = wherever a split form exists:
+ * transform a 2^13 / 2^14-point block with TWO workgroups that each do half of the stage coupling its halves while
+ * loading (csrc/ntt.hip).  Only the inverse direction (values -> coefficients) has a split form; the forward
+ * transforms and coset LDEs are not affected.  Results are identical either way. */
 void bp_tune_ntt_split(int mode);
-/* 2^14-point coset-LDE blocks as persistent workgroups that prefetch the next block's coefficients while the last pass
- * of the current one computes and stores (csrc/ntt.hip, ntt16_dit_persist_kernel): on = 1 / 0 = the one-shot grid (the
- * default: the persistent form measured 8 % slower, profiles/r5_ntt_stalls.txt); resident_workgroups > 0 sets the grid (default 256 = one per CU).  Same values either way (tests). */
-void bp_tune_ntt_persist(int on, int resident_workgroups);
 /* NTT blocks as three radix-16 passes whose 16-point DFTs are int8 MFMAs on the bytes of the elements
  * (csrc/ntt_mx.cuh): 0 = never (the VALU butterfly kernels everywhere), 1 = 2^12- and 2^13-point blocks, 2 = 2^14-point
- * blocks too, 3 (default) = 2^13-point blocks while fewer than 6 provers are at work on the device, 4 / 5 = like 1 for
- * the inverse (DIF) / forward (DIT) direction only (measurement).  Alone
- * on the chip the form is level to +17 %; under the multi-stream block run its register footprint loses 12 %
+ * blocks too, 3 (default, and any value out of range) = 2^13-point blocks while fewer than 6 provers are at work on
+ * the device.  Alone on the chip the form is level to +17 %; under the multi-stream block run its register footprint loses 12 %
  * (DESIGN.md section 7).  Results are identical either way. */
 void bp_tune_ntt_mx(int mode);
-/* Measurement knob: resident workgroups per CU of the (persistent) matrix-core NTT kernels; 0 = default. */
-void bp_tune_ntt_mx_wg_per_cu(int n);
+/* Every bp_tune_* knob back to its default (csrc/tune.hpp holds them). */
+void bp_tune_reset(void);
+/* Host only: the current value of every knob as "name=value\n" lines in a fixed order, NUL-terminated, into buf
+ * (cap bytes; BP_ERR_INVALID_INPUT if it does not fit: 512 is plenty). */
+int bp_debug_tune_state(char* buf, size_t cap);
 /* Host only (no GPU needed): the constants the matrix-core kernels run on, as the device gets them, so that CPU tests
  * can pin them to an independent derivation.  NTT (csrc/ntt_mx.cuh): kind 0 = DIF / 1 = DIT matrix, inverse = root
  * direction; out_a 8192 bytes ([row block 8][lane 64][16] int8, K-chunk 0), out_c 128 i32, out_tw256 4096 u64,

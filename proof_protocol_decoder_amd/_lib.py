@@ -75,6 +75,11 @@ def lib_path():
     return _PATH
 
 
+# the bp_tune_* knobs (include/bpg.h; their defaults live in csrc/tune.hpp), in bp_debug_tune_state's order
+KNOBS = ("quad_threshold", "assume_loaded", "merkle_fused", "merkle_wide", "poseidon_mx", "poseidon_mx_sets",
+         "poseidon_grouped", "ntt_mx", "ntt_split", "k5_spread", "host_wait", "host_poseidon", "rec_batch",
+         "witness_threads", "side_lanes")
+
 _lib = None
 
 
@@ -137,16 +142,13 @@ def lib():
                                            C.POINTER(C.c_size_t)]
     L.bp_free_buffer.argtypes = [C.POINTER(C.c_uint8)]
     L.bp_free_buffer.restype = None
-    L.bp_tune_quad_threshold.argtypes = [u64]
-    L.bp_tune_quad_threshold.restype = None
-    L.bp_tune_ntt_mx.argtypes = [i]
-    L.bp_tune_ntt_mx.restype = None
-    L.bp_tune_ntt_mx_wg_per_cu.argtypes = [i]
-    L.bp_tune_ntt_mx_wg_per_cu.restype = None
-    L.bp_tune_poseidon_mx.argtypes = [i]
-    L.bp_tune_poseidon_mx.restype = None
-    L.bp_tune_poseidon_mx_sets.argtypes = [i]
-    L.bp_tune_poseidon_mx_sets.restype = None
+    for knob in KNOBS:
+        fn = getattr(L, "bp_tune_" + knob)
+        fn.argtypes = [u64 if knob == "quad_threshold" else i]
+        fn.restype = None
+    L.bp_tune_reset.argtypes = []
+    L.bp_tune_reset.restype = None
+    L.bp_debug_tune_state.argtypes = [C.c_char_p, C.c_size_t]
     _lib = L
     return L
 

@@ -14,6 +14,7 @@
 #include "poseidon.cuh"
 #include "poseidon_mx.cuh"
 #include "stark_kernels.hpp"
+#include "tune.hpp"
 
 namespace {
 
@@ -224,25 +225,25 @@ merkle_level_kernel(const uint64_t* __restrict__ child, uint64_t* __restrict__ p
 // instead of 2.98 Gperm/s and gain nothing under load (profiles/r3_poseidon_occ4_ab.txt); six- and twelve-wave
 // workgroups (to share a 67 KB table image) lose a quarter of their resident waves (r3_poseidon_three_groups.txt).
 #define BPG_MX_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
-// GR (NS = 4 only): 0 = every round by itself; 2 = the partial rounds 4..19 in two groups of eight; 3 = all 22 partial
-// rounds in groups (8 + 8 + 6).  gtab = the device image of the operand tables (poseidon_mx.cuh, grp), copied into LDS.
+// GR (NS = 4 only): false = every round by itself; true = all 22 partial rounds in groups (8 + 8 + 6).  gtab = the
+// device image of the operand tables (poseidon_mx.cuh, grp), copied into LDS.
 #define BPG_MX_TABLES(NS, GR, gtab)                                                                           \
   static_assert(!(GR) || (NS) == 4, "groups exist for four sets per wave");                                   \
   __shared__ __attribute__((aligned(16)))                                                                     \
-      uint32_t cin[(GR) ? poseidon::mx::CIN_GROUPED_WORDS<(GR) ? (GR) : 2> : poseidon::mx::CIN_WORDS];        \
-  __shared__ __attribute__((aligned(16))) uint32_t gt[(GR) ? poseidon::mx::grp::TABLE_WORDS<(GR) ? (GR) : 2> : 4]; \
-  if constexpr ((GR) != 0) {                                                                                  \
-    poseidon::mx::build_cin_grouped<(GR) ? (GR) : 2>(cin);                                                    \
-    poseidon::mx::grp::load_tables<(GR) ? (GR) : 2>(gt, gtab);                                                \
+      uint32_t cin[(GR) ? poseidon::mx::CIN_GROUPED_WORDS : poseidon::mx::CIN_WORDS];                         \
+  __shared__ __attribute__((aligned(16))) uint32_t gt[(GR) ? poseidon::mx::grp::TABLE_WORDS : 4];             \
+  if constexpr (GR) {                                                                                         \
+    poseidon::mx::build_cin_grouped(cin);                                                                     \
+    poseidon::mx::grp::load_tables(gt, gtab);                                                                 \
   } else {                                                                                                    \
     poseidon::mx::build_cin(cin);                                                                             \
   }                                                                                                           \
   __syncthreads();
-#define BPG_MX_PERMUTE(NS, GR, e, c, gtab)                                                      \
-  if constexpr ((GR) != 0) poseidon::mx::permute_grouped<(GR) ? (GR) : 2>(e, c, gt, gtab);  \
+#define BPG_MX_PERMUTE(NS, GR, e, c, gtab)                                  \
+  if constexpr (GR) poseidon::mx::permute_grouped(e, c, gt, gtab);          \
   else poseidon::mx::permute<NS>(e, c);
 
-template <int NS, int GR>
+template <int NS, bool GR>
 __global__ void BPG_MX_BOUNDS perm_batch_mx_kernel(uint64_t* __restrict__ states, uint64_t n,
                                                             const uint32_t* __restrict__ gtab) {
   BPG_MX_TABLES(NS, GR, gtab)
@@ -266,7 +267,7 @@ __global__ void BPG_MX_BOUNDS perm_batch_mx_kernel(uint64_t* __restrict__ states
   }
 }
 
-template <int NS, int GR>
+template <int NS, bool GR>
 __global__ void BPG_MX_BOUNDS
 leaf_hash_mx_kernel(const uint64_t* __restrict__ lde, uint64_t stride, uint32_t n_cols, uint32_t log_n,
                     uint32_t rate_bits, uint64_t* __restrict__ digests, uint64_t lde_bstride, uint64_t dig_bstride,
@@ -318,7 +319,7 @@ leaf_hash_mx_kernel(const uint64_t* __restrict__ lde, uint64_t stride, uint32_t 
   }
 }
 
-template <int NS, int GR>
+template <int NS, bool GR>
 __global__ void BPG_MX_BOUNDS
 merkle_level_mx_kernel(const uint64_t* __restrict__ child, uint64_t* __restrict__ parent, uint64_t n_parents,
                        uint64_t* __restrict__ mirror, uint64_t dig_bstride, const uint32_t* __restrict__ gtab) {
@@ -581,71 +582,48 @@ __global__ void __launch_bounds__(256) field_ops_kernel(const uint64_t* __restri
 
 namespace bpg {
 
-
-// launches with fewer permutations than this use the quad-cooperative kernels (4x the waves)
-// 0 = automatic: the quad form (4x the waves, 1.22x the instructions) pays while the chip is not full, so
-// the threshold follows the number of provers at work: few -> 2^17 (measured alone: quad wins up to there),
-// many -> 2^13 (under 24-stream load the instruction count decides; 2^11..2^13 measured best by ~1 %).
-static std::atomic<uint64_t> g_quad_threshold{0};
-static bool g_poseidon_mx_on();
+// The knobs these decisions read, their defaults and the measurements behind them: tune.hpp.
 static std::atomic<int> g_active_provers{0};
 void prover_active(int delta) { g_active_provers.fetch_add(delta, std::memory_order_relaxed); }
 int provers_active() { return g_active_provers.load(std::memory_order_relaxed); }
-static std::atomic<int> g_assume_loaded{-1};  // -1: by the count of provers at work; 0 / 1: stated by the caller
 bool device_loaded() {  // several provers share the chip
-  const int a = g_assume_loaded.load(std::memory_order_relaxed);
+  const int a = tune().assume_loaded.load(std::memory_order_relaxed);
   return a < 0 ? g_active_provers.load(std::memory_order_relaxed) >= 6 : a != 0;
 }
+bool poseidon_mx() { return tune().poseidon_mx.load(std::memory_order_relaxed) != 0; }
+// launches with fewer permutations than this use the quad-cooperative kernels (4x the waves)
 uint64_t quad_threshold() {
-  const uint64_t t = g_quad_threshold.load(std::memory_order_relaxed);
+  const uint64_t t = tune().quad_threshold.load(std::memory_order_relaxed);
   if (t) return t;
   const bool loaded = device_loaded();
   // with the matrix-core forms the small-launch form (one set per wave) costs 0.65x the quad form's instructions
   // and wins alone up to 2^18 items (tools/kernel_bench.py: 2^17 rows 1.8-2.0 against 1.5-1.8 Gperm/s for four sets)
-  if (g_poseidon_mx_on()) return (uint64_t)1 << (loaded ? 13 : 19);
+  if (poseidon_mx()) return (uint64_t)1 << (loaded ? 13 : 19);
   return (uint64_t)1 << (loaded ? 13 : 17);
 }
-// Levels near the root are each one latency-bound launch (a lone txn proof spends ~30 % of its kernel time in them,
-// and under the 24-stream load they are 40 % of all launches, each stretched from 19 to ~120 us by sharing:
-// profiles/r2b_kernel_stats_4txn_1stream.csv, r3_kernel_stats_64txn_24streams.csv).  merkle_subtree_mx_kernel hands
-// up to seven levels of at most 2048 nodes down through LDS in one launch, in the one-set matrix-core form.
-// Measured in round 3 (profiles/r3_small_shards.txt), fused against one launch per level: 256 txns 36.2 against 35.2
-// txn-proofs/s, 32 txns 33.6 against 32.5, 16 txns 33.1 against 31.6, a lone pair of txns 150.8 against 148.2 ms.
-// (With the quad-cooperative permutation -- round 2's fused kernel, still used when the matrix-core forms are switched
-// off -- the fused form lost 0-4 %: ~12 us per level cost what the launch gaps saved.)
-// 1 = fused (default), 0 = one launch per level, -1 = fused only while fewer than six provers are at work.
-static std::atomic<int> g_merkle_fused{1};
-static std::atomic<int> g_merkle_wide_log2{0};  // levels of up to 2^k parents go to merkle_subtree_wide_kernel (0: none)
-// launches at or above the quad threshold: 1 = matrix-core form (poseidon_mx.cuh), 0 = one lane per state
-static std::atomic<int> g_poseidon_mx{1};
-bool poseidon_mx() { return g_poseidon_mx.load(std::memory_order_relaxed) != 0; }
-static bool g_poseidon_mx_on() { return poseidon_mx(); }
 // Sets of 16 states per wave for an mx launch of n items (0 = matrix-core form off).  Four sets are the throughput
 // form (all 64 lanes busy in the partial-round S-box); a launch below the quad threshold takes fewer sets = more
 // waves, as the quad form did (which the one-set form replaces at 0.65x the instructions).
-static std::atomic<int> g_mx_sets{0};  // 0 = by size, else 1 / 2 / 4
 int mx_sets(uint64_t n) {
   if (!poseidon_mx()) return 0;
-  const int f = g_mx_sets.load(std::memory_order_relaxed);
+  const int f = tune().poseidon_mx_sets.load(std::memory_order_relaxed);
   if (f) return f;
   const uint64_t t = quad_threshold();
   return n >= t ? 4 : (n >= t / 2 ? 2 : 1);
 }
 // ---- operand tables of the grouped partial rounds (poseidon_group.hpp): built once per process on the host,
 // uploaded once per device; the four-set kernels copy them into LDS.  nullptr = per-round form (knob, or no tables).
-static std::atomic<int> g_poseidon_grouped{3};  // 0, 2 or 3 groups (bp_tune_poseidon_grouped)
 static std::mutex g_group_mu;
-static const uint32_t* g_group_dev[2][16] = {};
-static std::atomic<int> g_group_state[2][16];  // [n_groups - 2][device]: 0 not tried, 1 ready, -1 failed
-static std::vector<uint32_t>* g_group_image[2] = {nullptr, nullptr};
+static const uint32_t* g_group_dev[16] = {};
+static std::atomic<int> g_group_state[16];  // [device]: 0 not tried, 1 ready, -1 failed
+static std::vector<uint32_t>* g_group_image = nullptr;
 
-template <int NG>
 static bool build_group_image() {
   namespace pg = poseidon::group;
   namespace gx = poseidon::mx::grp;
-  if (g_group_image[NG - 2]) return true;
-  auto img = std::make_unique<std::vector<uint32_t>>(gx::IMAGE_WORDS<NG>, 0);
-  for (int g = 0; g < NG; g++) {
+  if (g_group_image) return true;
+  auto img = std::make_unique<std::vector<uint32_t>>(gx::IMAGE_WORDS, 0);
+  for (int g = 0; g < gx::N_GROUPS; g++) {
     pg::Tables t;
     uint32_t* c = img->data() + gx::OPS_WORDS + g * gx::C_WORDS;
     if (g < 2) {
@@ -668,7 +646,7 @@ static bool build_group_image() {
           if (blank ? v6 != 0 : v6 != v8) return false;
         }
       }
-      std::memcpy(img->data() + gx::TABLE_WORDS<NG>, t.ops.data() + (size_t)L6.main_base * 1024, 18 * 1024);
+      std::memcpy(img->data() + gx::TABLE_WORDS, t.ops.data() + (size_t)L6.main_base * 1024, 18 * 1024);
     }
     std::memcpy(c, t.cform.data(), pg::CFORM_WORDS * 4);
     std::memcpy(c + pg::CFORM_WORDS, t.cmain.data(), pg::CMAIN_WORDS * 4);
@@ -676,32 +654,30 @@ static bool build_group_image() {
   // the per-round MDS layer's A operands as poseidon::mx::make_ctx builds them: lane (r, kb), dword a =
   // M[(r >> 2) + 4g][kb + 4a] << 8 (r & 3)
   static const uint32_t MC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-  uint32_t* am = img->data() + gx::OPS_WORDS + NG * gx::C_WORDS;
+  uint32_t* am = img->data() + gx::OPS_WORDS + gx::N_GROUPS * gx::C_WORDS;
   for (uint32_t g = 0; g < 3; g++)
     for (uint32_t lane = 0; lane < 64; lane++)
       for (uint32_t a = 0; a < 3; a++) {
         const uint32_t r = lane & 15, kb = lane >> 4, i = (r >> 2) + 4 * g, k = kb + 4 * a;
         am[(g * 64 + lane) * 4 + a] = (MC[(k + 12 - i) % 12] + ((i | k) == 0 ? 8u : 0u)) << (8 * (r & 3));
       }
-  g_group_image[NG - 2] = img.release();
+  g_group_image = img.release();
   return true;
 }
-// the current device's copy of the image (uploaded on first use) and the number of groups it serves, or nullptr
-const uint32_t* group_tables(int* n_groups) {
-  const int ng = g_poseidon_grouped.load(std::memory_order_relaxed);
-  if (n_groups) *n_groups = ng;
-  if (ng != 2 && ng != 3) return nullptr;
+// the current device's copy of the image (uploaded on first use), or nullptr
+const uint32_t* group_tables() {
+  if (!tune().poseidon_grouped.load(std::memory_order_relaxed)) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  std::atomic<int>& state = g_group_state[ng - 2][dev];
-  const uint32_t*& slot = g_group_dev[ng - 2][dev];
+  std::atomic<int>& state = g_group_state[dev];
+  const uint32_t*& slot = g_group_dev[dev];
   if (state.load(std::memory_order_acquire) > 0) return slot;  // the state is set after the pointer
   std::lock_guard<std::mutex> lk(g_group_mu);
   if (const int st = state.load(std::memory_order_acquire)) return st > 0 ? slot : nullptr;
   void* d = nullptr;
-  const size_t bytes = (size_t)(ng == 3 ? poseidon::mx::grp::IMAGE_WORDS<3> : poseidon::mx::grp::IMAGE_WORDS<2>) * 4;
-  if (!(ng == 3 ? build_group_image<3>() : build_group_image<2>()) || hipMalloc(&d, bytes) != hipSuccess ||
-      hipMemcpy(d, g_group_image[ng - 2]->data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  const size_t bytes = (size_t)poseidon::mx::grp::IMAGE_WORDS * 4;
+  if (!build_group_image() || hipMalloc(&d, bytes) != hipSuccess ||
+      hipMemcpy(d, g_group_image->data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
     if (d) (void)hipFree(d);
     state.store(-1, std::memory_order_release);
     return nullptr;
@@ -714,19 +690,14 @@ const uint32_t* group_tables(int* n_groups) {
 // ITEMS: rows / nodes / states of ONE tree; BATCH trees (grid.z) of that size in the launch
 #define BPG_MX_DISPATCH(NS_EXPR, KERNEL, ITEMS, BATCH, ...)                                                 \
   switch (NS_EXPR) {                                                                                       \
-    case 4: {                                                                                              \
-      int ng_ = 0;                                                                                         \
-      const uint32_t* gtab_ = bpg::group_tables(&ng_);                                                     \
-      if (gtab_ && ng_ == 3)                                                                               \
-        KERNEL<4, 3><<<dim3(ceil_div((ITEMS), 256), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, gtab_);       \
-      else if (gtab_)                                                                                      \
-        KERNEL<4, 2><<<dim3(ceil_div((ITEMS), 256), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, gtab_);       \
+    case 4:                                                                                                \
+      if (const uint32_t* gtab_ = bpg::group_tables())                                                     \
+        KERNEL<4, true><<<dim3(ceil_div((ITEMS), 256), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, gtab_);    \
       else                                                                                                 \
-        KERNEL<4, 0><<<dim3(ceil_div((ITEMS), 256), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr);     \
+        KERNEL<4, false><<<dim3(ceil_div((ITEMS), 256), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr); \
       break;                                                                                               \
-    }                                                                                                      \
-    case 2: KERNEL<2, 0><<<dim3(ceil_div((ITEMS), 128), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr); break; \
-    default: KERNEL<1, 0><<<dim3(ceil_div((ITEMS), 64), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr); break; \
+    case 2: KERNEL<2, false><<<dim3(ceil_div((ITEMS), 128), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr); break; \
+    default: KERNEL<1, false><<<dim3(ceil_div((ITEMS), 64), 1, (BATCH)), 256, 0, st>>>(__VA_ARGS__, nullptr); break; \
   }
 
 // `mirror` (nullable): host-visible buffer that receives the 2^cap_height cap digests directly from
@@ -744,13 +715,13 @@ int merkle_upper_levels(uint64_t* d_digests, uint32_t log_leaves, uint32_t cap_h
     const uint64_t cnt = (uint64_t)1 << l, parents = cnt / 2;
     uint64_t* nxt = lvl + cnt * 4;
     // fuse only what fits in <= 64 workgroups: those launches are latency-critical and run at raised priority
-    const int fmode = g_merkle_fused.load(std::memory_order_relaxed);
+    const int fmode = tune().merkle_fused.load(std::memory_order_relaxed);
     // from 2^11 nodes down (measured 2^10 / 2^11 / 2^12 / 2^13 / 2^14: 36.9 / 37.0 / 36.8 / 35.2 / 34.7 txn-proofs/s: wider
-    // levels are throughput work for the four-set kernels); modes 8..20 of the knob = fuse from 2^mode nodes down
-    const uint64_t flimit = fmode >= 8 ? (uint64_t)1 << fmode : 2048;
-    const bool fused = parents <= flimit && (parents < quad_threshold() || fmode >= 8) && (fmode > 0 || (fmode < 0 && !device_loaded()));
+    // levels are throughput work for the four-set kernels)
+    constexpr uint64_t flimit = 2048;
+    const bool fused = parents <= flimit && parents < quad_threshold() && (fmode > 0 || (fmode < 0 && !device_loaded()));
     // the levels above the one-set fused tail, 256 parents per workgroup, nine levels per launch (knob: wide limit)
-    const uint64_t wlimit = (uint64_t)1 << g_merkle_wide_log2.load(std::memory_order_relaxed);
+    const uint64_t wlimit = (uint64_t)1 << tune().merkle_wide.load(std::memory_order_relaxed);
     if (!fused && fmode > 0 && poseidon_mx() && parents >= 256 && parents <= wlimit && parents % 256 == 0) {
       uint32_t levels = l - cap_height;
       if (levels > 9) levels = 9;
@@ -833,9 +804,6 @@ int bp_debug_mul_pow2(const uint64_t* d_a, uint64_t* d_out, uint64_t n, void* st
   return BP_OK;
 }
 
-void bp_tune_merkle_fused(int mode) { bpg::g_merkle_fused.store(mode < 0 ? -1 : (mode >= 8 && mode <= 20 ? mode : (mode != 0))); }
-void bp_tune_quad_threshold(uint64_t n_perms) { bpg::g_quad_threshold.store(n_perms); }
-void bp_tune_poseidon_mx(int on) { bpg::g_poseidon_mx.store(on != 0); }
 // Host only: the C-operand table of the matrix-core Poseidon kernels (poseidon_mx.cuh), 30 x 4 x 24 u32, for the CPU test
 // that re-derives it from the round constants.
 int bp_debug_poseidon_mx_cin(uint32_t* out) {
@@ -844,15 +812,6 @@ int bp_debug_poseidon_mx_cin(uint32_t* out) {
   for (int i = 0; i < poseidon::mx::CIN_WORDS; i++) out[i] = t.v[i];
   return BP_OK;
 }
-/* 1 (default): the four-set matrix-core kernels take the partial rounds 4..19 in two groups of eight
- * (csrc/poseidon_mx.cuh, grp); 0: every round by itself.  Results are identical. */
-/* The load-dependent choices (kernel forms, one-pass K5 / FRI combination): -1 (default) = by the number of
- * bp_generate_*_proof calls at work on the device (six or more = loaded); 0 / 1 = stated by a caller that drives the
- * L0 / L0.5 entry points from its own threads, or by a test that pins both paths. */
-void bp_tune_merkle_wide(int log2_parents) { bpg::g_merkle_wide_log2.store(log2_parents < 8 || log2_parents > 24 ? 0 : log2_parents); }
-void bp_tune_assume_loaded(int mode) { bpg::g_assume_loaded.store(mode < 0 ? -1 : (mode != 0)); }
-// 0: every round by itself; 2: rounds 4..19 in two groups; 3 (or 1, the default): all 22 partial rounds in three
-void bp_tune_poseidon_grouped(int mode) { bpg::g_poseidon_grouped.store(mode == 0 ? 0 : (mode == 2 ? 2 : 3)); }
 
 // Host only: the operand images of one group as the device gets them (tests/test_mx_tables.py pins them to the
 // integer model tools/poseidon_group_model.py).  out_ops: bp_debug_poseidon_group_ops(K) x 1024 bytes, out_cform: 64
@@ -871,8 +830,6 @@ int bp_debug_poseidon_group_tables(uint32_t K, uint32_t r0, uint8_t* out_ops, in
   return BP_OK;
 }
 BPG_ABI_CATCH("bp_debug_poseidon_group_tables")
-
-void bp_tune_poseidon_mx_sets(int sets) { bpg::g_mx_sets.store(sets == 1 || sets == 2 || sets == 4 ? sets : 0); }
 
 uint64_t bp_merkle_digest_words(uint32_t log_leaves, uint32_t cap_height) {
   return (((uint64_t)2 << log_leaves) - ((uint64_t)1 << cap_height)) * 4;

@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "gl.hpp"
 #include "mx_arith.cuh"
+#include "tune.hpp"
 
 namespace {
 
@@ -435,16 +436,14 @@ struct Ntt16Args {
   const uint64_t* scale;  // DIT: [coset][n_total] input scale, nullable
   uint64_t out_scalar;    // DIF: 1/n (1 = none)
   uint32_t log_n_total, n_cosets, n_units;  // n_units = columns * blocks per column (1-D grid mapping)
-  const uint64_t* tw_top; // split kernels (F = 1): w_{2B}^e, e < B: the stage that joins the two halves
+  const uint64_t* tw_top; // split DIF kernel (F = 1): w_{2B}^e, e < B: the stage that joins the two halves
   const uint64_t* lay;    // twiddle layers of the radix-16 passes (get_table kind 4 / 5 for B): see dit16 / dif16
 };
 
-// ---- "split" forms (template parameter F = 1): a block of 2^(L+1) elements is transformed by TWO workgroups of
-// the 2^L-point kernel, each doing half of the one radix-2 stage that couples the halves while it loads:
-//   DIF: workgroup h reads x[i] and x[i + 2^L] and keeps (h = 0) x[i] + x[i + 2^L] or (h = 1) their twiddled
-//        difference -- then it owns an independent 2^L-point transform (output half h);
-//   DIT: the same split on the COEFFICIENT index (pairs of adjacent bit-reversed positions 2p, 2p+1), after which
-//        workgroup h owns the outputs of parity h (stride-2 stores; the partner fills the other half of each line).
+// ---- "split" form of the DIF kernel (template parameter F = 1): a block of 2^(L+1) elements is transformed by TWO
+// workgroups of the 2^L-point kernel, each doing half of the one radix-2 stage that couples the halves while it loads:
+// workgroup h reads x[i] and x[i + 2^L] and keeps (h = 0) x[i] + x[i + 2^L] or (h = 1) their twiddled difference --
+// then it owns an independent 2^L-point transform (output half h).
 // Both read the whole 2^(L+1) block (the second read is an L2 hit: the pair sits on one XCD, see the grid
 // mapping below) but no multiply is done twice.  Why: a 2^14-point block is ONE 128 KiB workgroup per CU, whose
 // load, compute and store phases cannot overlap with anything (73 % VALU-busy); as two 64 KiB workgroups they
@@ -556,69 +555,24 @@ __global__ void __launch_bounds__((1 << L) / 16) ntt16_dif_kernel(Ntt16Args a) {
 // XCD at about the same time and lets its L2 serve all but the first read (PMC: fetched bytes drop
 // from 2^r x to ~1 x the coefficients).  id -> xcd = id % 8, k = id / 8, coset = k % n_cosets,
 // unit = (k / n_cosets) * 8 + xcd, unit = column * blocks_per_column + block.  A speed choice only.
-// F = 1 (split form, see Ntt16Args): k -> (coset, h) = ((k % (2 n_cosets)) / 2, k % 2), unit counts 2^(L+1)-blocks.
-template <int L, int F>
+template <int L>
 __global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per_eu(4, 8))) ntt16_dit_kernel(Ntt16Args a) {
   if (gridDim.x <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
   extern __shared__ uint64_t buf[];
   constexpr uint32_t T = (1u << L) / 16;
   constexpr int RT = (L % 4 == 0) ? 4 : (L % 4);  // stages of the outermost pass
   const uint32_t id = blockIdx.x, k = id >> 3;
-  const uint32_t per = a.n_cosets << F;
-  const uint32_t ch = k % per, coset = ch >> F, h = F ? (ch & 1) : 0, unit = (k / per) * 8 + (id & 7);
+  const uint32_t coset = k % a.n_cosets, unit = (k / a.n_cosets) * 8 + (id & 7);
   if (unit >= a.n_units) return;  // padding of the last group of eight (whole workgroup leaves together)
-  const uint32_t log_bpc = a.log_n_total - (L + F);  // blocks per column
+  const uint32_t log_bpc = a.log_n_total - L;  // blocks per column
   const uint32_t col = unit >> log_bpc, blk = unit & ((1u << log_bpc) - 1);
   const uint32_t t = threadIdx.x;
-  const uint64_t off = (uint64_t)blk << (L + F);
+  const uint64_t off = (uint64_t)blk << L;
   const uint64_t* src = a.in + col * a.in_stride + off;
   const uint64_t* tw = a.tw;
   uint64_t x[16];
   const uint32_t base = gl::bitrev(t, L - 4) << 4;
-  if (F) {
-    // coefficient pairs (2p, 2p + 1): p = m*T + t is the input position of this workgroup's 2^L-point problem
-    const ulonglong2* src2 = reinterpret_cast<const ulonglong2*>(src);
-    const ulonglong2* sc2 = a.scale ? reinterpret_cast<const ulonglong2*>(a.scale + ((uint64_t)coset << a.log_n_total) + off) : nullptr;
-    constexpr uint32_t BR4[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
-#pragma unroll
-    for (int m0 = 0; m0 < 16; m0 += 4) {
-      uint64_t c0[4], c1[4], r[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const ulonglong2 c = src2[(m0 + i) * T + t];
-        c0[i] = c.x;
-        c1[i] = c.y;
-      }
-      if (sc2) {
-        uint64_t s0[4], s1[4], p0[4], p1[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const ulonglong2 sc = sc2[(m0 + i) * T + t];
-          s0[i] = sc.x;
-          s1[i] = sc.y;
-        }
-        gl::mul_n<4>(c0, s0, p0);
-        gl::mul_n<4>(c1, s1, p1);
-        gl::canon_n<4>(p1);
-#pragma unroll
-        for (int i = 0; i < 4; i++) { c0[i] = p0[i]; c1[i] = p1[i]; }
-      } else {
-        gl::canon_n<4>(c1);  // unscaled: straight from caller memory, any u64
-      }
-      if (h == 0) {
-        gl::add_n<4>(c0, c1, r);
-      } else {
-        uint64_t d[4], w[4];
-        gl::sub_n<4>(c0, c1, d);
-        // twiddle of coefficient index bitrev_L(p) = (bitrev_{L-4}(t) << 4) | bitrev_4(m)
-#pragma unroll
-        for (int i = 0; i < 4; i++) w[i] = a.tw_top[base | BR4[m0 + i]];
-        gl::mul_n<4>(d, w, r);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; i++) buf[swz<L>((m0 + i) * T + t)] = r[i];  // reduced, not canonical: fine as a butterfly input
-    }
-  } else if (a.scale) {
+  if (a.scale) {
     const uint64_t* sc = a.scale + ((uint64_t)coset << a.log_n_total) + off;
 #pragma unroll
     for (int m0 = 0; m0 < 16; m0 += 4) {
@@ -667,117 +621,7 @@ __global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per
     uint64_t v[4] = {x[m0], x[m0 + 1], x[m0 + 2], x[m0 + 3]};
     gl::canon_n<4>(v);
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      if (F) dst[2 * ((m0 + i) * T + t2) + h] = v[i];  // outputs of parity h
-      else dst[(m0 + i) * T + t2] = v[i];
-    }
-  }
-}
-
-// The 2^14-point form of ntt16_dit_kernel<L, 0> as a PERSISTENT workgroup.  A 2^14-point block is 128 KiB of LDS: one
-// workgroup per CU, so nothing overlaps its memory phases -- SQ counters (profiles/r5_ntt_stalls.txt): VALU busy
-// 58..74 % of the launch, the rest is the coefficient load at the head of every block, the drain of its stores and the
-// next workgroup's start.  Here the workgroup walks over its share of the (block, coset) items itself and loads the NEXT
-// item's coefficients into registers while the last pass of the current one computes and stores (16 words per lane: the
-// kernel has the registers, 48 of the 128 a four-wave SIMD allows).  The walk keeps id mod 8 (the XCD) and the
-// coset-adjacent dispatch order of the one-shot grid: gridDim.x is a multiple of 8 * n_cosets.  No barrier between items:
-// a lane's first LDS stores of an item go to the addresses its own last loads of the previous item read.
-template <int L>
-__global__ void __launch_bounds__((1 << L) / 16) __attribute__((amdgpu_waves_per_eu(4, 4)))
-ntt16_dit_persist_kernel(Ntt16Args a, uint32_t n_items) {
-  extern __shared__ uint64_t buf[];
-  constexpr uint32_t T = (1u << L) / 16;
-  constexpr int RT = (L % 4 == 0) ? 4 : (L % 4);
-  const uint32_t t = threadIdx.x;
-  const uint32_t log_bpc = a.log_n_total - L;
-  const uint64_t* tw = a.tw;
-  auto source_of = [&](uint32_t id) -> const uint64_t* {  // null: a padding id of the last group of eight
-    const uint32_t k = id >> 3, unit = (k / a.n_cosets) * 8 + (id & 7);
-    if (id >= n_items || unit >= a.n_units) return nullptr;
-    const uint32_t col = unit >> log_bpc, blk = unit & ((1u << log_bpc) - 1);
-    return a.in + col * a.in_stride + ((uint64_t)blk << L);
-  };
-  uint64_t xn[16];
-  {
-    const uint64_t* s0 = source_of(blockIdx.x);
-    if (s0) {
-#pragma unroll
-      for (int m = 0; m < 16; m++) xn[m] = s0[m * T + t];
-    }
-  }
-  for (uint32_t id = blockIdx.x; id < n_items; id += gridDim.x) {
-    const uint32_t k = id >> 3, coset = k % a.n_cosets, unit = (k / a.n_cosets) * 8 + (id & 7);
-    const uint64_t* next_src = source_of(id + gridDim.x);
-    // opaque copies of the lane id, one per phase: every LDS and global address below is recomputed in the item it is
-    // used in (hoisted out of the item loop they are ~100 registers: the kernel then spills, as its one-shot form would
-    // without its own opaque copy)
-    uint32_t ta = t, tb = t, tc = t;
-    asm volatile("" : "+v"(ta));
-    if (unit >= a.n_units) {  // padding (the whole workgroup agrees): nothing was prefetched for it; fetch for the next one
-      if (next_src) {
-#pragma unroll
-        for (int m = 0; m < 16; m++) xn[m] = next_src[m * T + t];
-      }
-      continue;
-    }
-    const uint32_t col = unit >> log_bpc, blk = unit & ((1u << log_bpc) - 1);
-    const uint64_t off = (uint64_t)blk << L;
-    if (a.scale) {
-      const uint64_t* sc = a.scale + ((uint64_t)coset << a.log_n_total) + off;
-#pragma unroll
-      for (int m0 = 0; m0 < 16; m0 += 4) {
-        uint64_t v[4], w[4], r[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          v[i] = xn[m0 + i];
-          w[i] = sc[(m0 + i) * T + ta];
-        }
-        gl::mul_n<4>(v, w, r);
-#pragma unroll
-        for (int i = 0; i < 4; i++) buf[swz<L>((m0 + i) * T + ta)] = r[i];
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < 16; m++) buf[swz<L>(m * T + ta)] = xn[m];
-    }
-    __syncthreads();
-    asm volatile("" : "+v"(tb));
-    const uint32_t base = gl::bitrev(tb, L - 4) << 4;
-    uint64_t x[16];
-#pragma unroll
-    for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(base | m)];
-    dit16<true>(x, a.lay, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 16; m++) buf[swz<L>(base | m)] = x[m];
-    __syncthreads();
-#pragma unroll
-    for (int b = 4; b + 4 <= L - RT; b += 4) {
-      asm volatile("" : "+v"(tc));
-#pragma unroll
-      for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(insert4(tc, m, b))];
-      dit16(x, a.lay, tc & ((1u << b) - 1), b);
-#pragma unroll
-      for (int m = 0; m < 16; m++) buf[swz<L>(insert4(tc, m, b))] = x[m];
-      __syncthreads();
-    }
-    // the next item's coefficients start their way now: they fly while the last pass computes and stores
-    uint32_t t2 = t;
-    asm volatile("" : "+v"(t2));
-    if (next_src) {
-#pragma unroll
-      for (int m = 0; m < 16; m++) xn[m] = next_src[m * T + t2];
-    }
-#pragma unroll
-    for (int m = 0; m < 16; m++) x[m] = buf[swz<L>(m * T + t2)];
-    sub_butterflies<RT, 4 - RT, false, false>(x, tw, t2, L - 4, L - RT, 0, a.lay);
-    uint64_t* dst = a.out + col * a.out_stride + coset * a.out_coset_stride + off;
-#pragma unroll
-    for (int m0 = 0; m0 < 16; m0 += 4) {
-      uint64_t v[4] = {x[m0], x[m0 + 1], x[m0 + 2], x[m0 + 3]};
-      gl::canon_n<4>(v);
-#pragma unroll
-      for (int i = 0; i < 4; i++) dst[(m0 + i) * T + t2] = v[i];
-    }
+    for (int i = 0; i < 4; i++) dst[(m0 + i) * T + t2] = v[i];
   }
 }
 
@@ -985,26 +829,11 @@ int get_table(int kind, uint32_t log_n, uint32_t rate_bits, const uint64_t** out
   return BP_OK;
 }
 
-// Matrix-core form of the block kernels (ntt_mx.cuh).  0: never; 1: 2^12- and 2^13-point blocks; 2: 2^14-point blocks
-// too (tests); 3 (default): 2^13-point blocks -- where it wins a little -- while the device is not loaded (fewer than
-// six provers at work).  Measured (bench.py --ntt-mx 1 / 0 back to back on one box; HISTORY.md, round 2):
-//   first version, MFMA constants in 96 VGPRs, 224-240 VGPRs = two waves per SIMD (profiles/r2_ntt_mx_probe.txt,
-//   r2_ntt_mx_block_ab.txt): alone level at 2^12 points, +7 % LDE / +17 % inverse at 2^13 x 135 rate 8, -25 % at 2^14
-//   (spills); under the 24-stream block run 29.8 against 34.1 txn-proofs/s -- its fat waves crowd out the Poseidon
-//   kernels' waves;
-//   this version, constants cut to 32 VGPRs (chunk 1 = +-chunk 0, C operands in LDS), 136-168 VGPRs = three waves per
-//   SIMD (profiles/r2_ntt_mx_lean_ab.txt): alone level at 2^12, +3..4 % at 2^13 x 135, still behind at 2^14; under
-//   load 34.7 against 35.3.
-// It issues half the VALU instructions of the butterfly kernels, but every 16 elements of a pass cost one MFMA, which
-// blocks its SIMD for ~12 cycles (tools/mfma_probe.hip), and the kernel stays latency-bound at three waves: no win
-// over the VALU kernels on this workload, so it is used only where it measures ahead.
+// Matrix-core form of the block kernels (ntt_mx.cuh): the modes and their measurements are at Tune::ntt_mx (tune.hpp).
 bool device_loaded();  // hash_kernels.hip
-static std::atomic<int> g_ntt_mx{3};
-static bool use_ntt_mx(uint32_t log_blk, bool dit) {
-  const int m = g_ntt_mx.load(std::memory_order_relaxed);
+static bool use_ntt_mx(uint32_t log_blk) {
+  const int m = tune().ntt_mx.load(std::memory_order_relaxed);
   if (m == 3) return log_blk == 13 && !device_loaded();
-  if (m == 4) return !dit && log_blk <= 13;   // measurement modes: one direction only
-  if (m == 5) return dit && log_blk <= 13;
   return m == 2 || (m == 1 && log_blk <= 13);
 }
 // Constants of the matrix-core kernels, one device image per (device, kind, direction), built once.
@@ -1013,15 +842,13 @@ static std::map<std::tuple<int, int, int>, mxn::Tables*> g_mx_tabs;
 // Persistent grid of the matrix-core kernels: every workgroup loads the 24 KB of MFMA constants once and then walks
 // over its share of the work items, so the grid is what is resident at once (a multiple of 8: the XCD-aware id
 // mapping of the DIT kernel needs id mod 8 to stay fixed along a workgroup's walk).
-static std::atomic<int> g_mx_wg_per_cu{0};  // 0 = default (2 for 2^12-point blocks, 1 above)
 static uint32_t mx_grid(uint32_t items, uint32_t log_blk) {
   static const int cus = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  int per = g_mx_wg_per_cu.load(std::memory_order_relaxed);
-  if (per <= 0) per = log_blk == 12 ? 2 : 1;
+  const int per = log_blk == 12 ? 2 : 1;  // workgroups per CU
   const uint32_t resident = ((uint32_t)cus * per + 7) / 8 * 8;
   return items < resident ? items : resident;
 }
@@ -1076,26 +903,18 @@ static NttPlan plan_ntt(uint32_t log_n) {
 }
 static uint32_t pick_log_blk(uint32_t log_n) { return plan_ntt(log_n).log_blk; }
 
-// Persistent 2^14-point DIT workgroups (ntt16_dit_persist_kernel): 0 = the one-shot grid (default), 1 = on; resident
-// workgroups: one per CU.  Measured and NOT adopted (profiles/r5_ntt_stalls.txt): 2^14 x 2432 at rate 2 takes 893..919 us
-// persistent against 795..857 us one-shot on the same box -- the prefetched words push the kernel to the 128-VGPR edge
-// of four waves per SIMD (140 bytes of scratch per lane), and a one-shot grid already overlaps a finishing workgroup's
-// store drain with its successor's start on the same CU.
-static std::atomic<int> g_ntt_persist{0};
-static std::atomic<int> g_ntt_persist_wgs{256};
-// Split form (Ntt16Args), out of place only.
-static std::atomic<int> g_ntt_split{0};  // 0 = automatic, 1 = never, 2 = wherever possible, 3 = automatic + small DIT launches (measurement knobs)
-static bool use_split(uint32_t log_blk, uint64_t workgroups, const void* src, const void* dst, bool dit) {
-  const int mode = g_ntt_split.load(std::memory_order_relaxed);
+// Split form of the DIF block kernels (Ntt16Args), out of place only.  Tune::ntt_split: 0 = automatic, 1 = never,
+// 2 = wherever possible.
+static bool use_split(uint32_t log_blk, uint64_t workgroups, const void* src, const void* dst) {
+  const int mode = tune().ntt_split.load(std::memory_order_relaxed);
   // never in place: each of the two workgroups reads the WHOLE block while its partner may already be storing
   if (mode == 1 || log_blk < 13 || src == dst) return false;
   if (mode == 2) return true;
-  // The DIT form stays off by default: its stride-2 stores (each workgroup writes every other word of a line)
-  // inflate the HBM write traffic of the 2^14 x 2432 LDE by 1.66x (PMC WRITE_SIZE: 1,036,585 KiB against
-  // 622,592 KiB algorithmic) for a 6 % shorter launch, and it gains nothing on small launches.  The DIF form
-  // writes contiguous halves: 2^14-point blocks always (+23 %), 2^13-point blocks when the launch has too few
-  // workgroups to fill the chip (2^13 x 16: 23 -> 19 us).
-  if (dit) return mode == 3 && log_blk == 13 && workgroups < 512;  // 3: measurement mode, small DIT launches only
+  // The DIF form writes contiguous halves: 2^14-point blocks always (+23 %), 2^13-point blocks when the launch has
+  // too few workgroups to fill the chip (2^13 x 16: 23 -> 19 us).  (There was a split DIT form too: its stride-2
+  // stores -- each workgroup wrote every other word of a line -- inflated the HBM write traffic of the 2^14 x 2432 LDE
+  // by 1.66x, PMC WRITE_SIZE 1,036,585 KiB against 622,592 KiB algorithmic, for a 6 % shorter launch, and it gained
+  // nothing on small launches: profiles/r2_ntt_split_probe.txt.)
   return log_blk == 14 || workgroups < 512;
 }
 
@@ -1166,7 +985,7 @@ int intt_nat2br(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t 
     if ((rc = get_table(5, log_blk, 0, &b.lay))) return rc;
     b.log_n_total = log_n; b.n_cosets = 1; b.n_units = 0;
     KernelTimer kt(PROF_INTT_DIF, st, 16.0 * (double)n_cols * (double)((uint64_t)1 << log_n));
-    if (use_ntt_mx(log_blk, false)) {
+    if (use_ntt_mx(log_blk)) {
       const mxn::Tables* tab = nullptr;
       if ((rc = get_mx_tables(0, inverse, &tab))) return rc;
       b.n_units = n_cols << (log_n - log_blk);
@@ -1174,7 +993,7 @@ int intt_nat2br(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t 
       if (log_blk == 12) mxn::ntt_mx_dif_kernel<0><<<g, 256, (8u << 12) + 4 * mxn::C_LDS_WORDS, st>>>(b, tab);
       else if (log_blk == 13) mxn::ntt_mx_dif_kernel<1><<<g, 512, (8u << 13) + 4 * mxn::C_LDS_WORDS, st>>>(b, tab);
       else mxn::ntt_mx_dif_kernel<2><<<g, 512, (8u << 14) + 4 * mxn::C_LDS_WORDS, st>>>(b, tab);
-    } else if (use_split(log_blk, (uint64_t)n_cols << (log_n - log_blk), src, out, false)) {
+    } else if (use_split(log_blk, (uint64_t)n_cols << (log_n - log_blk), src, out)) {
       // two workgroups of the next smaller kernel per block (see Ntt16Args)
       if ((rc = get_table(inverse ? 1 : 0, log_blk - 1, 0, &b.tw))) return rc;
       b.tw_top = tw_b;
@@ -1225,33 +1044,18 @@ int ntt_br2nat(const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t o
     {
       // (attached: the kernel's own start / stop events -- this family is bench.py's `roofline`)
       KernelTimer kt(PROF_LDE_DIT, st, 8.0 * (double)n_cols * (double)((uint64_t)1 << log_n) * (1.0 + n_cosets), true);
-      if (use_ntt_mx(log_blk, true)) {
+      if (use_ntt_mx(log_blk)) {
         const mxn::Tables* tab = nullptr;
         if ((rc = get_mx_tables(1, inverse, &tab))) return rc;
         const uint32_t g = mx_grid((b.n_units + 7) / 8 * 8 * n_cosets, log_blk);
         if (log_blk == 12) BPG_LAUNCH_TIMED(kt, mxn::ntt_mx_dit_kernel<0>, g, 256, (8u << 12) + 4 * mxn::C_LDS_WORDS, st, b, tab);
         else if (log_blk == 13) BPG_LAUNCH_TIMED(kt, mxn::ntt_mx_dit_kernel<1>, g, 512, (8u << 13) + 4 * mxn::C_LDS_WORDS, st, b, tab);
         else BPG_LAUNCH_TIMED(kt, mxn::ntt_mx_dit_kernel<2>, g, 512, (8u << 14) + 4 * mxn::C_LDS_WORDS, st, b, tab);
-      } else if (use_split(log_blk, (uint64_t)b.n_units * n_cosets, in, out, true)) {
-        if ((rc = get_table(inverse ? 1 : 0, log_blk - 1, 0, &b.tw))) return rc;
-        b.tw_top = tw_b;
-        const dim3 grid1((b.n_units + 7) / 8 * 8 * n_cosets * 2);
-        if (log_blk == 14) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_kernel<13, 1>), grid1, 512, 8u << 13, st, b);
-        else BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_kernel<12, 1>), grid1, 256, 8u << 12, st, b);
       } else {
         const dim3 grid16((b.n_units + 7) / 8 * 8 * n_cosets);
-        if (log_blk == 12) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_kernel<12, 0>), grid16, 256, 8u << 12, st, b);
-        else if (log_blk == 13) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_kernel<13, 0>), grid16, 512, 8u << 13, st, b);
-        else {
-          // 2^14-point blocks: one workgroup per CU either way; with more items than CUs the workgroups are persistent and
-          // prefetch (ntt16_dit_persist_kernel).  Grid: a multiple of 8 * n_cosets, at most one workgroup per CU.
-          const uint32_t items = grid16.x, group = 8 * n_cosets;
-          const uint32_t resident = std::max<uint32_t>(group, (uint32_t)g_ntt_persist_wgs.load(std::memory_order_relaxed) / group * group);
-          if (g_ntt_persist.load(std::memory_order_relaxed) && items > resident && in != out)
-            BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_persist_kernel<14>), dim3(resident), 1024, 8u << 14, st, b, items);
-          else
-            BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(ntt16_dit_kernel<14, 0>), grid16, 1024, 8u << 14, st, b);
-        }
+        if (log_blk == 12) BPG_LAUNCH_TIMED(kt, ntt16_dit_kernel<12>, grid16, 256, 8u << 12, st, b);
+        else if (log_blk == 13) BPG_LAUNCH_TIMED(kt, ntt16_dit_kernel<13>, grid16, 512, 8u << 13, st, b);
+        else BPG_LAUNCH_TIMED(kt, ntt16_dit_kernel<14>, grid16, 1024, 8u << 14, st, b);
       }
     }
     BPG_LAUNCH_CHECK();
@@ -1292,13 +1096,11 @@ static int init_ntt_kernels_once() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << LOG_BLK_MAX));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dif_kernel<14, 0>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 14));
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_kernel<14, 0>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 14));
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_persist_kernel<14>),
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_kernel<14>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 14));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dif_kernel<13, 0>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 13));
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_kernel<13, 0>),
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_kernel<13>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 13));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mxn::ntt_mx_dif_kernel<1>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (8 << 13) + 4 * mxn::C_LDS_WORDS));
@@ -1309,8 +1111,6 @@ static int init_ntt_kernels_once() {
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mxn::ntt_mx_dit_kernel<2>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (8 << 14) + 4 * mxn::C_LDS_WORDS));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dif_kernel<13, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 13));
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt16_dit_kernel<13, 1>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 << 13));
   return BP_OK;
 }
@@ -1324,14 +1124,6 @@ int init_ntt_kernels() {
 }  // namespace bpg
 
 extern "C" {
-
-void bp_tune_ntt_split(int mode) { bpg::g_ntt_split.store(mode); }
-void bp_tune_ntt_persist(int on, int resident_workgroups) {
-  bpg::g_ntt_persist.store(on != 0);
-  if (resident_workgroups > 0) bpg::g_ntt_persist_wgs.store(resident_workgroups);
-}
-void bp_tune_ntt_mx(int mode) { bpg::g_ntt_mx.store(mode < 0 || mode > 5 ? 3 : mode); }
-void bp_tune_ntt_mx_wg_per_cu(int n) { bpg::g_mx_wg_per_cu.store(n); }
 
 // Host only (no device call): the constants of the matrix-core NTT kernels as the device gets them, for the CPU tests
 // that pin them to the integer model (tools/ntt_mx_model.py).  out_a: 8192 bytes, out_c: 128 i32,

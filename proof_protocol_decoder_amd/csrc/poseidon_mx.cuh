@@ -208,27 +208,27 @@ __device__ __forceinline__ void sbox_full(uint64_t (&e)[NS][3]) {
 namespace grp {
 constexpr int K = 8;
 constexpr poseidon::group::Layout LAY = poseidon::group::layout(K);
-// NG = number of groups: 2 = partial rounds 4..11 and 12..19, rounds 20..25 in the per-round form;
-//      3 = also rounds 20..25, as a SHORT group: steps 0..5 on the same form operands (the rows of forms 6 and 7 are
-//          garbage nobody reads), the new state from the MAIN operands of a six-round group (18 more operands,
-//          read from global memory).
+// Three groups: partial rounds 4..11, 12..19, and 20..25 as a SHORT group: steps 0..5 on the same form operands (the
+// rows of forms 6 and 7 are garbage nobody reads), the new state from the MAIN operands of a six-round group (18 more
+// operands, read from global memory).  (Two groups with rounds 20..25 one by one lost:
+// profiles/r3_poseidon_three_groups.txt.)
+constexpr int N_GROUPS = 3;
 constexpr int SHORT_K = 6;
 constexpr int OPS_WORDS = LAY.n_ops * 256;        // 40 KiB
 constexpr int C_WORDS = poseidon::group::CFORM_WORDS + poseidon::group::CMAIN_WORDS;
 constexpr int MDS_A_WORDS = 3 * 256;              // the per-round MDS layer's three A operands (Ctx::A), read from LDS
                                                   // per round instead of living in 12 VGPRs through the groups
 // device image: group operands, per group cform + cmain, the MDS layer's A operands -- this much goes to LDS --, then
-// (NG = 3) the short group's 18 MAIN operands, which stay in global memory (L2): with them in LDS a workgroup needs
+// the short group's 18 MAIN operands, which stay in global memory (L2): with them in LDS a workgroup needs
 // 67 KB, two per CU, and the kernels lose a quarter of their resident waves (profiles/r3_poseidon_three_groups.txt)
-template <int NG> constexpr int TABLE_WORDS = OPS_WORDS + NG * C_WORDS + MDS_A_WORDS;
-template <int NG> constexpr int IMAGE_WORDS = TABLE_WORDS<NG> + (NG == 3 ? 18 * 256 : 0);
+constexpr int TABLE_WORDS = OPS_WORDS + N_GROUPS * C_WORDS + MDS_A_WORDS;
+constexpr int IMAGE_WORDS = TABLE_WORDS + 18 * 256;
 
 // the whole workgroup copies the image into LDS, 16 bytes per lane and step (call once, then __syncthreads)
-template <int NG>
 __device__ __forceinline__ void load_tables(uint32_t* __restrict__ lds, const uint32_t* __restrict__ glob) {
   const uint4* src = (const uint4*)glob;
   uint4* dst = (uint4*)lds;
-  for (uint32_t i = threadIdx.x; i < (uint32_t)TABLE_WORDS<NG> / 4; i += blockDim.x) dst[i] = src[i];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)TABLE_WORDS / 4; i += blockDim.x) dst[i] = src[i];
 }
 
 // step 0: x[m] holds set m's word 0 in lane group 0; afterwards x[0] holds set j's in lane group j -- set j's form 0
@@ -368,12 +368,11 @@ __device__ __forceinline__ void step(State& s, uint64_t (&e)[4][3], const v4i* o
 }
 
 // rounds r0 .. r0 + 7 of the partial rounds: e = t(r0) in, t(r0 + 8) out (S-box-input form, constants included);
-// the third group of NG = 3 is short: rounds 20..25, t(26) out
-template <int NG>
+// the third group is short: rounds 20..25, t(26) out
 __device__ __forceinline__ void partial_group(State& s, Lanes& o, uint64_t (&e)[4][3], const uint32_t* tab,
                                               const uint32_t* __restrict__ gtab, int grp) {
   const uint32_t lane = threadIdx.x & 63, kb = lane >> 4;
-  const bool full = NG == 2 || grp < 2;   // wave-uniform
+  const bool full = grp < 2;   // wave-uniform
   const v4i* ops = (const v4i*)tab;
   const int* cform = (const int*)(tab + OPS_WORDS + grp * C_WORDS);
   const int* cmain = cform + poseidon::group::CFORM_WORDS;
@@ -399,7 +398,7 @@ __device__ __forceinline__ void partial_group(State& s, Lanes& o, uint64_t (&e)[
   // the new state: twelve words over (w, sigma_0 .. sigma_7 / sigma_5), recombined as in mds(); the sigma chunk is
   // read with its k-blocks rotated by m (bsig[m] is)
   const v4i* lops = ops + LAY.main_base * 64;
-  const v4i* gops = (const v4i*)(gtab + TABLE_WORDS<NG>);
+  const v4i* gops = (const v4i*)(gtab + TABLE_WORDS);
 #pragma unroll
   for (int g = 0; g < 3; g++) {
     v4i d[4][2];
@@ -437,24 +436,21 @@ __device__ __forceinline__ void partial_group(State& s, Lanes& o, uint64_t (&e)[
 }  // namespace grp
 
 // The grouped kernels keep the C table of the per-round MDS layer only for the rounds that still use it: 0..3 and
-// 20..29 (NG = 2: 14 x 384 bytes instead of 30 x 384: with the 45 KiB of group operands three workgroups still fit a
-// CU's LDS) or 0..3 and 26..29 (NG = 3)
-template <int NG> constexpr int CIN_GROUPED_ROUNDS = NG == 3 ? 8 : 14;
-template <int NG> constexpr int CIN_GROUPED_WORDS = CIN_GROUPED_ROUNDS<NG> * CIN_PER_ROUND;
-template <int NG> __device__ __forceinline__ int cin_slot(int rnd) { return rnd < 4 ? rnd : rnd - (30 - CIN_GROUPED_ROUNDS<NG>); }
-template <int NG>
+// 26..29 (8 x 384 bytes instead of 30 x 384: with the 45 KiB of group operands three workgroups still fit a CU's LDS)
+constexpr int CIN_GROUPED_ROUNDS = 8;
+constexpr int CIN_GROUPED_WORDS = CIN_GROUPED_ROUNDS * CIN_PER_ROUND;
+__device__ __forceinline__ int cin_slot(int rnd) { return rnd < 4 ? rnd : rnd - (30 - CIN_GROUPED_ROUNDS); }
 __device__ __forceinline__ void build_cin_grouped(uint32_t* __restrict__ cin) {
   const uint4* src = (const uint4*)CIN_TABLE.v;
   uint4* dst = (uint4*)cin;
-  for (uint32_t i = threadIdx.x; i < (uint32_t)CIN_GROUPED_WORDS<NG> / 4; i += blockDim.x)
-    dst[i] = src[i < 4 * CIN_PER_ROUND / 4 ? i : i + (30 - CIN_GROUPED_ROUNDS<NG>) * CIN_PER_ROUND / 4];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)CIN_GROUPED_WORDS / 4; i += blockDim.x)
+    dst[i] = src[i < 4 * CIN_PER_ROUND / 4 ? i : i + (30 - CIN_GROUPED_ROUNDS) * CIN_PER_ROUND / 4];
 }
 
 // mds<4> with the A operands read from the LDS image (one ds_read_b128 each per round, shared by the four sets)
-template <int NG>
 __device__ __forceinline__ void mds4_lds(uint64_t (&e)[4][3], const Ctx& c, int rnd, const uint32_t* tab) {
-  const v4i* cr = (const v4i*)(c.cin + cin_slot<NG>(rnd) * CIN_PER_ROUND);
-  const v4i* am = (const v4i*)(tab + grp::OPS_WORDS + NG * grp::C_WORDS) + (threadIdx.x & 63);
+  const v4i* cr = (const v4i*)(c.cin + cin_slot(rnd) * CIN_PER_ROUND);
+  const v4i* am = (const v4i*)(tab + grp::OPS_WORDS + grp::N_GROUPS * grp::C_WORDS) + (threadIdx.x & 63);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     v4i blo, bhi;
@@ -478,9 +474,8 @@ __device__ __forceinline__ void mds4_lds(uint64_t (&e)[4][3], const Ctx& c, int 
   }
 }
 
-// The permutation with the partial rounds grouped (four sets per wave; tab = the LDS image of grp::load_tables<NG>):
-// NG = 2: rounds 4..19 in two groups, 20..25 one by one; NG = 3: all 22 partial rounds in groups (8 + 8 + 6)
-template <int NG>
+// The permutation with the partial rounds grouped (four sets per wave; tab = the LDS image of grp::load_tables):
+// all 22 partial rounds in groups (8 + 8 + 6)
 __device__ __forceinline__ void permute_grouped(uint64_t (&e)[4][3], const Ctx& c, const uint32_t* tab,
                                                 const uint32_t* __restrict__ gtab) {
 #pragma unroll
@@ -493,25 +488,18 @@ __device__ __forceinline__ void permute_grouped(uint64_t (&e)[4][3], const Ctx& 
 #pragma unroll 1
   for (int k = 0; k < 4; k++, rnd++) {
     sbox_full<4>(e);
-    mds4_lds<NG>(e, c, rnd, tab);
+    mds4_lds(e, c, rnd, tab);
   }
   grp::State s;
   grp::init_state(s);
   grp::Lanes o = grp::lanes_of(threadIdx.x & 63);
 #pragma unroll 1
-  for (int g = 0; g < NG; g++) grp::partial_group<NG>(s, o, e, tab, gtab, g);
-  rnd = NG == 3 ? 26 : 20;
-  if constexpr (NG == 2) {
-#pragma unroll 1
-    for (; rnd < 26; rnd++) {
-      sbox_word0<4>(e, c);
-      mds4_lds<NG>(e, c, rnd, tab);
-    }
-  }
+  for (int g = 0; g < grp::N_GROUPS; g++) grp::partial_group(s, o, e, tab, gtab, g);
+  rnd = 26;
 #pragma unroll 1
   for (int k = 0; k < 4; k++, rnd++) {
     sbox_full<4>(e);
-    mds4_lds<NG>(e, c, rnd, tab);
+    mds4_lds(e, c, rnd, tab);
   }
 }
 

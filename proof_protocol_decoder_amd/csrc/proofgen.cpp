@@ -19,6 +19,7 @@
 #include "air_check.hpp"
 #include "mpt.hpp"
 #include "prover.hpp"
+#include "tune.hpp"
 
 using namespace bpg;
 extern "C" int bp_use_blocking_sync(int device);
@@ -201,16 +202,13 @@ int emit_box(uint64_t kind, uint64_t circuit, const std::vector<uint64_t>& pi, c
 }
 
 // Recursion-shaped proofs; transcript of each = circuit digest, hash of the public inputs, trace cap.  `n` proofs of
-// the state's one recursion shape are proved in lock-step, up to g_rec_batch at a time (stark_prove_batch: every
+// the state's one recursion shape are proved in lock-step, up to Tune::rec_batch at a time (stark_prove_batch: every
 // launch and every host wait is shared; circuits, public inputs and transcripts are each proof's own).
-std::atomic<uint32_t> g_rec_batch{MAX_BATCH};  // bp_tune_rec_batch: 1 = one proof at a time
-std::atomic<int> g_witness_threads{7};           // bp_tune_witness_threads: host threads a lone prover makes its Poseidon-row witness on
-std::atomic<int> g_side_lanes{1};               // bp_tune_side_lanes: 0 = no side lanes, n = while at most n provers are at work
 // paths (nullable): per proof the witness of the Merkle paths its circuit walks (Circuit::lay.n_paths of them)
 // first_leaf (nullable, 4 words per proof): the digest of the trace leaf each proof's first query opens
 int rec_prove_batch(Worker& w, const StarkCfg& rc, uint32_t n, const Circuit* const* circ, const std::vector<uint64_t>* pi,
                     std::vector<uint64_t>* proofs, const std::vector<PathWitness>* paths = nullptr, uint64_t* first_leaf = nullptr) {
-  const uint32_t cap = std::min<uint32_t>(std::min<uint32_t>(MAX_BATCH, std::max<uint32_t>(1, g_rec_batch.load(std::memory_order_relaxed))),
+  const uint32_t cap = std::min<uint32_t>(std::min<uint32_t>(MAX_BATCH, std::max<uint32_t>(1, tune().rec_batch.load(std::memory_order_relaxed))),
                                           std::max<uint32_t>(1, MAX_BATCH_QUERIES / std::max<uint32_t>(1, rc.num_queries)));
   const uint64_t N = (uint64_t)1 << rc.log_n;
   for (uint32_t first = 0; first < n; first += cap) {
@@ -275,7 +273,7 @@ int rec_prove_batch(Worker& w, const StarkCfg& rc, uint32_t n, const Circuit* co
       }
     };
     {
-      const uint32_t max_threads = (uint32_t)std::max(1, g_witness_threads.load(std::memory_order_relaxed));
+      const uint32_t max_threads = (uint32_t)std::max(1, tune().witness_threads.load(std::memory_order_relaxed));
       const uint32_t n_threads = (provers_active() <= 1 && jobs.size() >= 4) ? (uint32_t)std::min<size_t>(max_threads, jobs.size()) : 1;
       std::atomic<size_t> next{0};
       std::atomic<bool> oom{false};
@@ -432,10 +430,6 @@ void root_after(const uint64_t root_before[4], uint64_t seed, uint64_t txn_numbe
 }  // namespace
 
 extern "C" {
-
-void bp_tune_rec_batch(int n) { g_rec_batch.store(n < 1 ? 1 : (n > (int)MAX_BATCH ? MAX_BATCH : (uint32_t)n)); }
-void bp_tune_side_lanes(int n) { g_side_lanes.store(n < 0 ? 0 : n); }
-void bp_tune_witness_threads(int n) { g_witness_threads.store(n < 1 ? 1 : (n > 16 ? 16 : n)); }
 
 void bp_config_default(bp_config* c) {
   // constants.rs:6-18, positional order of prover_state.rs:85-93
@@ -950,7 +944,7 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
   // shard -- borrows the streams of up to three idle workers and the commitments overlap: the wide Keccak table's long
   // sponge chains no longer have the chip to themselves (largest first, each to the lane with the least work so far).
   std::vector<std::unique_ptr<SideLane>> sides;
-  if (s && provers_active() <= g_side_lanes.load(std::memory_order_relaxed))
+  if (s && provers_active() <= tune().side_lanes.load(std::memory_order_relaxed))
     for (int k = 0; k < 3; k++) {
       std::unique_ptr<SideLane> l = SideLane::try_acquire(s);
       if (!l) break;

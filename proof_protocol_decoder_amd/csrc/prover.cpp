@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "prover.hpp"
+#include "tune.hpp"
 #include <algorithm>
 #include <chrono>
 #if defined(__x86_64__)
@@ -109,12 +110,10 @@ __attribute__((always_inline)) static inline void poseidon_host_body(uint64_t s[
 __attribute__((target("avx2"))) static void poseidon_host_avx2(uint64_t s[12]) { poseidon_host_body<true>(s); }
 #endif
 static void poseidon_host_scalar(uint64_t s[12]) { poseidon_host_body<false>(s); }
-static std::atomic<int> g_host_poseidon{0};  // bp_tune_host_poseidon: 0 = by the CPU, 1 = scalar form (tests)
-void tune_host_poseidon(int mode) { g_host_poseidon.store(mode == 1 ? 1 : 0); }
 void poseidon_host(uint64_t s[12]) {
 #if defined(__x86_64__)
   static const bool avx2 = __builtin_cpu_supports("avx2");
-  if (avx2 && g_host_poseidon.load(std::memory_order_relaxed) == 0) return poseidon_host_avx2(s);
+  if (avx2 && tune().host_poseidon.load(std::memory_order_relaxed) == 0) return poseidon_host_avx2(s);
 #endif
   poseidon_host_scalar(s);
 }
@@ -147,7 +146,7 @@ __attribute__((target("avx2"))) static void permutation_wires_avx2(uint64_t (&s)
 static void permutation_wires(uint64_t (&s)[12], uint64_t* w) {
 #if defined(__x86_64__)
   static const bool avx2 = __builtin_cpu_supports("avx2");
-  if (avx2 && g_host_poseidon.load(std::memory_order_relaxed) == 0) return permutation_wires_avx2(s, w);
+  if (avx2 && tune().host_poseidon.load(std::memory_order_relaxed) == 0) return permutation_wires_avx2(s, w);
 #endif
   permutation_wires_body<false>(s, w);
 }
@@ -216,7 +215,6 @@ static uint32_t n_fri_layers(const StarkCfg& c) {  // FriReductionStrategy::Cons
   }
   return n;
 }
-std::atomic<int> g_k5_spread_all{0};  // measurement knob (bp_tune_k5_spread): the loaded-device spreading rule for the synthetic AIR too
 int check_cfg(const StarkCfg& c) {
   const air::Desc* ai = air::info(c.air_id);
   const auto program = ai ? nullptr : air::prog::find(c.air_id);
@@ -354,12 +352,10 @@ void Worker::destroy() {
 // txn-proofs/s).  There the wait is the library's own: poll the event, and once the wait is older than a few
 // microseconds sleep between polls, an eighth of the time waited so far (at most 200 us): the latency added to a
 // stage is bounded by 1/8 of the stage, the CPU time of a waiting thread by the poll rate.
-static std::atomic<int> g_host_wait{0};  // 0: by the device's mode; 1: always the runtime's wait; 2: always poll + sleep
-void tune_host_wait(int mode) { g_host_wait.store(mode < 0 || mode > 2 ? 0 : mode); }
 extern "C" int bp_host_wait_mode(int device);
 int Worker::wait_recorded() {
   using clock = std::chrono::steady_clock;
-  const int knob = g_host_wait.load(std::memory_order_relaxed);
+  const int knob = tune().host_wait.load(std::memory_order_relaxed);
   // While few provers are at work on the device (a lone transaction, the end of a shard, the aggregation tree's last
   // levels) every host wait is on the proof's critical path and there are cores to spare: poll without sleeping for
   // a while first -- an interrupt-driven wake-up costs 50..100 us, a poll sees the event within a few --, then wait
@@ -509,7 +505,7 @@ int quotient_args(const StarkCfg& cfg, const Ctl& ctl, uint64_t alpha0, uint64_t
   // critical path (Keccak sponge, 2^9 rows: 2.6 ms against 0.11 ms spread, profiles/r3_k5_air_probe.txt), so their
   // units are spread until the launch has 256 workgroups.  The proofs of a batch (grid.z) count as rows of the launch.
   const uint32_t n_units = qa.n_air_units + qa.n_ctl_units, wg_x = (uint32_t)((M + 255) / 256) * std::max<uint32_t>(1, batch);
-  const uint32_t loaded_rows = (cfg.air_id == air::SYNTHETIC && !g_k5_spread_all.load(std::memory_order_relaxed))
+  const uint32_t loaded_rows = (cfg.air_id == air::SYNTHETIC && !tune().k5_spread.load(std::memory_order_relaxed))
                                    ? 1 : std::min<uint32_t>(n_units, std::max<uint32_t>(1, (256 + wg_x - 1) / wg_x));
   const bool is_loaded = loaded < 0 ? device_loaded() : loaded != 0;
   const uint32_t want_rows = is_loaded ? loaded_rows : std::min<uint32_t>(n_units, std::max<uint32_t>(1, (2048 + wg_x - 1) / wg_x));

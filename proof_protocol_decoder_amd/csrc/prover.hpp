@@ -75,7 +75,6 @@ struct ProofLayout {
 };
 constexpr uint64_t PROOF_MAGIC = 0x4B52415453475042ULL;  // "BPGSTARK"
 constexpr size_t PROOF_HDR_WORDS = 16;
-extern std::atomic<int> g_k5_spread_all;
 int check_cfg(const StarkCfg& c);
 ProofLayout proof_layout(const StarkCfg& c);
 void proof_digest(const StarkCfg& c, const uint64_t* proof, uint64_t out[4]);
@@ -169,8 +168,6 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t batch, const Comm
                       const Committed* trace, const uint64_t* const* d_trace_values, const Ctl* ctl, Challenger* ch,
                       std::vector<uint64_t>* proofs, uint64_t* first_trace_leaf = nullptr);
 
-void tune_host_wait(int mode);  // bp_tune_host_wait
-void tune_host_poseidon(int mode);  // bp_tune_host_poseidon
 // hash_kernels.hip: +1 / -1 as a prover starts / finishes (the Poseidon kernel choice follows the load)
 void prover_active(int delta);
 int provers_active();  // how many are at work right now

@@ -1286,9 +1286,9 @@ __global__ void __launch_bounds__(256) pow_grind_kernel(bpg::BatchOf<bpg::PowArg
 }
 // The same search with the MDS layer on the matrix cores (poseidon_mx.cuh): a wave takes 64 consecutive candidates
 // as four sets of 16, lane (n, kb) holds words kb, kb + 4, kb + 8 of candidate 16m + n; word 7 is slot 1 of lanes kb = 3.
-// GR: 0 = every round by itself; 2 / 3 = the partial rounds in groups (gtab = the device image of the operand tables,
-// as in hash_kernels.hip).
-template <int GR>
+// GR: false = every round by itself; true = the partial rounds in groups (gtab = the device image of the operand
+// tables, as in hash_kernels.hip).
+template <bool GR>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
 pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result, const uint32_t* __restrict__ gtab) {
   const bpg::PowArgs& a = batch.a[blockIdx.z];
@@ -1304,12 +1304,11 @@ pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result
     beaten = __hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base + (uint64_t)blockIdx.x * 256;
   __syncthreads();
   if (beaten) return;
-  constexpr int NG = GR ? GR : 2;
-  __shared__ __attribute__((aligned(16))) uint32_t cin[GR ? poseidon::mx::CIN_GROUPED_WORDS<NG> : poseidon::mx::CIN_WORDS];
-  __shared__ __attribute__((aligned(16))) uint32_t gt[GR ? poseidon::mx::grp::TABLE_WORDS<NG> : 4];
-  if constexpr (GR != 0) {
-    poseidon::mx::build_cin_grouped<NG>(cin);
-    poseidon::mx::grp::load_tables<NG>(gt, gtab);
+  __shared__ __attribute__((aligned(16))) uint32_t cin[GR ? poseidon::mx::CIN_GROUPED_WORDS : poseidon::mx::CIN_WORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t gt[GR ? poseidon::mx::grp::TABLE_WORDS : 4];
+  if constexpr (GR) {
+    poseidon::mx::build_cin_grouped(cin);
+    poseidon::mx::grp::load_tables(gt, gtab);
   } else {
     poseidon::mx::build_cin(cin);
   }
@@ -1326,7 +1325,7 @@ pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result
 #pragma unroll
     for (int m = 0; m < 4; m++) e[m][s] = mine ? cand0 + 16 * m : w;
   }
-  if constexpr (GR != 0) poseidon::mx::permute_grouped<NG>(e, c, gt, gtab);
+  if constexpr (GR) poseidon::mx::permute_grouped(e, c, gt, gtab);
   else poseidon::mx::permute<4>(e, c);
   if (c.kb == 3) {
 #pragma unroll
@@ -1695,11 +1694,9 @@ int launch_pow(const PowArgs* a, uint32_t batch, uint32_t n_candidates, unsigned
   const BatchOf<PowArgs> ab = batch_of(a, batch);
   const dim3 grid(n_candidates / 256, 1, batch);
   if (poseidon_mx()) {
-    int ng = 0;
-    const uint32_t* gtab = group_tables(&ng);
-    if (gtab && ng == 3) pow_grind_mx_kernel<3><<<grid, 256, 0, st>>>(ab, d_result, gtab);
-    else if (gtab) pow_grind_mx_kernel<2><<<grid, 256, 0, st>>>(ab, d_result, gtab);
-    else pow_grind_mx_kernel<0><<<grid, 256, 0, st>>>(ab, d_result, nullptr);
+    const uint32_t* gtab = group_tables();
+    if (gtab) pow_grind_mx_kernel<true><<<grid, 256, 0, st>>>(ab, d_result, gtab);
+    else pow_grind_mx_kernel<false><<<grid, 256, 0, st>>>(ab, d_result, nullptr);
   } else
     pow_grind_kernel<<<grid, 256, 0, st>>>(ab, d_result);
   BPG_LAUNCH_CHECK();

@@ -1,0 +1,62 @@
+// tune.cpp -- the bp_tune_* entry points (bpg.h): each clamps its argument and stores it in bpg::Tune (tune.hpp).
+#include "tune.hpp"
+#include <cstdio>
+#include "common.hpp"
+#include "stark_kernels.hpp"
+
+namespace bpg {
+Tune& tune() {
+  static Tune t;
+  return t;
+}
+static_assert(MAX_BATCH == 8, "Tune::rec_batch's default is MAX_BATCH");
+}  // namespace bpg
+
+// every knob, in the order bp_debug_tune_state reports them
+#define BPG_KNOBS(X)                                                                                            \
+  X(quad_threshold) X(assume_loaded) X(merkle_fused) X(merkle_wide) X(poseidon_mx) X(poseidon_mx_sets)          \
+  X(poseidon_grouped) X(ntt_mx) X(ntt_split) X(k5_spread) X(host_wait) X(host_poseidon) X(rec_batch)            \
+  X(witness_threads) X(side_lanes)
+
+extern "C" {
+
+void bp_tune_quad_threshold(uint64_t n_perms) { bpg::tune().quad_threshold.store(n_perms); }
+void bp_tune_assume_loaded(int mode) { bpg::tune().assume_loaded.store(mode < 0 ? -1 : (mode != 0)); }
+void bp_tune_merkle_fused(int mode) { bpg::tune().merkle_fused.store(mode < 0 ? -1 : (mode != 0)); }
+void bp_tune_merkle_wide(int log2_parents) { bpg::tune().merkle_wide.store(log2_parents < 8 || log2_parents > 24 ? 0 : log2_parents); }
+void bp_tune_poseidon_mx(int on) { bpg::tune().poseidon_mx.store(on != 0); }
+void bp_tune_poseidon_mx_sets(int sets) { bpg::tune().poseidon_mx_sets.store(sets == 1 || sets == 2 || sets == 4 ? sets : 0); }
+void bp_tune_poseidon_grouped(int on) { bpg::tune().poseidon_grouped.store(on != 0); }
+void bp_tune_ntt_mx(int mode) { bpg::tune().ntt_mx.store(mode < 0 || mode > 3 ? 3 : mode); }
+void bp_tune_ntt_split(int mode) { bpg::tune().ntt_split.store(mode == 1 || mode == 2 ? mode : 0); }
+void bp_tune_k5_spread(int on) { bpg::tune().k5_spread.store(on != 0); }
+void bp_tune_host_wait(int mode) { bpg::tune().host_wait.store(mode < 0 || mode > 2 ? 0 : mode); }
+void bp_tune_host_poseidon(int mode) { bpg::tune().host_poseidon.store(mode == 1 ? 1 : 0); }
+void bp_tune_rec_batch(int n) { bpg::tune().rec_batch.store(n < 1 ? 1 : (n > (int)bpg::MAX_BATCH ? (int)bpg::MAX_BATCH : n)); }
+void bp_tune_witness_threads(int n) { bpg::tune().witness_threads.store(n < 1 ? 1 : (n > 16 ? 16 : n)); }
+void bp_tune_side_lanes(int n) { bpg::tune().side_lanes.store(n < 0 ? 0 : n); }
+
+void bp_tune_reset(void) {
+  const bpg::Tune defaults;
+  bpg::Tune& t = bpg::tune();
+#define X(k) t.k.store(defaults.k.load());
+  BPG_KNOBS(X)
+#undef X
+}
+
+int bp_debug_tune_state(char* buf, size_t cap) {
+  if (!buf || !cap) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_tune_state: no buffer");
+  const bpg::Tune& t = bpg::tune();
+  size_t n = 0;
+#define X(k)                                                                                   \
+  if (n < cap) {                                                                               \
+    const int w = std::snprintf(buf + n, cap - n, #k "=%lld\n", (long long)t.k.load());         \
+    n += w > 0 ? (size_t)w : 0;                                                                \
+  }
+  BPG_KNOBS(X)
+#undef X
+  if (n >= cap) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_tune_state: buffer of %zu bytes is too small", cap);
+  return BP_OK;
+}
+
+}  // extern "C"

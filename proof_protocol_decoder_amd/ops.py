@@ -4,18 +4,51 @@ torch is used only for device memory and streams (int64 tensors carry the u64 bi
 Layouts are the ones documented in include/bpg.h: column-major matrices, natural-order values,
 bit-reversed coefficients, coset-major LDE.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
-from ._lib import StarkCfg, check, lib, take_buffer
+from ._lib import KNOBS, StarkCfg, check, lib, take_buffer
 
 NTT_FWD_BR2NAT, NTT_INV_NAT2BR, NTT_FWD_NAT, NTT_INV_NAT = 0, 1, 2, 3
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+_tuned_active = False
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """Set the named bp_tune_* knobs (tuned(ntt_mx=0, ntt_split=2) calls bp_tune_ntt_mx(0), bp_tune_ntt_split(2)) for
+    the body; on the way out, exception or not, bp_tune_reset() puts EVERY knob back to the library's default.
+    So blocks do not nest: an inner one would drop the outer one's knobs on its way out, and is refused."""
+    global _tuned_active
+    if _tuned_active:
+        raise RuntimeError("ops.tuned() inside ops.tuned(): name all the knobs in one call")
+    unknown = sorted(set(knobs) - set(KNOBS))
+    if unknown:
+        raise TypeError("no such knob: %s (there are: %s)" % (", ".join(unknown), ", ".join(KNOBS)))
+    L = lib()
+    _tuned_active = True
+    try:
+        for name, value in knobs.items():
+            getattr(L, "bp_tune_" + name)(value)
+        yield
+    finally:
+        _tuned_active = False
+        L.bp_tune_reset()
+
+
+def tune_state():
+    """bp_debug_tune_state: the current value of every knob, "name=value" lines in a fixed order."""
+    buf = C.create_string_buffer(1024)
+    check(lib().bp_debug_tune_state(buf, len(buf)))
+    return buf.value.decode()
 
 
 def _require_cuda(t):

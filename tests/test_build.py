@@ -59,9 +59,9 @@ def test_no_throughput_kernel_spills_sgprs(tmp_path):
             if m and int(m.group(1)):
                 # scratch (VGPR spills or per-lane arrays) is a decision, not an accident (HISTORY.md section 10): the
                 # kernels that have some today -- the two Keccak witness generators (per-lane 25-lane states), the
-                # Keccak-f evaluator held to three waves per SIMD, two opt-in NTT forms -- are listed with a cap; a new
+                # Keccak-f evaluator held to three waves per SIMD, one opt-in NTT form -- are listed with a cap; a new
                 # one, or one that grows, fails the build check
-                known = {"quotient_air_kernelILj1E": 128, "ntt16_dit_persist_kernel": 160, "keccak_trace_kernel": 512,
+                known = {"quotient_air_kernelILj1E": 128, "keccak_trace_kernel": 512,
                          "keccak_sponge_trace_kernel": 384, "leaf_hash_rows_kernel": 16, "ntt_mx_dit_kernelILi2E": 64}
                 cap = next((v for k, v in known.items() if k in name), 0)
                 if int(m.group(1)) > cap:

@@ -57,12 +57,9 @@ def test_quotient_eval_equals_the_built_in_kernel(bpg, air_id, log_n, loaded):
     ctl = [int(v) for v in rng.integers(2, P, size=4, dtype=np.uint64)]
     alphas = [int(v) for v in rng.integers(2, P, size=2, dtype=np.uint64)]
     cfg = bpg.ops.stark_cfg(log_n, d.n_cols)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         want = bpg.ops.quotient_eval(cfg, trace, aux, None, ctl, alphas, air_id=air_id)
         got = bpg.ops.quotient_eval(cfg, trace, aux, None, ctl, alphas, air_id=reg)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape == (2, rows)
     assert bool((got == want).all()), "first mismatch at %s" % (got != want).nonzero()[0].tolist()
     assert bool((want != 0).any())
@@ -115,12 +112,9 @@ def test_a_registered_transcription_gives_the_built_ins_proof(bpg, air_id, log_n
     reg = cases.register(PROGRAM[air_id]())
     cfg = cases.cfg_for(air_id, log_n, num_queries=nq, pow_bits=pb)
     trace = getattr(bpg.ops, TRACE[air_id])(log_n, seed=SEED + log_n)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         want = bpg.ops.stark_prove_trace(air_id, cfg, trace)
         got = bpg.ops.stark_prove_trace(reg, cfg, trace)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape and int(got[14]) == reg and int(want[14]) == air_id
     diff = np.nonzero(got != want)[0]
     assert diff.tolist() == [14], diff[:10]
@@ -281,12 +275,9 @@ def test_device_checker_on_a_random_program(bpg, name, log_n):
     assert host.n_violated_rows >= 2 and host.rows[0] == 0 and host.rows[-1] == n - 1
     assert reported(host)[:16] == rnd.violations(c.b, bad, consts, pub, host.rows)[:16]
     for loaded in (0, 1):
-        bpg.lib().bp_tune_assume_loaded(loaded)
-        try:
+        with bpg.ops.tuned(assume_loaded=loaded):
             r = bpg.ops.check_air_trace(reg, t, consts=cd, pub=pub)
             dev = bpg.ops.check_air_trace(reg, to_dev(bad), consts=cd, pub=pub, max_rows=64, max_viol=4096)
-        finally:
-            bpg.lib().bp_tune_assume_loaded(-1)
         assert r.ok and r.rows == [] and r.violations == [], (loaded, r)
         assert key(dev) == key(host), loaded
 
@@ -334,11 +325,8 @@ def test_quotient_eval_of_a_random_program_equals_the_fold_over_python_integers(
     cfg = bpg.ops.stark_cfg(log_n, c.b.n_cols, n_const=c.b.n_const, deg_pow=c.deg_pow, rate_bits=r)
     got = []
     for loaded in (0, 1):
-        bpg.lib().bp_tune_assume_loaded(loaded)
-        try:
+        with bpg.ops.tuned(assume_loaded=loaded):
             got.append(bpg.ops.quotient_eval(cfg, lde, aux, clde, ctl, alphas, air_id=reg))
-        finally:
-            bpg.lib().bp_tune_assume_loaded(-1)
     assert got[0].shape == got[1].shape == (2, rows) and bool((got[0] == got[1]).all()), "spread != one-pass"
     assert bool((got[0] != 0).any())
     ms = [0, 1, n - 2, n - 1]
@@ -371,11 +359,8 @@ def test_a_random_program_proves_and_verifies(bpg, name, log_n):
     cap = constants_cap(bpg, cd, log_n, rate_bits=c.rate_bits)
     rng = np.random.default_rng([0x902, c.kw["seed"], log_n])
     for loaded in ((0, 1) if log_n <= 8 else ((rnd.CASES.index(name) + log_n) % 2,)):
-        bpg.lib().bp_tune_assume_loaded(loaded)
-        try:
+        with bpg.ops.tuned(assume_loaded=loaded):
             proof = bpg.ops.stark_prove_trace(reg, cfg, t, consts=cd, pub=pub)
-        finally:
-            bpg.lib().bp_tune_assume_loaded(-1)
         assert int(proof[14]) == reg
         assert cases.verify(reg, cfg, proof, cap, pub) == 0, (loaded, bpg.lib().bp_last_error())
     flipped = proof.copy()

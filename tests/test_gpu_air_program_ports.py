@@ -222,11 +222,8 @@ def test_quotient_eval_of_a_program_with_ports_equals_the_fold_over_python_integ
     assert d.n_aux == 2 * len(b.ports)
     ctl, alphas = challenges(seed + 2), challenges(seed + 3, 2)
     cfg = bpg.ops.stark_cfg(log_n, 8, deg_pow=deg_pow, rate_bits=r)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         got = bpg.ops.quotient_eval(cfg, lde, aux, None, ctl, alphas, air_id=reg)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     rng = np.random.default_rng(seed + 4)
     pos = [0, n - 1, rows - n, rows - 1, n, 2 * n - 1] + [int(v) for v in rng.integers(0, rows, size=18)]
     nxt = [(p >> log_n) * n + ((p & (n - 1)) + 1) % n for p in pos]
@@ -282,12 +279,9 @@ def test_memory_transcription_with_a_port_gives_the_built_in_quotient(bpg, log_n
     trace, aux = random_lde(45, rows, 0xC200 + log_n), random_lde(2, rows, 0xC201 + log_n)
     ctl, alphas = challenges(0xC202 + log_n), challenges(0xC203 + log_n, 2)
     cfg = bpg.ops.stark_cfg(log_n, 45)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         want = bpg.ops.quotient_eval(cfg, trace, aux, None, ctl, alphas, air_id=3)
         got = bpg.ops.quotient_eval(cfg, trace, aux, None, ctl, alphas, air_id=reg)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape == (2, rows)
     assert bool((got == want).all()), "first mismatch at %s" % (got != want).nonzero()[0].tolist()
     assert bool((want != 0).any())

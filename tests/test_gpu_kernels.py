@@ -10,9 +10,8 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(params=["mx", "valu"])
 def ntt_form(request, bpg):
     """2^12..2^14-point blocks: 16-point DFTs on the matrix cores (ntt_mx.cuh) / VALU butterflies"""
-    bpg.lib().bp_tune_ntt_mx(2 if request.param == "mx" else 0)   # 2: also the 2^14-point blocks
-    yield request.param
-    bpg.lib().bp_tune_ntt_mx(3)
+    with bpg.ops.tuned(ntt_mx=2 if request.param == "mx" else 0):   # 2: also the 2^14-point blocks
+        yield request.param
 
 
 @pytest.mark.parametrize("log_n,n_cols", [(0, 3), (1, 2), (2, 5), (3, 4), (5, 7), (9, 16), (12, 9), (13, 3), (14, 5),
@@ -56,18 +55,16 @@ def test_ntt_takes_any_u64_in_every_kernel_form(bpg, log_n, n_cols):
     raw[:, n // 2 + 1::7] = np.uint64(P + 12345)
     red = raw % np.uint64(P)
     br = bitrev_perm(log_n)
-    try:
-        outs = {}
-        for mode in (1, 2, 0):                    # never split / split wherever possible / automatic
-            bpg.lib().bp_tune_ntt_split(mode)
-            for mx in (0, 3):
-                bpg.lib().bp_tune_ntt_mx(mx)
+    outs = {}
+    for mode in (1, 2, 0):                    # never split / split wherever possible / automatic
+        for mx in (0, 3):
+            with bpg.ops.tuned(ntt_split=mode, ntt_mx=mx):
                 d = to_dev(raw)
                 inv = to_host(bpg.ops.intt_batch(d))                      # out of place: split DIF eligible
                 assert (to_host(d) == raw).all()
                 inv_red = to_host(bpg.ops.intt_batch(to_dev(red)))
                 assert (inv == inv_red).all(), ("inverse", mode, mx)
-                _, lde = bpg.ops.lde_batch(to_dev(raw[:, br]), 1, from_coeffs=True)   # unscaled + scaled split DIT
+                _, lde = bpg.ops.lde_batch(to_dev(raw[:, br]), 1, from_coeffs=True)   # unscaled + scaled DIT
                 _, lde_red = bpg.ops.lde_batch(to_dev(red[:, br]), 1, from_coeffs=True)
                 assert (to_host(lde) == to_host(lde_red)).all(), ("lde", mode, mx)
                 fwd = to_host(bpg.ops.ntt_batch_(to_dev(raw[:, br]), bpg.ops.NTT_FWD_BR2NAT))
@@ -75,12 +72,9 @@ def test_ntt_takes_any_u64_in_every_kernel_form(bpg, log_n, n_cols):
                 assert (fwd == fwd_red).all(), ("forward", mode, mx)
                 outs[(mode, mx)] = (inv, to_host(lde), fwd)
                 assert (inv < np.uint64(P)).all() and (fwd < np.uint64(P)).all()
-        first = outs[(1, 0)]
-        for k, v in outs.items():
-            assert all((a == b).all() for a, b in zip(first, v)), k
-    finally:
-        bpg.lib().bp_tune_ntt_split(0)
-        bpg.lib().bp_tune_ntt_mx(3)
+    first = outs[(1, 0)]
+    for k, v in outs.items():
+        assert all((a == b).all() for a, b in zip(first, v)), k
 
 
 @pytest.mark.parametrize("log_n,rate_bits,n_cols", [(3, 1, 2), (6, 1, 5), (9, 1, 16), (12, 3, 7), (14, 1, 4),
@@ -100,33 +94,22 @@ def test_lde_matches_oracle(bpg, oracle, log_n, rate_bits, n_cols, ntt_form):
     assert (to_host(lde2) == to_host(lde)).all() and (to_host(c2) == to_host(coeffs)).all()
 
 
-def test_persistent_lde_workgroups_give_the_one_shot_grid_s_values(bpg, oracle):
-    """2^14-point coset-LDE blocks run as persistent workgroups that prefetch the next block's coefficients
-    (ntt16_dit_persist_kernel) once a launch has more (block, coset) items than resident workgroups: with 8 / 16 / 32
-    resident workgroups -- every workgroup walks over several items, padding ids included (37 columns: the last group of
-    eight is padded) -- the values are those of the one-shot grid and of the oracle; inputs may be any u64."""
-    import ctypes as C
-    L = bpg.lib()
-    L.bp_tune_ntt_persist.argtypes = [C.c_int, C.c_int]
-    L.bp_tune_ntt_persist.restype = None
+def test_lde_of_2_14_point_blocks_with_a_padded_last_group_of_eight(bpg, oracle):
+    """2^14-point coset-LDE blocks, one workgroup each (ntt16_dit_kernel<14>), on the XCD-aware grid that deals the
+    (block, coset) items out in groups of eight: with 37 columns the last group is padded and its spare workgroups must
+    leave without touching memory.  Inputs may be any u64: all 37 columns equal the LDE of the reduced input, and the
+    first two the oracle's."""
     rng = np.random.default_rng(77)
     log_n, n_cols = 14, 37
     vals = rng.integers(0, 1 << 64, size=(n_cols, 1 << log_n), dtype=np.uint64)
     vals[:, ::5] = np.uint64(2**64 - 1)
-    try:
-        L.bp_tune_ntt_mx(0)
+    red = vals % np.uint64(P)
+    with bpg.ops.tuned(ntt_mx=0):
         for r in (1, 3):
-            outs = []
-            for on, wgs in ((0, 256), (1, 8), (1, 16), (1, 32)):
-                L.bp_tune_ntt_persist(on, wgs)
-                outs.append(to_host(bpg.ops.lde_batch(to_dev(vals), r)[1]))
-            for k in range(1, len(outs)):
-                assert (outs[k] == outs[0]).all(), "persistent form %d differs from the one-shot grid (rate bits %d)" % (k, r)
-            _, want = oracle.lde_batch(vals[:2] % np.uint64(P), r)
-            assert (outs[1][:2][:, coset_major_to_natural(log_n, r)] == want).all()
-    finally:
-        L.bp_tune_ntt_persist(0, 256)
-        L.bp_tune_ntt_mx(3)
+            got = to_host(bpg.ops.lde_batch(to_dev(vals), r)[1])
+            assert (got == to_host(bpg.ops.lde_batch(to_dev(red), r)[1])).all(), "rate bits %d" % r
+            _, want = oracle.lde_batch(red[:2], r)
+            assert (got[:2][:, coset_major_to_natural(log_n, r)] == want).all(), "rate bits %d" % r
 
 
 def test_field_ops_against_big_integers(bpg):
@@ -163,18 +146,15 @@ def test_field_ops_against_big_integers(bpg):
         assert got[13][i] == x % P and got[14][i] == y % P, (i, hex(x), hex(y))
 
 
-@pytest.fixture(params=["mx4", "mx4-ungrouped", "mx4-2groups", "mx2", "mx1", "lane"])
+@pytest.fixture(params=["mx4", "mx4-ungrouped", "mx2", "mx1", "lane"])
 def perm_form(request, bpg):
     """the forms of the batch permutation: MDS on the matrix cores with 4 / 2 / 1 sets of 16 states per wave (four
-    sets: all 22 partial rounds in three groups, rounds 4..19 in two groups of eight, or every round by itself), and
-    one lane per state"""
-    bpg.lib().bp_tune_poseidon_mx(0 if request.param == "lane" else 1)
-    bpg.lib().bp_tune_poseidon_mx_sets(int(request.param[2:3]) if request.param != "lane" else 0)
-    bpg.lib().bp_tune_poseidon_grouped(0 if request.param.endswith("-ungrouped") else 2 if request.param.endswith("-2groups") else 3)
-    yield request.param
-    bpg.lib().bp_tune_poseidon_mx(1)
-    bpg.lib().bp_tune_poseidon_mx_sets(0)
-    bpg.lib().bp_tune_poseidon_grouped(3)
+    sets: all 22 partial rounds in three groups, or every round by itself), and one lane per state"""
+    knobs = {"poseidon_mx": 0} if request.param == "lane" else {"poseidon_mx_sets": int(request.param[2:3])}
+    if request.param.endswith("-ungrouped"):
+        knobs["poseidon_grouped"] = 0
+    with bpg.ops.tuned(**knobs):
+        yield request.param
 
 
 def test_poseidon_kat_and_random(bpg, oracle, perm_form):
@@ -216,7 +196,7 @@ def test_poseidon_byte_plane_extremes(bpg, oracle, perm_form):
 
 
 @pytest.mark.parametrize("quad", ["quad", "lane", "mx4", "mx2", "mx1", "mx", "mx+fused", "mx+fused+wide", "quad+fused",
-                                  "mx4-ungrouped", "mx4-2groups"])
+                                  "mx4-ungrouped"])
 @pytest.mark.parametrize("log_n,rate_bits,n_cols,cap_h", [(3, 1, 3, 4), (4, 1, 4, 0), (6, 1, 8, 4), (7, 3, 19, 4),
                                                           (10, 1, 135, 4), (12, 1, 33, 2), (9, 3, 2, 4), (5, 1, 9, 1),
                                                           (6, 1, 13, 3)])
@@ -224,29 +204,26 @@ def test_merkle_commit_matches_oracle(bpg, oracle, log_n, rate_bits, n_cols, cap
     # the three Poseidon kernel families: 4 lanes per state with DPP exchange / one lane per state / MDS on the
     # matrix cores (four sets of 16 states per wave)
     # "+fused": up to seven levels of at most 4096 nodes per launch (LDS hand-down), in the matrix-core one-set form or
-    # the quad form; "mx4-ungrouped" / "mx4-2groups": four sets per wave with every partial round by itself / only rounds
-    # 4..19 grouped (the default groups all 22)
-    bpg.lib().bp_tune_quad_threshold((1 << 40) if quad.startswith("quad") else 1)  # 1: never quad; 0 would be automatic
-    bpg.lib().bp_tune_poseidon_mx(1 if quad.startswith("mx") else 0)
-    bpg.lib().bp_tune_poseidon_mx_sets(int(quad[2:3]) if quad[:3] in ("mx4", "mx2", "mx1") else 0)  # "mx": sets by launch size
-    bpg.lib().bp_tune_merkle_fused(1 if "+fused" in quad else 0)
-    bpg.lib().bp_tune_merkle_wide(14 if quad.endswith("+wide") else 0)   # nine levels per launch from 256 parents up
-    bpg.lib().bp_tune_poseidon_grouped(0 if quad.endswith("-ungrouped") else 2 if quad.endswith("-2groups") else 3)
+    # the quad form; "mx4-ungrouped": four sets per wave with every partial round by itself (the default groups all 22)
+    knobs = {"quad_threshold": (1 << 40) if quad.startswith("quad") else 1,   # 1: never quad; 0 would be automatic
+             "poseidon_mx": 1 if quad.startswith("mx") else 0,
+             "merkle_fused": 1 if "+fused" in quad else 0}
+    if quad[:3] in ("mx4", "mx2", "mx1"):
+        knobs["poseidon_mx_sets"] = int(quad[2:3])    # "mx": sets by launch size
+    if quad.endswith("+wide"):
+        knobs["merkle_wide"] = 14                     # nine levels per launch from 256 parents up
+    if quad.endswith("-ungrouped"):
+        knobs["poseidon_grouped"] = 0
     if quad in ("mx", "mx+fused", "mx+fused+wide"):
-        bpg.lib().bp_tune_quad_threshold(1 << (log_n + rate_bits))  # leaves with 4 sets, then 2, then 1 up the tree
+        knobs["quad_threshold"] = 1 << (log_n + rate_bits)  # leaves with 4 sets, then 2, then 1 up the tree
     rng = np.random.default_rng(300 + log_n)
     rows = 1 << (log_n + rate_bits)
     lde_cm = rand_field(rng, (n_cols, rows))          # coset-major, as the LDE kernel writes it
     idx = coset_major_to_natural(log_n, rate_bits)
     lde_nat = np.ascontiguousarray(lde_cm[:, idx])    # natural order for the oracle
     want_dig, want_cap = oracle.merkle_commit(lde_nat, cap_h, bitrev_rows=True)
-    dig = to_host(bpg.ops.merkle_commit(to_dev(lde_cm), log_n, rate_bits, cap_h))
-    bpg.lib().bp_tune_quad_threshold(0)  # back to automatic
-    bpg.lib().bp_tune_poseidon_mx(1)
-    bpg.lib().bp_tune_poseidon_mx_sets(0)
-    bpg.lib().bp_tune_merkle_fused(0)
-    bpg.lib().bp_tune_merkle_wide(0)
-    bpg.lib().bp_tune_poseidon_grouped(3)
+    with bpg.ops.tuned(**knobs):
+        dig = to_host(bpg.ops.merkle_commit(to_dev(lde_cm), log_n, rate_bits, cap_h))
     assert (dig == want_dig).all()
     assert (dig[-(1 << cap_h):] == want_cap).all()
 
@@ -292,45 +269,38 @@ def test_quotient_scratch_fits_whatever_the_load_state_is_at_launch(bpg, oracle)
     cfg = bpg.ops.stark_cfg(log_n, n_cols, rate_bits=rate_bits)
     L = bpg.lib()
     want = None
-    try:
-        for at_size, at_launch in ((1, 0), (0, 1), (0, 0), (1, 1)):
-            L.bp_tune_assume_loaded(at_size)
+    for at_size, at_launch in ((1, 0), (0, 1), (0, 0), (1, 1)):
+        with bpg.ops.tuned(assume_loaded=at_size):
             words = int(L.bp_quotient_scratch_words(0, C.byref(cfg)))
-            guard = 4096
-            buf = torch.full((words + guard,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
-            out = torch.empty((2, rows), dtype=torch.int64, device="cuda")
-            L.bp_tune_assume_loaded(at_launch)
+        guard = 4096
+        buf = torch.full((words + guard,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        out = torch.empty((2, rows), dtype=torch.int64, device="cuda")
+        with bpg.ops.tuned(assume_loaded=at_launch):
             t, a = to_dev(trace), to_dev(aux)
             bpg._lib.check(L.bp_quotient_eval(0, C.byref(cfg), t.data_ptr(), a.data_ptr(), None,
                                               (C.c_uint64 * 4)(*[int(x) for x in ctl]), (C.c_uint64 * 2)(*[int(x) for x in alphas]),
                                               buf.data_ptr(), out.data_ptr(), None))
             torch.cuda.synchronize()
-            assert (buf[words:] == 0x5A5A5A5A5A5A5A5A).all(), "the launch wrote past the scratch it was sized"
-            got = to_host(out)
-            if want is None:
-                want = got
-            assert (got == want).all()
-    finally:
-        L.bp_tune_assume_loaded(-1)
+        assert (buf[words:] == 0x5A5A5A5A5A5A5A5A).all(), "the launch wrote past the scratch it was sized"
+        got = to_host(out)
+        if want is None:
+            want = got
+        assert (got == want).all()
 
 
 def test_merkle_commit_of_a_tiny_matrix_with_forced_sets(bpg, oracle):
     """bp_tune_poseidon_mx_sets(4) on a 16-row matrix: the four-set kernel would read 48 rows past the last column;
     the launcher takes fewer sets for trees smaller than a wave's sets.  Same digests in every form."""
     rng = np.random.default_rng(78)
-    L = bpg.lib()
     for log_n, r in ((3, 1), (4, 0), (5, 0)):
         rows = (1 << log_n) << r
         lde = rand_field(rng, (9, rows))
         ref = None
-        try:
-            for sets in (0, 1, 2, 4):
-                L.bp_tune_poseidon_mx_sets(sets)
+        for sets in (0, 1, 2, 4):
+            with bpg.ops.tuned(poseidon_mx_sets=sets):
                 got = to_host(bpg.ops.merkle_commit(to_dev(lde), log_n, r, 2))
-                ref = got if ref is None else ref
-                assert (got == ref).all()
-        finally:
-            L.bp_tune_poseidon_mx_sets(0)
+            ref = got if ref is None else ref
+            assert (got == ref).all()
 
 
 @pytest.mark.parametrize("log_nl,rate_bits", [(4, 1), (6, 1), (9, 3), (13, 3), (16, 1)])

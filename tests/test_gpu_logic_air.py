@@ -70,11 +70,8 @@ def test_table_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
     logic range (constants.rs:14).  loaded: K5 in ONE pass, as the library runs it while provers share the device."""
     cfg, want, ctl, chv = oracle_proof(oracle, log_n, nq, pb, SEED)
     pc = bpg.ops.stark_cfg(log_n, 524, num_queries=nq, pow_bits=pb)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         got = bpg.ops.stark_prove_air(2, pc, SEED)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape and int(got[14]) == 2
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)

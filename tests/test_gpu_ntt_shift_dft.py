@@ -64,36 +64,34 @@ def reference(oracle, log_n, n_cols, rates):
 
 @pytest.fixture
 def valu_kernels(bpg):
-    bpg.lib().bp_tune_ntt_mx(0)
-    yield bpg.lib()
-    bpg.lib().bp_tune_ntt_mx(3)
-    bpg.lib().bp_tune_ntt_split(0)
+    with bpg.ops.tuned(ntt_mx=0):
+        yield
 
 
 @pytest.mark.parametrize("split", [1, 2])   # never / two workgroups per block wherever possible
 @pytest.mark.parametrize("log_n,n_cols", [(12, 3), (13, 3), (14, 2)])
-def test_valu_block_kernels_match_the_oracle(bpg, oracle, valu_kernels, log_n, n_cols, split):
-    rates = (1, 3)
-    ref = reference(oracle, log_n, n_cols, rates)
-    raw, br = ref["raw"], ref["br"]
-    valu_kernels.bp_tune_ntt_split(split)
-    # inverse, out of place (split eligible) and in place
-    d = to_dev(raw.copy())
-    got = to_host(bpg.ops.intt_batch(d))
-    assert (to_host(d) == raw).all()
-    assert (got[:, br] == ref["coeffs"]).all(), "inverse, out of place"
-    got = to_host(bpg.ops.ntt_batch_(to_dev(raw.copy()), bpg.ops.NTT_INV_NAT2BR))
-    assert (got[:, br] == ref["coeffs"]).all(), "inverse, in place"
-    # forward
-    got = to_host(bpg.ops.ntt_batch_(to_dev(raw.copy()), bpg.ops.NTT_FWD_BR2NAT))
-    assert (got == ref["vals"]).all(), "forward"
-    for r in rates:
-        idx = coset_major_to_natural(log_n, r)
-        coeffs, lde = bpg.ops.lde_batch(to_dev(raw.copy()), r)
-        assert (to_host(coeffs)[:, br] == ref["coeffs"]).all(), ("lde: coefficients", r)
-        assert (to_host(lde)[:, idx] == ref["lde", r]).all(), ("lde from values", r)
-        _, lde = bpg.ops.lde_batch(to_dev(raw.copy()), r, from_coeffs=True)
-        assert (to_host(lde)[:, idx] == ref["lde_from_coeffs", r]).all(), ("lde from coefficients", r)
+def test_valu_block_kernels_match_the_oracle(bpg, oracle, log_n, n_cols, split):
+    with bpg.ops.tuned(ntt_mx=0, ntt_split=split):
+        rates = (1, 3)
+        ref = reference(oracle, log_n, n_cols, rates)
+        raw, br = ref["raw"], ref["br"]
+        # inverse, out of place (split eligible) and in place
+        d = to_dev(raw.copy())
+        got = to_host(bpg.ops.intt_batch(d))
+        assert (to_host(d) == raw).all()
+        assert (got[:, br] == ref["coeffs"]).all(), "inverse, out of place"
+        got = to_host(bpg.ops.ntt_batch_(to_dev(raw.copy()), bpg.ops.NTT_INV_NAT2BR))
+        assert (got[:, br] == ref["coeffs"]).all(), "inverse, in place"
+        # forward
+        got = to_host(bpg.ops.ntt_batch_(to_dev(raw.copy()), bpg.ops.NTT_FWD_BR2NAT))
+        assert (got == ref["vals"]).all(), "forward"
+        for r in rates:
+            idx = coset_major_to_natural(log_n, r)
+            coeffs, lde = bpg.ops.lde_batch(to_dev(raw.copy()), r)
+            assert (to_host(coeffs)[:, br] == ref["coeffs"]).all(), ("lde: coefficients", r)
+            assert (to_host(lde)[:, idx] == ref["lde", r]).all(), ("lde from values", r)
+            _, lde = bpg.ops.lde_batch(to_dev(raw.copy()), r, from_coeffs=True)
+            assert (to_host(lde)[:, idx] == ref["lde_from_coeffs", r]).all(), ("lde from coefficients", r)
 
 
 def test_valu_block_kernels_under_a_global_pass(bpg, oracle, valu_kernels):

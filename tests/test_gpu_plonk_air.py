@@ -100,12 +100,9 @@ def test_quotient_eval_matches_oracle(bpg, oracle, log_n, loaded):
         cm = np.empty_like(mat)
         cm[:, idx] = mat
         return to_dev(cm)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         got = bpg.ops.quotient_eval(bpg.ops.stark_cfg(log_n, 135, n_const=85, deg_pow=3, rate_bits=3), to_cm(trace), to_cm(aux),
                                     to_cm(consts), ctl, alphas, air_id=8)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert (to_host(got)[:, idx] == want).all()
 
 
@@ -136,11 +133,8 @@ def product_verify(bpg, pc, proof, cap, pub):
 def test_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
     cfg, want, ctl, chv, cap, pub = oracle_proof(oracle, log_n, nq, pb, SEED, CSEED)
     pc = bpg.ops.stark_cfg(log_n, 135, n_const=85, deg_pow=3, rate_bits=3, num_queries=nq, pow_bits=pb)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         got = bpg.ops.stark_prove_air(8, pc, SEED, const_seed=CSEED)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape and int(got[14]) == 8 and int(got[4]) == 20
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)
@@ -190,10 +184,7 @@ def test_recursion_layer_on_the_plonk_circuit_matches_the_oracle(bpg, oracle):
         assert (np.frombuffer(blk.intern, dtype=np.uint64) == ost.block(None, oa)).all()
         pg.VerifierState.from_prover_state(st).verify(blk)
         assert ost.verify(np.frombuffer(blk.intern, dtype=np.uint64)) == 0
-        bpg.lib().bp_tune_rec_batch(1)
-        try:
+        with bpg.ops.tuned(rec_batch=1):
             assert pg.generate_txn_proof(st, ir0).intern == t0.intern
-        finally:
-            bpg.lib().bp_tune_rec_batch(8)
     finally:
         st.close()

@@ -78,16 +78,10 @@ def test_lock_step_batches_do_not_change_a_byte(pg, p_state, bpg, chain):
     size -- one proof at a time, uneven splits, all seven at once -- and whichever way the host waits, the txn proof is
     the same bytes (which test_txn_agg_block_bytes_match_oracle pins to the oracle)."""
     t0 = chain[0]
-    L = bpg.lib()
-    try:
-        for n, wait in ((1, 0), (2, 0), (3, 2), (5, 0), (7, 2), (8, 1)):
-            L.bp_tune_rec_batch(n)
-            L.bp_tune_host_wait(wait)
+    for n, wait in ((1, 0), (2, 0), (3, 2), (5, 0), (7, 2), (8, 1)):
+        with bpg.ops.tuned(rec_batch=n, host_wait=wait):
             again = pg.generate_txn_proof(p_state, make_ir(pg, 7, 0, 0x5EED0001))
-            assert again.intern == t0.intern, "batch size %d, host wait mode %d" % (n, wait)
-    finally:
-        L.bp_tune_rec_batch(8)
-        L.bp_tune_host_wait(0)
+        assert again.intern == t0.intern, "batch size %d, host wait mode %d" % (n, wait)
 
 
 def test_side_lanes_do_not_change_a_byte(pg, bpg, oracle):
@@ -96,7 +90,6 @@ def test_side_lanes_do_not_change_a_byte(pg, bpg, oracle):
     worker), and with the borrowing switched off the txn proof is the same bytes, and they are the oracle's; two
     transactions at once (at most one of them finds itself alone) agree as well."""
     from concurrent.futures import ThreadPoolExecutor
-    L = bpg.lib()
     want = oracle.PgState(**SMALL).txn(ir_words(7, 0, 0x5EED0001))
     proofs = []
     for n_workers, lanes in ((4, 1), (1, 1), (4, 0)):
@@ -105,15 +98,14 @@ def test_side_lanes_do_not_change_a_byte(pg, bpg, oracle):
             getattr(b, "set_%s_circuit_size" % name)(range(SMALL["table_log_lo"][t], SMALL["table_log_hi"][t]))
         b.set(**{k: v for k, v in SMALL.items() if not k.startswith("table_")}, n_workers=n_workers, arena_bytes=256 << 20)
         st = b.build()
-        L.bp_tune_side_lanes(lanes)
         try:
-            proofs.append(pg.generate_txn_proof(st, make_ir(pg, 7, 0, 0x5EED0001)).intern)
-            if n_workers == 4 and lanes:
-                with ThreadPoolExecutor(2) as pool:
-                    both = list(pool.map(lambda _: pg.generate_txn_proof(st, make_ir(pg, 7, 0, 0x5EED0001)).intern, range(2)))
-                assert both[0] == both[1] == proofs[-1]
+            with bpg.ops.tuned(side_lanes=lanes):
+                proofs.append(pg.generate_txn_proof(st, make_ir(pg, 7, 0, 0x5EED0001)).intern)
+                if n_workers == 4 and lanes:
+                    with ThreadPoolExecutor(2) as pool:
+                        both = list(pool.map(lambda _: pg.generate_txn_proof(st, make_ir(pg, 7, 0, 0x5EED0001)).intern, range(2)))
+                    assert both[0] == both[1] == proofs[-1]
         finally:
-            L.bp_tune_side_lanes(1)
             st.close()
     assert proofs[0] == proofs[1] == proofs[2]
     assert (words(proofs[0]) == want).all()

@@ -43,12 +43,9 @@ def test_table_proof_bit_exact(bpg, oracle, case, loaded):
     log_n, C, K, e, r, nq, pb = case
     seed, const_seed = 0x5EED000000000000 + log_n, 77
     cfg, want, ctl, chv, const_cap = oracle_proof(oracle, case, seed, const_seed)
-    bpg.lib().bp_tune_assume_loaded(loaded)
-    try:
+    with bpg.ops.tuned(assume_loaded=loaded):
         got = bpg.ops.stark_prove_synthetic(
             bpg.ops.stark_cfg(log_n, C, n_const=K, deg_pow=e, rate_bits=r, num_queries=nq, pow_bits=pb), seed, const_seed)
-    finally:
-        bpg.lib().bp_tune_assume_loaded(-1)
     assert got.shape == want.shape
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)

@@ -26,6 +26,54 @@ def test_abi_library_loads_and_exports_every_declared_symbol():
     assert L.bp_version().startswith(b"bpg")
 
 
+def test_every_knob_goes_back_to_its_default():
+    """The bp_tune_* knobs are host state with one home (csrc/tune.hpp): every one of them shows in
+    bp_debug_tune_state, moves when it is set, and is put back by bp_tune_reset -- which ops.tuned calls on the way
+    out, also when its body raises.  The values set here are two legal ones per knob, whichever is not the current."""
+    import proof_protocol_decoder_amd as pkg
+    from proof_protocol_decoder_amd._lib import KNOBS
+    ops, L = pkg.ops, pkg.lib()
+    at_load = ops.tune_state()
+    L.bp_tune_reset()
+    assert ops.tune_state() == at_load, "a knob was not at its default when this test began"
+
+    def fields(text):
+        pairs = [line.split("=") for line in text.splitlines()]
+        assert [k for k, _ in pairs] == list(KNOBS), "one name=value line per knob, in the declared order"
+        return {k: int(v) for k, v in pairs}
+    legal = {"quad_threshold": (1 << 12, 1 << 20), "assume_loaded": (0, 1), "merkle_fused": (0, 1), "merkle_wide": (12, 14),
+             "poseidon_mx": (0, 1), "poseidon_mx_sets": (2, 4), "poseidon_grouped": (0, 1), "ntt_mx": (1, 2),
+             "ntt_split": (1, 2), "k5_spread": (0, 1), "host_wait": (1, 2), "host_poseidon": (0, 1), "rec_batch": (2, 3),
+             "witness_threads": (2, 3), "side_lanes": (2, 3)}
+    assert sorted(legal) == sorted(KNOBS)
+    before = fields(at_load)
+    moved = {k: next(v for v in legal[k] if v != before[k]) for k in KNOBS}
+    try:
+        for k, v in moved.items():
+            getattr(L, "bp_tune_" + k)(v)
+        assert fields(ops.tune_state()) == moved, "every field changed, to the value set"
+    finally:
+        L.bp_tune_reset()
+    assert ops.tune_state() == at_load
+    with pytest.raises(ZeroDivisionError):
+        with ops.tuned(**moved):
+            assert fields(ops.tune_state()) == moved
+            1 // 0
+    assert ops.tune_state() == at_load
+    with pytest.raises(TypeError):
+        with ops.tuned(no_such_knob=1):
+            pass
+    with pytest.raises(RuntimeError):      # the exit of an inner block would drop the outer block's knobs
+        with ops.tuned(**moved):
+            with ops.tuned(ntt_mx=0):
+                pass
+    assert ops.tune_state() == at_load
+    # arguments are clamped as include/bpg.h says: retired or out-of-range modes fall back, they are not stored
+    with ops.tuned(ntt_mx=4, merkle_fused=12, poseidon_grouped=2, ntt_split=3, rec_batch=99):
+        got = fields(ops.tune_state())
+        assert (got["ntt_mx"], got["merkle_fused"], got["poseidon_grouped"], got["ntt_split"], got["rec_batch"]) == (3, 1, 1, 0, 8)
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     import torch
     if torch.cuda.is_available():
@@ -109,7 +157,6 @@ def test_host_transcript_permutation_matches_the_oracle_in_both_forms(oracle):
     import proof_protocol_decoder_amd as pkg
     L = pkg.lib()
     L.bp_debug_poseidon_host.argtypes = [C.c_void_p, C.c_size_t]
-    L.bp_tune_host_poseidon.argtypes = [C.c_int]
     P = 0xFFFFFFFF00000001
     rng = np.random.default_rng(5)
     states = rng.integers(0, 2**64, size=(257, 12), dtype=np.uint64)
@@ -119,14 +166,11 @@ def test_host_transcript_permutation_matches_the_oracle_in_both_forms(oracle):
     states[2] = np.uint64(2**64 - 1)
     states[3] = np.uint64(P - 1)
     want = oracle.poseidon(states % np.uint64(P))
-    try:
-        for mode in (0, 1):
-            L.bp_tune_host_poseidon(mode)
+    for mode in (0, 1):
+        with pkg.ops.tuned(host_poseidon=mode):
             got = states.copy()
             assert L.bp_debug_poseidon_host(got.ctypes.data, got.shape[0]) == 0
             assert (got == want).all(), "host permutation differs from the oracle (form %d)" % mode
-    finally:
-        L.bp_tune_host_poseidon(0)
     assert [hex(int(x)) for x in want[0][:2]] == ["0x3c18a9786cb0b359", "0xc4055e3364a246c3"]   # SURVEY.md appendix A, recalled KAT
 
 

@@ -10,7 +10,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import proof_protocol_decoder_amd as bpg
 
-L = bpg.lib()
 COUNTERS = "--counters" in sys.argv
 CASES = [  # name, air_id, columns, log_n (the S1 height of the table), in the counters pass
     ("synthetic 128 cols (S1 arithmetic width)", 0, 128, 16, False),
@@ -44,26 +43,25 @@ for name, air, C_, log_n, in_counters in CASES:
     alg = 8.0 * rows * (C_ + d.n_aux + (rec["n_const"] if rec else 0) + 2)
     cfg = bpg.ops.stark_cfg(log_n, C_, **rec) if rec else bpg.ops.stark_cfg(log_n, C_)
     if COUNTERS:
-        L.bp_tune_assume_loaded(0)
-        bpg.ops.quotient_eval(cfg, tr, aux, cst, (3, 5, 7, 11), (13, 17), air_id=air)
-        torch.cuda.synchronize()
+        with bpg.ops.tuned(assume_loaded=0):
+            bpg.ops.quotient_eval(cfg, tr, aux, cst, (3, 5, 7, 11), (13, 17), air_id=air)
+            torch.cuda.synchronize()
         print("counters case: air %d %s rows %d cols %d aux %d constraints %d alg_bytes %d" % (air, d.name.decode(), rows, C_, d.n_aux, n_cons, alg), flush=True)
         continue
     out = []
     for loaded in (0, 1):
-        L.bp_tune_assume_loaded(loaded)
-        bpg.ops.quotient_eval(cfg, tr, aux, cst, (3, 5, 7, 11), (13, 17), air_id=air)
-        torch.cuda.synchronize()
-        best = 1e9
-        for _ in range(5):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
+        with bpg.ops.tuned(assume_loaded=loaded):
             bpg.ops.quotient_eval(cfg, tr, aux, cst, (3, 5, 7, 11), (13, 17), air_id=air)
-            b.record()
             torch.cuda.synchronize()
-            best = min(best, a.elapsed_time(b))
+            best = 1e9
+            for _ in range(5):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                bpg.ops.quotient_eval(cfg, tr, aux, cst, (3, 5, 7, 11), (13, 17), air_id=air)
+                b.record()
+                torch.cuda.synchronize()
+                best = min(best, a.elapsed_time(b))
         out.append(best)
-    L.bp_tune_assume_loaded(-1)
     print("%-44s 2^%d x %d (+%d aux), %4d constraints: %8.1f us spread over workgroup rows (%6.1f GB/s algorithmic), %8.1f us in the form taken "
           "under load (one pass for the synthetic AIR, 256 workgroups for the others); %6.2f G constraint evaluations/s, %5.1f ns per row"
           % (name, log_n, C_, d.n_aux, n_cons, out[0] * 1e3, alg / (out[0] * 1e-3) / 1e9, out[1] * 1e3,

@@ -1,6 +1,6 @@
 """The NTT / LDE kernels alone on the chip, a few launches each, for rocprofv3 --pmc passes (tools/prof_round5_ntt.sh):
-  * coset LDE from coefficients, 2^14 x 2432, rate 2  (ntt16_dit_kernel<14,0> / ntt_mx_dit_kernel<1>: bench `roofline_isolated`)
-  * coset LDE from coefficients, 2^12 x 2048, rate 2  (ntt16_dit_kernel<12,0>)
+  * coset LDE from coefficients, 2^14 x 2432, rate 2  (ntt16_dit_kernel<14> / ntt_mx_dit_kernel<1>: bench `roofline_isolated`)
+  * coset LDE from coefficients, 2^12 x 2048, rate 2  (ntt16_dit_kernel<12>)
   * inverse NTT 2^14 x 2048 and 2^12 x 2048           (ntt16_dif_kernel<14> / <12>: bench `ntt_hbm_gbps`)
 With --time it prints the HIP-event time of each instead (no profiler)."""
 import os
@@ -35,18 +35,7 @@ def run(time_it):
 
 
 if __name__ == "__main__":
-    if "--persist" in sys.argv:   # the 2^14-point LDE blocks as one-shot grid / persistent prefetching workgroups
-        import ctypes as C
-        L = bpg.lib()
-        L.bp_tune_ntt_persist.argtypes = [C.c_int, C.c_int]
-        L.bp_tune_ntt_mx(0)
-        for on, wgs in ((0, 256), (1, 256), (1, 512), (0, 256), (1, 256)):
-            L.bp_tune_ntt_persist(on, wgs)
-            print("bp_tune_ntt_persist(%d, %d)" % (on, wgs), flush=True)
-            run(True)
-        sys.exit(0)
-    for knob in ([0, 3] if "--both" in sys.argv else [None]):
-        if knob is not None:
-            bpg.lib().bp_tune_ntt_mx(knob)
-            print("bp_tune_ntt_mx(%d)" % knob, flush=True)
-        run("--time" in sys.argv)
+    for knobs in ([{"ntt_mx": 0}, {}] if "--both" in sys.argv else [{}]):   # VALU kernels / the default choice
+        with bpg.ops.tuned(**knobs):
+            print("tuned(%s)" % knobs, flush=True)
+            run("--time" in sys.argv)

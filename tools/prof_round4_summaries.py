@@ -102,8 +102,9 @@ def hash_summary():
     for r in rows((RND + "_hash_sq1", RND + "_hash_sq2")):
         k = r["Kernel_Name"]
         if "leaf_hash" in k:
-            m = re.search(r"leaf_hash_mx_kernel<(\d+), (\d+)>", k) or re.search(r"leaf_hash_mx_kernelILi(\d+)ELi(\d+)E", k)
-            name = ("leaf_hash_mx_kernel<4, %s>" % {"0": "per round", "2": "two groups", "3": "three groups"}[m.group(2)]) if m \
+            # leaf_hash_mx_kernel<NS, GR>: GR = true is the grouped form (all 22 partial rounds in three groups)
+            m = re.search(r"leaf_hash_mx_kernel<\d+, (true|false)>", k) or re.search(r"leaf_hash_mx_kernelILi\d+ELb([01])E", k)
+            name = ("leaf_hash_mx_kernel<4, %s>" % ("three groups" if m.group(1) in ("true", "1") else "per round")) if m \
                 else "leaf_hash_kernel (one lane per state)"
             acc[name][r["Counter_Name"]] += float(r["Counter_Value"])
     if not acc:

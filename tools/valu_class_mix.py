@@ -19,11 +19,11 @@ CSRC = os.path.join(ROOT, "proof_protocol_decoder_amd", "csrc")
 CHEAP = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshrrev_b32", "v_lshlrev_b32",
          "v_mov_b32", "v_not_b32", "v_bfe_u32", "v_add_f32", "v_mul_f32"}
 FAMILIES = [  # (family in the SQ summary, source, mangled-name fragments of the kernel form the loaded run uses)
-    ("leaf_hash_mx_kernel", "hash_kernels.hip", ["leaf_hash_mx_kernelILi4ELi3E", "leaf_hash_mx_kernelILi4E"]),
-    ("ntt", "ntt.hip", ["ntt16_dit_kernelILi13ELi0E", "ntt16_dif_kernelILi13ELi0E"]),
+    ("leaf_hash_mx_kernel", "hash_kernels.hip", ["leaf_hash_mx_kernelILi4ELb1E", "leaf_hash_mx_kernelILi4E"]),
+    ("ntt", "ntt.hip", ["ntt16_dit_kernelILi13EE", "ntt16_dif_kernelILi13ELi0E"]),
     ("merkle_level_mx_kernel", "hash_kernels.hip", ["merkle_level_mx_kernel"]),
     ("quotient_air_kernel", "stark_kernels.hip", ["quotient_air_kernelILj8E", "quotient_air_kernelILj0E"]),
-    ("pow_grind", "stark_kernels.hip", ["pow_grind_mx_kernelILi3E"]),
+    ("pow_grind", "stark_kernels.hip", ["pow_grind_mx_kernelILb1E"]),
     ("quotient_plonk_hash_kernel", "stark_kernels.hip", ["quotient_plonk_hash_kernel"]),   # AIR 8's Poseidon-gate pass
 ]
 

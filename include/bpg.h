@@ -74,27 +74,42 @@ int bp_host_wait_mode(int device);
  * reverse_index_bits order.
  * ------------------------------------------------------------------------------------------ */
 
+/* Buffers of the L0 entries.  A column stride (in elements) may be any value >= the column's length, so a call can
+ * work on a slice of a wider arena: the words between the end of one column and the start of the next are never read
+ * as data and never written, and nothing before the first column or after the last is touched.  Every output and
+ * scratch buffer is written within the size stated for it and nowhere else; input buffers of out-of-place calls are
+ * left as they are.  Bad arguments -- a null pointer, a stride shorter than the column, overlapping buffers, too many
+ * columns -- are refused with BP_ERR_INVALID_INPUT (bp_last_error() says which) before anything is launched or
+ * written. */
+
+/* The K2 entries take at most this many columns per call (the kernels index columns by grid.y); a wider matrix
+ * goes in several calls on column ranges. */
+#define BP_NTT_MAX_COLS 65535u
+
 /* K2.  plonky2_field fft/ifft semantics on a batch of columns, in place.
  *   dir = BP_NTT_FWD_BR2NAT: coefficients (bit-reversed order) -> values (natural)
  *   dir = BP_NTT_INV_NAT2BR: values (natural) -> coefficients (bit-reversed), includes 1/n
- *   dir = BP_NTT_FWD_NAT / BP_NTT_INV_NAT: natural in, natural out (adds one permutation pass) */
+ *   dir = BP_NTT_FWD_NAT / BP_NTT_INV_NAT: natural in, natural out (adds one permutation pass)
+ * Inputs may be any u64 (reduced mod p on the way in), outputs are canonical.  n_cols <= BP_NTT_MAX_COLS. */
 enum { BP_NTT_FWD_BR2NAT = 0, BP_NTT_INV_NAT2BR = 1, BP_NTT_FWD_NAT = 2, BP_NTT_INV_NAT = 3 };
 int bp_ntt_batch(uint64_t* d_cols, uint32_t log_n, uint32_t n_cols, uint64_t col_stride, int dir,
                  void* stream);
 
 /* K2.  The inverse transform out of place (what PolynomialBatch::from_values does first: the values stay, the
- * coefficients, bit-reversed and scaled by 1/n, go to d_coeffs_out).  The two buffers must be the same pointer
- * (in place) or not overlap. */
+ * coefficients, bit-reversed and scaled by 1/n, go to d_coeffs_out).  The two buffers (first column to the end of the
+ * last, pad words included) must not overlap, or be the same pointer WITH THE SAME STRIDE (in place: the same
+ * columns); the same pointer with two different strides is refused, as is any other overlap.
+ * n_cols <= BP_NTT_MAX_COLS. */
 int bp_intt_batch(const uint64_t* d_values, uint64_t in_stride, uint64_t* d_coeffs_out, uint64_t out_stride,
                   uint32_t log_n, uint32_t n_cols, void* stream);
 
 /* K2.  PolynomialBatch::from_values / from_coeffs low-degree extension.
  *   d_in: n_cols columns of n values (natural) or, if from_coeffs, n coefficients (bit-reversed);
- *   d_coeffs_out (nullable if from_coeffs): n_cols x n coefficients, bit-reversed; the same pointer as d_in
- *   (in place) or not overlapping it;
+ *   d_coeffs_out (nullable if from_coeffs): n_cols x n coefficients, bit-reversed; not overlapping d_in, or the same
+ *   pointer as d_in with coeffs_stride == in_stride (in place; the same pointer with another stride is refused);
  *   d_lde_out: n_cols x (n << rate_bits), coset-major, overlapping neither.  Strides in elements.
  * Inputs may be any u64 (reduced mod p on the way in), outputs are canonical; overlapping buffers are refused
- * with BP_ERR_INVALID_INPUT. */
+ * with BP_ERR_INVALID_INPUT.  n_cols <= BP_NTT_MAX_COLS. */
 int bp_lde_batch(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_coeffs_out, uint64_t coeffs_stride,
                  uint64_t* d_lde_out, uint64_t lde_stride, uint32_t log_n, uint32_t rate_bits,
                  uint32_t n_cols, int from_coeffs, void* stream);
@@ -212,6 +227,7 @@ int bp_poseidon_perm_batch(uint64_t* d_states, uint64_t n, void* stream);
 
 /* K4.  MerkleTree::new(leaves, cap_height) over the rows of a coset-major LDE matrix.
  *   n_leaves = n << rate_bits rows of n_cols elements; leaf digest = hash_or_noop(row).
+ *   d_lde: column c at d_lde + c * lde_stride (elements; >= n << rate_bits, refused otherwise);
  *   d_digests: level-order buffer of bp_merkle_digest_words(log_leaves, cap_height) words
  *   (leaf digests in leaf-index order first, ..., the 2^cap_height cap digests last). */
 uint64_t bp_merkle_digest_words(uint32_t log_leaves, uint32_t cap_height);

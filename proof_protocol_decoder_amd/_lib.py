@@ -97,6 +97,7 @@ def lib():
     L.bp_version.restype = C.c_char_p
     L.bp_device_count.restype = i
     L.bp_ntt_batch.argtypes = [vp, u32, u32, u64, i, vp]
+    L.bp_intt_batch.argtypes = [vp, u64, vp, u64, u32, u32, vp]
     L.bp_lde_batch.argtypes = [vp, u64, vp, u64, vp, u64, u32, u32, u32, i, vp]
     L.bp_poseidon_perm_batch.argtypes = [vp, u64, vp]
     L.bp_debug_field_ops.argtypes = [vp, vp, vp, u64, vp]

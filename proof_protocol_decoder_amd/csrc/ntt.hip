@@ -776,6 +776,15 @@ __global__ void bitrev_permute_kernel(uint64_t* cols, uint64_t stride, uint32_t 
   }
 }
 
+// bp_lde_batch from coefficients with a coefficient buffer of its own: the caller's words, reduced (outputs are
+// canonical whatever came in).  grid = (ceil(n / 256), columns).
+__global__ void canon_copy_kernel(const uint64_t* __restrict__ in, uint64_t in_stride, uint64_t* __restrict__ out,
+                                  uint64_t out_stride, uint32_t log_n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (1u << log_n)) return;
+  out[blockIdx.y * out_stride + i] = gl::canon(in[blockIdx.y * in_stride + i]);
+}
+
 // ---- per-device table cache ----------------------------------------------------------------
 struct TableKey {
   int dev, kind;  // kind 0: fwd twiddles, 1: inv twiddles, 2: coset scales, 3: inverse coset scales, 4 / 5: fwd / inv radix-16 layers
@@ -1121,6 +1130,13 @@ int init_ntt_kernels() {
   return rc;
 }
 
+// The launchers put the column index in grid.y (ntt_lds_kernel, ntt16_dif_kernel<L, 0>, the global passes,
+// bitrev_permute_kernel), which the device limits to 65535: more columns are refused before anything is launched.
+static_assert(BP_NTT_MAX_COLS == 65535, "BP_NTT_MAX_COLS is the largest grid.y");
+static int too_many_cols(const char* entry, uint32_t n_cols) {
+  return fail(BP_ERR_INVALID_INPUT, "%s: %u columns, at most %u per call (BP_NTT_MAX_COLS)", entry, n_cols, (unsigned)BP_NTT_MAX_COLS);
+}
+
 }  // namespace bpg
 
 extern "C" {
@@ -1151,6 +1167,7 @@ int bp_ntt_batch(uint64_t* d_cols, uint32_t log_n, uint32_t n_cols, uint64_t col
   if (log_n > 30 || col_stride < ((uint64_t)1 << log_n))
     return bpg::fail(BP_ERR_INVALID_INPUT, "bp_ntt_batch: bad shape (log_n=%u stride=%llu)", log_n,
                      (unsigned long long)col_stride);
+  if (n_cols > BP_NTT_MAX_COLS) return bpg::too_many_cols("bp_ntt_batch", n_cols);
   hipStream_t st = bpg::as_stream(stream);
   int rc;
   if ((rc = bpg::init_ntt_kernels())) return rc;
@@ -1179,6 +1196,11 @@ int bp_intt_batch(const uint64_t* d_values, uint64_t in_stride, uint64_t* d_coef
   if (!d_values || !d_coeffs_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_intt_batch: null buffer");
   const uint64_t n = (uint64_t)1 << log_n;
   if (log_n > 30 || in_stride < n || out_stride < n) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_intt_batch: bad shape (log_n=%u)", log_n);
+  if (n_cols > BP_NTT_MAX_COLS) return bpg::too_many_cols("bp_intt_batch", n_cols);
+  // in place = the same columns: with another stride column c's output would land on a later column's input
+  if (d_values == d_coeffs_out && in_stride != out_stride)
+    return bpg::fail(BP_ERR_INVALID_INPUT, "bp_intt_batch: in place (same pointer) needs in_stride == out_stride (%llu, %llu)",
+                     (unsigned long long)in_stride, (unsigned long long)out_stride);
   const uint64_t span_in = in_stride * (n_cols - 1) + n, span_out = out_stride * (n_cols - 1) + n;
   if (d_values != d_coeffs_out && d_values < d_coeffs_out + span_out && d_coeffs_out < d_values + span_in)
     return bpg::fail(BP_ERR_INVALID_INPUT, "bp_intt_batch: buffers overlap (use the same pointer for in place)");
@@ -1198,6 +1220,10 @@ int bp_lde_batch(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_coeffs_ou
   if (log_n + rate_bits > 30 || rate_bits > 4 || in_stride < n || lde_stride < (n << rate_bits) ||
       (d_coeffs_out && coeffs_stride < n))
     return bpg::fail(BP_ERR_INVALID_INPUT, "bp_lde_batch: bad shape (log_n=%u rate_bits=%u)", log_n, rate_bits);
+  if (n_cols > BP_NTT_MAX_COLS) return bpg::too_many_cols("bp_lde_batch", n_cols);
+  if (d_coeffs_out == d_in && coeffs_stride != in_stride)  // as bp_intt_batch
+    return bpg::fail(BP_ERR_INVALID_INPUT, "bp_lde_batch: in place (d_coeffs_out == d_in) needs coeffs_stride == in_stride (%llu, %llu)",
+                     (unsigned long long)coeffs_stride, (unsigned long long)in_stride);
   if (d_coeffs_out && d_coeffs_out != d_in) {  // as bp_intt_batch: the split kernels read a block while its partner stores
     const uint64_t span_in = in_stride * (n_cols - 1) + n, span_c = coeffs_stride * (n_cols - 1) + n;
     if (d_in < d_coeffs_out + span_c && d_coeffs_out < d_in + span_in)
@@ -1220,8 +1246,8 @@ int bp_lde_batch(const uint64_t* d_in, uint64_t in_stride, uint64_t* d_coeffs_ou
     coeffs = d_coeffs_out;
     cstride = coeffs_stride;
   } else if (d_coeffs_out && d_coeffs_out != d_in) {
-    BPG_HIP(hipMemcpy2DAsync(d_coeffs_out, coeffs_stride * 8, d_in, in_stride * 8, n * 8, n_cols,
-                             hipMemcpyDeviceToDevice, st));
+    canon_copy_kernel<<<dim3(bpg::ceil_div(n, 256), n_cols), 256, 0, st>>>(d_in, in_stride, d_coeffs_out, coeffs_stride, log_n);
+    BPG_LAUNCH_CHECK();
   }
   const uint64_t* scale = nullptr;
   if ((rc = bpg::get_table(2, log_n, rate_bits, &scale))) return rc;

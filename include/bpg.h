@@ -175,6 +175,11 @@ void bp_tune_rec_batch(int n);
  * (1, default); 0 = always on the prover's own stream; n > 1 = also while up to n provers are at work (measured: no gain,
  * profiles/r5_block_size_series.txt).  Results are identical. */
 void bp_tune_side_lanes(int n);
+/* Inside bp_prove_shard / bp_prove_shard_gi / bp_aggregate_proofs a transaction's root proof and the tree's aggregation
+ * proofs ride in the spare slot of other transactions' lock-step batches, and what is left at the end of a tree is proved
+ * a batch at a time (1, default); 0 = every node is proved where it is started, one proof per chain of launches.  Read
+ * once per call.  Results are identical.  (Not listed by bp_debug_tune_state; bp_tune_reset puts it back.) */
+void bp_tune_rec_riders(int on);
 /* The witness of a recursion circuit's Poseidon rows (the sponge over its public-input list, its children's Merkle paths,
  * the sponges over their opened rows: independent pieces) is made on the host; a prover that is alone on the device makes
  * the pieces of a lock-step batch on up to n threads (default 7; 1 = on the prover's own thread).  Results are identical. */

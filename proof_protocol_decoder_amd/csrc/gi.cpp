@@ -15,7 +15,9 @@
 //    transactions still waiting for a thread.  The headline rate of bench.py is a property of this policy as much as of
 //    the kernels, so it belongs to the library.
 //
-// Built on the public ABI (include/bpg.h) only -- what a host in any language could do itself.
+// Built on the public ABI (include/bpg.h) -- what a host in any language could do itself -- with one exception: a
+// state-backed shard hands the transactions' root proofs and the aggregation proofs to the prover as jobs (rec_pool.hpp),
+// which ride in batches that the public calls prove one at a time.
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +31,8 @@
 #include "common.hpp"
 #include "gl.hpp"
 #include "mpt.hpp"
+#include "rec_pool.hpp"
+#include "tune.hpp"
 
 namespace {
 
@@ -293,165 +297,92 @@ int chain_start(const std::vector<Entry>& es, bp_gi_chain* chain) {
   for (int i = 0; i < 4; i++) chain->state_root[i] = le64(h.data() + 8 * i) % gl::P;
   return BP_OK;
 }
+// pool (nullable): the shard's job pool -- the proof's root is then posted as the job of `node` instead of being proved here
 int prove_entry(const bp_state* s, const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, const volatile uint8_t* abort_flag,
-                uint8_t** out, size_t* out_len) {
+                uint8_t** out, size_t* out_len, bpg::RecPool* pool = nullptr, uint32_t node = 0) {
   EntryWork w;
   if (int rc = entry_work(e, o, chain, true, &w)) return rc;
-  if (!w.any_witness) return bp_generate_txn_proof_u8(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), abort_flag, out, out_len);
+  if (!w.any_witness) {
+    if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), nullptr, abort_flag, pool, node);
+    return bp_generate_txn_proof_u8(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), abort_flag, out, out_len);
+  }
   bp_txn_witness tw;
   std::memset(&tw, 0, sizeof(tw));
   tw.keccak_inputs = w.perms.data(); tw.n_perms = w.perms.size() / 25; tw.has_keccak = 1;
   if (o.flags & BP_GI_KECCAK_SPONGE_AIR) { tw.sponge_rows = w.rows.data(); tw.n_sponge_rows = w.rows.size() / 44; tw.has_keccak_sponge = 1; }
   if (o.flags & BP_GI_MEMORY_AIR) { tw.memory_log = w.log.data(); tw.n_memory_ops = w.log.size() / 11; tw.has_memory = 1; }
   if (o.flags & BP_GI_BYTE_PACKING_AIR) { tw.byte_sequences = w.seqs.data(); tw.n_byte_sequences = w.seqs.size() / 6; tw.has_byte_packing = 1; }
+  if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, pool, node);
   return bp_generate_txn_proof_witness(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, out, out_len);
 }
 
 // ---------------------------------------------------------------- aggregation plan + scheduler
-// Entry k of the plan is node n + k = (left, right) node ids; the last entry is the root.  Aggregation needs contiguous
-// ranges (proof_types.rs:23-24) and nothing else.  0 = balanced: adjacent pairs level by level, an odd tail carried up;
-// 1 = pairs_then_chain: adjacent leaves paired, the pair results folded left to right.
+// (the plan's two shapes and the scheduler itself: rec_pool.hpp, built alone by tools/rec_pool_check.cpp)
 int make_plan(uint32_t n, uint32_t shape, std::vector<std::pair<uint32_t, uint32_t>>* plan) {
   if (n < 1) return fail(BP_ERR_INVALID_INPUT, "nothing to aggregate");
   if (shape > 1) return fail(BP_ERR_INVALID_INPUT, "unknown tree shape %u (0 balanced, 1 pairs_then_chain)", shape);
-  plan->clear();
-  if (shape == 0) {
-    std::vector<uint32_t> level(n);
-    for (uint32_t i = 0; i < n; i++) level[i] = i;
-    while (level.size() > 1) {
-      std::vector<uint32_t> nxt;
-      for (size_t k = 0; k + 1 < level.size(); k += 2) {
-        plan->push_back({level[k], level[k + 1]});
-        nxt.push_back(n + (uint32_t)plan->size() - 1);
-      }
-      if (level.size() % 2) nxt.push_back(level.back());
-      level.swap(nxt);
-    }
-    return BP_OK;
-  }
-  std::vector<uint32_t> heads;
-  for (uint32_t k = 0; k + 1 < n; k += 2) {
-    plan->push_back({k, k + 1});
-    heads.push_back(n + (uint32_t)plan->size() - 1);
-  }
-  if (n % 2) heads.push_back(n - 1);
-  uint32_t acc = heads[0];
-  for (size_t i = 1; i < heads.size(); i++) {
-    plan->push_back({acc, heads[i]});
-    acc = n + (uint32_t)plan->size() - 1;
-  }
+  bpg::tree_plan(n, shape, plan);
   return BP_OK;
 }
 
-struct Buf {
-  uint8_t* p = nullptr;
-  size_t n = 0;
-};
-// All leaves of a contiguous slice and its tree.  Every aggregation starts the moment both of its children exist and goes
-// AHEAD of the leaves still waiting for a thread (priority 0 before 1, each kind in index order), so the tree advances
-// with the proving instead of piling up behind it.  The first failure stops the pool; its status and message are the call's.
+// All leaves of a contiguous slice and its tree (bpg::TreeRun).  Every aggregation starts the moment both of its children
+// exist and goes AHEAD of the leaves still waiting for a thread, so the tree advances with the proving instead of piling
+// up behind it.  The first failure stops the pool; its status and message are the call's.
+// With a state (s non-null, Tune::rec_riders on) the roots of the transactions and the aggregations are JOBS: they ride
+// in the spare slot of the lock-step batches of the transactions being proved, and a thread with no leaf to start proves
+// what is ready a batch at a time -- the end of the tree, and all of bp_aggregate_proofs.  bp_run_shard's callbacks are
+// opaque: every node is proved where it is started.
 // leaf_is_agg (nullable): the kinds of the leaves when they are proofs made elsewhere (bp_aggregate_proofs); else txn proofs
+// pooled_leaf (nullable): the leaf callback of a run with jobs -- posts node i's root as a job instead of proving it
+using PooledLeaf = int (*)(void* ctx, uint32_t i, bpg::RecPool* pool);
 int run_tree(uint32_t n, const bp_shard_options* opt, bp_shard_leaf_fn leaf, bp_shard_agg_fn agg, void* ctx,
              const volatile uint8_t* abort_flag, uint8_t** root_out, size_t* root_len, uint8_t** leaf_out, size_t* leaf_len,
-             const int* leaf_is_agg = nullptr) {
+             const int* leaf_is_agg = nullptr, const bp_state* s = nullptr, PooledLeaf pooled_leaf = nullptr) {
   if (!leaf || !agg || !root_out || !root_len) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: null argument");
   if ((leaf_out == nullptr) != (leaf_len == nullptr)) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: leaf_out and leaf_len go together");
   std::vector<std::pair<uint32_t, uint32_t>> plan;
   if (int rc = make_plan(n, opt ? opt->tree_shape : 0, &plan)) return rc;
-  const uint32_t total = n + (uint32_t)plan.size(), root = total - 1;
-  std::vector<uint32_t> parent_of(total, ~0u);
-  for (uint32_t k = 0; k < plan.size(); k++) parent_of[plan[k].first] = parent_of[plan[k].second] = n + k;
-  std::vector<Buf> res(total);
-  std::vector<char> done(total, 0);
-  std::mutex mu;
-  std::condition_variable cv;
-  using Item = std::pair<int, uint32_t>;
-  std::priority_queue<Item, std::vector<Item>, std::greater<Item>> queue;
-  for (uint32_t i = 0; i < n; i++) queue.push({1, i});
-  bool stop = false;
-  int first_rc = BP_OK;
-  std::string first_msg;
-  auto worker = [&] {
-    for (;;) {
-      uint32_t nid;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || !queue.empty(); });
-        if (stop) return;
-        nid = queue.top().second;
-        queue.pop();
-      }
-      Buf b;
-      int rc;
-      try {
-        if (abort_flag && *abort_flag) rc = fail(BP_ERR_ABORTED, "aborted before node %u of the shard", nid);
-        else if (nid < n) rc = leaf(ctx, nid, &b.p, &b.n);
-        else {
-          const uint32_t l = plan[nid - n].first, r = plan[nid - n].second;
-          const int la = l >= n || (leaf_is_agg && leaf_is_agg[l]), ra = r >= n || (leaf_is_agg && leaf_is_agg[r]);
-          rc = agg(ctx, res[l].p, res[l].n, la, res[r].p, res[r].n, ra, &b.p, &b.n);
-        }
-        if (rc == BP_OK && !b.p) rc = fail(BP_ERR_DEVICE, "node %u of the shard returned no proof", nid);
-      } catch (...) {
-        rc = fail(BP_ERR_DEVICE, "node %u of the shard: exception in a callback", nid);
-      }
-      std::lock_guard<std::mutex> lk(mu);
-      if (rc) {
-        if (!first_rc) { first_rc = rc; first_msg = bp_last_error(); }
-        std::free(b.p);
-        stop = true;
-        cv.notify_all();
-        return;
-      }
-      res[nid] = b;
-      done[nid] = 1;
-      if (nid >= n) {  // the children have been consumed: leaves stay when the caller wants them
-        const uint32_t ch[2] = {plan[nid - n].first, plan[nid - n].second};
-        for (uint32_t c : ch)
-          if (c >= n || !leaf_out) { std::free(res[c].p); res[c] = Buf(); }
-      }
-      const uint32_t par = parent_of[nid];
-      if (par != ~0u && done[plan[par - n].first] && done[plan[par - n].second]) queue.push({0, par});
-      if (nid == root) stop = true;
-      cv.notify_all();
+  bpg::TreeOps ops;
+  ops.pooled = s && bpg::tune().rec_riders.load(std::memory_order_relaxed) != 0;
+  ops.cap = ops.pooled ? bpg::rec_batch_cap(s) : 1;
+  ops.last_error = [] { return std::string(bp_last_error()); };
+  ops.leaf = [=](uint32_t i, bpg::RecPool* pool, uint8_t** out, size_t* out_len, bool* posted) {
+    if (pool && pooled_leaf) {
+      *posted = true;
+      return pooled_leaf(ctx, i, pool);
     }
+    return leaf(ctx, i, out, out_len);
   };
-  uint32_t n_threads = opt && opt->n_threads ? opt->n_threads : 1;
-  n_threads = std::min<uint32_t>(std::min<uint32_t>(n_threads, n), 256);
-  std::vector<std::thread> pool;
-  struct Joiner {
-    std::vector<std::thread>& p;
-    ~Joiner() { for (auto& t : p) if (t.joinable()) t.join(); }
-  } joiner{pool};
-  for (uint32_t i = 1; i < n_threads; i++) {
-    try {
-      pool.emplace_back(worker);
-    } catch (const std::system_error&) {  // no more threads to be had: the ones there are do the work
-      break;
-    }
-  }
-  worker();  // the calling thread is one of the pool
-  for (auto& t : pool) t.join();
-  pool.clear();
-  if (first_rc) {
-    for (auto& b : res) std::free(b.p);
-    return fail(first_rc, "%s", first_msg.c_str());
-  }
-  *root_out = res[root].p;
-  *root_len = res[root].n;
+  ops.agg = [=](const bpg::TreeBuf& l, int la, const bpg::TreeBuf& r, int ra, uint8_t** out, size_t* out_len) {
+    return agg(ctx, l.p, l.n, la, r.p, r.n, ra, out, out_len);
+  };
+  ops.agg_prepare = [=](const bpg::TreeBuf& l, int la, const bpg::TreeBuf& r, int ra, bpg::RecJob* job) {
+    return bpg::agg_proof_prepare(s, l.p, l.n, la, r.p, r.n, ra, job);
+  };
+  ops.prove_batch = [=](const std::vector<std::unique_ptr<bpg::RecJob>>& jobs, std::vector<bpg::TreeBuf>* out) {
+    return bpg::rec_prove_jobs(s, jobs, abort_flag, out);
+  };
+  bpg::TreeRun run(n, std::move(plan), ops, abort_flag, leaf_is_agg, leaf_out != nullptr);
+  const uint32_t n_threads = opt && opt->n_threads ? opt->n_threads : 1;
+  if (int rc = run.run(n_threads)) return fail(rc, "%s", run.error().c_str());
   if (leaf_out) {
-    for (uint32_t i = 0; i < n; i++) {
-      if (n == 1) {  // the root IS the leaf: the caller gets its own copy to free
-        leaf_out[0] = static_cast<uint8_t*>(std::malloc(res[0].n));
-        if (!leaf_out[0]) { std::free(res[0].p); *root_out = nullptr; return fail(BP_ERR_DEVICE, "host allocation failed"); }
-        std::memcpy(leaf_out[0], res[0].p, res[0].n);
-        leaf_len[0] = res[0].n;
-      } else {
-        leaf_out[i] = res[i].p;
-        leaf_len[i] = res[i].n;
+    if (n == 1) {  // the root IS the leaf: the caller gets its own copy to free
+      const bpg::TreeBuf& r0 = run.result(0);
+      leaf_out[0] = static_cast<uint8_t*>(std::malloc(r0.n));
+      if (!leaf_out[0]) return fail(BP_ERR_DEVICE, "host allocation failed");
+      std::memcpy(leaf_out[0], r0.p, r0.n);
+      leaf_len[0] = r0.n;
+    } else {
+      for (uint32_t i = 0; i < n; i++) {
+        const bpg::TreeBuf b = run.release(i);
+        leaf_out[i] = b.p;
+        leaf_len[i] = b.n;
       }
     }
   }
+  const bpg::TreeBuf top = run.release(run.root());
+  *root_out = top.p;
+  *root_len = top.n;
   return BP_OK;
 }
 
@@ -464,6 +395,10 @@ struct IrShard {
 int ir_leaf(void* ctx, uint32_t i, uint8_t** out, size_t* out_len) {
   const IrShard* c = static_cast<const IrShard*>(ctx);
   return bp_generate_txn_proof_u8(c->s, c->irs + (size_t)i * c->stride, BP_IR_WORDS * 8, c->abort_flag, out, out_len);
+}
+int ir_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
+  const IrShard* c = static_cast<const IrShard*>(ctx);
+  return bpg::txn_proof_pooled(c->s, c->irs + (size_t)i * c->stride, BP_IR_WORDS * 8, nullptr, c->abort_flag, pool, i);
 }
 int state_agg(void* ctx, const uint8_t* l, size_t ln, int l_agg, const uint8_t* r, size_t rn, int r_agg, uint8_t** out, size_t* out_len) {
   return bp_generate_agg_proof(*static_cast<const bp_state* const*>(ctx), l, ln, l_agg, r, rn, r_agg, out, out_len);
@@ -480,6 +415,11 @@ int gi_leaf(void* ctx, uint32_t i, uint8_t** out, size_t* out_len) {
   const GiShard* c = static_cast<const GiShard*>(ctx);
   bp_gi_chain ch = (*c->chain_before)[c->first + i];
   return prove_entry(c->s, (*c->es)[c->first + i], *c->o, &ch, c->abort_flag, out, out_len);
+}
+int gi_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
+  const GiShard* c = static_cast<const GiShard*>(ctx);
+  bp_gi_chain ch = (*c->chain_before)[c->first + i];
+  return prove_entry(c->s, (*c->es)[c->first + i], *c->o, &ch, c->abort_flag, nullptr, nullptr, pool, i);
 }
 uint32_t default_threads(const bp_state* s, const bp_shard_options* opt) {
   if (opt && opt->n_threads) return opt->n_threads;
@@ -570,7 +510,7 @@ int bp_aggregate_proofs(const bp_state* s, const uint8_t* const* proofs, const s
     return (int)BP_OK;
   };
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
-  return run_tree(n, &o, leaf, state_agg, &c, nullptr, out, out_len, nullptr, nullptr, kinds.data());
+  return run_tree(n, &o, leaf, state_agg, &c, nullptr, out, out_len, nullptr, nullptr, kinds.data(), s);
 }
 BPG_ABI_CATCH("bp_aggregate_proofs")
 
@@ -581,7 +521,8 @@ int bp_prove_shard(const bp_state* s, const uint8_t* irs, size_t ir_stride, uint
   struct Ctx { const bp_state* s; IrShard sh; } c{s, {s, irs, ir_stride, abort_flag}};
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
   auto leaf = [](void* ctx, uint32_t i, uint8_t** out, size_t* out_len) { return ir_leaf(&static_cast<Ctx*>(ctx)->sh, i, out, out_len); };
-  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len);
+  auto pooled = [](void* ctx, uint32_t i, bpg::RecPool* pool) { return ir_leaf_pooled(&static_cast<Ctx*>(ctx)->sh, i, pool); };
+  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, pooled);
 }
 BPG_ABI_CATCH("bp_prove_shard")
 
@@ -604,7 +545,7 @@ int bp_prove_shard_gi(const bp_state* s, const uint8_t* geni, size_t len, uint32
   }
   GiShard c{s, &es, gi, first, &before, abort_flag};
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
-  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len);
+  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, gi_leaf_pooled);
 }
 BPG_ABI_CATCH("bp_prove_shard_gi")
 

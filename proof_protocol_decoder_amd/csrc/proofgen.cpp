@@ -19,6 +19,7 @@
 #include "air_check.hpp"
 #include "mpt.hpp"
 #include "prover.hpp"
+#include "rec_pool.hpp"
 #include "tune.hpp"
 
 using namespace bpg;
@@ -53,13 +54,7 @@ struct Circuit {  // one preprocessed recursion circuit: constants commitment + 
   uint64_t digest[4];
   air::plonk::Layout lay{};  // AIR 8: the list the circuit hashes and the Merkle paths it walks
 };
-// One Merkle path a recursion circuit walks in its Poseidon rows: the leaf digest and the cap entry are words of the
-// proof's public-input list (Layout::path_pi0), the position and the siblings are witness.
-struct PathWitness {
-  uint64_t index = 0;
-  std::vector<uint64_t> siblings;  // 4 words per level, leaf upward
-  std::vector<uint64_t> leaf_row;  // the opened row the leaf digest is the hash of (circuits that hash it: Layout::leaf_len)
-};
+// (PathWitness, one Merkle path a recursion circuit walks: rec_pool.hpp -- a job carries them)
 struct LightCircuit {
   std::vector<uint64_t> cap;
   uint64_t digest[4];
@@ -201,6 +196,11 @@ int emit_box(uint64_t kind, uint64_t circuit, const std::vector<uint64_t>& pi, c
   return BP_OK;
 }
 
+// proofs of shape rc one lock-step batch holds: MAX_BATCH, Tune::rec_batch, and the query launches' index limit
+uint32_t batch_cap(const StarkCfg& rc) {
+  return std::min<uint32_t>(std::min<uint32_t>(MAX_BATCH, std::max<uint32_t>(1, tune().rec_batch.load(std::memory_order_relaxed))),
+                            std::max<uint32_t>(1, MAX_BATCH_QUERIES / std::max<uint32_t>(1, rc.num_queries)));
+}
 // Recursion-shaped proofs; transcript of each = circuit digest, hash of the public inputs, trace cap.  `n` proofs of
 // the state's one recursion shape are proved in lock-step, up to Tune::rec_batch at a time (stark_prove_batch: every
 // launch and every host wait is shared; circuits, public inputs and transcripts are each proof's own).
@@ -208,8 +208,7 @@ int emit_box(uint64_t kind, uint64_t circuit, const std::vector<uint64_t>& pi, c
 // first_leaf (nullable, 4 words per proof): the digest of the trace leaf each proof's first query opens
 int rec_prove_batch(Worker& w, const StarkCfg& rc, uint32_t n, const Circuit* const* circ, const std::vector<uint64_t>* pi,
                     std::vector<uint64_t>* proofs, const std::vector<PathWitness>* paths = nullptr, uint64_t* first_leaf = nullptr) {
-  const uint32_t cap = std::min<uint32_t>(std::min<uint32_t>(MAX_BATCH, std::max<uint32_t>(1, tune().rec_batch.load(std::memory_order_relaxed))),
-                                          std::max<uint32_t>(1, MAX_BATCH_QUERIES / std::max<uint32_t>(1, rc.num_queries)));
+  const uint32_t cap = batch_cap(rc);
   const uint64_t N = (uint64_t)1 << rc.log_n;
   for (uint32_t first = 0; first < n; first += cap) {
     const uint32_t B = std::min(cap, n - first);
@@ -420,6 +419,20 @@ int verify_foreign(const bp_state* s, const Box& b, const char* what) {
 
 int verify_child(const bp_state* s, const Box& b, const char* what, const uint8_t* bytes, size_t len) {
   return produced_here(s, bytes, len) ? BP_OK : verify_foreign(s, b, what);
+}
+
+// A job's finished proof words become its container -- this state's own, like every container it emits.
+int box_of_job(const bp_state* s, const RecJob& job, const std::vector<uint64_t>& words, TreeBuf* out) {
+  if (int r = emit_box(job.kind, CIRCUIT_ROOT + job.kind, job.pi, words, &out->p, &out->n)) return r;
+  remember_proof(s, out->p, out->n);
+  return BP_OK;
+}
+// ... and, for a rider, go back to the pool it was taken from
+int finish_job(const bp_state* s, const RecJob& job, const std::vector<uint64_t>& words, RecPool* pool) {
+  TreeBuf b;
+  if (int r = box_of_job(s, job, words, &b)) return r;
+  pool->complete(job, b.p, b.n);
+  return BP_OK;
 }
 
 void root_after(const uint64_t root_before[4], uint64_t seed, uint64_t txn_number, uint64_t out[4]) {
@@ -1007,8 +1020,8 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
 
 static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
                           const volatile uint8_t* abort_flag_u8, uint8_t** out, size_t* out_len,
-                          const TxnWitness* wit = nullptr, bool tables_only = false) {
-  if (!s || !ir || !out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
+                          const TxnWitness* wit = nullptr, bool tables_only = false, RecPool* pool = nullptr, uint32_t node = 0) {
+  if (!s || !ir || ((!out || !out_len) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
   if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
   const uint64_t* I = reinterpret_cast<const uint64_t*>(ir);
   const bp_config& cfg = s->cfg;
@@ -1061,9 +1074,16 @@ static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   // chain was its own sequence of 6..16-column launches: 88 of a transaction's 118 LDE launches and most of its
   // 1,620 kernel launches.)  Level 0 is proved by the circuit of the table's height (its child is the table's STARK
   // proof), the levels above by the table's shrink circuit.
+  // With a pool (a shard's scheduler, gi.cpp) each of these batches also carries ready jobs of the pool -- other
+  // transactions' root proofs, the tree's aggregation proofs -- in the slots the seven chains leave free: one more
+  // circuit, list and transcript in launches that are made anyway.  A rider's container is handed back the moment its
+  // batch is done; a state whose batches hold seven proofs or fewer carries none.
   {
-    const Circuit* circ[BP_NUM_TABLES];
-    std::vector<uint64_t> pis[BP_NUM_TABLES], chain_proof[BP_NUM_TABLES];
+    const Circuit* circ[MAX_BATCH];
+    std::vector<uint64_t> pis[MAX_BATCH], chain_proof[MAX_BATCH];
+    std::vector<PathWitness> slot_path[MAX_BATCH];
+    for (int t = 0; t < BP_NUM_TABLES; t++) slot_path[t] = std::move(child_path[t]);
+    const uint32_t cap = batch_cap(s->rec_cfg);
     for (uint32_t depth = 0; depth < cfg.shrink_depth; depth++) {
       if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted in the recursion chains (level %u)", depth);
       for (int t = 0; t < BP_NUM_TABLES; t++) {
@@ -1071,13 +1091,23 @@ static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
         pis[t] = {digest[t][0], digest[t][1], digest[t][2], digest[t][3], (uint64_t)t, depth};
         pis[t].insert(pis[t].end(), leaf_cap[t], leaf_cap[t] + 8);
       }
-      uint64_t first_leaf[BP_NUM_TABLES][4];
-      if ((r = rec_prove_batch(w, s->rec_cfg, BP_NUM_TABLES, circ, pis, chain_proof, child_path, &first_leaf[0][0]))) return r;
+      std::vector<std::unique_ptr<RecJob>> riders;
+      if (pool && cap > BP_NUM_TABLES) pool->take(cap - BP_NUM_TABLES, &riders);
+      for (size_t k = 0; k < riders.size(); k++) {
+        circ[BP_NUM_TABLES + k] = static_cast<const Circuit*>(riders[k]->circuit);
+        pis[BP_NUM_TABLES + k] = riders[k]->pi;
+        slot_path[BP_NUM_TABLES + k] = std::move(riders[k]->paths);
+      }
+      uint64_t first_leaf[MAX_BATCH][4];
+      if ((r = rec_prove_batch(w, s->rec_cfg, BP_NUM_TABLES + (uint32_t)riders.size(), circ, pis, chain_proof, slot_path, &first_leaf[0][0]))) return r;
+      for (size_t k = 0; k < riders.size(); k++)
+        if ((r = finish_job(s, *riders[k], chain_proof[BP_NUM_TABLES + k], pool))) return r;
       for (int t = 0; t < BP_NUM_TABLES; t++) {
         proof_digest(s->rec_cfg, chain_proof[t].data(), digest[t]);
-        first_query_trace_path(s->rec_cfg, chain_proof[t].data(), leaf_cap[t], leaf_cap[t] + 4, &child_path[t][0], first_leaf[t]);
+        first_query_trace_path(s->rec_cfg, chain_proof[t].data(), leaf_cap[t], leaf_cap[t] + 4, &slot_path[t][0], first_leaf[t]);
       }
     }
+    for (int t = 0; t < BP_NUM_TABLES; t++) child_path[t] = std::move(slot_path[t]);
   }
   // root proof: the seven chains' digests, their seven (leaf digest, cap entry) pairs, the public values
   std::vector<uint64_t> pi;
@@ -1088,6 +1118,16 @@ static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     root_paths[t] = std::move(child_path[t][0]);
   }
   pi.insert(pi.end(), pv.begin(), pv.end());
+  if (pool) {  // the root rides in another transaction's batch, or in a batch of the jobs that are left at the end
+    std::unique_ptr<RecJob> job(new RecJob());
+    job->node = node;
+    job->kind = 0;
+    job->circuit = &s->special[0];
+    job->pi = std::move(pi);
+    job->paths = std::move(root_paths);
+    pool->post(std::move(job));
+    return BP_OK;
+  }
   if ((r = rec_prove(w, s->rec_cfg, s->special[0], pi, proof, &root_paths))) return r;
   if ((r = emit_box(0, CIRCUIT_ROOT, pi, proof, out, out_len))) return r;
   remember_proof(s, *out, *out_len);
@@ -1361,9 +1401,11 @@ int bp_verify_txn_table_proofs_for(const bp_config* cfg, const uint8_t* ir, size
 }
 BPG_ABI_CATCH("bp_verify_txn_table_proofs_for")
 
-int bp_generate_agg_proof(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg,
-                          const uint8_t* rhs, size_t rhs_len, int rhs_is_agg, uint8_t** out, size_t* out_len) try {
-  if (!s || !lhs || !rhs || !out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_generate_agg_proof: null argument");
+// The host half of an aggregation: the children parsed, checked for contiguity and verified (or recognised as this
+// state's own), the public-input list and the two path witnesses of the aggregation circuit.  No device work.
+static int agg_prepare(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg, const uint8_t* rhs, size_t rhs_len,
+                       int rhs_is_agg, std::vector<uint64_t>* pi_out, std::vector<PathWitness>* paths_out) {
+  if (!s || !lhs || !rhs) return fail(BP_ERR_INVALID_INPUT, "bp_generate_agg_proof: null argument");
   Box L, R;
   int r;
   if ((r = parse_box(lhs, lhs_len, s->rec_cfg, &L)) || (r = parse_box(rhs, rhs_len, s->rec_cfg, &R))) return r;
@@ -1410,18 +1452,30 @@ int bp_generate_agg_proof(const bp_state* s, const uint8_t* lhs, size_t lhs_len,
     if (r) return fail(r, "%s", lhs_err.c_str());
     if (r_rhs) return fail(r_rhs, "%s", rhs_err.c_str());
   }
-  std::vector<uint64_t> pi(AGG_PATH_PI0 + 16 + BP_PV_WORDS);
+  std::vector<uint64_t>& pi = *pi_out;
+  pi.assign(AGG_PATH_PI0 + 16 + BP_PV_WORDS, 0);
   proof_digest(s->rec_cfg, L.stark, &pi[0]);
   proof_digest(s->rec_cfg, R.stark, &pi[4]);
   pi[8] = lhs_is_agg != 0; pi[9] = rhs_is_agg != 0;
   // per child the opened trace row of its first query and the cap entry above it: the circuit walks the path between them
-  std::vector<PathWitness> paths(2);
+  std::vector<PathWitness>& paths = *paths_out;
+  paths.assign(2, PathWitness());
   first_query_trace_path(s->rec_cfg, L.stark, &pi[AGG_PATH_PI0], &pi[AGG_PATH_PI0 + 4], &paths[0]);
   first_query_trace_path(s->rec_cfg, R.stark, &pi[AGG_PATH_PI0 + 8], &pi[AGG_PATH_PI0 + 12], &paths[1]);
   uint64_t* pv = &pi[AGG_PATH_PI0 + 16];
   pv[0] = L.pv[0]; pv[1] = R.pv[1]; pv[2] = L.pv[2]; pv[3] = R.pv[3];
   std::memcpy(pv + 4, L.pv + 4, 32); std::memcpy(pv + 8, R.pv + 8, 32);
   pv[12] = L.pv[12];
+  return BP_OK;
+}
+
+int bp_generate_agg_proof(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg,
+                          const uint8_t* rhs, size_t rhs_len, int rhs_is_agg, uint8_t** out, size_t* out_len) try {
+  if (!s || !lhs || !rhs || !out || !out_len) return fail(BP_ERR_INVALID_INPUT, "bp_generate_agg_proof: null argument");
+  std::vector<uint64_t> pi;
+  std::vector<PathWitness> paths;
+  int r = agg_prepare(s, lhs, lhs_len, lhs_is_agg, rhs, rhs_len, rhs_is_agg, &pi, &paths);
+  if (r) return r;
   (void)hipSetDevice(s->cfg.device);
   WorkerLease lease(s);
   std::vector<uint64_t> proof;
@@ -1532,3 +1586,58 @@ int bp_verify_block_proof(const bp_verifier_state* v, const uint8_t* proof, size
 BPG_ABI_CATCH("bp_verify_block_proof")
 
 }  // extern "C"
+
+// ---- the prover's side of a shard's job pool (rec_pool.hpp; the scheduler is gi.cpp's) ------------------------------
+namespace bpg {
+
+uint32_t rec_batch_cap(const bp_state* s) { return s ? batch_cap(s->rec_cfg) : 1; }
+
+int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
+                     const volatile uint8_t* abort_flag, RecPool* pool, uint32_t node) {
+  if (!pool) return fail(BP_ERR_INVALID_INPUT, "txn_proof_pooled: no pool");
+  if (!data) return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, nullptr, false, pool, node);
+  TxnWitness wit;
+  if (int r = witness_of(data, &wit)) return r;
+  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, &wit, false, pool, node);
+}
+
+int agg_proof_prepare(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg, const uint8_t* rhs, size_t rhs_len,
+                      int rhs_is_agg, RecJob* job) {
+  if (!job) return fail(BP_ERR_INVALID_INPUT, "agg_proof_prepare: no job");
+  if (int r = agg_prepare(s, lhs, lhs_len, lhs_is_agg, rhs, rhs_len, rhs_is_agg, &job->pi, &job->paths)) return r;
+  job->kind = 1;
+  job->circuit = &s->special[1];
+  return BP_OK;
+}
+
+int rec_prove_jobs(const bp_state* s, const std::vector<std::unique_ptr<RecJob>>& jobs, const volatile uint8_t* abort_flag,
+                   std::vector<TreeBuf>* out) {
+  if (!s || !out || jobs.empty()) return fail(BP_ERR_INVALID_INPUT, "rec_prove_jobs: nothing to prove");
+  const size_t n = jobs.size();
+  std::vector<const Circuit*> circ(n);
+  std::vector<std::vector<uint64_t>> pi(n), proofs(n);
+  std::vector<std::vector<PathWitness>> paths(n);
+  for (size_t k = 0; k < n; k++) {
+    circ[k] = static_cast<const Circuit*>(jobs[k]->circuit);
+    pi[k] = jobs[k]->pi;
+    paths[k] = jobs[k]->paths;
+  }
+  (void)hipSetDevice(s->cfg.device);
+  {
+    WorkerLease lease(s);
+    Worker& w = *lease.w;
+    w.abort_flag_u8 = abort_flag;
+    if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before a batch of %zu recursion jobs", n);
+    if (int r = rec_prove_batch(w, s->rec_cfg, (uint32_t)n, circ.data(), pi.data(), proofs.data(), paths.data())) return r;
+  }
+  out->assign(n, TreeBuf());
+  for (size_t k = 0; k < n; k++)
+    if (int r = box_of_job(s, *jobs[k], proofs[k], &(*out)[k])) {
+      for (auto& b : *out) std::free(b.p);
+      out->clear();
+      return r;
+    }
+  return BP_OK;
+}
+
+}  // namespace bpg

@@ -35,6 +35,9 @@ void bp_tune_host_poseidon(int mode) { bpg::tune().host_poseidon.store(mode == 1
 void bp_tune_rec_batch(int n) { bpg::tune().rec_batch.store(n < 1 ? 1 : (n > (int)bpg::MAX_BATCH ? (int)bpg::MAX_BATCH : n)); }
 void bp_tune_witness_threads(int n) { bpg::tune().witness_threads.store(n < 1 ? 1 : (n > 16 ? 16 : n)); }
 void bp_tune_side_lanes(int n) { bpg::tune().side_lanes.store(n < 0 ? 0 : n); }
+// A switch between two schedules of the same proofs, not one of the kernel knobs that bp_debug_tune_state lists (its
+// lines are a fixed set); bp_tune_reset puts it back like the others.
+void bp_tune_rec_riders(int on) { bpg::tune().rec_riders.store(on != 0); }
 
 void bp_tune_reset(void) {
   const bpg::Tune defaults;
@@ -42,6 +45,7 @@ void bp_tune_reset(void) {
 #define X(k) t.k.store(defaults.k.load());
   BPG_KNOBS(X)
 #undef X
+  t.rec_riders.store(defaults.rec_riders.load());
 }
 
 int bp_debug_tune_state(char* buf, size_t cap) {

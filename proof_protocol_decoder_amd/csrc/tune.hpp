@@ -63,6 +63,13 @@ struct Tune {
   std::atomic<int> rec_batch{8};      // recursion proofs proved in lock-step (MAX_BATCH); 1 = one proof at a time
   std::atomic<int> witness_threads{7};  // host threads a lone prover makes its Poseidon-row witness on
   std::atomic<int> side_lanes{1};     // 0 = no side lanes, n = while at most n provers are at work
+
+  // ---- shard scheduler (gi.cpp, rec_pool.hpp)
+  // 1 = inside bp_prove_shard / bp_prove_shard_gi / bp_aggregate_proofs the root proof of a transaction and the
+  // aggregation proofs are jobs that ride in the spare slot of other transactions' lock-step batches, and what is left
+  // at the end of the tree is proved a batch at a time; 0 = every node is proved where it is started, one proof per
+  // chain of launches (the scheduling up to this knob).  Read once per call.  Measurements: profiles/rec_riders_ab.txt.
+  std::atomic<int> rec_riders{1};
 };
 
 Tune& tune();  // the process's one instance (tune.cpp)

@@ -428,7 +428,8 @@ int bp_air_check_trace_host(uint32_t air_id, const struct bp_stark_cfg* shape, c
  * (any u64; lane x + 5y), or NULL to draw them from `seed` (splitmix64(seed ^ (lane << 32) ^ permutation)). */
 int bp_keccak_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 /* Witness of AIR 2 (the logic table: one AND / OR / XOR of two 256-bit words per row): n = 2^log_n rows x 524 columns
- * (the last one, the filter of the lookup keccak_sponge -> logic, zero), column-major.  d_inputs: [n][9] = operation code (0 none = a padding row, 1 and, 2 or, 3 xor), then the four 64-bit
+ * (the last one, the filter of the lookup keccak_sponge -> logic, zero), column-major.  d_inputs: [n][9] = operation code (0 none = a padding row, 1 and, 2 or, 3 xor;
+ * only the low two bits of the word count), then the four 64-bit
  * words of operand 0 and of operand 1, least significant first; or NULL to draw them from `seed`
  * (code = splitmix64(seed ^ (0xFF << 32) ^ row) & 3, word w of operand j = splitmix64(seed ^ ((1 + 4 j + w) << 32) ^ row)). */
 int bp_logic_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
@@ -436,30 +437,39 @@ int bp_logic_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint
  * 45 columns (the last one, the lookup's filter, zero), column-major.  d_inputs: [n][11] = is_read, address (< 2^32), timestamp (< 2^32), eight 32-bit value
  * limbs, ALREADY SORTED (the kernel derives the address_changed flag and the gap bits from neighbouring rows; a log
  * that is out of order, or whose reads do not return the previous value, gives a witness the verifier rejects); or NULL
- * for a log drawn from `seed` (four operations per address; csrc/stark_kernels.hip, memory_trace_kernel). */
+ * for a log drawn from `seed` (four operations per address; csrc/stark_kernels.hip, memory_trace_kernel).
+ * Any u64 is accepted.  Outside the ranges above the kernel does what the oracle does: is_read is bit 0 of its word;
+ * address, timestamp and value limbs are stored reduced mod p; address_changed compares the 64-bit words; the gap is
+ * the 64-bit difference (address' - address - 1 across a change, timestamp' - timestamp - 1 within) taken modulo 2^32.
+ * The witness is then rejected at that row (the gap constraint) unless the difference of the STORED values, minus one,
+ * is that 32-bit number in the field, i.e. unless the true gap fits: an address step from 3 to 2^32 proves (gap
+ * 2^32 - 4), a timestamp step of 2^32 + 1, equal timestamps on one address or a descending address do not
+ * (tests/witness_edges.py, tests/test_witness_edges.py, tests/test_gpu_witness_edges.py). */
 int bp_memory_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 /* Witness of AIR 4 (the additive part of the arithmetic table: ADD / SUB / LT / GT on 256-bit words as sixteen 16-bit
  * limbs with a carry chain): n = 2^log_n rows x 309 columns, column-major.  d_inputs: [n][9] = operation code (0 none,
- * 1 add, 2 sub, 3 lt, 4 gt), then the four 64-bit words of x and of y, least significant first; or NULL to draw them
+ * 1 add, 2 sub, 3 lt, 4 gt; any other 64-bit value: none), then the four 64-bit words of x and of y, least significant first; or NULL to draw them
  * from `seed` (code = splitmix64(seed ^ (0xFE << 32) ^ row) % 5, words as in bp_logic_trace). */
 int bp_arithmetic_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 /* Witness of AIR 5 (the byte-packing table: a big-endian sequence of 1..32 bytes and the 256-bit word it spells, what
  * MLOAD_32BYTES / MSTORE_32BYTES move): n = 2^log_n rows x 299 columns, column-major.  d_inputs: [n][6] = word 0:
  * is_read (bit 0) | timestamp << 8; word 1: len (low byte; 0 = a padding row; above 32: 32) | address << 8 -- the 32-bit
  * address and timestamp of the memory operation that moves the word (the lookup byte_packing -> memory sends
- * (is_read, address, timestamp, value limbs) to the memory table; zero when the caller does not care) --; then the 32
+ * (is_read, address, timestamp, value limbs) to the memory table; zero when the caller does not care; bits 1..7 of word
+ * 0 and bits 40..63 of both words are ignored) --; then the 32
  * byte slots as four 64-bit words (slot i = byte i % 8 of word i / 8; slots from len on are ignored); or NULL to draw
  * them from `seed` (address = row, timestamp = 2 + row). */
 int bp_byte_packing_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 /* Witness of AIR 6 (the Keccak sponge table: the absorbing side of Keccak-256, one 136-byte block per row): n =
- * 2^log_n rows x 2414 columns, column-major.  d_inputs: [n][44] = flags (1 full block, 2 final block, 0 padding row),
+ * 2^log_n rows x 2414 columns, column-major.  d_inputs: [n][44] = flags (1 full block, 2 final block, 0 or 3 padding row; the low two bits count),
  * message bytes in the block, the block as absorbed (17 words, pad10*1 included), the 25 lanes of the state before the
  * block -- bp_keccak256_sponge_rows makes them for a message; or NULL for one single-block message per row drawn from
  * `seed`.  The kernel computes the XOR and the permutation of every row. */
 int bp_keccak_sponge_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 /* Witness of AIR 7 (the multiplicative half of the arithmetic table, a table of its own here: x * y = z + 2^256 w as a
- * 32-column schoolbook product over 16-bit limbs with 21-bit carries): n = 2^log_n rows x 1217 columns, column-major.
- * d_inputs: [n][9] = is_mul (0 = a padding row), the four 64-bit words of x and of y; or NULL to draw them from `seed`. */
+ * 32-column schoolbook product over 16-bit limbs with 21-bit carries; the largest carry any operands produce is
+ * 0xFFFEF, out of column 15 of (2^256 - 1)^2, so bit 20 of every carry is zero): n = 2^log_n rows x 1217 columns, column-major.
+ * d_inputs: [n][9] = is_mul (bit 0 of the word; 0 = a padding row), the four 64-bit words of x and of y; or NULL to draw them from `seed`. */
 int bp_arithmetic_mul_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
 
 /* AIR 8 (plonk): the 85 preprocessed constant columns of the fixed circuit (selectors, gate constants drawn from `seed`,

@@ -696,9 +696,9 @@ int bp_generate_txn_proof_keccak(const bp_state* s, const uint8_t* ir, size_t ir
  * side derives it from GenerationInputs: proof_protocol_decoder_amd/block_driver.py).  A table is given data when its
  * has_* field is non-zero (n may be 0: a table of padding only) and its IR flag is set (bp_ir_set_*_air).  Items beyond
  * n are padding: Keccak permutations of the all-zero state, rows without an operation, and for the memory log reads of
- * the last address at later and later times.  Layouts as for the bp_*_trace entry points: keccak_inputs [n][25],
- * logic_ops / arithmetic_ops [n][9], memory_log [n][11] sorted by (address, timestamp), byte_sequences [n][6] (with the address and timestamp of the
- * memory operation each names when the memory table is real too: bp_byte_packing_trace).  When the sponge table and the
+ * the last address at later and later times.  Layouts as for the bp_*_trace entry points, [n][words of an item]: the
+ * table above bp_ir_set_*_air lists them (byte_sequences with the address and timestamp of the memory operation each
+ * names when the memory table is real too: bp_byte_packing_trace).  When the sponge table and the
  * logic table are both proven by their AIRs the logic table's FIRST rows are not the caller's: rows 5 p + m are the XOR of
  * limbs 8 m .. 8 m + 7 of sponge row p's rate with its block (the lookup keccak_sponge -> logic), for the min(sponge rows,
  * logic rows / 5) sponge rows the table has room for; logic_ops (or seeded operations) follow them, and more operations
@@ -713,7 +713,7 @@ typedef struct bp_txn_witness {
   const uint64_t* memory_log;      size_t n_memory_ops;      int has_memory;
   const uint64_t* arithmetic_ops;  size_t n_arithmetic_ops;  int has_arithmetic;
   const uint64_t* byte_sequences;  size_t n_byte_sequences;  int has_byte_packing;
-  const uint64_t* sponge_rows;     size_t n_sponge_rows;     int has_keccak_sponge;  /* [n][44], bp_keccak256_sponge_rows */
+  const uint64_t* sponge_rows;     size_t n_sponge_rows;     int has_keccak_sponge;
 } bp_txn_witness;
 int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
                                   const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len);
@@ -769,6 +769,25 @@ int bp_check_txn_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, co
 /* the same for bp_generate_txn_proof_keccak's inputs */
 int bp_check_txn_witness_keccak(const bp_state* s, const uint8_t* ir, size_t ir_len, const uint64_t* keccak_inputs,
                                 size_t n_perms, bp_witness_report* out);
+/* Test entry, host only (no state, no device): what the prover and the pre-flight make of an IR and its witness data
+ * (data: nullable) before they touch the GPU -- per table the AIR, width and height the IR's flags select, whether the
+ * table is made from the caller's data and how many items of how many words it holds (the table above bp_ir_set_*_air);
+ * per lookup of air::ctl::pairs() its two sides and whether it exists for these tables; the sponge rows whose XORs the
+ * logic table holds first and the rows the seeded sponge table may absorb in (UINT32_MAX: all).  Every refusal that
+ * depends only on the IR, the shapes and which tables are given is this call's too, with the same status and message. */
+typedef struct bp_txn_plan_table {
+  uint32_t air_id, n_cols, log_n, given, item_words;
+  uint64_t capacity;
+} bp_txn_plan_table;
+typedef struct bp_txn_plan_lookup {
+  uint32_t active, looking_table, looking_air, looked_table, looked_air;
+} bp_txn_plan_lookup;
+typedef struct bp_txn_plan {
+  bp_txn_plan_table table[7];
+  bp_txn_plan_lookup lookup[3];
+  uint32_t logic_covered, sponge_row_limit;
+} bp_txn_plan;
+int bp_debug_txn_plan(const bp_config* cfg, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data, bp_txn_plan* out);
 /* the same call taking the reference's own flag: Arc<AtomicBool> is ONE byte, `flag.as_ptr()` binds here directly */
 int bp_generate_txn_proof_u8(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile uint8_t* abort_flag,
                              uint8_t** out, size_t* out_len);
@@ -801,24 +820,28 @@ int bp_ir_encode(uint64_t block_number, uint64_t txn_number_before, uint64_t gas
 int bp_ir_encode_dummy(uint64_t block_number, uint64_t txn_number, uint64_t gas_used, const uint64_t state_root[4],
                        uint64_t seed, const uint32_t table_log_n[BP_NUM_TABLES],
                        const uint32_t table_width[BP_NUM_TABLES], uint64_t ir_out[BP_IR_WORDS]);
-/* Marks an encoded IR (flag 0x100 of the version word) so that its Keccak table -- table index 3 in the positional
- * order of prover_state.rs:85-93 -- is proven with the Keccak-f[1600] AIR (air_id 1: 2431 columns, the witness is
- * ceil(2^log_n / 24) permutations drawn from the seed) instead of the synthetic AIR.  The table's width must be 2431. */
+/* bp_ir_set_<x>_air marks an encoded IR (a flag above the version byte of word 1) so that one of the transaction's
+ * tables is proven with its AIR instead of the synthetic one; the table's width must then be the AIR's.  Tables by their
+ * position in upstream's order (prover_state.rs:85-93); the witness is drawn from the seed unless bp_txn_witness gives it:
+ *
+ *   table          index  setter                        AIR                 flag    width  witness item (u64 words)
+ *   arithmetic       0    bp_ir_set_arithmetic_air      4 arithmetic        0x800    309   9: operation, x, y
+ *                         bp_ir_set_arithmetic_mul_air  7 arithmetic_mul    0x4000  1217   9: is_mul, x, y (x * y = z + 2^256 w per row)
+ *   byte_packing     1    bp_ir_set_byte_packing_air    5 byte_packing      0x1000   299   6: a sequence
+ *   cpu              2    -- (always synthetic)
+ *   keccak           3    bp_ir_set_keccak_air          1 keccak_f          0x100   2431   25: a permutation's input lanes; one per 24 rows
+ *   keccak_sponge    4    bp_ir_set_keccak_sponge_air   6 keccak_sponge     0x2000  2414   44: bp_keccak256_sponge_rows
+ *   logic            5    bp_ir_set_logic_air           2 logic             0x200    524   9: operation, in0, in1
+ *   memory           6    bp_ir_set_memory_air          3 memory            0x400     45   11: a log entry, sorted by (address, timestamp)
+ *
+ * A table of 2^log_n rows holds one item per row, the Keccak table ceil(2^log_n / 24).  The arithmetic table is proven by
+ * ONE AIR: AIR 4 or, instead, AIR 7 (the multiplicative half of upstream's arithmetic table). */
 int bp_ir_set_keccak_air(uint64_t ir[BP_IR_WORDS], int on);
-/* The same for the logic table (flag 0x200; table index 5): proven with the logic AIR (air_id 2: 524 columns, one
- * operation per row drawn from the seed).  The table's width must be 524. */
 int bp_ir_set_logic_air(uint64_t ir[BP_IR_WORDS], int on);
-/* ... and for the memory table (flag 0x400; table index 6): the memory AIR (air_id 3: 45 columns, a sorted log drawn
- * from the seed).  The table's width must be 45. */
 int bp_ir_set_memory_air(uint64_t ir[BP_IR_WORDS], int on);
-/* ... and for the arithmetic table (flag 0x800; table index 0): the arithmetic AIR (air_id 4: 309 columns). */
 int bp_ir_set_arithmetic_air(uint64_t ir[BP_IR_WORDS], int on);
-/* ... or, instead (one AIR per table), with the multiplication AIR (flag 0x4000; air_id 7: 1217 columns, x * y = z + 2^256 w
- * per row; arithmetic_ops then are [n][9] = is_mul, the words of x, the words of y).  The table's width must be 1217. */
 int bp_ir_set_arithmetic_mul_air(uint64_t ir[BP_IR_WORDS], int on);
-/* ... and for the byte-packing table (flag 0x1000; table index 1): the byte-packing AIR (air_id 5: 299 columns). */
 int bp_ir_set_byte_packing_air(uint64_t ir[BP_IR_WORDS], int on);
-/* ... and for the Keccak sponge table (flag 0x2000; table index 4): the Keccak sponge AIR (air_id 6: 2414 columns). */
 int bp_ir_set_keccak_sponge_air(uint64_t ir[BP_IR_WORDS], int on);
 /* public values of a proof container: txn_before, txn_after, gas_before, gas_after, root_before[4],
  * root_after[4], block_number */

@@ -385,31 +385,26 @@ class BlockDriver:
             self.pool.shutdown()
 
 
+def _widths_with_airs(table_width, **air_flags):
+    """table_width with, for every flag of pg.TXN_TABLE_AIRS that is set, the width of that AIR at its table."""
+    from .ops import AIR_COLS
+    width = list(table_width)
+    for field, t, air_id, *_ in reversed(pg.TXN_TABLE_AIRS):   # (reversed: with both arithmetic flags AIR 4's width stays,
+        if air_flags.get(field):                                #  and to_bytes names the multiplication AIR's as the one that is off)
+            width[t] = AIR_COLS[air_id]
+    return tuple(width)
+
+
 def synthetic_block_irs(block_number, n_txns, table_log_n, table_width, seed_base=0x5EED000000000000,
                         root0=(1, 2, 3, 4), keccak_air=False, logic_air=False, memory_air=False, arithmetic_air=False,
                         byte_packing_air=False, keccak_sponge_air=False, arithmetic_mul_air=False):
     """The synthetic block of SURVEY.md section 8(d): n_txns txns with distinct seeds whose public
     values chain (state root, txn number, gas) like decoding.rs:106-154 chains GenerationInputs.
-    keccak_air: every transaction's Keccak table (index 3) is a real Keccak-f[1600] trace (AIR 1; the table's width
-    becomes 2431).  logic_air / memory_air: likewise the logic table (index 5) with the logic AIR (AIR 2; width 524) and
-    the memory table (index 6) with the memory AIR (AIR 3; width 45); arithmetic_air: the arithmetic table (index 0)
-    with the arithmetic AIR (AIR 4; width 309); byte_packing_air: the byte-packing table (index 1) with AIR 5 (width 299);
-    keccak_sponge_air: the Keccak sponge table (index 4) with AIR 6 (width 2414); arithmetic_mul_air (instead of
-    arithmetic_air): the arithmetic table with the multiplication AIR (AIR 7; width 1217)."""
-    if keccak_air:
-        table_width = tuple(2431 if t == 3 else w for t, w in enumerate(table_width))
-    if arithmetic_mul_air:
-        table_width = tuple(1217 if t == 0 else w for t, w in enumerate(table_width))
-    if logic_air:
-        table_width = tuple(524 if t == 5 else w for t, w in enumerate(table_width))
-    if memory_air:
-        table_width = tuple(45 if t == 6 else w for t, w in enumerate(table_width))
-    if arithmetic_air:
-        table_width = tuple(309 if t == 0 else w for t, w in enumerate(table_width))
-    if byte_packing_air:
-        table_width = tuple(299 if t == 1 else w for t, w in enumerate(table_width))
-    if keccak_sponge_air:
-        table_width = tuple(2414 if t == 4 else w for t, w in enumerate(table_width))
+    keccak_air, logic_air, ...: the table of that name is proven with its AIR instead of the synthetic one and its width
+    becomes the AIR's (pg.TXN_TABLE_AIRS; arithmetic_mul_air instead of arithmetic_air: the multiplication AIR)."""
+    table_width = _widths_with_airs(table_width, keccak_air=keccak_air, logic_air=logic_air, memory_air=memory_air,
+                                    arithmetic_air=arithmetic_air, byte_packing_air=byte_packing_air,
+                                    keccak_sponge_air=keccak_sponge_air, arithmetic_mul_air=arithmetic_mul_air)
     import ctypes as C
     L = pg._bind()
     L.bp_state_root_after.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -625,7 +620,7 @@ def irs_from_generation_inputs(gen_inputs, block_number, table_log_n, table_widt
     root (folded into four field elements) and chains entry to entry.  Entries without a transaction (dummy
     padding, the withdrawal carrier) become dummy IRs: proven, counters do not advance (decoding.rs:484-520) --
     a prepended dummy is renumbered to its position, as pad_with_dummy_irs documents.
-    keccak_air: every entry's Keccak table (index 3) becomes a real Keccak-f[1600] trace (AIR 1, 2431 columns) whose
+    keccak_air: every entry's Keccak table (index 3) becomes a real Keccak-f[1600] trace (AIR 1) whose
     permutations are the entry's OWN hashing work (keccak_inputs_of_generation_inputs): the table then attests data of
     the decoded transaction, not only a seed; its height grows to hold them (24 rows per permutation).
     keccak_trie_nodes: the hashing of the entry's partial tries is part of that work (the prover state's Keccak range
@@ -644,20 +639,12 @@ def irs_from_generation_inputs(gen_inputs, block_number, table_log_n, table_widt
     first = gen_inputs[0].tries.state_trie.hash()
     root = tuple(int.from_bytes(first[8 * i:8 * i + 8], "little") % P for i in range(4))
     irs, txn_no, gas = [], 0, 0
-    if keccak_air:
-        table_width = tuple(2431 if t == 3 else w for t, w in enumerate(table_width))
     if (memory_air or byte_packing_air or keccak_sponge_air) and not keccak_air:
         raise ValueError("the memory / byte-packing / sponge work is that of the hashed bytes: it needs keccak_air")
-    if keccak_sponge_air:
-        table_width = tuple(2414 if t == 4 else w for t, w in enumerate(table_width))
-    if logic_air:
-        if not keccak_sponge_air:
-            raise ValueError("the logic table's work is the sponge table's XORs: logic_air needs keccak_sponge_air")
-        table_width = tuple(524 if t == 5 else w for t, w in enumerate(table_width))
-    if memory_air:
-        table_width = tuple(45 if t == 6 else w for t, w in enumerate(table_width))
-    if byte_packing_air:
-        table_width = tuple(299 if t == 1 else w for t, w in enumerate(table_width))
+    if logic_air and not keccak_sponge_air:
+        raise ValueError("the logic table's work is the sponge table's XORs: logic_air needs keccak_sponge_air")
+    table_width = _widths_with_airs(table_width, keccak_air=keccak_air, keccak_sponge_air=keccak_sponge_air, logic_air=logic_air,
+                                    memory_air=memory_air, byte_packing_air=byte_packing_air)
     base_log_n = tuple(table_log_n)
     for k, g in enumerate(gen_inputs):
         kw = {}

@@ -33,10 +33,12 @@
 #include "mpt.hpp"
 #include "rec_pool.hpp"
 #include "tune.hpp"
+#include "txn_tables.hpp"
 
 namespace {
 
 using bpg::fail;
+using namespace bpg::txn;
 using mpt::Bytes;
 using mpt::H256;
 
@@ -207,8 +209,8 @@ uint32_t ceil_log2(uint64_t n) {
 
 struct EntryWork {  // everything bp_generate_txn_proof_witness needs for one entry
   uint64_t ir[BP_IR_WORDS];
-  bool any_witness = false;
-  std::vector<uint64_t> perms, rows, log, seqs;
+  bool given[BP_NUM_TABLES] = {};               // the tables made from the entry's own work ...
+  std::vector<uint64_t> items[BP_NUM_TABLES];  // ... and their witness items
 };
 // IR (+ witness when `with_witness`) of entry e given the chain before it; *chain moves to after the entry.
 int entry_work(const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, bool with_witness, EntryWork* w) {
@@ -221,11 +223,8 @@ int entry_work(const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, bool 
   uint32_t log_n[BP_NUM_TABLES], width[BP_NUM_TABLES];
   std::memcpy(log_n, o.table_log_n, sizeof(log_n));
   std::memcpy(width, o.table_width, sizeof(width));
-  if (f & BP_GI_KECCAK_AIR) width[3] = 2431;
-  if (f & BP_GI_KECCAK_SPONGE_AIR) width[4] = 2414;
-  if (f & BP_GI_MEMORY_AIR) width[6] = 45;
-  if (f & BP_GI_BYTE_PACKING_AIR) width[1] = 299;
-  if (f & BP_GI_LOGIC_AIR) width[5] = 524;
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    if (f & TABLES[t].gi_flag) width[t] = bpg::air::DESC[TABLES[t].airs[0].air_id].n_cols;
   if (f & BP_GI_KECCAK_AIR) {
     // the heights grow to hold the work (24 rows per permutation); the witness itself only when it is asked for
     std::vector<Bytes> pre;
@@ -236,19 +235,21 @@ int entry_work(const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, bool 
       n_rows += m.size() / 136 + 1;
       n_chunks += (m.size() + 31) / 32;
     }
-    log_n[3] = std::max(log_n[3], ceil_log2(std::max<uint64_t>(24 * n_perms, 1)));
-    if (f & BP_GI_KECCAK_SPONGE_AIR) log_n[4] = std::max(log_n[4], ceil_log2(std::max<uint64_t>(n_rows, 1)));
+    log_n[T_KECCAK] = std::max(log_n[T_KECCAK], ceil_log2(std::max<uint64_t>(24 * n_perms, 1)));
+    if (f & BP_GI_KECCAK_SPONGE_AIR) log_n[T_KECCAK_SPONGE] = std::max(log_n[T_KECCAK_SPONGE], ceil_log2(std::max<uint64_t>(n_rows, 1)));
     // (five XORs per absorbed block, of every row of the sponge table's final height: keccak_sponge -> logic)
-    if (f & BP_GI_LOGIC_AIR) log_n[5] = std::max(log_n[5], ceil_log2(5ull << log_n[4]));
-    if (f & BP_GI_MEMORY_AIR) log_n[6] = std::max(log_n[6], ceil_log2(std::max<uint64_t>(2 * n_chunks, 1)));
-    if (f & BP_GI_BYTE_PACKING_AIR) log_n[1] = std::max(log_n[1], ceil_log2(std::max<uint64_t>(n_chunks, 1)));
+    if (f & BP_GI_LOGIC_AIR) log_n[T_LOGIC] = std::max(log_n[T_LOGIC], ceil_log2(5ull << log_n[T_KECCAK_SPONGE]));
+    if (f & BP_GI_MEMORY_AIR) log_n[T_MEMORY] = std::max(log_n[T_MEMORY], ceil_log2(std::max<uint64_t>(2 * n_chunks, 1)));
+    if (f & BP_GI_BYTE_PACKING_AIR) log_n[T_BYTE_PACKING] = std::max(log_n[T_BYTE_PACKING], ceil_log2(std::max<uint64_t>(n_chunks, 1)));
     if (with_witness) {
-      w->any_witness = true;
+      // every flagged table holds the entry's own work, but the logic table: its first rows are derived from the sponge
+      // table inside the library (keccak_sponge -> logic), the rest drawn from the seed
+      for (int t = 0; t < BP_NUM_TABLES; t++) w->given[t] = (f & TABLES[t].gi_flag) && t != T_LOGIC;
       for (const Bytes& m : pre) {
-        mpt::keccak256_traced(m.data(), m.size(), &w->perms);
-        if (f & BP_GI_KECCAK_SPONGE_AIR) mpt::keccak256_sponge_rows(m.data(), m.size(), &w->rows);
+        mpt::keccak256_traced(m.data(), m.size(), &w->items[T_KECCAK]);
+        if (w->given[T_KECCAK_SPONGE]) mpt::keccak256_sponge_rows(m.data(), m.size(), &w->items[T_KECCAK_SPONGE]);
       }
-      if (f & (BP_GI_MEMORY_AIR | BP_GI_BYTE_PACKING_AIR)) memory_and_byte_packing_work(pre, &w->log, &w->seqs);
+      if (w->given[T_MEMORY] || w->given[T_BYTE_PACKING]) memory_and_byte_packing_work(pre, &w->items[T_MEMORY], &w->items[T_BYTE_PACKING]);
     }
   }
   // the witness seed binds the proof to the decoded state transition: keccak(signed_txn | roots after | withdrawals)
@@ -281,11 +282,8 @@ int entry_work(const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, bool 
     }
   }
   if (rc) return rc;
-  if ((f & BP_GI_KECCAK_AIR) && (rc = bp_ir_set_keccak_air(w->ir, 1))) return rc;
-  if ((f & BP_GI_KECCAK_SPONGE_AIR) && (rc = bp_ir_set_keccak_sponge_air(w->ir, 1))) return rc;
-  if ((f & BP_GI_MEMORY_AIR) && (rc = bp_ir_set_memory_air(w->ir, 1))) return rc;
-  if ((f & BP_GI_BYTE_PACKING_AIR) && (rc = bp_ir_set_byte_packing_air(w->ir, 1))) return rc;
-  if ((f & BP_GI_LOGIC_AIR) && (rc = bp_ir_set_logic_air(w->ir, 1))) return rc;
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    if ((f & TABLES[t].gi_flag) && (rc = ir_set_air(w->ir, t, 0, 1))) return rc;
   return BP_OK;
 }
 int chain_start(const std::vector<Entry>& es, bp_gi_chain* chain) {
@@ -302,16 +300,18 @@ int prove_entry(const bp_state* s, const Entry& e, const bp_gi_options& o, bp_gi
                 uint8_t** out, size_t* out_len, bpg::RecPool* pool = nullptr, uint32_t node = 0) {
   EntryWork w;
   if (int rc = entry_work(e, o, chain, true, &w)) return rc;
-  if (!w.any_witness) {
+  if (!w.given[T_KECCAK]) {  // (every other table's work is that of the hashed bytes: entry_work)
     if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), nullptr, abort_flag, pool, node);
     return bp_generate_txn_proof_u8(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), abort_flag, out, out_len);
   }
   bp_txn_witness tw;
   std::memset(&tw, 0, sizeof(tw));
-  tw.keccak_inputs = w.perms.data(); tw.n_perms = w.perms.size() / 25; tw.has_keccak = 1;
-  if (o.flags & BP_GI_KECCAK_SPONGE_AIR) { tw.sponge_rows = w.rows.data(); tw.n_sponge_rows = w.rows.size() / 44; tw.has_keccak_sponge = 1; }
-  if (o.flags & BP_GI_MEMORY_AIR) { tw.memory_log = w.log.data(); tw.n_memory_ops = w.log.size() / 11; tw.has_memory = 1; }
-  if (o.flags & BP_GI_BYTE_PACKING_AIR) { tw.byte_sequences = w.seqs.data(); tw.n_byte_sequences = w.seqs.size() / 6; tw.has_byte_packing = 1; }
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    if (!w.given[t]) continue;
+    tw.*TABLES[t].data = w.items[t].data();
+    tw.*TABLES[t].n = w.items[t].size() / TABLES[t].item_words;
+    tw.*TABLES[t].has = 1;
+  }
   if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, pool, node);
   return bp_generate_txn_proof_witness(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, out, out_len);
 }

@@ -21,22 +21,21 @@
 #include "prover.hpp"
 #include "rec_pool.hpp"
 #include "tune.hpp"
+#include "txn_tables.hpp"
 
 using namespace bpg;
+using namespace bpg::txn;
 extern "C" int bp_use_blocking_sync(int device);
 extern "C" int bp_host_wait_mode(int device);
 
 namespace {
 
-constexpr uint64_t IR_MAGIC = 0x52494E5854475042ULL;     // "BPGTXNIR"
 constexpr uint64_t PROOF_BOX_MAGIC = 0x464F4F5250475042ULL;  // "BPGPROOF"
-constexpr uint64_t TABLES_MAGIC = 0x534C424154475042ULL;     // "BPGTABLS"
 constexpr uint32_t CIRCUIT_ROOT = 7, CIRCUIT_AGG = 8, CIRCUIT_BLOCK = 9;
 constexpr uint32_t AGG_PATH_PI0 = 10, BLOCK_PATH_PI0 = 9;  // where the children's (leaf digest, cap entry) words sit in the list
 constexpr uint32_t CHAIN_PATH_PI0 = 6, ROOT_PATH_PI0 = 4 * BP_NUM_TABLES;  // ... of a chain circuit's one child, of the root circuit's seven
 constexpr uint32_t SHRINK_SEED_DEGREE = 255;  // circuit_seed(table, 255): the table's shrink circuit (levels >= 1 of its chain)
 constexpr size_t BOX_HDR = 4;
-const char* TABLE_NAMES[BP_NUM_TABLES] = {"arithmetic", "byte_packing", "cpu", "keccak", "keccak_sponge", "logic", "memory"};
 
 uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ULL;
@@ -142,11 +141,6 @@ StarkCfg rec_cfg_of(const bp_config& c) {
   return StarkCfg{c.rec_log_n, c.rec_n_cols, c.rec_n_const, 3, c.rec_rate_bits, c.stark_cap_height,
                   c.rec_num_queries, c.rec_pow_bits, c.arity_bits, c.final_poly_bits, c.rec_air_id};
 }
-StarkCfg table_cfg_of(const bp_config& c, uint32_t log_n, uint32_t width) {
-  return StarkCfg{log_n, width, 0, 1, c.stark_rate_bits, c.stark_cap_height, c.stark_num_queries,
-                  c.stark_pow_bits, c.arity_bits, c.final_poly_bits};
-}
-
 // lay (AIR 8): the public-input list the circuit's hash rows absorb -- 6 words for a table's chain circuits (digest,
 // table, depth), 7 x 4 + 13 for the root circuit, 10 + 2 x 8 + 13 / 9 + 8 + 13 for the aggregation / block circuit -- and
 // the Merkle paths it walks: one per child proof of the aggregation circuit, the aggregation child's of the block circuit
@@ -435,11 +429,6 @@ int finish_job(const bp_state* s, const RecJob& job, const std::vector<uint64_t>
   return BP_OK;
 }
 
-void root_after(const uint64_t root_before[4], uint64_t seed, uint64_t txn_number, uint64_t out[4]) {
-  uint64_t in[6] = {root_before[0], root_before[1], root_before[2], root_before[3], gl::canon(seed), gl::canon(txn_number)};
-  hash_no_pad_host(in, 6, out);
-}
-
 }  // namespace
 
 extern "C" {
@@ -471,7 +460,7 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
   uint32_t n_circ = 0;
   for (int t = 0; t < BP_NUM_TABLES; t++) {
     if (cfg->table_log_lo[t] >= cfg->table_log_hi[t] || cfg->table_log_hi[t] > 31)
-      return fail(BP_ERR_INVALID_INPUT, "empty or invalid range for table %s", TABLE_NAMES[t]);
+      return fail(BP_ERR_INVALID_INPUT, "empty or invalid range for table %s", TABLES[t].name);
     StarkCfg tc = table_cfg_of(*cfg, cfg->table_log_lo[t], 8);
     if ((r = check_cfg(tc))) return r;
     n_circ += cfg->table_log_hi[t] - cfg->table_log_lo[t];
@@ -601,93 +590,6 @@ uint64_t bp_state_device_bytes(const bp_state* s) {
   return s->builder.arena.capacity() + (uint64_t)s->workers.size() * s->cfg.arena_bytes;
 }
 
-int bp_ir_encode(uint64_t block_number, uint64_t txn_number_before, uint64_t gas_used_before,
-                 uint64_t gas_used_after, const uint64_t state_root_before[4], uint64_t seed,
-                 const uint32_t table_log_n[BP_NUM_TABLES], const uint32_t table_width[BP_NUM_TABLES],
-                 uint64_t o[BP_IR_WORDS]) {
-  if (!state_root_before || !table_log_n || !table_width || !o) return fail(BP_ERR_INVALID_INPUT, "bp_ir_encode: null argument");
-  o[0] = IR_MAGIC; o[1] = 1; o[2] = block_number; o[3] = txn_number_before; o[4] = gas_used_before; o[5] = gas_used_after;
-  for (int i = 0; i < 4; i++) {
-    if (state_root_before[i] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "state root word is not a canonical field element");
-    o[6 + i] = state_root_before[i];
-  }
-  o[10] = seed;
-  for (int t = 0; t < BP_NUM_TABLES; t++) { o[11 + t] = table_log_n[t]; o[18 + t] = table_width[t]; }
-  return BP_OK;
-}
-
-int bp_ir_set_keccak_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_keccak_air: not an IR");
-  if (on && ir[18 + 3] != air::keccak::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the Keccak-f AIR has %u columns: the IR gives table keccak %llu", air::keccak::N_COLS,
-                (unsigned long long)ir[18 + 3]);
-  ir[1] = (ir[1] & ~(uint64_t)0x100) | (on ? 0x100 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_logic_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_logic_air: not an IR");
-  if (on && ir[18 + 5] != air::logic::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the logic AIR has %u columns: the IR gives table logic %llu", air::logic::N_COLS,
-                (unsigned long long)ir[18 + 5]);
-  ir[1] = (ir[1] & ~(uint64_t)0x200) | (on ? 0x200 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_memory_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_memory_air: not an IR");
-  if (on && ir[18 + 6] != air::memory::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the memory AIR has %u columns: the IR gives table memory %llu", air::memory::N_COLS,
-                (unsigned long long)ir[18 + 6]);
-  ir[1] = (ir[1] & ~(uint64_t)0x400) | (on ? 0x400 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_arithmetic_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_arithmetic_air: not an IR");
-  if (on && ir[18 + 0] != air::arithmetic::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the arithmetic AIR has %u columns: the IR gives table arithmetic %llu",
-                air::arithmetic::N_COLS, (unsigned long long)ir[18 + 0]);
-  ir[1] = (ir[1] & ~(uint64_t)0x800) | (on ? 0x800 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_arithmetic_mul_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_arithmetic_mul_air: not an IR");
-  if (on && ir[18 + 0] != air::arithmetic_mul::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the multiplication AIR has %u columns: the IR gives table arithmetic %llu",
-                air::arithmetic_mul::N_COLS, (unsigned long long)ir[18 + 0]);
-  if (on && (ir[1] & 0x800)) return fail(BP_ERR_INVALID_INPUT, "the arithmetic table is proven by ONE AIR: clear bp_ir_set_arithmetic_air first");
-  ir[1] = (ir[1] & ~(uint64_t)0x4000) | (on ? 0x4000 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_byte_packing_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_byte_packing_air: not an IR");
-  if (on && ir[18 + 1] != air::byte_packing::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the byte-packing AIR has %u columns: the IR gives table byte_packing %llu",
-                air::byte_packing::N_COLS, (unsigned long long)ir[18 + 1]);
-  ir[1] = (ir[1] & ~(uint64_t)0x1000) | (on ? 0x1000 : 0);
-  return BP_OK;
-}
-
-int bp_ir_set_keccak_sponge_air(uint64_t ir[BP_IR_WORDS], int on) {
-  if (!ir || ir[0] != IR_MAGIC) return fail(BP_ERR_INVALID_INPUT, "bp_ir_set_keccak_sponge_air: not an IR");
-  if (on && ir[18 + 4] != air::keccak_sponge::N_COLS)
-    return fail(BP_ERR_INVALID_INPUT, "the Keccak sponge AIR has %u columns: the IR gives table keccak_sponge %llu",
-                air::keccak_sponge::N_COLS, (unsigned long long)ir[18 + 4]);
-  ir[1] = (ir[1] & ~(uint64_t)0x2000) | (on ? 0x2000 : 0);
-  return BP_OK;
-}
-
-int bp_ir_encode_dummy(uint64_t block_number, uint64_t txn_number, uint64_t gas_used, const uint64_t state_root[4],
-                       uint64_t seed, const uint32_t table_log_n[BP_NUM_TABLES], const uint32_t table_width[BP_NUM_TABLES],
-                       uint64_t o[BP_IR_WORDS]) {
-  int rc = bp_ir_encode(block_number, txn_number, gas_used, gas_used, state_root, seed, table_log_n, table_width, o);
-  if (rc == BP_OK) o[1] = 2;
-  return rc;
-}
-
 // root_after of one txn (the synthetic "state transition"): hash_no_pad(root_before, seed, txn_number).
 // Host-side, like the decoder that chains GenerationInputs in the reference (decoding.rs:106-154).
 int bp_state_root_after(const uint64_t root_before[4], uint64_t seed, uint64_t txn_number, uint64_t out[4]) {
@@ -708,33 +610,6 @@ int bp_proof_public_values(const uint8_t* proof, size_t len, uint64_t pv_out[BP_
 }
 BPG_ABI_CATCH("bp_proof_public_values")
 
-// Witness data given by the caller instead of drawn from the seed, per table (bp_txn_witness): in[t] nullable, n[t]
-// items of WITNESS_WORDS[t] words; the table must carry its AIR flag.  The rest of the table is padding: permutations
-// of the all-zero state (as upstream pads its Keccak table), rows without an operation, and for the memory log reads
-// of the last address at later and later times (a memory that is left alone).
-struct TxnWitness {
-  const uint64_t* in[BP_NUM_TABLES] = {};
-  size_t n[BP_NUM_TABLES] = {};
-};
-static const uint32_t WITNESS_WORDS[BP_NUM_TABLES] = {9, 6, 0, 25, 44, 9, 11};  // arithmetic, byte packing, -, keccak, sponge, logic, memory
-static const uint32_t WITNESS_AIR[BP_NUM_TABLES] = {air::ARITHMETIC, air::BYTE_PACKING, ~0u, air::KECCAK_F, air::KECCAK_SPONGE, air::LOGIC, air::MEMORY};
-// items a table of N rows holds: one permutation per 24 rows for Keccak (the last one may be cut), else one per row
-static size_t witness_capacity(int t, uint64_t N) { return t == 3 ? (size_t)((N + 23) / 24) : (size_t)N; }
-// the table's full input array (capacity x words), the caller's items first, then padding
-static void fill_table_inputs(int t, uint64_t N, const uint64_t* in, size_t n, uint64_t* dst) {
-  const size_t cap = witness_capacity(t, N), wds = WITNESS_WORDS[t];
-  std::memcpy(dst, in, n * wds * 8);
-  std::memset(dst + n * wds, 0, (cap - n) * wds * 8);
-  if (t == 6) {  // memory: keep reading the last cell (a first-row read of zero memory when the log is empty)
-    uint64_t last[11] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (n) std::memcpy(last, in + (n - 1) * 11, sizeof(last));
-    last[0] = 1;
-    for (size_t i = n; i < cap; i++) {
-      last[2] += 1;
-      std::memcpy(dst + i * 11, last, sizeof(last));
-    }
-  }
-}
 // What upstream's `prove` returns before the recursion starts (AllProof: the seven table proofs, the lookup
 // challenges, the public values) -- kept by bp_generate_txn_table_proofs, digested by bp_generate_txn_proof.
 struct TableProofs {
@@ -744,194 +619,85 @@ struct TableProofs {
   std::vector<uint64_t> proof[BP_NUM_TABLES];
   uint64_t first_leaf[BP_NUM_TABLES][4];  // per table proof: the digest of the trace leaf its first query opens (stark_prove)
 };
-static int parse_ir(const bp_config& cfg, const uint64_t* I, const TxnWitness* wit, StarkCfg tcfg[BP_NUM_TABLES],
-                    std::vector<uint64_t>* pv_out) {
-  // version 1: a transaction; version 2: a dummy entry (decoding.rs:484-520): txn number, gas and state
-  // root do not advance, the same tables are proven
-  // flags above the version byte: 0x100 = the Keccak table (index 3, prover_state.rs:85-93) is proven with the
-  // Keccak-f AIR (air.hpp, AIR 1) instead of the synthetic one: 2431 columns, witness drawn from the seed;
-  // 0x200 = the logic table (index 5) is proven with the logic AIR (AIR 2): 523 columns, operations drawn from the seed;
-  // 0x400 = the memory table (index 6) with the memory AIR (AIR 3): 45 columns, a sorted log drawn from the seed;
-  // 0x800 = the arithmetic table (index 0) with the arithmetic AIR (AIR 4): 309 columns;
-  // 0x1000 = the byte-packing table (index 1) with the byte-packing AIR (AIR 5): 299 columns;
-  // 0x2000 = the Keccak sponge table (index 4) with the Keccak sponge AIR (AIR 6): 2414 columns;
-  // 0x4000 = the arithmetic table (index 0) with the MULTIPLICATION AIR (AIR 7, the multiplicative half of upstream's
-  //          arithmetic table: 1217 columns) instead of AIR 4 -- one or the other
-  const uint64_t ver = I[1] & 0xFF, flags = I[1] >> 8;
-  if (I[0] != IR_MAGIC || (ver != 1 && ver != 2) || flags > 127) return fail(BP_ERR_INVALID_INPUT, "IR: bad magic/version");
-  if ((flags & 8) && (flags & 64)) return fail(BP_ERR_INVALID_INPUT, "IR: the arithmetic table is proven by ONE AIR (flags 0x800 and 0x4000 are both set)");
-  const bool dummy = ver == 2;
-  // table index -> the AIR its flag selects (bit t' of flags; WITNESS_AIR lists them by table)
-  static const uint32_t FLAG_OF_TABLE[BP_NUM_TABLES] = {8, 16, 0, 1, 32, 2, 4};
-  if (wit) {
-    for (int t = 0; t < BP_NUM_TABLES; t++) {
-      if (!wit->in[t]) continue;
-      if (!(flags & (FLAG_OF_TABLE[t] | (t == 0 ? 64u : 0u))))
-        return fail(BP_ERR_INVALID_INPUT, "witness data for table %s needs an IR whose %s table is proven with its AIR (bp_ir_set_*_air)",
-                    TABLE_NAMES[t], TABLE_NAMES[t]);
-      if (I[11 + t] < 40 && wit->n[t] > witness_capacity(t, (uint64_t)1 << I[11 + t]))
-        return fail(BP_ERR_RANGE, "%zu witness items do not fit table %s of 2^%llu rows%s", wit->n[t], TABLE_NAMES[t],
-                    (unsigned long long)I[11 + t], t == 3 ? " (24 rows per Keccak permutation)" : "");
-    }
-  }
-  if (I[5] < I[4]) return fail(BP_ERR_INVALID_INPUT, "IR: gas_used_after < gas_used_before");
-  if (dummy && I[5] != I[4]) return fail(BP_ERR_INVALID_INPUT, "IR: a dummy entry must not use gas (decoding.rs:503-506)");
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    const uint64_t ln = I[11 + t], wd = I[18 + t];
-    if (ln < cfg.table_log_lo[t] || ln >= cfg.table_log_hi[t])
-      return fail(BP_ERR_RANGE, "table %s needs 2^%llu rows, outside the configured range %u..%u", TABLE_NAMES[t],
-                  (unsigned long long)ln, cfg.table_log_lo[t], cfg.table_log_hi[t]);
-    if (wd > 65536) return fail(BP_ERR_INVALID_INPUT, "table %s: width out of range", TABLE_NAMES[t]);
-    tcfg[t] = table_cfg_of(cfg, (uint32_t)ln, (uint32_t)wd);
-    if (flags & FLAG_OF_TABLE[t]) tcfg[t].air_id = WITNESS_AIR[t];  // check_cfg insists on the AIR's own width
-    if (t == 0 && (flags & 64)) tcfg[t].air_id = air::ARITHMETIC_MUL;
-    int r = check_cfg(tcfg[t]);
-    if (r) return r;
-  }
-  for (int i = 0; i < 4; i++) if (I[6 + i] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "IR: non-canonical state root");
-  // PublicValues
-  std::vector<uint64_t>& pv = *pv_out;
-  pv.assign(BP_PV_WORDS, 0);
-  pv[0] = I[3]; pv[1] = I[3] + (dummy ? 0 : 1); pv[2] = I[4]; pv[3] = I[5];
-  std::memcpy(&pv[4], I + 6, 32);
-  if (dummy) std::memcpy(&pv[8], I + 6, 32);
-  else root_after(I + 6, I[10], I[3], &pv[8]);
-  pv[12] = I[2];
-  for (auto& v : pv) v = gl::canon(v);
-  return BP_OK;
-}
-
-// The cross-table lookups of a transaction's table proofs (air::ctl::pairs): for both challenge sets the first-row
-// value of the looking running product equals that of the looked one.  Only pairs whose two tables are proven with
-// their AIRs exist (a synthetic table has nothing to look up).  Shared by the prover (which refuses to go on with
-// tables that do not form one statement: upstream's root circuit checks this in-circuit) and bp_verify_txn_table_proofs.
-static int check_lookups(const StarkCfg tcfg[BP_NUM_TABLES], const std::vector<uint64_t> proof[BP_NUM_TABLES]) {
-  const air::ctl::Pair* P = air::ctl::pairs();
-  for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
-    const air::ctl::Pair& p = P[i];
-    if (tcfg[p.looking_table].air_id != p.looking_air || tcfg[p.looked_table].air_id != p.looked_air) continue;
-    const ProofLayout La = proof_layout(tcfg[p.looking_table]), Lb = proof_layout(tcfg[p.looked_table]);
-    for (uint32_t c = 0; c < 2; c++) {
-      // the first-row values of the looking side's product columns, multiplied together, against the looked side's
-      gl::Ext a = gl::ext(1);
-      for (uint32_t m = 0; m < p.n_looking; m++) {
-        const uint64_t* v = proof[p.looking_table].data() + La.open_first + 2 * (p.looking_col + p.stride * m + c);
-        a = gl::mul(a, gl::Ext{v[0], v[1]});
-      }
-      const uint64_t* b = proof[p.looked_table].data() + Lb.open_first + 2 * (p.looked_col + c);
-      if (a.c0 != b[0] || a.c1 != b[1])
-        return fail(BP_ERR_VERIFY, "cross-table lookup %s does not hold (challenge set %u): the %s table asks for tuples the %s table "
-                    "does not expose", p.name, c, TABLE_NAMES[p.looking_table], TABLE_NAMES[p.looked_table]);
-    }
-  }
-  return BP_OK;
-}
-
-// whether table t is made from the caller's data (its AIR flag set and data given)
-static bool given_table(const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES], int t) {
-  return wit && wit->in[t] && (tcfg[t].air_id == WITNESS_AIR[t] || (t == 0 && tcfg[t].air_id == air::ARITHMETIC_MUL));
-}
-// generate_traces: the seven witnesses of a transaction in the worker's arena (d_trace[t]: n_cols x 2^log_n, column-major),
-// with the refusals of data that cannot form one statement.  Shared by the prover and the witness pre-flight.
+// generate_traces: the seven witnesses of a transaction in the worker's arena (d_trace[t]: n_cols x 2^log_n, column-major).
+// What is to be made, and the refusals of data that cannot form one statement, are plan_traces' (txn_tables.cpp); here
+// are the allocations, the staging and the launches.  Shared by the prover and the witness pre-flight.
 static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES],
                         uint64_t* d_trace[BP_NUM_TABLES]) {
   int r;
-  auto given = [&](int t) { return given_table(wit, tcfg, t); };
-  // Two seeded tables that a lookup ties together are ONE statement: the seeded sponge table asks for no more
-  // permutations than the Keccak-f table holds in full, and the seeded Keccak-f table's first permutations are the
-  // ones the sponge rows ask for (air::ctl, keccak_sponge -> keccak_f).  Tables given by the caller are taken as they are.
-  const bool lookup_kf = tcfg[3].air_id == air::KECCAK_F && tcfg[4].air_id == air::KECCAK_SPONGE;
-  // keccak_sponge -> logic: the XOR of every absorbed block with the rate is five operations of the logic table, whose
-  // first rows are then derived from the sponge table's trace (five per covered sponge row; the caller's or seeded
-  // operations follow them); the seeded sponge table absorbs no more blocks than the logic table can hold
-  const bool lookup_sl = tcfg[4].air_id == air::KECCAK_SPONGE && tcfg[5].air_id == air::LOGIC;
-  const uint32_t logic_covered = lookup_sl ? (uint32_t)std::min<uint64_t>((uint64_t)1 << tcfg[4].log_n, ((uint64_t)1 << tcfg[5].log_n) / 5) : 0;
-  const uint32_t sponge_row_limit = std::min<uint32_t>(lookup_kf ? (uint32_t)(((uint64_t)1 << tcfg[3].log_n) / 24) : ~0u,
-                                                       lookup_sl ? logic_covered : ~0u);
-  // byte_packing -> memory: the memory table that is not given by the caller is the log of the byte-packing table's
-  // words (two operations per packing row); it must be tall enough to hold them
-  const bool lookup_bm = tcfg[1].air_id == air::BYTE_PACKING && tcfg[6].air_id == air::MEMORY;
-  if (lookup_bm && given(1) && !given(6))
-    return fail(BP_ERR_INVALID_INPUT, "byte-packing sequences are given but the memory log is not: the memory table is looked up by them "
-                "(byte_packing -> memory) and cannot be drawn from the seed");
-  // the mirror cases: a LOOKED table given by the caller while its looking table is drawn from the seed cannot be one
-  // statement with it either (the seeded sponge rows ask for permutations of their own; the seeded packing rows move
-  // words of their own) -- refused here, before seven table proofs are made and check_lookups blames the tables
-  if (lookup_kf && given(3) && !given(4))
-    return fail(BP_ERR_INVALID_INPUT, "Keccak-f permutations are given but the sponge rows are not: with both tables proven by their "
-                "AIRs the sponge table looks the permutations up (keccak_sponge -> keccak_f); give the sponge rows too "
-                "(bp_txn_witness.sponge_rows, bp_keccak256_sponge_rows) or clear the sponge table's AIR flag");
-  if (lookup_bm && given(6) && !given(1))
-    return fail(BP_ERR_INVALID_INPUT, "the memory log is given but the byte-packing sequences are not: the seeded byte-packing table "
-                "looks up operations of its own (byte_packing -> memory); give the sequences too or clear one of the two AIR flags");
-  if (lookup_bm && !given(6) && tcfg[6].log_n < tcfg[1].log_n + 1)
-    return fail(BP_ERR_INVALID_INPUT, "the memory table (2^%u rows) cannot hold the operations of the byte-packing table (2^%u rows): "
-                "two per row", tcfg[6].log_n, tcfg[1].log_n);
-  static const int GEN_ORDER[BP_NUM_TABLES] = {4, 0, 1, 2, 3, 5, 6};  // a looking table before the table it looks up (sponge before Keccak-f, byte packing before memory)
+  bool given[BP_NUM_TABLES];
+  size_t n_given[BP_NUM_TABLES];
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    given[t] = given_table(wit, tcfg, t);
+    n_given[t] = given[t] ? wit->n[t] : 0;
+  }
+  TracePlan plan;
+  if ((r = plan_traces(tcfg, given, n_given, &plan))) return r;
+  const bool lookup_kf = plan.lookup[L_SPONGE_KECCAK], lookup_bm = plan.lookup[L_PACKING_MEMORY], lookup_sl = plan.lookup[L_SPONGE_LOGIC];
+  // a looking table before the table it looks up (sponge before Keccak-f, byte packing before memory)
+  static const int GEN_ORDER[BP_NUM_TABLES] = {T_KECCAK_SPONGE, T_ARITHMETIC, T_BYTE_PACKING, T_CPU, T_KECCAK, T_LOGIC, T_MEMORY};
   for (int t = 0; t < BP_NUM_TABLES; t++) {
     const uint64_t N = (uint64_t)1 << tcfg[t].log_n;
     d_trace[t] = w.arena.alloc_words((size_t)tcfg[t].n_cols * N);
-    if (!d_trace[t]) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLE_NAMES[t]);
+    if (!d_trace[t]) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLES[t].name);
   }
+  const uint64_t* d_sponge = d_trace[T_KECCAK_SPONGE];
+  const uint32_t sponge_log_n = tcfg[T_KECCAK_SPONGE].log_n;
+  const uint64_t sponge_N = (uint64_t)1 << sponge_log_n;
   for (int gi = 0; gi < BP_NUM_TABLES; gi++) {
     const int t = GEN_ORDER[gi];
     const uint64_t N = (uint64_t)1 << tcfg[t].log_n, seed = I[10] ^ splitmix64(t + 1);
+    const size_t wds = TABLES[t].item_words, cap = witness_capacity(t, N);
     const size_t mark = w.arena.mark();
     uint64_t* d_in = nullptr;
-    if (t == 5 && lookup_sl) {
+    if (t == T_LOGIC && lookup_sl) {
       // [five operations per covered sponge row][the caller's operations, or seeded ones]
-      const size_t n_given = given(5) ? wit->n[5] : 0;
-      if (n_given > N - 5ull * logic_covered)
-        return fail(BP_ERR_INVALID_INPUT, "the logic table (2^%u rows) holds the sponge table's %u XORs first: room for %llu operations, %zu given",
-                    tcfg[5].log_n, 5 * logic_covered, (unsigned long long)(N - 5ull * logic_covered), n_given);
-      d_in = w.arena.alloc_words((size_t)N * 9 + n_given * 9);
+      const size_t n_ops = n_given[t], covered = (size_t)air::ctl::SPONGE_LOGIC_OPS * plan.logic_covered;
+      d_in = w.arena.alloc_words((size_t)N * wds + n_ops * wds);
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the logic table's operations");
       uint64_t* d_given = nullptr;
-      if (n_given) {
-        if (n_given * 9 > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "too many logic operations for the input staging buffer");
-        std::memcpy(w.pinned, wit->in[5], n_given * 9 * 8);
-        d_given = d_in + (size_t)N * 9;
-        BPG_HIP(hipMemcpyAsync(d_given, w.pinned, n_given * 9 * 8, hipMemcpyHostToDevice, w.stream));
+      if (n_ops) {
+        if (n_ops * wds > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "too many logic operations for the input staging buffer");
+        std::memcpy(w.pinned, wit->in[t], n_ops * wds * 8);
+        d_given = d_in + (size_t)N * wds;
+        BPG_HIP(hipMemcpyAsync(d_given, w.pinned, n_ops * wds * 8, hipMemcpyHostToDevice, w.stream));
       }
-      if ((r = launch_logic_inputs_from_sponge(d_trace[4], tcfg[4].log_n, logic_covered, given(5) ? d_given : nullptr, (uint32_t)n_given,
+      if ((r = launch_logic_inputs_from_sponge(d_sponge, sponge_log_n, plan.logic_covered, given[t] ? d_given : nullptr, (uint32_t)n_ops,
                                                d_in, (uint32_t)N, seed, w.stream))) return r;
-      if (given(5) && !d_given) {  // an empty list was given: padding operations, not seeded ones
-        BPG_HIP(hipMemsetAsync(d_in + (size_t)5 * logic_covered * 9, 0, ((size_t)N - 5 * logic_covered) * 9 * 8, w.stream));
+      if (given[t] && !d_given) {  // an empty list was given: padding operations, not seeded ones
+        BPG_HIP(hipMemsetAsync(d_in + covered * wds, 0, ((size_t)N - covered) * wds * 8, w.stream));
       }
-    } else if (given(t)) {
+    } else if (given[t]) {
       // the caller's items, then padding up to the table's height, staged through the pinned buffer
-      const size_t words = witness_capacity(t, N) * WITNESS_WORDS[t];
+      const size_t words = cap * wds;
       d_in = w.arena.alloc_words(words);
-      if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the witness data of table %s", TABLE_NAMES[t]);
-      if (words > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "table %s too tall for the input staging buffer", TABLE_NAMES[t]);
+      if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the witness data of table %s", TABLES[t].name);
+      if (words > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "table %s too tall for the input staging buffer", TABLES[t].name);
       fill_table_inputs(t, N, wit->in[t], wit->n[t], w.pinned);
       BPG_HIP(hipMemcpyAsync(d_in, w.pinned, words * 8, hipMemcpyHostToDevice, w.stream));
-    } else if (t == 3 && lookup_kf) {
-      const uint32_t n_perms = (uint32_t)witness_capacity(3, N);
-      d_in = w.arena.alloc_words((size_t)n_perms * 25);
+    } else if (t == T_KECCAK && lookup_kf) {
+      d_in = w.arena.alloc_words(cap * wds);
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the Keccak-f table's inputs");
-      if ((r = launch_keccak_inputs_from_sponge(d_trace[4], tcfg[4].log_n, d_in, n_perms, seed, w.stream))) return r;
-    } else if (t == 6 && lookup_bm) {
-      d_in = w.arena.alloc_words((size_t)N * 11);
+      if ((r = launch_keccak_inputs_from_sponge(d_sponge, sponge_log_n, d_in, (uint32_t)cap, seed, w.stream))) return r;
+    } else if (t == T_MEMORY && lookup_bm) {
+      d_in = w.arena.alloc_words((size_t)N * wds);
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the memory table's log");
-      if ((r = launch_memory_inputs_from_byte_packing(d_trace[1], tcfg[1].log_n, d_in, (uint32_t)N, w.stream))) return r;
+      if ((r = launch_memory_inputs_from_byte_packing(d_trace[T_BYTE_PACKING], tcfg[T_BYTE_PACKING].log_n, d_in, (uint32_t)N, w.stream))) return r;
     }
     r = tcfg[t].air_id == air::SYNTHETIC
             ? launch_synth_trace(d_trace[t], nullptr, tcfg[t].log_n, tcfg[t].n_cols, 0, 1, seed, w.stream)
-            : launch_air_trace(tcfg[t].air_id, d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream, sponge_row_limit);
+            : launch_air_trace(tcfg[t].air_id, d_trace[t], d_in, tcfg[t].log_n, d_in ? 0 : seed, w.stream, plan.sponge_row_limit);
     if (r) return r;
     // the filter column of a looked table (air::ctl) is part of its TRACE: written here, committed with the trace, i.e.
     // before the lookup challenges are drawn.  The looking table's trace is there already (GEN_ORDER).
-    if (t == 3 && lookup_kf) {  // the permutations the sponge table asks for: its flag columns, row p <-> permutation p
-      const uint64_t N4 = (uint64_t)1 << tcfg[4].log_n;
-      r = launch_lookup_filter(air::KECCAK_F, d_trace[3], tcfg[3].log_n, d_trace[4] + (size_t)air::keccak_sponge::COL_FULL * N4,
-                               d_trace[4] + (size_t)air::keccak_sponge::COL_FINAL * N4, (uint32_t)N4, w.stream);
-    } else if (t == 6 && lookup_bm) {  // the operations the byte-packing table looks up: its trace (address, timestamp per row)
-      r = launch_lookup_filter(air::MEMORY, d_trace[6], tcfg[6].log_n, d_trace[1], nullptr, (uint32_t)1 << tcfg[1].log_n, w.stream);
-    } else if (t == 5 && lookup_sl) {  // the XORs the sponge table asks for: rows 5 p + m of the rows p that absorb a block
-      const uint64_t N4 = (uint64_t)1 << tcfg[4].log_n;
-      r = launch_lookup_filter(air::LOGIC, d_trace[5], tcfg[5].log_n, d_trace[4] + (size_t)air::keccak_sponge::COL_FULL * N4,
-                               d_trace[4] + (size_t)air::keccak_sponge::COL_FINAL * N4, logic_covered, w.stream);
+    if (t == T_KECCAK && lookup_kf) {  // the permutations the sponge table asks for: its flag columns, row p <-> permutation p
+      r = launch_lookup_filter(air::KECCAK_F, d_trace[t], tcfg[t].log_n, d_sponge + (size_t)air::keccak_sponge::COL_FULL * sponge_N,
+                               d_sponge + (size_t)air::keccak_sponge::COL_FINAL * sponge_N, (uint32_t)sponge_N, w.stream);
+    } else if (t == T_MEMORY && lookup_bm) {  // the operations the byte-packing table looks up: its trace (address, timestamp per row)
+      r = launch_lookup_filter(air::MEMORY, d_trace[t], tcfg[t].log_n, d_trace[T_BYTE_PACKING], nullptr, (uint32_t)1 << tcfg[T_BYTE_PACKING].log_n, w.stream);
+    } else if (t == T_LOGIC && lookup_sl) {  // the XORs the sponge table asks for: rows 5 p + m of the rows p that absorb a block
+      r = launch_lookup_filter(air::LOGIC, d_trace[t], tcfg[t].log_n, d_sponge + (size_t)air::keccak_sponge::COL_FULL * sponge_N,
+                               d_sponge + (size_t)air::keccak_sponge::COL_FINAL * sponge_N, plan.logic_covered, w.stream);
     }
     if (r) return r;
     if (d_in) {  // the staging buffer and the input words are reused by the next table
@@ -999,7 +765,7 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
   for (int i = 0; i < 4; i++) ctl.v[i] = ch.challenge();
   // table proofs: sequential, one transcript threaded through all of them (plonky2_evm prover)
   for (int t = 0; t < BP_NUM_TABLES; t++) {
-    if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before table %s", TABLE_NAMES[t]);
+    if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before table %s", TABLES[t].name);
     const size_t mark = w.arena.mark();
     Challenger before = ch;  // the transcript as the verifier of this table proof starts from it
     if ((r = stark_prove(w, tcfg[t], nullptr, trace[t], d_trace[t], ctl, ch, tp->proof[t], tp->first_leaf[t]))) return r;
@@ -1009,7 +775,7 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
       // proof just made -- a log that is not a memory, a block that is not padded, ... ends the call.
       if (stark_verify(tcfg[t], nullptr, ctl, before, tp->proof[t].data(), tp->proof[t].size()) != BP_OK) {
         const std::string why = bp_last_error();
-        return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: %s", TABLE_NAMES[t], why.c_str());
+        return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: %s", TABLES[t].name, why.c_str());
       }
     }
     w.arena.release(mark);
@@ -1151,36 +917,16 @@ BPG_ABI_CATCH("bp_generate_txn_proof_u8")
 int bp_generate_txn_proof_keccak(const bp_state* s, const uint8_t* ir, size_t ir_len, const uint64_t* keccak_inputs,
                                  size_t n_perms, const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len) try {
   if (!keccak_inputs && n_perms) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof_keccak: null inputs");
-  static const uint64_t none = 0;
   TxnWitness wit;
-  wit.in[3] = keccak_inputs ? keccak_inputs : &none;
-  wit.n[3] = n_perms;
+  wit.give(T_KECCAK, keccak_inputs, n_perms);
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_keccak")
-// bp_txn_witness (include/bpg.h) -> the per-table form
-static int witness_of(const bp_txn_witness* data, TxnWitness* wit) {
-  static const uint64_t none = 0;
-  const struct { int t; const uint64_t* p; size_t n; int given; } f[6] = {
-      {4, data->sponge_rows, data->n_sponge_rows, data->has_keccak_sponge},
-      {3, data->keccak_inputs, data->n_perms, data->has_keccak}, {5, data->logic_ops, data->n_logic_ops, data->has_logic},
-      {6, data->memory_log, data->n_memory_ops, data->has_memory}, {0, data->arithmetic_ops, data->n_arithmetic_ops, data->has_arithmetic},
-      {1, data->byte_sequences, data->n_byte_sequences, data->has_byte_packing}};
-  for (const auto& x : f) {
-    if (!x.given) continue;
-    if (!x.p && x.n) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof_witness: null data for table %s", TABLE_NAMES[x.t]);
-    wit->in[x.t] = x.p ? x.p : &none;
-    wit->n[x.t] = x.n;
-  }
-  return BP_OK;
-}
 // The general form: witness data for any of the tables that have an AIR (bp_txn_witness, include/bpg.h).
 int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
                                   const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len) try {
-  if (!data) return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len);
   TxnWitness wit;
-  int r = witness_of(data, &wit);
-  if (r) return r;
+  if (int r = witness_of(data, &wit)) return r;
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_witness")
@@ -1257,7 +1003,7 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     if (status == BP_OK && o.given && o.n_violated_rows) {
       char buf[256];
       std::snprintf(buf, sizeof(buf), "the witness data given for table %s does not satisfy its AIR: row %u violates constraint %u "
-                    "(family %u), %llu rows in all", TABLE_NAMES[t], o.viol[0].row, o.viol[0].constraint, o.viol[0].family,
+                    "(family %u), %llu rows in all", TABLES[t].name, o.viol[0].row, o.viol[0].constraint, o.viol[0].family,
                     (unsigned long long)o.n_violated_rows);
       status = BP_ERR_VERIFY;
       why = buf;
@@ -1271,7 +1017,7 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     const air::ctl::Pair& p = P[i];
     bp_witness_lookup& o = out->lookup[i];
     o.first_looking_row = o.first_looked_row = -1;
-    if (tcfg[p.looking_table].air_id != p.looking_air || tcfg[p.looked_table].air_id != p.looked_air) continue;
+    if (!pair_active(tcfg, p)) continue;
     o.checked = 1;
     uint64_t beta, gamma;
     do beta = g() % gl::P; while (beta < 2);
@@ -1286,8 +1032,8 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     if (status == BP_OK && !o.holds) {
       char buf[256];
       std::snprintf(buf, sizeof(buf), "cross-table lookup %s does not hold: first unmatched looking row %lld (table %s), looked row "
-                    "%lld (table %s)", p.name, (long long)o.first_looking_row, TABLE_NAMES[p.looking_table], (long long)o.first_looked_row,
-                    TABLE_NAMES[p.looked_table]);
+                    "%lld (table %s)", p.name, (long long)o.first_looking_row, TABLES[p.looking_table].name, (long long)o.first_looked_row,
+                    TABLES[p.looked_table].name);
       status = BP_ERR_VERIFY;
       why = buf;
     }
@@ -1295,20 +1041,16 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   return status == BP_OK ? BP_OK : fail(status, "%s", why.c_str());
 }
 int bp_check_txn_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data, bp_witness_report* out) try {
-  if (!data) return check_txn_impl(s, ir, ir_len, nullptr, out);
   TxnWitness wit;
-  int r = witness_of(data, &wit);
-  if (r) return r;
+  if (int r = witness_of(data, &wit)) return r;
   return check_txn_impl(s, ir, ir_len, &wit, out);
 }
 BPG_ABI_CATCH("bp_check_txn_witness")
 int bp_check_txn_witness_keccak(const bp_state* s, const uint8_t* ir, size_t ir_len, const uint64_t* keccak_inputs, size_t n_perms,
                                 bp_witness_report* out) try {
   if (!keccak_inputs && n_perms) return fail(BP_ERR_INVALID_INPUT, "bp_check_txn_witness_keccak: null inputs");
-  static const uint64_t none = 0;
   TxnWitness wit;
-  wit.in[3] = keccak_inputs ? keccak_inputs : &none;
-  wit.n[3] = n_perms;
+  wit.give(T_KECCAK, keccak_inputs, n_perms);
   return check_txn_impl(s, ir, ir_len, &wit, out);
 }
 BPG_ABI_CATCH("bp_check_txn_witness_keccak")
@@ -1317,89 +1059,11 @@ BPG_ABI_CATCH("bp_check_txn_witness_keccak")
 // transcript, with the public values and the lookup challenges.  data as for bp_generate_txn_proof_witness (nullable).
 int bp_generate_txn_table_proofs(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
                                  const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len) try {
-  if (!data) return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, nullptr, true);
   TxnWitness wit;
-  int r = witness_of(data, &wit);
-  if (r) return r;
+  if (int r = witness_of(data, &wit)) return r;
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit, true);
 }
 BPG_ABI_CATCH("bp_generate_txn_table_proofs")
-
-// verify_proof(all_stark, all_proof, config) of upstream, on the CPU: every table proof against the shared transcript
-// (trace caps and public values observed, four lookup challenges drawn, then table after table), and the cross-table
-// lookups between the tables that are proven with their AIRs (air::ctl).  cfg supplies the STARK parameters only.
-// expect (nullable): the statement the caller wants proven -- per table the AIR, height and width, and the public values --
-// as parse_ir derives it from the transaction's IR.  Without it the header of the blob is the PROVER's claim.
-static int verify_table_proofs(const bp_config* cfg, const StarkCfg* expect, const uint64_t* expect_pv, const uint8_t* bytes, size_t len) {
-  if (!cfg || !bytes) return fail(BP_ERR_INVALID_INPUT, "bp_verify_txn_table_proofs: null argument");
-  if (len % 8 || len < (2 + BP_PV_WORDS + 4) * 8) return fail(BP_ERR_INVALID_INPUT, "table proofs: truncated");
-  const uint64_t* W = reinterpret_cast<const uint64_t*>(bytes);
-  const size_t n_words = len / 8;
-  if (W[0] != TABLES_MAGIC || W[1] != BP_NUM_TABLES) return fail(BP_ERR_INVALID_INPUT, "table proofs: bad magic");
-  const uint64_t* pv = W + 2;
-  const uint64_t* ctl_in = pv + BP_PV_WORDS;
-  for (size_t i = 0; i < BP_PV_WORDS + 4; i++) if (pv[i] >= gl::P) return fail(BP_ERR_VERIFY, "non-canonical public value or challenge");
-  StarkCfg tcfg[BP_NUM_TABLES];
-  std::vector<uint64_t> proof[BP_NUM_TABLES];
-  size_t off = 2 + BP_PV_WORDS + 4;
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    if (off + 4 > n_words) return fail(BP_ERR_INVALID_INPUT, "table proofs: truncated at table %s", TABLE_NAMES[t]);
-    const uint64_t air_id = W[off], log_n = W[off + 1], n_cols = W[off + 2], pw = W[off + 3];
-    off += 4;
-    if (air_id >= air::COUNT || log_n > 30 || n_cols > 65536) return fail(BP_ERR_INVALID_INPUT, "table proofs: bad header of table %s", TABLE_NAMES[t]);
-    if (air_id != air::SYNTHETIC && air_id != WITNESS_AIR[t] && !(t == 0 && air_id == air::ARITHMETIC_MUL))
-      return fail(BP_ERR_VERIFY, "table %s is proven with AIR %llu, which is not that table's", TABLE_NAMES[t], (unsigned long long)air_id);
-    tcfg[t] = table_cfg_of(*cfg, (uint32_t)log_n, (uint32_t)n_cols);
-    tcfg[t].air_id = (uint32_t)air_id;
-    if (expect && (expect[t].air_id != air_id || expect[t].log_n != log_n || expect[t].n_cols != n_cols))
-      return fail(BP_ERR_VERIFY, "table %s is proven as AIR %llu, 2^%llu rows x %llu columns; the transaction's statement is AIR %u, 2^%u x %u "
-                  "(a relabelled table would drop its constraints and its lookups)", TABLE_NAMES[t], (unsigned long long)air_id,
-                  (unsigned long long)log_n, (unsigned long long)n_cols, expect[t].air_id, expect[t].log_n, expect[t].n_cols);
-    int r = check_cfg(tcfg[t]);
-    if (r) return r;
-    if (pw != proof_layout(tcfg[t]).total || off + pw > n_words) return fail(BP_ERR_INVALID_INPUT, "table proofs: wrong length of table %s", TABLE_NAMES[t]);
-    proof[t].assign(W + off, W + off + pw);
-    off += pw;
-  }
-  if (off != n_words) return fail(BP_ERR_INVALID_INPUT, "table proofs: trailing words");
-  if (expect_pv && std::memcmp(pv, expect_pv, BP_PV_WORDS * 8) != 0)
-    return fail(BP_ERR_VERIFY, "the public values of the table proofs are not those of the transaction's IR");
-  Challenger ch;
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    const ProofLayout L = proof_layout(tcfg[t]);
-    ch.observe(proof[t].data() + L.trace_cap, L.cap_words);
-  }
-  ch.observe(pv, BP_PV_WORDS);
-  Ctl ctl;
-  for (int i = 0; i < 4; i++) {
-    ctl.v[i] = ch.challenge();
-    if (ctl.v[i] != ctl_in[i]) return fail(BP_ERR_VERIFY, "the lookup challenges do not follow from the trace commitments");
-  }
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    int r = stark_verify(tcfg[t], nullptr, ctl, ch, proof[t].data(), proof[t].size());
-    if (r) {
-      const std::string why = bp_last_error();
-      return fail(r, "table %s: %s", TABLE_NAMES[t], why.c_str());
-    }
-  }
-  return check_lookups(tcfg, proof);
-}
-int bp_verify_txn_table_proofs(const bp_config* cfg, const uint8_t* bytes, size_t len) try {
-  return verify_table_proofs(cfg, nullptr, nullptr, bytes, len);
-}
-BPG_ABI_CATCH("bp_verify_txn_table_proofs")
-// verify_proof(all_stark, ...) where the VERIFIER fixes the statement, as upstream's does: which AIR proves each table,
-// the table shapes and the public values come from the transaction's IR, not from the blob.
-int bp_verify_txn_table_proofs_for(const bp_config* cfg, const uint8_t* ir, size_t ir_len, const uint8_t* bytes, size_t len) try {
-  if (!cfg || !ir) return fail(BP_ERR_INVALID_INPUT, "bp_verify_txn_table_proofs_for: null argument");
-  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
-  StarkCfg expect[BP_NUM_TABLES];
-  std::vector<uint64_t> pv;
-  int r = parse_ir(*cfg, reinterpret_cast<const uint64_t*>(ir), nullptr, expect, &pv);
-  if (r) return r;
-  return verify_table_proofs(cfg, expect, pv.data(), bytes, len);
-}
-BPG_ABI_CATCH("bp_verify_txn_table_proofs_for")
 
 // The host half of an aggregation: the children parsed, checked for contiguity and verified (or recognised as this
 // state's own), the public-input list and the two path witnesses of the aggregation circuit.  No device work.
@@ -1595,7 +1259,6 @@ uint32_t rec_batch_cap(const bp_state* s) { return s ? batch_cap(s->rec_cfg) : 1
 int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
                      const volatile uint8_t* abort_flag, RecPool* pool, uint32_t node) {
   if (!pool) return fail(BP_ERR_INVALID_INPUT, "txn_proof_pooled: no pool");
-  if (!data) return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, nullptr, false, pool, node);
   TxnWitness wit;
   if (int r = witness_of(data, &wit)) return r;
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, &wit, false, pool, node);

@@ -174,7 +174,7 @@ int observe_set(Challenger& ch, const bp_set_table* tables, uint32_t n_tables, c
   return BP_OK;
 }
 // Every link on the first-row openings: for both challenge sets the product of the looking ports' values is the looked
-// port's (check_lookups' identity, proofgen.cpp, with a looking count).
+// port's (check_lookups' identity, txn_tables.cpp, with a looking count).
 int check_links(const SetShape& sh, const bp_set_link* links, uint32_t n_links, const std::vector<uint64_t>* proof) {
   for (uint32_t k = 0; k < n_links; k++) {
     const bp_set_link& l = links[k];

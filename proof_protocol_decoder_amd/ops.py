@@ -120,6 +120,8 @@ ARITHMETIC_COLS = 309
 BYTE_PACKING_COLS = 299
 KECCAK_SPONGE_COLS = 2414
 ARITHMETIC_MUL_COLS = 1217
+AIR_COLS = {1: KECCAK_COLS, 2: LOGIC_COLS, 3: MEMORY_COLS, 4: ARITHMETIC_COLS, 5: BYTE_PACKING_COLS, 6: KECCAK_SPONGE_COLS,
+            7: ARITHMETIC_MUL_COLS}   # by AIR id
 
 
 def air_describe(air_id, n_cols=0, n_const=0, deg_pow=1):

@@ -21,6 +21,22 @@ IR_WORDS, PV_WORDS = 25, 13
 
 ProofGenError = BpgError  # Result<T, ProofGenError(String)> -> exception carrying the message
 
+# The AIRs that can prove a table of a transaction instead of the synthetic one (csrc/txn_tables.hpp holds the same rows;
+# include/bpg.h lists them above bp_ir_set_*_air): TxnProofGenIR field, table index, AIR id, setter, the bp_txn_witness
+# members that carry the table's witness items, u64 words per item.  In the order to_bytes sets the flags.
+TXN_TABLE_AIRS = (
+    ("keccak_air", 3, 1, "bp_ir_set_keccak_air", ("keccak_inputs", "n_perms", "has_keccak"), 25),
+    ("logic_air", 5, 2, "bp_ir_set_logic_air", ("logic_ops", "n_logic_ops", "has_logic"), 9),
+    ("memory_air", 6, 3, "bp_ir_set_memory_air", ("memory_log", "n_memory_ops", "has_memory"), 11),
+    ("arithmetic_air", 0, 4, "bp_ir_set_arithmetic_air", ("arithmetic_ops", "n_arithmetic_ops", "has_arithmetic"), 9),
+    ("byte_packing_air", 1, 5, "bp_ir_set_byte_packing_air", ("byte_sequences", "n_byte_sequences", "has_byte_packing"), 6),
+    ("keccak_sponge_air", 4, 6, "bp_ir_set_keccak_sponge_air", ("sponge_rows", "n_sponge_rows", "has_keccak_sponge"), 44),
+    ("arithmetic_mul_air", 0, 7, "bp_ir_set_arithmetic_mul_air", ("arithmetic_ops", "n_arithmetic_ops", "has_arithmetic"), 9),
+)
+# table index -> (pointer, count, has_* member of bp_txn_witness, words per item)
+WITNESS_FIELDS = {t: (*members, words) for _, t, _, _, members, words in TXN_TABLE_AIRS}
+KECCAK_LANES, SPONGE_ROW_WORDS = WITNESS_FIELDS[3][3], WITNESS_FIELDS[4][3]
+
 
 class BpConfig(C.Structure):
     """bp_config (include/bpg.h)."""
@@ -62,13 +78,8 @@ def _bind():
                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.bp_ir_encode_dummy.argtypes = [C.c_uint64] * 3 + [C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32),
                                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.bp_ir_set_keccak_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_logic_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_memory_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_arithmetic_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_arithmetic_mul_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_byte_packing_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_ir_set_keccak_sponge_air.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+    for row in TXN_TABLE_AIRS:
+        getattr(L, row[3]).argtypes = [C.POINTER(C.c_uint64), C.c_int]
     L.bp_keccak256_sponge_rows.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
                                            C.POINTER(C.c_size_t)]
     L.bp_keccak256_permutation_inputs.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
@@ -128,15 +139,15 @@ class TxnProofGenIR:
     table_log_n: tuple
     table_width: tuple
     dummy: bool = False   # a padding entry (decoding.rs:484-520): proven, but txn number / gas / state root stay
-    keccak_air: bool = False   # the Keccak table (index 3) is a real Keccak-f[1600] trace (AIR 1, 2431 columns)
+    keccak_air: bool = False   # the Keccak table is a real Keccak-f[1600] trace (this and the flags below: TXN_TABLE_AIRS)
     keccak_inputs: tuple = None   # ... attesting THESE permutations ([n][25] lanes) instead of seeded ones; not part of
                                   # the 25-word IR: handed to bp_generate_txn_proof_keccak beside it
-    logic_air: bool = False    # the logic table (index 5) is proven with the logic AIR (AIR 2, 524 columns)
-    memory_air: bool = False   # the memory table (index 6) with the memory AIR (AIR 3, 45 columns)
-    arithmetic_air: bool = False   # the arithmetic table (index 0) with the arithmetic AIR (AIR 4, 309 columns)
-    byte_packing_air: bool = False   # the byte-packing table (index 1) with the byte-packing AIR (AIR 5, 299 columns)
-    keccak_sponge_air: bool = False  # the Keccak sponge table (index 4) with the Keccak sponge AIR (AIR 6, 2414 columns)
-    arithmetic_mul_air: bool = False   # the arithmetic table (index 0) with the multiplication AIR instead (AIR 7, 1217 columns)
+    logic_air: bool = False    # the logic table is proven with the logic AIR
+    memory_air: bool = False   # the memory table with the memory AIR
+    arithmetic_air: bool = False   # the arithmetic table with the arithmetic AIR
+    byte_packing_air: bool = False   # the byte-packing table with the byte-packing AIR
+    keccak_sponge_air: bool = False  # the Keccak sponge table with the Keccak sponge AIR
+    arithmetic_mul_air: bool = False   # the arithmetic table with the multiplication AIR instead (one or the other)
     witness: tuple = None   # ((table index, ((words of an item), ...)), ...): data for tables with an AIR instead of a
                             # seeded witness (bp_generate_txn_proof_witness); like keccak_inputs not part of the 25-word IR
 
@@ -153,20 +164,9 @@ class TxnProofGenIR:
         else:
             check(L.bp_ir_encode(self.block_number, self.txn_number_before, self.gas_used_before, self.gas_used_after,
                                  root, self.seed, logs, widths, out))
-        if self.keccak_air:
-            check(L.bp_ir_set_keccak_air(out, 1))
-        if self.logic_air:
-            check(L.bp_ir_set_logic_air(out, 1))
-        if self.memory_air:
-            check(L.bp_ir_set_memory_air(out, 1))
-        if self.arithmetic_air:
-            check(L.bp_ir_set_arithmetic_air(out, 1))
-        if self.byte_packing_air:
-            check(L.bp_ir_set_byte_packing_air(out, 1))
-        if self.keccak_sponge_air:
-            check(L.bp_ir_set_keccak_sponge_air(out, 1))
-        if self.arithmetic_mul_air:
-            check(L.bp_ir_set_arithmetic_mul_air(out, 1))
+        for field, _, _, setter, _, _ in TXN_TABLE_AIRS:
+            if getattr(self, field):
+                check(getattr(L, setter)(out, 1))
         return struct.pack("<%dQ" % IR_WORDS, *out)
 
 
@@ -288,24 +288,16 @@ def keccak256_permutation_inputs(data: bytes):
     L = _bind()
     n = C.c_size_t()
     check(L.bp_keccak256_permutation_inputs(data, len(data), None, None, 0, C.byref(n)))
-    states, digest = (C.c_uint64 * (25 * n.value))(), C.create_string_buffer(32)
+    k = KECCAK_LANES
+    states, digest = (C.c_uint64 * (k * n.value))(), C.create_string_buffer(32)
     check(L.bp_keccak256_permutation_inputs(data, len(data), digest, states, n.value, C.byref(n)))
-    return digest.raw, [list(states[25 * i:25 * i + 25]) for i in range(n.value)]
+    return digest.raw, [list(states[k * i:k * i + k]) for i in range(n.value)]
 
 
 class TxnWitness(C.Structure):
-    """bp_txn_witness (include/bpg.h)"""
-    _fields_ = [(n, t) for name in ("keccak_inputs:n_perms:has_keccak", "logic_ops:n_logic_ops:has_logic",
-                                    "memory_log:n_memory_ops:has_memory", "arithmetic_ops:n_arithmetic_ops:has_arithmetic",
-                                    "byte_sequences:n_byte_sequences:has_byte_packing",
-                                    "sponge_rows:n_sponge_rows:has_keccak_sponge")
-                for n, t in zip(name.split(":"), (C.c_void_p, C.c_size_t, C.c_int))]
-
-
-WITNESS_FIELDS = {3: ("keccak_inputs", "n_perms", "has_keccak", 25), 5: ("logic_ops", "n_logic_ops", "has_logic", 9),
-                  6: ("memory_log", "n_memory_ops", "has_memory", 11), 0: ("arithmetic_ops", "n_arithmetic_ops", "has_arithmetic", 9),
-                  1: ("byte_sequences", "n_byte_sequences", "has_byte_packing", 6),
-                  4: ("sponge_rows", "n_sponge_rows", "has_keccak_sponge", 44)}
+    """bp_txn_witness (include/bpg.h): its members in the header's order"""
+    _fields_ = [(n, t) for table in (3, 5, 6, 0, 1, 4)
+                for n, t in zip(WITNESS_FIELDS[table], (C.c_void_p, C.c_size_t, C.c_int))]
 
 
 def keccak256_sponge_rows(data: bytes):
@@ -314,9 +306,10 @@ def keccak256_sponge_rows(data: bytes):
     L = _bind()
     n = C.c_size_t()
     check(L.bp_keccak256_sponge_rows(data, len(data), None, None, 0, C.byref(n)))
-    rows, digest = (C.c_uint64 * (44 * n.value))(), C.create_string_buffer(32)
+    k = SPONGE_ROW_WORDS
+    rows, digest = (C.c_uint64 * (k * n.value))(), C.create_string_buffer(32)
     check(L.bp_keccak256_sponge_rows(data, len(data), digest, rows, n.value, C.byref(n)))
-    return digest.raw, [list(rows[44 * i:44 * i + 44]) for i in range(n.value)]
+    return digest.raw, [list(rows[k * i:k * i + k]) for i in range(n.value)]
 
 
 def generate_txn_proof(p_state, gen_inputs, abort_signal=None, keccak_inputs=None, witness=None):
@@ -324,40 +317,26 @@ def generate_txn_proof(p_state, gen_inputs, abort_signal=None, keccak_inputs=Non
     ctypes.c_uint8 / c_bool (one byte, what AtomicBool is: bp_generate_txn_proof_u8) or a ctypes.c_int32.
     keccak_inputs: the permutation inputs ([n][25] lanes) of the transaction's Keccak table, for an IR with
     keccak_air=True (bp_generate_txn_proof_keccak); default: gen_inputs.keccak_inputs if it has any.
-    witness: {table index: [[words of an item], ...]} for the tables proven with an AIR (0 arithmetic [9], 1 byte packing
-    [6], 3 Keccak [25], 4 Keccak sponge [44], 5 logic [9], 6 memory [11]; bp_generate_txn_proof_witness); default:
-    gen_inputs.witness."""
+    witness: {table index: [[words of an item], ...]} for the tables proven with an AIR (TXN_TABLE_AIRS has the words of
+    an item; bp_generate_txn_proof_witness); default: gen_inputs.witness."""
     L = _bind()
     ir = gen_inputs.to_bytes() if isinstance(gen_inputs, TxnProofGenIR) else bytes(gen_inputs)
     out, n = _out()
     flag = C.byref(abort_signal) if abort_signal is not None else None
     if keccak_inputs is None:
         keccak_inputs = getattr(gen_inputs, "keccak_inputs", None)
-    if witness is None and getattr(gen_inputs, "witness", None) is not None:
-        witness = dict(gen_inputs.witness)
-    if witness is not None:
-        if keccak_inputs is not None and 3 not in witness:
-            witness = {**witness, 3: keccak_inputs}
+    if witness is not None or getattr(gen_inputs, "witness", None) is not None:
         if abort_signal is not None and C.sizeof(abort_signal) != 1:
             raise ValueError("bp_generate_txn_proof_witness takes the one-byte abort flag")
-        w, keep = TxnWitness(), []
-        for t, items in witness.items():
-            ptr_f, n_f, has_f, words = WITNESS_FIELDS[t]
-            flat = [int(x) for it in items for x in it]
-            if len(flat) % words:
-                raise ValueError("witness items of table %d have %d words each" % (t, words))
-            a = (C.c_uint64 * max(len(flat), 1))(*flat)
-            keep.append(a)
-            setattr(w, ptr_f, C.cast(a, C.c_void_p))
-            setattr(w, n_f, len(flat) // words)
-            setattr(w, has_f, 1)
+        w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
         check(L.bp_generate_txn_proof_witness(p_state._h, ir, len(ir), C.byref(w), flag, C.byref(out), C.byref(n)))
+        del keep
     elif keccak_inputs is not None:
         flat = [int(x) for st in keccak_inputs for x in st]
         arr = (C.c_uint64 * max(len(flat), 1))(*flat)
         if abort_signal is not None and C.sizeof(abort_signal) != 1:
             raise ValueError("bp_generate_txn_proof_keccak takes the one-byte abort flag")
-        check(L.bp_generate_txn_proof_keccak(p_state._h, ir, len(ir), arr, len(flat) // 25, flag, C.byref(out), C.byref(n)))
+        check(L.bp_generate_txn_proof_keccak(p_state._h, ir, len(ir), arr, len(flat) // KECCAK_LANES, flag, C.byref(out), C.byref(n)))
     elif abort_signal is not None and C.sizeof(abort_signal) == 1:
         L.bp_generate_txn_proof_u8.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p,
                                                C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
@@ -451,7 +430,7 @@ def check_txn_witness(p_state, gen_inputs, keccak_inputs=None, witness=None):
         flat = [int(x) for st in keccak_inputs for x in st]
         arr = (C.c_uint64 * max(len(flat), 1))(*flat)
         L.bp_check_txn_witness_keccak.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = L.bp_check_txn_witness_keccak(p_state._h, ir, len(ir), arr, len(flat) // 25, C.byref(rep))
+        rc = L.bp_check_txn_witness_keccak(p_state._h, ir, len(ir), arr, len(flat) // KECCAK_LANES, C.byref(rep))
     else:
         w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
         L.bp_check_txn_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -358,7 +358,37 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
  *               emit in a port unit; n_ports > 8; n_tuple outside 1 .. 128.  Each with the word offset, as above.
  * The trace checker is unchanged: it checks the AIR's own constraints only, ports dropped, as for the built-in tables.
  * bp_stark_prove_trace on a program with ports proves it alone: its ports are linked to nothing, their constraints are
- * checked; bp_quotient_eval (d_aux_lde: 2 n_ports columns) and bp_stark_verify_air(_pub) take the id as any other. */
+ * checked; bp_quotient_eval (d_aux_lde: 2 n_ports columns) and bp_stark_verify_air(_pub) take the id as any other.
+ *
+ * Log ports and range checks: the format "BPGAIRP3" (0x3350524941475042).  "BPGAIRP1" and "BPGAIRP2" stay valid and
+ * untouched: bytes, ids, digests, proofs.  "BPGAIRP3" is "BPGAIRP2" word for word except the port-table word of port l,
+ * which is  n_tuple | kind << 32  (any other bit set is refused):
+ *   kind 0      a product port, exactly the one above
+ *   kind 1      a LOG port whose filter is a bit
+ *   kind 2      a LOG port whose filter is a MULTIPLICITY: any field value (the looked side of a range table, which
+ *               answers many looking rows with one row; or a looking side that sends a tuple several times)
+ * Sizes, limits and the port-unit rules are unchanged, and the id is taken from the bytes as before, so the kinds are part
+ * of the digest a table set's transcript observes.  What the library derives from a log port l, with
+ * d_c = gamma_c + v_c:
+ *   auxiliary columns: the same two, at 2l and 2l + 1: s_(l,c)[i] = sum_(i' >= i) f[i'] / d_c[i'] (backwards, like
+ *               every running column here; no helper column; n_aux = 2 n_ports whatever the kinds)
+ *   constraints: the same five slots at n_constraints + 5l: slot 0, all rows, f f - f for kind 1 and identically zero
+ *               for kind 2; then for c = 0, 1: transition (s_c - s_c') d_c - f, last row s_c d_c - f.
+ *               bp_air_describe reports them as for product ports, with the degrees max(1, 2 deg f) for slot 0 (1 for
+ *               kind 2's zero slot) and max(1 + deg t, deg f) for the transition and the last-row slots.
+ *   refused:    kind 3 or a stray bit in the port word; max(1 + max_j deg t_j, deg f) > degree; the same quantity above
+ *               the first-row / last-row bound (s d - f is a last-row constraint: a degree-3 program takes linear tuples
+ *               only); for kind 1 also 2 deg f > degree.  Each with the word offset, as above.
+ * What a link of log ports MEANS (bp_stark_prove_table_set): for every tuple value, the sum of f over the looking rows
+ * that carry it equals the sum of f over the looked rows that carry it.  That every sent tuple is IN the looked table
+ * follows only when the looking filters are bits -- a filter of 1 on one row and p - 1 on another sends a tuple the table
+ * does not hold and still balances -- which is why kind 1 exists and why the library, not the program's author, adds
+ * f f - f.  A range check of k-bit limbs: the limb columns go out through kind-1 ports with tuple (limb), the table
+ * exposes a constant column 0 .. 2^k - 1 through a kind-2 port whose filter is a trace column of multiplicities
+ * (bp_range_multiplicities makes it); the link may stay inside one table.
+ * A pole: a row where d_c = 0 contributes 0 when f = 0 there; where f != 0 the sum has no value, and the prover (or
+ * bp_air_port_products) fails with BP_ERR_VERIFY naming the port, the challenge set and the smallest such row.  With
+ * challenges drawn from a transcript that is a 2^-64-ish event per row. */
 int bp_air_register(const uint64_t* program, size_t n_words, uint32_t* air_id_out);
 int bp_air_unregister(uint32_t air_id);
 int bp_air_program_digest(uint32_t air_id, uint8_t out[32]); /* Keccak-256 of the registered bytes */
@@ -386,9 +416,26 @@ int bp_quotient_eval(uint32_t air_id, const struct bp_stark_cfg* shape, const ui
 /* The running products of a registered program's ports on the trace domain, without a proof around them: what the prover
  * commits as the table's auxiliary columns.  air_id: a registered program with ports (anything else: BP_ERR_INVALID_INPUT).
  * shape, d_trace, stride, d_consts, pub: as bp_air_check_trace's.  ctl = beta0, gamma0, beta1, gamma1.
- * d_aux_out: 2 n_ports columns x 2^log_n words, column stride 2^log_n: port l's z_0 at column 2l, z_1 at 2l + 1. */
+ * d_aux_out: 2 n_ports columns x 2^log_n words, column stride 2^log_n: port l's z_0 at column 2l, z_1 at 2l + 1; for a
+ * log port ("BPGAIRP3") the running sums s_0, s_1 in the same places.  A pole of a log port: BP_ERR_VERIFY (above); the
+ * call waits for the stream when the program has a log port. */
 int bp_air_port_products(uint32_t air_id, const struct bp_stark_cfg* shape, const uint64_t* d_trace, uint64_t stride,
                          const uint64_t* d_consts, const uint64_t pub[4], const uint64_t ctl[4], uint64_t* d_aux_out, void* stream);
+
+/* Multiplicities for a range-check lookup: over n_cols column-major columns (column c at d_values + c * stride, n_rows
+ * words each) counts how often every value of [0, 2^log_range) occurs on the rows the filter keeps, and ADDS the counts
+ * to d_mult (2^log_range words: zero them for a fresh count, or call several times to count several groups of columns).
+ * d_filter: n_rows words of 0 / 1, one per row for all columns, or NULL = every row.  log_range: 1 .. 24.
+ * A value >= 2^log_range on a kept row: BP_ERR_RANGE, and *first_bad (a host word) is the smallest col * n_rows + row
+ * that holds one (the in-range values have been counted); otherwise *first_bad = UINT64_MAX.  Values on rows the filter
+ * drops are not looked at.  Counts are integer adds: the result does not depend on any order.  The call waits for the
+ * stream.  Up to 2^13 values (bp_tune_range_lds_log) are counted in per-workgroup LDS histograms, more with global
+ * atomics; a wave adds its most common value once. */
+int bp_range_multiplicities(const uint64_t* d_values, uint64_t stride, uint32_t n_cols, uint64_t n_rows, const uint64_t* d_filter,
+                            uint32_t log_range, uint64_t* d_mult, uint64_t* first_bad, void* stream);
+/* bp_range_multiplicities counts in LDS up to 2^log_range values: 1 .. 14 (default 13); anything else = the default.
+ * Results are identical.  (Not listed by bp_debug_tune_state; bp_tune_reset puts it back.) */
+void bp_tune_range_lds_log(int log_range);
 
 /* Test entry: the auxiliary columns (bp_air_desc.n_aux of them: helper columns, then the running products; column
  * stride 2^log_n) the prover commits for a BUILT-IN table with a lookup side (AIR 1, 2, 3, 5, 6), from a trace of column
@@ -571,6 +618,11 @@ int bp_stark_verify_air_pub(uint32_t air_id, const bp_stark_cfg* cfg, const uint
  * side of a link a port is on: the identity is symmetric.  A link states, for both challenge sets,
  *   prod over its looking ports of z(first row) = z_looked(first row):
  * the multiset of tuples the looking ports send on their filtered rows is the multiset the looked port exposes.
+ * A link of LOG ports (a registered "BPGAIRP3" program's kinds 1 and 2) states the sum instead,
+ *   sum over its looking ports of s(first row) = s_looked(first row)
+ * (what that means: "Log ports and range checks" above).  A link's ports are all product ports or all log ports -- the
+ * ports of a built-in member are product ports -- else it is refused with BP_ERR_INVALID_INPUT naming the link and the
+ * port, before a device is touched.  Both ends of a link may be in the same table: a table that range-checks itself.
  * At most 8 tables and 16 links; every port of every member is in exactly one link (an unlinked port or a port named
  * twice is refused, before a device is touched).
  * Transcript: a fresh challenger observes the statement -- "BPGTSET1", n_tables, n_links; per table air_id, log_n,

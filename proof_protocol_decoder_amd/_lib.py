@@ -126,6 +126,9 @@ def lib():
                                        C.POINTER(C.c_size_t)]
     L.bp_debug_air_aux.argtypes = [u32, C.POINTER(StarkCfg), vp, C.POINTER(u64), vp, vp]
     L.bp_air_port_products.argtypes = [u32, C.POINTER(StarkCfg), vp, u64, vp, C.POINTER(u64), C.POINTER(u64), vp, vp]
+    L.bp_range_multiplicities.argtypes = [vp, u64, u32, u64, vp, u32, vp, C.POINTER(u64), vp]
+    L.bp_tune_range_lds_log.argtypes = [i]
+    L.bp_tune_range_lds_log.restype = None
     L.bp_stark_prove_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(SetLink), u32, u32, i,
                                            C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.bp_stark_verify_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(C.POINTER(u64)), C.POINTER(SetLink), u32,

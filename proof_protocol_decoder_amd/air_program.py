@@ -19,6 +19,15 @@ A lookup PORT makes the table a side of a cross-table lookup (AIRS.md section 3,
 The program only states the filter and the tuple; the two running products of the port and their five constraints are
 the library's (include/bpg.h).  A builder without a port assembles the "BPGAIRP1" bytes it always did.
 
+A LOG port's running columns are sums of fractions f / (gamma + v) instead of products, so its filter may be a
+multiplicity -- which is what a range check needs (AIRS.md section 3, "Log links and range checks"):
+
+    for k in range(8):
+        b.log_port(b.loc(8), [b.loc(k)])                    # the rows where loc(8) is 1 send limb k; the library adds f f - f
+    b.log_port(b.loc(9), [b.cst(0)], multiplicity=True)     # constant column 0 .. 2^k - 1, loc(9) = how often each is asked for
+    words = b.assemble()                                    # a builder with a log port assembles "BPGAIRP3"
+    cols = b.port_running_columns(trace, ctl, consts)       # every port's two running columns over Python integers
+
 Expressions are built from loc(c), nxt(c), cst(c), pub(j), x and integers with + - *; equal subexpressions are one node
 (hash-consing), so a value used twice in a unit is computed once.  assemble() schedules every unit's emits in order,
 allocates registers by last use (a leaf -- a load or a constant -- is re-issued for each emit instead of being kept, which
@@ -30,6 +39,8 @@ import numpy as np
 P = 2 ** 64 - 2 ** 32 + 1
 MAGIC = int.from_bytes(b"BPGAIRP1", "little")
 MAGIC2 = int.from_bytes(b"BPGAIRP2", "little")
+MAGIC3 = int.from_bytes(b"BPGAIRP3", "little")
+PORT_PRODUCT, PORT_LOG_BIT, PORT_LOG_MULT = 0, 1, 2   # a port's kind: "BPGAIRP3" carries it in the port word, << 32
 OP_PORT = 10
 MAX_PORTS, MAX_TUPLE, MAX_FAMILIES_WITH_PORTS = 8, 128, 21
 ALL_ROWS, TRANSITION, FIRST_ROW, LAST_ROW = 0, 1, 2, 3
@@ -80,6 +91,7 @@ class Builder:
         self.families = []   # (first_index, count, kind, degree)
         self.units = []      # lists of (index, Expr)
         self.ports = []      # (filter Expr, [tuple Exprs])
+        self.port_kinds = []  # per port PORT_PRODUCT / PORT_LOG_BIT / PORT_LOG_MULT
         self._nodes = {}     # key -> Expr
         self._order = []     # every node, operands before users
 
@@ -182,11 +194,35 @@ class Builder:
         if len(self.ports) == MAX_PORTS:
             raise ValueError("a program has at most %d ports" % MAX_PORTS)
         self.ports.append((f, t))
+        self.port_kinds.append(PORT_PRODUCT)
         return len(self.ports) - 1
+
+    def log_port(self, filter_expr, tuple_exprs, multiplicity=False):
+        """A log port: the port's two running columns are sums of filter / (gamma + compressed tuple).  With
+        multiplicity=False the filter is a bit (the library adds f f - f): the rows where it is 1 send the tuple.  With
+        multiplicity=True the filter is any field value: the row exposes (or sends) its tuple that many times.  Returns
+        the port's index.  The degrees bp_air_register asks for -- max(1 + max deg t, deg f) <= degree and <=
+        boundary_degree(degree), and 2 deg f <= degree for a bit filter -- are checked by assemble()."""
+        l = self.port(filter_expr, tuple_exprs)
+        self.port_kinds[l] = PORT_LOG_MULT if multiplicity else PORT_LOG_BIT
+        return l
+
+    @staticmethod
+    def _port_degree(kind, df, dt):
+        """the degree a port's derived constraints need of the program"""
+        if kind == PORT_PRODUCT:
+            return max(2 * df, 1 + df + dt)
+        return max(1 + dt, df, 2 * df if kind == PORT_LOG_BIT else 0)
 
     def _check_ports(self, degree):
         for l, (f, t) in enumerate(self.ports):
             dt = max(e.degree for e in t)
+            kind = self.port_kinds[l]
+            if kind != PORT_PRODUCT:
+                if self._port_degree(kind, f.degree, dt) > degree or max(1 + dt, f.degree) > boundary_degree(degree):
+                    raise ValueError("log port %d: a filter of degree %d and a tuple of degree %d do not fit a program of degree %d"
+                                     % (l, f.degree, dt, degree))
+                continue
             if 2 * f.degree > degree or 1 + f.degree + dt > degree or f.degree + dt > boundary_degree(degree):
                 raise ValueError("port %d: a filter of degree %d and a tuple of degree %d do not fit a program of degree %d"
                                  % (l, f.degree, dt, degree))
@@ -231,6 +267,40 @@ class Builder:
         """Per port (f, [t_j]) mod p at one row, over Python integers."""
         val = self._values(row, next_row, consts, pub, x)
         return [(val[f.n], [val[e.n] for e in t]) for f, t in self.ports]
+
+    def port_running_columns(self, trace, ctl, consts=None, pub=(0, 0, 0, 0)):
+        """[2 * n_ports][n] Python integers: the two running columns of every port over the trace ([n_cols][n], and consts
+        [n_const][n]), as the prover's witness sees the rows (nxt wraps at the last row, x = w^i): port l's columns at 2l,
+        2l + 1, column c under the challenge set (beta, gamma) = ctl[2c], ctl[2c + 1].  A product port:
+        z[i] = prod_{i' >= i} (1 + f (gamma + v - 1)).  A log port: s[i] = sum_{i' >= i} f / (gamma + v), the inverse as
+        pow(d, P - 2, P); a row where gamma + v = 0 contributes 0 when f = 0 and raises ValueError (a pole) otherwise."""
+        n = len(trace[0])
+        log_n = n.bit_length() - 1
+        w = pow(7, (P - 1) >> log_n, P)
+        rows = [[int(col[i]) for col in trace] for i in range(n)]
+        crow = [[int(col[i]) for col in consts] for i in range(n)] if consts is not None else [()] * n
+        terms = [[0] * n for _ in range(2 * len(self.ports))]
+        x = 1
+        for i in range(n):
+            for l, (f, t) in enumerate(self.evaluate_ports(rows[i], rows[(i + 1) % n], crow[i], pub, x)):
+                for c in range(2):
+                    d = (ctl[2 * c + 1] + sum(pow(ctl[2 * c], j, P) * tj for j, tj in enumerate(t))) % P
+                    if self.port_kinds[l] == PORT_PRODUCT:
+                        terms[2 * l + c][i] = (1 + f * (d - 1)) % P
+                    elif d == 0 and f != 0:
+                        raise ValueError("a pole: port %d, challenge set %d, row %d" % (l, c, i))
+                    else:
+                        terms[2 * l + c][i] = f * pow(d, P - 2, P) % P
+            x = x * w % P
+        out = []
+        for k, col in enumerate(terms):
+            product = self.port_kinds[k // 2] == PORT_PRODUCT
+            run, acc = [0] * n, 1 if product else 0
+            for i in range(n - 1, -1, -1):
+                acc = acc * col[i] % P if product else (acc + col[i]) % P
+                run[i] = acc
+            out.append(run)
+        return out
 
     # ---- the words
     def _schedule(self, emits):
@@ -317,8 +387,9 @@ class Builder:
         return words, top
 
     def assemble(self, check_ports=True):
-        """The program as numpy uint64 words (bp_air_register's input): "BPGAIRP1", or "BPGAIRP2" when the builder has a
-        port.  check_ports=False leaves the ports' degree rules to bp_air_register (the tests of its refusals)."""
+        """The program as numpy uint64 words (bp_air_register's input): "BPGAIRP1"; "BPGAIRP2" when the builder has a
+        port; "BPGAIRP3" only when one of them is a log port, so programs that existed before keep their bytes.
+        check_ports=False leaves the ports' degree rules to bp_air_register (the tests of its refusals)."""
         if not self.families or not self.units:
             raise ValueError("a program has at least one family and one unit")
         code, offsets, n_regs = [], [0], 1
@@ -334,9 +405,11 @@ class Builder:
             n_regs = max(n_regs, top)
         if n_regs > MAX_REGS:
             raise ValueError("the program needs %d registers, the library takes %d: split the unit" % (n_regs, MAX_REGS))
-        # the declared degree, else what the families and the ports' derived constraints (f f - f, z - z' term) need
+        # the declared degree, else what the families and the ports' derived constraints (f f - f, z - z' term;
+        # (s - s') d - f) need
         degree = self.degree if self.degree is not None else max(
-            [f[3] for f in self.families] + [max(2 * f.degree, 1 + f.degree + max(e.degree for e in t)) for f, t in self.ports])
+            [f[3] for f in self.families] + [self._port_degree(kind, f.degree, max(e.degree for e in t))
+                                             for (f, t), kind in zip(self.ports, self.port_kinds)])
         for f in self.families:
             self._check_boundary(f[2], f[3], degree)
         hdr = [MAGIC, self.n_cols, self.n_const, self.n_public, degree, self.n_constraints, len(self.families), n_regs,
@@ -345,6 +418,6 @@ class Builder:
         if self.ports:
             if check_ports:
                 self._check_ports(degree)
-            hdr = [MAGIC2] + hdr[1:] + [len(self.ports)]
-            fam += [len(t) for _, t in self.ports]
+            hdr = [MAGIC3 if any(self.port_kinds) else MAGIC2] + hdr[1:] + [len(self.ports)]
+            fam += [len(t) | kind << 32 for (_, t), kind in zip(self.ports, self.port_kinds)]
         return np.array(hdr + fam + offsets + code, dtype=np.uint64)

@@ -36,10 +36,11 @@ int refuse(size_t off, const char* fmt, ...) {
 // Fills *p from the words or refuses them, naming the offending word.
 int validate(const uint64_t* w, size_t n_words, Program* p) {
   if (!w || n_words < HDR_WORDS) REFUSE(0, "a program has at least the %u header words, got %zu", HDR_WORDS, n_words);
-  if (w[0] != MAGIC && w[0] != MAGIC2) REFUSE(0, "bad magic (expected \"BPGAIRP1\" or \"BPGAIRP2\")");
-  const bool p2 = w[0] == MAGIC2;
+  if (w[0] != MAGIC && w[0] != MAGIC2 && w[0] != MAGIC3) REFUSE(0, "bad magic (expected \"BPGAIRP1\", \"BPGAIRP2\" or \"BPGAIRP3\")");
+  const bool p3 = w[0] == MAGIC3, p2 = w[0] == MAGIC2 || p3;  // "BPGAIRP3" is "BPGAIRP2" with a kind in the port words
   const size_t hdr_words = p2 ? HDR_WORDS2 : HDR_WORDS;
-  if (n_words < hdr_words) REFUSE(0, "a \"BPGAIRP2\" program has at least the %u header words, got %zu", HDR_WORDS2, n_words);
+  if (n_words < hdr_words)
+    REFUSE(0, "a \"BPGAIRP%c\" program has at least the %u header words, got %zu", p3 ? '3' : '2', HDR_WORDS2, n_words);
   struct Range { uint32_t* out; uint64_t lo, hi; const char* name; };
   const Range hdr[9] = {{&p->n_cols, MIN_COLS, MAX_COLS, "n_cols"}, {&p->n_const, 0, MAX_CONST, "n_const"},
                         {&p->n_public, 0, MAX_PUBLIC, "n_public"}, {&p->degree, 1, MAX_DEGREE, "degree"},
@@ -66,9 +67,19 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
   if (n_words != total) REFUSE(9, "the header's sizes make a program of %zu words, got %zu", total, n_words);
   p->off0 = off0;
   for (uint32_t l = 0; l < p->n_ports; l++) {
-    if (w[port0 + l] < 1 || w[port0 + l] > MAX_TUPLE)
-      REFUSE(port0 + l, "port %u: n_tuple = %llu is outside 1 .. %u", l, (unsigned long long)w[port0 + l], MAX_TUPLE);
-    p->n_tuple[l] = (uint32_t)w[port0 + l];
+    uint64_t n_tuple = w[port0 + l];
+    if (p3) {  // n_tuple | kind << 32
+      const uint64_t kind = (w[port0 + l] >> 32) & 3;
+      if (w[port0 + l] >> 34)
+        REFUSE(port0 + l, "port %u: the port word 0x%llx has bits set above n_tuple | kind << 32", l, (unsigned long long)w[port0 + l]);
+      if (kind >= PORT_KINDS) REFUSE(port0 + l, "port %u: kind %llu (0 product, 1 log with a bit filter, 2 log with a multiplicity)", l,
+                                     (unsigned long long)kind);
+      p->port_kind[l] = (uint32_t)kind;
+      n_tuple &= 0xffffffffu;
+    }
+    if (n_tuple < 1 || n_tuple > MAX_TUPLE)
+      REFUSE(port0 + l, "port %u: n_tuple = %llu is outside 1 .. %u", l, (unsigned long long)n_tuple, MAX_TUPLE);
+    p->n_tuple[l] = (uint32_t)n_tuple;
   }
   // the family table tiles [0, n_constraints)
   std::vector<uint8_t> fam_of(p->n_constraints);
@@ -182,6 +193,20 @@ int validate(const uint64_t* w, size_t n_words, Program* p) {
       const int deg_f = slot_deg[0];
       p->port_deg_f[port] = (uint32_t)deg_f;
       p->port_deg_t[port] = (uint32_t)deg_t;
+      if (p->port_kind[port] != PORT_PRODUCT) {
+        // a log port: (s - s') d - f on transitions, s d - f on the last row (d = gamma + v), f f - f for a bit filter
+        const int deg_s = 1 + deg_t > deg_f ? 1 + deg_t : deg_f;
+        if (deg_s > (int)p->degree)
+          REFUSE(off0 + u, "degree violation: log port %u has a filter of degree %d and a tuple of degree %d, (s - s') d - f must fit the "
+                 "program's degree %u", port, deg_f, deg_t, p->degree);
+        if (deg_s > (int)boundary_degree(p->degree))
+          REFUSE(off0 + u, "degree violation: log port %u has a filter of degree %d and a tuple of degree %d, the last-row constraint "
+                 "s d - f takes degree %u in a program of degree %u", port, deg_f, deg_t, boundary_degree(p->degree), p->degree);
+        if (p->port_kind[port] == PORT_LOG_BIT && 2 * deg_f > (int)p->degree)
+          REFUSE(off0 + u, "degree violation: log port %u has a bit filter of degree %d, f f - f must fit the program's degree %u", port,
+                 deg_f, p->degree);
+        continue;
+      }
       // f f - f on all rows, z - z' term on transitions, z - term on the last row (term = 1 + f (gamma + v - 1))
       if (2 * deg_f > (int)p->degree)
         REFUSE(off0 + u, "degree violation: port %u has a filter of degree %d, f f - f must fit the program's degree %u", port, deg_f, p->degree);

@@ -20,6 +20,12 @@
 // so the beta-power table is read like the code, with scalar loads.  K5 then hands the port's five constraints to the
 // same DevEmit (prog::port_constraints).  The witness of a port's two product columns is program_port_terms_kernel (the
 // terms, a lane per trace row) followed by aux_suffix_product_kernel in the form AIR 8 uses (stark_kernels.hip).
+//
+// Log ports ("BPGAIRP3").  The kinds travel in the image behind the port offsets and are read like them, with scalar
+// loads: which of the two constraint forms a port unit ends in is a wave-uniform branch.  The kernels of a program with a
+// log port are instantiations of their own (LOG): a program without one runs the code it ran before log ports existed.
+// The witness of a log port is h_c = f / d_c in its two columns (one inversion per lane for both challenge sets) followed
+// by the suffix SUM of port_running_columns_kernel (stark_kernels.hip).
 #include <mutex>
 #include "air_check_dev.cuh"
 #include "air_program.hpp"
@@ -51,7 +57,8 @@ __device__ __forceinline__ LdsRegs lds_regs_of_lane() { return LdsRegs{lds_regs 
 // grid = (rows / 256, workgroup rows, proofs) as quotient_air_kernel's; dynamic LDS = n_regs * 2 KiB.
 // n_code: the program's code words; the port units' offsets (n_ports + 1 words) follow them in the image.
 // PORTS: the program has lookup ports; without them the kernel is the one it was before ports existed.
-template <bool PORTS>
+// LOG: one of them is a log port; the kinds (n_ports words) follow the port units' offsets in the image.
+template <bool PORTS, bool LOG = false>
 __global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg::QuotArgs> batch, const uint64_t* __restrict__ image,
                                                                uint32_t n_code) {
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
@@ -78,7 +85,11 @@ __global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg:
       const uint64_t* __restrict__ port_off = code + n_code;
       prog::PortAcc<uint64_t> acc{q.apow + 2 * (size_t)q.n_constraints + 48, 0, 0, 0};
       prog::run_port<uint64_t>(code, (uint32_t)port_off[l], (uint32_t)port_off[l + 1], regs, row, acc);
-      prog::port_constraints<uint64_t>(q.n_air_constraints + prog::PORT_CONSTRAINTS * l, l, q.ctl.v, acc, row, out);
+      const uint32_t base = q.n_air_constraints + prog::PORT_CONSTRAINTS * l;
+      uint32_t kind = prog::PORT_PRODUCT;
+      if constexpr (LOG) kind = (uint32_t)port_off[q.n_ports + 1 + l];
+      if (LOG && kind != prog::PORT_PRODUCT) prog::log_port_constraints<uint64_t>(base, l, kind, q.ctl.v, acc, row, out);
+      else prog::port_constraints<uint64_t>(base, l, q.ctl.v, acc, row, out);
     } else {
       // "a table no lookup is built for": the one constant running product AIR 4 and AIR 7 have
       const bpg::air::Shape cs{bpg::air::ARITHMETIC, q.n_cols, q.n_const, q.deg_pow};
@@ -134,16 +145,23 @@ __global__ void __launch_bounds__(256) beta_table_kernel(bpg::BatchOf<bpg::QuotA
 // x = w^i), runs the port units of its workgroup row and writes term_0, term_1 of each into the port's two auxiliary
 // columns, where aux_suffix_product_kernel multiplies them up.  The beta powers travel as a kernel argument (2 KiB,
 // read wave-uniformly).  grid = (ceil(n / 256), n_ports); dynamic LDS = n_regs * 2 KiB.
+// LOG (a program with a log port): a log port's columns get h_c = f / d_c, d_c = gamma_c + v_c, which the scan then sums.
+// Both inverses come from one inversion of d_0 d_1.  A zero denominator is taken as 1 before the product, so it spoils
+// neither the other challenge set's inverse nor anything else: with f = 0 the row contributes 0 either way, and with
+// f != 0 (a pole: the sum has no value) the row is reported through `pole` -- [n_ports][2] words, the smallest such row
+// per port and challenge set -- and the caller fails.
 struct PortTermsArgs {
   const uint64_t *trace, *consts;
   uint64_t* aux;  // [2 * n_ports][n]
   uint64_t stride;
-  uint32_t log_n, n_units, n_code;
+  uint32_t log_n, n_units, n_code, n_ports;
   uint64_t ctl[4], pub[4];
+  unsigned long long* pole;  // LOG only
 };
 struct BetaTab {
   uint64_t v[2 * prog::MAX_TUPLE];
 };
+template <bool LOG>
 __global__ void __launch_bounds__(256) program_port_terms_kernel(PortTermsArgs a, BetaTab bt, const uint64_t* __restrict__ image) {
   const uint64_t n = (uint64_t)1 << a.log_n;
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -155,6 +173,20 @@ __global__ void __launch_bounds__(256) program_port_terms_kernel(PortTermsArgs a
   const uint32_t l = blockIdx.y;
   prog::PortAcc<uint64_t> acc{bt.v, 0, 0, 0};
   prog::run_port<uint64_t>(code, (uint32_t)port_off[l], (uint32_t)port_off[l + 1], regs, row, acc);
+  if constexpr (LOG) {
+    if (port_off[a.n_ports + 1 + l] != prog::PORT_PRODUCT) {  // wave-uniform
+      const uint64_t d0 = acc.denom(0, a.ctl), d1 = acc.denom(1, a.ctl);
+      const uint64_t e0 = d0 ? d0 : 1, e1 = d1 ? d1 : 1;
+      const uint64_t fi = gl::mulc(acc.f, gl::inv(gl::mulc(e0, e1)));  // f / (d_0 d_1)
+      a.aux[(uint64_t)(2 * l) * n + pos] = d0 ? gl::mulc(fi, e1) : 0;
+      a.aux[(uint64_t)(2 * l + 1) * n + pos] = d1 ? gl::mulc(fi, e0) : 0;
+      if (acc.f != 0) {
+        if (d0 == 0) atomicMin(a.pole + 2 * l, (unsigned long long)pos);
+        if (d1 == 0) atomicMin(a.pole + 2 * l + 1, (unsigned long long)pos);
+      }
+      return;
+    }
+  }
   a.aux[(uint64_t)(2 * l) * n + pos] = acc.term(0, a.ctl);
   a.aux[(uint64_t)(2 * l + 1) * n + pos] = acc.term(1, a.ctl);
 }
@@ -172,8 +204,10 @@ int allow_large_lds() {
   const int bytes = (int)(prog::MAX_REGS * 256 * 8);
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quotient_program_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&air_check_program_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&program_port_terms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&program_port_terms_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  BPG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&program_port_terms_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   done.push_back(dev);
   return BP_OK;
 }
@@ -197,7 +231,8 @@ int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer&
   const uint64_t* d_image = nullptr;
   if (int rc = program_of(q.air_id, q.n_air_units, &p, &d_image)) return rc;
   if (q.n_ports != p->n_ports) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x: the launch was sized for another program", q.air_id);
-  if (q.n_ports) BPG_LAUNCH_TIMED(kt, quotient_program_kernel<true>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
+  if (p->log_ports()) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(quotient_program_kernel<true, true>), grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
+  else if (q.n_ports) BPG_LAUNCH_TIMED(kt, quotient_program_kernel<true>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
   else BPG_LAUNCH_TIMED(kt, quotient_program_kernel<false>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
   return BP_OK;
 }
@@ -210,18 +245,20 @@ int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t 
   return BP_OK;
 }
 
-int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st) {
+int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, uint64_t* d_pole, hipStream_t st) {
   std::shared_ptr<const prog::Program> p = prog::find(air_id);
   if (!p || !p->n_ports) return bpg::fail(BP_ERR_INVALID_INPUT, "air_id 0x%08x is no registered program with lookup ports", air_id);
   const uint64_t* d_image = nullptr;
   if (int rc = program_of(air_id, p->n_units, &p, &d_image)) return rc;
   if (p->n_const && !a.consts) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x reads %u constant columns: pass them", air_id, p->n_const);
-  PortTermsArgs pa{a.trace, a.consts, a.aux, trace_stride, log_n, p->n_units, p->n_code, {}, {}};
+  if (p->log_ports() && !d_pole) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x has log ports: the launch needs the pole words", air_id);
+  PortTermsArgs pa{a.trace, a.consts, a.aux, trace_stride, log_n, p->n_units, p->n_code, p->n_ports, {}, {}, reinterpret_cast<unsigned long long*>(d_pole)};
   for (int i = 0; i < 4; i++) { pa.ctl[i] = a.ctl.v[i]; pa.pub[i] = a.ctl.pub[i]; }
   BetaTab bt;
   prog::beta_powers(a.ctl.v, bt.v);
   const dim3 grid((unsigned)((((uint64_t)1 << log_n) + 255) / 256), p->n_ports);
-  program_port_terms_kernel<<<grid, 256, p->n_regs * 256 * 8, st>>>(pa, bt, d_image);
+  if (p->log_ports()) program_port_terms_kernel<true><<<grid, 256, p->n_regs * 256 * 8, st>>>(pa, bt, d_image);
+  else program_port_terms_kernel<false><<<grid, 256, p->n_regs * 256 * 8, st>>>(pa, bt, d_image);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

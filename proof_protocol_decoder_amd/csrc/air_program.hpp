@@ -47,6 +47,16 @@
 // and that a program with ports has at most 21 families of its own (bp_air_desc.families[24] holds them and the ports':
 // five per port where they fit, else three interleaved ones).  A "BPGAIRP2" program with no port keeps the one
 // constant product.
+//
+// "BPGAIRP3" is "BPGAIRP2" with a KIND per port: the port-table word of port l is n_tuple | kind << 32 (any other bit
+// refused).  Kind 0 is the product port above.  Kinds 1 and 2 are LOG ports: the running column is a sum of fractions,
+// s_c[i] = sum_{i' >= i} f[i'] / d_c[i'] with d_c = gamma_c + v_c, in the same two columns 2l, 2l + 1, and the same five
+// constraint slots at n_constraints + 5l: slot 0, all rows, f f - f for kind 1 (the filter is a bit) and identically
+// zero for kind 2 (the filter is a multiplicity: any field value); then for c = 0, 1 transition (s_c - s_c') d_c - f, last
+// row s_c d_c - f.  Registration checks max(1 + deg t, deg f) <= degree and <= boundary_degree(degree), and for kind 1
+// 2 deg f <= degree.  A link of log ports states, per tuple value, that the looking rows' filters sum to the looked
+// rows'; membership of every sent tuple follows only when the looking filters are bits, which is why kind 1 exists and
+// why f f - f is the library's.  Programs without a log port keep their "BPGAIRP1" / "BPGAIRP2" bytes, ids and proofs.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -61,6 +71,9 @@ namespace prog {
 
 constexpr uint64_t MAGIC = 0x3150524941475042ULL;  // "BPGAIRP1"
 constexpr uint64_t MAGIC2 = 0x3250524941475042ULL;  // "BPGAIRP2"
+constexpr uint64_t MAGIC3 = 0x3350524941475042ULL;  // "BPGAIRP3"
+// a port's kind ("BPGAIRP3"): a running product; a running sum whose filter is a bit; ... is a multiplicity
+constexpr uint32_t PORT_PRODUCT = 0, PORT_LOG_BIT = 1, PORT_LOG_MULT = 2, PORT_KINDS = 3;
 constexpr uint32_t HDR_WORDS = 10, HDR_WORDS2 = 11;
 constexpr uint32_t MAX_PORTS = 8, MAX_TUPLE = 128, PORT_CONSTRAINTS = 5, MAX_FAMILIES_WITH_PORTS = 21;
 // The limits of a program (include/bpg.h states them).  MAX_REGS: the device keeps the registers in LDS, [reg][lane] for
@@ -157,6 +170,8 @@ struct PortAcc {
     typedef Ops<T> F;
     return F::add(F::k(1), F::mul(f, F::sub(F::add(F::k(ctl[2 * c + 1]), c ? v1 : v0), F::k(1))));
   }
+  // d_c = gamma_c + v_c: the denominator of a log port's fraction
+  GL_HD T denom(uint32_t c, const uint64_t ctl[4]) const { return Ops<T>::add(Ops<T>::k(ctl[2 * c + 1]), c ? v1 : v0); }
 };
 inline void beta_powers(const uint64_t ctl[4], uint64_t out[2 * MAX_TUPLE]) {
   for (uint32_t c = 0; c < 2; c++) {
@@ -178,6 +193,21 @@ GL_HD void port_constraints(uint32_t base, uint32_t l, const uint64_t ctl[4], co
   }
 }
 
+// The five slots of LOG port l (kind 1 or 2): slot 0 is f f - f for a bit filter and identically zero -- nothing is
+// handed over -- for a multiplicity; s_c is the running sum in column 2l + c.
+template <class T, class Row, class Emit>
+GL_HD void log_port_constraints(uint32_t base, uint32_t l, uint32_t kind, const uint64_t ctl[4], const PortAcc<T>& acc, const Row& row,
+                                Emit& out) {
+  typedef Ops<T> F;
+  if (kind == PORT_LOG_BIT) out.all(base, F::sub(F::mul(acc.f, acc.f), acc.f));
+#pragma unroll 1
+  for (uint32_t c = 0; c < 2; c++) {
+    const T s = row.aux(2 * l + c), sn = row.aux_nxt(2 * l + c), d = acc.denom(c, ctl);
+    out.transition(base + 1 + 2 * c, F::sub(F::mul(F::sub(s, sn), d), acc.f));
+    out.last(base + 2 + 2 * c, F::sub(F::mul(s, d), acc.f));
+  }
+}
+
 template <class T>
 struct HostRegs {
   T r[MAX_REGS];
@@ -193,6 +223,7 @@ struct Program {
   uint32_t air_id = 0;
   uint32_t n_cols = 0, n_const = 0, n_public = 0, degree = 0, n_constraints = 0, n_families = 0, n_regs = 0, n_units = 0, n_code = 0;
   uint32_t n_ports = 0, n_tuple[MAX_PORTS] = {};  // "BPGAIRP2"
+  uint32_t port_kind[MAX_PORTS] = {};             // "BPGAIRP3": PORT_PRODUCT / PORT_LOG_BIT / PORT_LOG_MULT
   uint32_t port_deg_f[MAX_PORTS] = {}, port_deg_t[MAX_PORTS] = {};  // the propagated degrees of a port's filter and tuple
   size_t off0 = 0;                                // where the unit offsets start in `words`
   Family families[MAX_FAMILIES] = {};
@@ -211,12 +242,20 @@ struct Program {
   // a program without ports keeps the one constant running product AIR 4 and AIR 7 have
   uint32_t n_aux() const { return n_ports ? 2 * n_ports : 1; }
   uint32_t n_ctl_constraints() const { return n_ports ? PORT_CONSTRAINTS * n_ports : 2; }
+  // bit l: port l is a log port (its two columns are running sums)
+  uint32_t log_ports() const {
+    uint32_t m = 0;
+    for (uint32_t l = 0; l < n_ports; l++) m |= (uint32_t)(port_kind[l] != PORT_PRODUCT) << l;
+    return m;
+  }
   // The device image: the constraint units' offsets (n_units + 1), the code, then the port units' offsets
-  // (n_ports + 1) -- behind the code, so the kernels that know nothing of ports read the image they always read.
+  // (n_ports + 1) -- behind the code, so the kernels that know nothing of ports read the image they always read -- and
+  // behind those the ports' kinds (n_ports), which only the kernels of a program with a log port read.
   std::vector<uint64_t> image() const {
     std::vector<uint64_t> im(unit_off(), unit_off() + n_units + 1);
     im.insert(im.end(), code(), code() + n_code);
     im.insert(im.end(), unit_off() + n_units, unit_off() + n_units + n_ports + 1);
+    im.insert(im.end(), port_kind, port_kind + n_ports);
     return im;
   }
   // unit u over the host field policy

@@ -98,6 +98,8 @@ uint32_t set_ports_of(uint32_t air_id, uint32_t* first_product) {
 struct SetShape {
   StarkCfg cfg[SET_MAX_TABLES];
   uint32_t n_ports[SET_MAX_TABLES], first_product[SET_MAX_TABLES];
+  uint32_t log_ports[SET_MAX_TABLES];  // bit l: port l of the table is a log port (a registered "BPGAIRP3" program's)
+  bool log_link[SET_MAX_LINKS];        // the link's ports are log ports: its identity is a sum
 };
 // the statement of a set, refused or accepted without touching a device
 int check_set(const char* who, const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, SetShape* out) {
@@ -114,13 +116,14 @@ int check_set(const char* who, const bp_set_table* tables, uint32_t n_tables, co
       return fail(rc, "%s: table %u: %s", who, t, why.c_str());
     }
     out->n_ports[t] = set_ports_of(tables[t].air_id, &out->first_product[t]);
+    const auto program = air::prog::find(tables[t].air_id);
+    out->log_ports[t] = program ? program->log_ports() : 0;  // a built-in member's ports are product ports
     if (!out->n_ports[t])
       return fail(BP_ERR_INVALID_INPUT, "%s: table %u: air_id %u (0x%08x) has no lookup port: a member is a registered program with ports or "
                   "one of the built-in AIRs 1, 2, 3, 5, 6", who, t, tables[t].air_id, tables[t].air_id);
     if (tables[t].pub)
       for (int j = 0; j < 4; j++)
         if (tables[t].pub[j] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "%s: table %u: non-canonical public input", who, t);
-    const auto program = air::prog::find(tables[t].air_id);
     if (!tables[t].pub && (tables[t].air_id == air::PLONK || (program && program->n_public)))
       return fail(BP_ERR_INVALID_INPUT, "%s: table %u: the AIR reads public inputs: pass four words", who, t);
   }
@@ -135,6 +138,14 @@ int check_set(const char* who, const bp_set_table* tables, uint32_t n_tables, co
         return fail(BP_ERR_INVALID_INPUT, "%s: link %u names port %u of table %u, which has %u", who, k, e.port, e.table, out->n_ports[e.table]);
       if (used[e.table][e.port]++)
         return fail(BP_ERR_INVALID_INPUT, "%s: port %u of table %u is named twice (link %u): a port is in exactly one link", who, e.port, e.table, k);
+      // product ports multiply, log ports add: one link takes one kind.  (Both ends may be in the same table: a table
+      // that range-checks itself.)
+      const bool is_log = (out->log_ports[e.table] >> e.port) & 1;
+      if (m == 0) out->log_link[k] = is_log;
+      else if (is_log != out->log_link[k])
+        return fail(BP_ERR_INVALID_INPUT, "%s: link %u mixes product and log ports: port %u of table %u is a %s port, port %u of table %u a "
+                    "%s port", who, k, e.port, e.table, is_log ? "log" : "product", l.looking[0].port, l.looking[0].table,
+                    is_log ? "product" : "log");
     }
   }
   for (uint32_t t = 0; t < n_tables; t++)
@@ -174,7 +185,7 @@ int observe_set(Challenger& ch, const bp_set_table* tables, uint32_t n_tables, c
   return BP_OK;
 }
 // Every link on the first-row openings: for both challenge sets the product of the looking ports' values is the looked
-// port's (check_lookups' identity, txn_tables.cpp, with a looking count).
+// port's (check_lookups' identity, txn_tables.cpp, with a looking count); for a link of log ports, their sum.
 int check_links(const SetShape& sh, const bp_set_link* links, uint32_t n_links, const std::vector<uint64_t>* proof) {
   for (uint32_t k = 0; k < n_links; k++) {
     const bp_set_link& l = links[k];
@@ -184,8 +195,8 @@ int check_links(const SetShape& sh, const bp_set_link* links, uint32_t n_links, 
         const uint64_t* v = proof[e.table].data() + L.open_first + 2 * (size_t)(sh.first_product[e.table] + 2 * e.port + c);
         return gl::Ext{v[0], v[1]};
       };
-      gl::Ext a = gl::ext(1);
-      for (uint32_t m = 0; m < l.n_looking; m++) a = gl::mul(a, first_row(l.looking[m]));
+      gl::Ext a = gl::ext(sh.log_link[k] ? 0 : 1);
+      for (uint32_t m = 0; m < l.n_looking; m++) a = sh.log_link[k] ? gl::add(a, first_row(l.looking[m])) : gl::mul(a, first_row(l.looking[m]));
       const gl::Ext b = first_row(l.looked);
       if (a.c0 != b.c0 || a.c1 != b.c1)
         return fail(BP_ERR_VERIFY, "link %u does not hold (challenge set %u): port %u of table %u%s asks for tuples that port %u of table %u "
@@ -619,27 +630,43 @@ int bp_air_describe(uint32_t air_id, uint32_t n_cols, uint32_t n_const, uint32_t
       if (n < 24) out->families[n++] = bp_air_family{p->n_constraints, 1, 1, 3};
       if (n < 24) out->families[n++] = bp_air_family{p->n_constraints + 1, 1, 3, 2};
     }
-    // per port: the filter bit, then per challenge set the product's transition and last-row constraint, with the
-    // degrees registration propagated (air_program.hpp).  Where five families per port do not fit the description, three
-    // interleaved ones stand for all ports (period 5: the bits at b + 5l, the transitions at b + 5l + 1 and + 3, the
-    // last-row ones at b + 5l + 2 and + 4), with the largest degree among the ports.
+    // per port: the filter bit, then per challenge set the running column's transition and last-row constraint, with the
+    // degrees registration propagated (air_program.hpp): a product port's z - z' term and z - term, a log port's
+    // (s - s') d - f and s d - f, whose bit slot is identically zero when the filter is a multiplicity.  Where five
+    // families per port do not fit the description, three interleaved ones stand for all ports (period 5: the bits at
+    // b + 5l, the transitions at b + 5l + 1 and + 3, the last-row ones at b + 5l + 2 and + 4), with the largest degree
+    // among the ports.
+    auto port_degrees = [&](uint32_t l, uint32_t* bit, uint32_t* step, uint32_t* last) {
+      const uint32_t df = p->port_deg_f[l], dt = p->port_deg_t[l];
+      *bit = p->port_kind[l] == air::prog::PORT_LOG_MULT ? 1 : std::max(1u, 2 * df);
+      if (p->port_kind[l] != air::prog::PORT_PRODUCT) {
+        *step = *last = std::max(1 + dt, df);
+      } else {
+        *step = 1 + df + dt;
+        *last = std::max(1u, df + dt);
+      }
+    };
     if (n + air::prog::PORT_CONSTRAINTS * p->n_ports > 24) {
       uint32_t d0 = 1, d1 = 1, d2 = 1;
       for (uint32_t l = 0; l < p->n_ports; l++) {
-        d0 = std::max(d0, 2 * p->port_deg_f[l]);
-        d1 = std::max(d1, 1 + p->port_deg_f[l] + p->port_deg_t[l]);
-        d2 = std::max(d2, p->port_deg_f[l] + p->port_deg_t[l]);
+        uint32_t bit, step, last;
+        port_degrees(l, &bit, &step, &last);
+        d0 = std::max(d0, bit);
+        d1 = std::max(d1, step);
+        d2 = std::max(d2, last);
       }
       out->families[n++] = bp_air_family{p->n_constraints, p->n_ports, 0, d0};
       out->families[n++] = bp_air_family{p->n_constraints + 1, 2 * p->n_ports, 1, d1};
       out->families[n++] = bp_air_family{p->n_constraints + 2, 2 * p->n_ports, 3, d2};
     } else
     for (uint32_t l = 0; l < p->n_ports; l++) {
-      const uint32_t b = p->n_constraints + air::prog::PORT_CONSTRAINTS * l, df = p->port_deg_f[l], dt = p->port_deg_t[l];
-      out->families[n++] = bp_air_family{b, 1, 0, std::max(1u, 2 * df)};
+      const uint32_t b = p->n_constraints + air::prog::PORT_CONSTRAINTS * l;
+      uint32_t bit, step, last;
+      port_degrees(l, &bit, &step, &last);
+      out->families[n++] = bp_air_family{b, 1, 0, bit};
       for (uint32_t c = 0; c < 2; c++) {
-        out->families[n++] = bp_air_family{b + 1 + 2 * c, 1, 1, 1 + df + dt};
-        out->families[n++] = bp_air_family{b + 2 + 2 * c, 1, 3, std::max(1u, df + dt)};
+        out->families[n++] = bp_air_family{b + 1 + 2 * c, 1, 1, step};
+        out->families[n++] = bp_air_family{b + 2 + 2 * c, 1, 3, last};
       }
     }
     out->n_families = n;

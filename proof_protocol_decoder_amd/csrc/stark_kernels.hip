@@ -559,6 +559,64 @@ aux_suffix_product_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, uint
     done = gl::mulc(done, whole);
   }
 }
+// The running columns of a registered program that has a LOG port ("BPGAIRP3", air_program.hpp): aux_suffix_product_kernel
+// in its TERMS_IN_COLUMN form -- the same tiles, the same scan, still one launch for all of the table's columns -- with
+// the operation chosen per column, wave-uniformly: gl::mulc and 1 for a product port's terms, gl::addc and 0 for a log
+// port's fractions  s[i] = sum_{i' >= i} h[i'].  log_ports: bit l = port l (columns 2l, 2l + 1) is a log port.
+template <bool SUM>
+__device__ __forceinline__ void suffix_scan_in_column(uint64_t* __restrict__ z, uint32_t n, uint64_t* part) {
+  constexpr uint64_t neutral = SUM ? 0 : 1;
+  auto op = [](uint64_t a, uint64_t b) { return SUM ? gl::addc(a, b) : gl::mulc(a, b); };
+  const uint32_t T = blockDim.x, t = threadIdx.x;
+  const uint32_t per0 = n >= 8 * T ? 8 : (n >= T ? n / T : 1);
+  const uint32_t tile = n >= T ? per0 * T : n;
+  const uint32_t per = t * per0 < tile ? per0 : 0;       // 0: this lane has no elements
+  uint64_t done = neutral;                               // every tile after the current one
+  for (uint32_t base = n; base > 0;) {
+    base -= tile;
+    const uint32_t lo = base + t * per0;
+    uint64_t f[8], p = neutral;
+#pragma unroll
+    for (int j = 7; j >= 0; j--) {
+      if ((uint32_t)j < per) {
+        f[j] = z[lo + j];
+        p = op(p, f[j]);
+      }
+    }
+    part[t] = p;
+    __syncthreads();
+    for (uint32_t d = 1; d < T; d <<= 1) {  // inclusive suffix scan over the per-lane totals (Hillis-Steele)
+      const uint64_t v = part[t];
+      const uint64_t o = t + d < T ? part[t + d] : neutral;
+      __syncthreads();
+      part[t] = op(v, o);
+      __syncthreads();
+    }
+    uint64_t carry = op(t + 1 < T ? part[t + 1] : neutral, done);  // everything after my piece
+    const uint64_t whole = part[0];
+    __syncthreads();  // part is rewritten by the next tile
+#pragma unroll
+    for (int j = 7; j >= 0; j--) {
+      if ((uint32_t)j < per) {
+        carry = op(carry, f[j]);
+        f[j] = carry;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if ((uint32_t)j < per) z[lo + j] = f[j];
+    done = op(done, whole);
+  }
+}
+__global__ void __launch_bounds__(1024)
+port_running_columns_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, uint32_t log_ports) {
+  if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
+  __shared__ uint64_t part[1024];
+  const uint32_t n = 1u << log_n;
+  uint64_t* z = batch.a[blockIdx.z].aux + (uint64_t)blockIdx.x * n;
+  if ((log_ports >> (blockIdx.x >> 1)) & 1) suffix_scan_in_column<true>(z, n, part);
+  else suffix_scan_in_column<false>(z, n, part);
+}
 // The helper columns of the Keccak-f table's lookup (air::ctl): h_0 / h_1, the permutation's input compressed by beta_0 /
 // beta_1 and carried along its rows.  A lane owns a row; it reads the 50 input limbs of its permutation's first row.
 __global__ void __launch_bounds__(256)
@@ -1502,12 +1560,42 @@ int launch_plonk_trace(const PlonkTraceArgs* a, uint32_t batch, uint32_t log_n, 
 int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   const uint32_t n_aux = air::any_n_aux(air::Shape{air_id, 0, 0, 1});
-  for (uint32_t b = 0; b < batch; b++)
-    if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, st)) return rc;
+  const auto program = air::prog::find(air_id);
+  const uint32_t log_ports = program ? program->log_ports() : 0;
   const uint32_t threads = std::max(64u, std::min(1024u, 1u << log_n));
-  KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
-  BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ctl::TERMS_IN_COLUMN>, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, 0u);
-  BPG_LAUNCH_CHECK();
+  if (!log_ports) {
+    for (uint32_t b = 0; b < batch; b++)
+      if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, nullptr, st)) return rc;
+    KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
+    BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ctl::TERMS_IN_COLUMN>, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, 0u);
+    BPG_LAUNCH_CHECK();
+    return BP_OK;
+  }
+  // A program with a log port.  A fraction whose denominator gamma + v vanishes where the filter does not has no value:
+  // the terms kernel reports the smallest such row per port and challenge set, and the call waits for that word and
+  // fails -- the one wait a table with a log port adds to its proof.
+  struct PoleWords {
+    uint64_t* d = nullptr;
+    ~PoleWords() { (void)hipFree(d); }
+  } pole;
+  const size_t words = 2 * (size_t)air::prog::MAX_PORTS;
+  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&pole.d), batch * words * 8));
+  BPG_HIP(hipMemsetAsync(pole.d, 0xFF, batch * words * 8, st));
+  for (uint32_t b = 0; b < batch; b++)
+    if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, pole.d + b * words, st)) return rc;
+  {
+    KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
+    BPG_LAUNCH_TIMED(kt, port_running_columns_kernel, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, log_ports);
+    BPG_LAUNCH_CHECK();
+  }
+  uint64_t found[MAX_BATCH * 2 * air::prog::MAX_PORTS];
+  BPG_HIP(hipMemcpyAsync(found, pole.d, batch * words * 8, hipMemcpyDeviceToHost, st));
+  BPG_HIP(hipStreamSynchronize(st));
+  for (uint32_t b = 0; b < batch; b++)
+    for (uint32_t k = 0; k < n_aux; k++)
+      if (found[b * words + k] != ~0ULL)
+        return fail(BP_ERR_VERIFY, "AIR program 0x%08x: log port %u, challenge set %u, row %llu: gamma + v = 0 where the filter is not 0, "
+                    "so the port's running sum has no value (a pole)", air_id, k / 2, k % 2, (unsigned long long)found[b * words + k]);
   return BP_OK;
 }
 int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_cols, uint32_t log_n, hipStream_t st) {

@@ -220,7 +220,10 @@ int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer&
 int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t st);  // a port program's beta powers, behind apow's 48 coset words
 // air_program.hip: launch_aux's first half for a registered program with ports: term_0, term_1 of every port into the
 // port's two auxiliary columns (launch_aux then multiplies them up, aux_suffix_product_kernel<TERMS_IN_COLUMN>)
-int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st);
+// A program with a log port ("BPGAIRP3"): those ports' columns get f / d_c instead, which launch_aux then SUMS
+// (port_running_columns_kernel); d_pole: 2 * n_ports words the caller has set to all ones, the smallest row per port
+// and challenge set where d_c = 0 and f != 0 (nullptr for a program without a log port).
+int launch_port_terms(const AuxArgs& a, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, uint64_t* d_pole, hipStream_t st);
 // stark_kernels.hip: both halves, the running products of every port in a.aux ([2 * n_ports][n])
 int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t log_n, uint64_t trace_stride, hipStream_t st);
 int launch_quotient_chunks(const ChunkArgs* c, uint32_t batch, hipStream_t st);

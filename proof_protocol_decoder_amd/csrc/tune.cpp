@@ -38,6 +38,11 @@ void bp_tune_side_lanes(int n) { bpg::tune().side_lanes.store(n < 0 ? 0 : n); }
 // A switch between two schedules of the same proofs, not one of the kernel knobs that bp_debug_tune_state lists (its
 // lines are a fixed set); bp_tune_reset puts it back like the others.
 void bp_tune_rec_riders(int on) { bpg::tune().rec_riders.store(on != 0); }
+// The switch point between two forms of one kernel (range_mult.hip); like rec_riders outside bp_debug_tune_state's fixed
+// lines.  Out of range = the default.
+void bp_tune_range_lds_log(int log_range) {
+  bpg::tune().range_lds_log.store(log_range < 1 || log_range > 14 ? bpg::Tune().range_lds_log.load() : log_range);
+}
 
 void bp_tune_reset(void) {
   const bpg::Tune defaults;
@@ -46,6 +51,7 @@ void bp_tune_reset(void) {
   BPG_KNOBS(X)
 #undef X
   t.rec_riders.store(defaults.rec_riders.load());
+  t.range_lds_log.store(defaults.range_lds_log.load());
 }
 
 int bp_debug_tune_state(char* buf, size_t cap) {

@@ -70,6 +70,13 @@ struct Tune {
   // at the end of the tree is proved a batch at a time; 0 = every node is proved where it is started, one proof per
   // chain of launches (the scheduling up to this knob).  Read once per call.  Measurements: profiles/rec_riders_ab.txt.
   std::atomic<int> rec_riders{1};
+
+  // ---- range-check multiplicities (range_mult.hip)
+  // bp_range_multiplicities counts in a per-workgroup LDS histogram up to 2^k values (1 .. 14: 32-bit counters, 64 KiB at
+  // 14) and with global 64-bit atomics above.  13 = 32 KiB a workgroup keeps four workgroups on a CU; the flush costs up
+  // to 2^k atomics per workgroup, so the LDS form stops paying where a chunk of rows no longer outnumbers the bins.  Not
+  // yet swept on hardware (profiles/air_program_log_ports.txt has the one point measured).
+  std::atomic<int> range_lds_log{13};
 };
 
 Tune& tune();  // the process's one instance (tune.cpp)

@@ -156,7 +156,11 @@ int stark_verify(const StarkCfg& cfg, const uint64_t* const_cap, const Ctl& ctl,
       for (uint32_t l = 0; l < program->n_ports; l++) {
         air::prog::PortAcc<Ext> acc{bpow, {}, {}, {}};
         program->eval_port<Ext>(l, row, acc);
-        air::prog::port_constraints<Ext>(n_air + air::prog::PORT_CONSTRAINTS * l, l, ctl.v, acc, row, k);
+        const uint32_t base = n_air + air::prog::PORT_CONSTRAINTS * l;
+        if (program->port_kind[l] != air::prog::PORT_PRODUCT)
+          air::prog::log_port_constraints<Ext>(base, l, program->port_kind[l], ctl.v, acc, row, k);
+        else
+          air::prog::port_constraints<Ext>(base, l, ctl.v, acc, row, k);
       }
     } else {
       air::ctl::eval<Ext>(shape, n_air, 0, A, ctl.v, row, k);

@@ -385,7 +385,7 @@ def stark_prove_trace(air_id, cfg, trace, consts=None, pub=None, device=None):
 def air_port_products(air_id, trace, ctl, consts=None, pub=None):
     """bp_air_port_products: the running products [2 * n_ports, 2^log_n] of a registered program's lookup ports over
     `trace` ([n_cols, 2^log_n] int64 on the device; a column slice of a wider buffer keeps its stride): port l's z_0 at
-    row 2l, z_1 at 2l + 1.  ctl = beta0, gamma0, beta1, gamma1."""
+    row 2l, z_1 at 2l + 1; a log port's running sums in the same rows.  ctl = beta0, gamma0, beta1, gamma1."""
     if not trace.is_cuda or trace.dtype != torch.int64 or trace.stride(1) != 1:
         raise ValueError("air_port_products needs an int64 device tensor with contiguous columns")
     n_cols, n = trace.shape
@@ -399,6 +399,35 @@ def air_port_products(air_id, trace, ctl, consts=None, pub=None):
     check(lib().bp_air_port_products(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
                                      consts.data_ptr() if consts is not None else None, pub_arr,
                                      (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
+    return out
+
+
+def range_multiplicities(values, log_range, filter=None, out=None):
+    """bp_range_multiplicities: how often each value of [0, 2^log_range) occurs in `values` ([n_cols, n_rows] int64 on the
+    device; a column slice of a wider buffer keeps its stride) on the rows where `filter` ([n_rows] of 0 / 1; None = all) is
+    set.  The counts are ADDED to `out` ([2^log_range] int64; None = a fresh zeroed one), which is returned.  A kept value
+    outside the range raises BpgError(BP_ERR_RANGE); its .first_bad is the smallest col * n_rows + row holding one."""
+    from ._lib import BpgError
+    if not values.is_cuda or values.dtype != torch.int64 or values.dim() != 2 or values.stride(1) != 1:
+        raise ValueError("range_multiplicities needs a 2-d int64 device tensor with contiguous columns")
+    n_cols, n_rows = values.shape
+    if filter is not None:
+        _require_cuda(filter)
+        if filter.shape != (n_rows,):
+            raise ValueError("the filter has one word per row")
+    if out is None:
+        out = torch.zeros(1 << log_range, dtype=torch.int64, device=values.device)
+    _require_cuda(out)
+    if out.shape != (1 << log_range,):
+        raise ValueError("out holds 2^log_range words")
+    first_bad = C.c_uint64()
+    try:
+        check(lib().bp_range_multiplicities(values.data_ptr(), values.stride(0), n_cols, n_rows,
+                                            filter.data_ptr() if filter is not None else None, log_range, out.data_ptr(),
+                                            C.byref(first_bad), _stream()))
+    except BpgError as e:
+        e.first_bad = first_bad.value
+        raise
     return out
 
 

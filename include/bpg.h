@@ -180,6 +180,17 @@ void bp_tune_side_lanes(int n);
  * a batch at a time (1, default); 0 = every node is proved where it is started, one proof per chain of launches.  Read
  * once per call.  Results are identical.  (Not listed by bp_debug_tune_state; bp_tune_reset puts it back.) */
 void bp_tune_rec_riders(int on);
+/* Transactions a thread of bp_prove_shard / bp_prove_shard_gi starts at a time (1 .. 8; 1 = one transaction per thread;
+ * 0, the default = by the state: 3 where bp_state_build found fewer hardware queues (GPU_MAX_HW_QUEUES) than the state
+ * has prover streams, else 1 -- profiles/txn_groups_ab.txt).
+ * A thread that takes n transactions leases n provers whose arenas are neighbours in device memory -- fewer when fewer
+ * neighbours are idle at that moment, never waiting for them -- and proves table t of all its transactions as lock-step
+ * batches wherever their shapes agree, t = 0..6, every transaction on its own transcript; the recursion chains and the
+ * root follow, one transaction after the other.  bp_config.arena_bytes remains the memory of ONE transaction: a group
+ * uses the arenas of the provers it leases, and nothing that is provable alone fails because it was grouped (a batch
+ * that would pass a limit is split).  Read once per call.  Results are identical, byte for byte.  (Not listed by
+ * bp_debug_tune_state; bp_tune_reset puts it back.) */
+void bp_tune_txn_group(int n);
 /* The witness of a recursion circuit's Poseidon rows (the sponge over its public-input list, its children's Merkle paths,
  * the sponges over their opened rows: independent pieces) is made on the host; a prover that is alone on the device makes
  * the pieces of a lock-step batch on up to n threads (default 7; 1 = on the prover's own thread).  Results are identical. */
@@ -782,6 +793,13 @@ int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t i
  * that do not form one statement end the call with BP_ERR_VERIFY. */
 int bp_generate_txn_table_proofs(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
                                  const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len);
+/* bp_generate_txn_table_proofs for n transactions (IR i at irs + i * ir_stride; data nullable, and so is every
+ * data[i]), table t of the transactions whose shapes agree proved in lock-step on one group of provers (bp_tune_txn_group
+ * says how; the knob itself is not read, the caller has formed the group).  outs[i] / out_lens[i] are the blobs the single
+ * call gives, byte for byte; on a failure -- the first failing transaction's status and message -- nothing is handed out. */
+int bp_generate_txn_table_proofs_group(const bp_state* s, const uint8_t* irs, size_t ir_stride, uint32_t n,
+                                       const bp_txn_witness* const* data, const volatile uint8_t* abort_flag, uint8_t** outs,
+                                       size_t* out_lens);
 int bp_verify_txn_table_proofs(const bp_config* cfg, const uint8_t* table_proofs, size_t len);
 /* The same with the STATEMENT fixed by the verifier, as upstream's verify_proof has it (all_stark is the verifier's): ir
  * = the transaction's IR; a table whose header names another AIR, height or width than the IR does (e.g. a Keccak-f

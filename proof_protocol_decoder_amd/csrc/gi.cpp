@@ -334,10 +334,15 @@ int make_plan(uint32_t n, uint32_t shape, std::vector<std::pair<uint32_t, uint32
 // opaque: every node is proved where it is started.
 // leaf_is_agg (nullable): the kinds of the leaves when they are proofs made elsewhere (bp_aggregate_proofs); else txn proofs
 // pooled_leaf (nullable): the leaf callback of a run with jobs -- posts node i's root as a job instead of proving it
+// group_leaf (nullable): leaves ids[0..n) started as one group on the state's provers (TreeOps::leaf_group); with it and
+// Tune::txn_group > 1 a thread starts up to that many transactions at a time and proves their table proofs in lock-step
 using PooledLeaf = int (*)(void* ctx, uint32_t i, bpg::RecPool* pool);
+using GroupLeaf = int (*)(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
+                          bpg::TreeBuf* outs);
 int run_tree(uint32_t n, const bp_shard_options* opt, bp_shard_leaf_fn leaf, bp_shard_agg_fn agg, void* ctx,
              const volatile uint8_t* abort_flag, uint8_t** root_out, size_t* root_len, uint8_t** leaf_out, size_t* leaf_len,
-             const int* leaf_is_agg = nullptr, const bp_state* s = nullptr, PooledLeaf pooled_leaf = nullptr) {
+             const int* leaf_is_agg = nullptr, const bp_state* s = nullptr, PooledLeaf pooled_leaf = nullptr,
+             GroupLeaf group_leaf = nullptr) {
   if (!leaf || !agg || !root_out || !root_len) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: null argument");
   if ((leaf_out == nullptr) != (leaf_len == nullptr)) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: leaf_out and leaf_len go together");
   std::vector<std::pair<uint32_t, uint32_t>> plan;
@@ -353,6 +358,13 @@ int run_tree(uint32_t n, const bp_shard_options* opt, bp_shard_leaf_fn leaf, bp_
     }
     return leaf(ctx, i, out, out_len);
   };
+  if (s && group_leaf) {
+    ops.group = bpg::txn_group_of(s);
+    ops.lanes = bpg::state_workers(s);
+    ops.leaf_group = [=](const uint32_t* ids, uint32_t k, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted, bpg::TreeBuf* outs) {
+      return group_leaf(ctx, ids, k, pool, granted, outs);
+    };
+  }
   ops.agg = [=](const bpg::TreeBuf& l, int la, const bpg::TreeBuf& r, int ra, uint8_t** out, size_t* out_len) {
     return agg(ctx, l.p, l.n, la, r.p, r.n, ra, out, out_len);
   };
@@ -400,6 +412,13 @@ int ir_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
   const IrShard* c = static_cast<const IrShard*>(ctx);
   return bpg::txn_proof_pooled(c->s, c->irs + (size_t)i * c->stride, BP_IR_WORDS * 8, nullptr, c->abort_flag, pool, i);
 }
+int ir_leaf_group(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
+                  bpg::TreeBuf* outs) {
+  const IrShard* c = static_cast<const IrShard*>(ctx);
+  std::vector<const uint8_t*> irs(n);
+  for (uint32_t k = 0; k < n; k++) irs[k] = c->irs + (size_t)ids[k] * c->stride;
+  return bpg::txn_group_pooled(c->s, n, irs.data(), BP_IR_WORDS * 8, nullptr, c->abort_flag, pool, ids, granted, outs);
+}
 int state_agg(void* ctx, const uint8_t* l, size_t ln, int l_agg, const uint8_t* r, size_t rn, int r_agg, uint8_t** out, size_t* out_len) {
   return bp_generate_agg_proof(*static_cast<const bp_state* const*>(ctx), l, ln, l_agg, r, rn, r_agg, out, out_len);
 }
@@ -420,6 +439,30 @@ int gi_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
   const GiShard* c = static_cast<const GiShard*>(ctx);
   bp_gi_chain ch = (*c->chain_before)[c->first + i];
   return prove_entry(c->s, (*c->es)[c->first + i], *c->o, &ch, c->abort_flag, nullptr, nullptr, pool, i);
+}
+// a group of entries: the work of each as prove_entry makes it, then one call for the group
+int gi_leaf_group(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
+                  bpg::TreeBuf* outs) {
+  const GiShard* c = static_cast<const GiShard*>(ctx);
+  std::vector<EntryWork> w(n);
+  std::vector<bp_txn_witness> tw(n);
+  std::vector<const bp_txn_witness*> data(n, nullptr);
+  std::vector<const uint8_t*> irs(n);
+  for (uint32_t k = 0; k < n; k++) {
+    bp_gi_chain ch = (*c->chain_before)[c->first + ids[k]];
+    if (int rc = entry_work((*c->es)[c->first + ids[k]], *c->o, &ch, true, &w[k])) return rc;
+    irs[k] = reinterpret_cast<const uint8_t*>(w[k].ir);
+    if (!w[k].given[T_KECCAK]) continue;  // (every other table's work is that of the hashed bytes: entry_work)
+    std::memset(&tw[k], 0, sizeof(tw[k]));
+    for (int t = 0; t < BP_NUM_TABLES; t++) {
+      if (!w[k].given[t]) continue;
+      tw[k].*TABLES[t].data = w[k].items[t].data();
+      tw[k].*TABLES[t].n = w[k].items[t].size() / TABLES[t].item_words;
+      tw[k].*TABLES[t].has = 1;
+    }
+    data[k] = &tw[k];
+  }
+  return bpg::txn_group_pooled(c->s, n, irs.data(), sizeof(w[0].ir), data.data(), c->abort_flag, pool, ids, granted, outs);
 }
 uint32_t default_threads(const bp_state* s, const bp_shard_options* opt) {
   if (opt && opt->n_threads) return opt->n_threads;
@@ -522,7 +565,10 @@ int bp_prove_shard(const bp_state* s, const uint8_t* irs, size_t ir_stride, uint
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
   auto leaf = [](void* ctx, uint32_t i, uint8_t** out, size_t* out_len) { return ir_leaf(&static_cast<Ctx*>(ctx)->sh, i, out, out_len); };
   auto pooled = [](void* ctx, uint32_t i, bpg::RecPool* pool) { return ir_leaf_pooled(&static_cast<Ctx*>(ctx)->sh, i, pool); };
-  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, pooled);
+  auto group = [](void* ctx, const uint32_t* ids, uint32_t k, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted, bpg::TreeBuf* outs) {
+    return ir_leaf_group(&static_cast<Ctx*>(ctx)->sh, ids, k, pool, granted, outs);
+  };
+  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, pooled, group);
 }
 BPG_ABI_CATCH("bp_prove_shard")
 
@@ -545,7 +591,7 @@ int bp_prove_shard_gi(const bp_state* s, const uint8_t* geni, size_t len, uint32
   }
   GiShard c{s, &es, gi, first, &before, abort_flag};
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
-  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, gi_leaf_pooled);
+  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, gi_leaf_pooled, gi_leaf_group);
 }
 BPG_ABI_CATCH("bp_prove_shard_gi")
 

@@ -4,6 +4,7 @@
 // (DESIGN.md section 5); the control flow, ownership, threading and error behaviour follow the
 // reference (see include/bpg.h).
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include <system_error>
 #include <thread>
 #include <deque>
+#include <functional>
 #include <random>
 #include <set>
 #include <unordered_map>
@@ -22,6 +24,7 @@
 #include "rec_pool.hpp"
 #include "tune.hpp"
 #include "txn_tables.hpp"
+#include "worker_table.hpp"
 
 using namespace bpg;
 using namespace bpg::txn;
@@ -73,7 +76,13 @@ struct bp_state {
   mutable std::mutex mu;
   mutable std::condition_variable cv;
   mutable std::vector<std::unique_ptr<Worker>> workers;
-  mutable std::vector<Worker*> idle;
+  // The workers' arenas are slices of a few large device allocations (one, where the device grants it): the slices of a
+  // slab lie one behind the other, stride slice_stride, so a run of adjacent idle workers is one contiguous piece of
+  // memory (GroupLease).  table: who is idle, who is whose neighbour (worker_table.hpp); under mu.
+  std::vector<void*> slabs;
+  size_t slice_stride = 0;
+  mutable WorkerTable table;
+  uint32_t auto_txn_group = 1;  // Tune::txn_group = 0: what this state's queue count asks for (bp_state_build)
   // Keccak-256 of every proof container this state has produced (bounded): aggregation verifies its children on the
   // host (verify_child), which costs 10 ms of CPU per recursion-shaped proof against 5 ms of GPU to make one -- a child
   // that this very state has just produced, byte for byte, is recognised instead of being verified again
@@ -92,12 +101,13 @@ namespace {
 struct WorkerLease {
   const bp_state* s;
   Worker* w;
+  uint32_t index;
   size_t mark;
   explicit WorkerLease(const bp_state* st) : s(st) {
     std::unique_lock<std::mutex> lk(s->mu);
-    s->cv.wait(lk, [&] { return !s->idle.empty(); });
-    w = s->idle.back();
-    s->idle.pop_back();
+    s->cv.wait(lk, [&] { return s->table.any_idle(); });
+    index = (uint32_t)s->table.take_one();
+    w = s->workers[index].get();
     mark = w->arena.mark();
     prover_active(+1);
   }
@@ -108,8 +118,49 @@ struct WorkerLease {
     w->abort_flag = nullptr;
     w->abort_flag_u8 = nullptr;
     std::lock_guard<std::mutex> lk(s->mu);
-    s->idle.push_back(w);
-    s->cv.notify_one();
+    s->table.give(index);
+    s->cv.notify_all();
+  }
+};
+
+// A RUN of workers whose arenas are neighbours, for the transactions a prover takes at a time (Tune::txn_group): up to
+// `want` adjacent idle workers, all or nothing under bp_state::mu -- the longest adjacent run there is when `want` are
+// not to be had, never a wait for adjacency; it blocks only while no worker is idle, as WorkerLease does, and holds
+// nothing while it waits.  The first worker of the run leads: its stream, its mailbox, and for the time of the lease an
+// arena that spans the run's slices.  The others lend their pinned buffers (witness staging); their streams stay idle.
+// A worker that kept something in its arena across leases (none does: every lease releases to the mark it found, which
+// is 0) would end the run in front of it: the spanning view covers clean slices only.
+struct GroupLease {
+  const bp_state* s;
+  std::vector<Worker*> ws;  // ws[0] leads
+  uint32_t first = 0;
+  size_t mark = 0, own_cap = 0;
+  GroupLease(const bp_state* st, uint32_t want) : s(st) {
+    std::unique_lock<std::mutex> lk(s->mu);
+    s->cv.wait(lk, [&] { return s->table.any_idle(); });
+    uint32_t n = s->table.take_run(want, &first);
+    uint32_t clean = 1;
+    while (clean < n && s->workers[first + clean]->arena.mark() == 0) clean++;
+    for (uint32_t k = clean; k < n; k++) s->table.give(first + k);
+    n = clean;
+    for (uint32_t k = 0; k < n; k++) ws.push_back(s->workers[first + k].get());
+    Worker& lead = *ws[0];
+    mark = lead.arena.mark();
+    own_cap = lead.arena.capacity();
+    lead.arena.span((size_t)(n - 1) * s->slice_stride + own_cap);
+    prover_active((int)n);  // a group counts as the transactions it proves: the load-dependent choices see today's load
+  }
+  uint32_t size() const { return (uint32_t)ws.size(); }
+  ~GroupLease() {
+    prover_active(-(int)ws.size());
+    (void)hipStreamSynchronize(ws[0]->stream);
+    ws[0]->arena.release(mark);
+    ws[0]->arena.span(own_cap);
+    ws[0]->abort_flag = nullptr;
+    ws[0]->abort_flag_u8 = nullptr;
+    std::lock_guard<std::mutex> lk(s->mu);
+    for (uint32_t k = 0; k < ws.size(); k++) s->table.give(first + k);
+    s->cv.notify_all();
   }
 };
 
@@ -122,18 +173,18 @@ struct WorkerLease {
 struct SideLane {
   const bp_state* s;
   Worker* w;
+  uint32_t index;
   static std::unique_ptr<SideLane> try_acquire(const bp_state* st) {
     std::lock_guard<std::mutex> lk(st->mu);
-    if (st->idle.empty()) return nullptr;
-    std::unique_ptr<SideLane> l(new SideLane{st, st->idle.back()});
-    st->idle.pop_back();
-    return l;
+    const int i = st->table.take_one();
+    if (i < 0) return nullptr;
+    return std::unique_ptr<SideLane>(new SideLane{st, st->workers[i].get(), (uint32_t)i});
   }
   ~SideLane() {
     (void)hipStreamSynchronize(w->stream);  // nothing of ours is left on the lane when its owner gets it back
     std::lock_guard<std::mutex> lk(s->mu);
-    s->idle.push_back(w);
-    s->cv.notify_one();
+    s->table.give(index);
+    s->cv.notify_all();
   }
 };
 
@@ -499,6 +550,7 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
     ~Unbuild() {
       if (!s) return;
       for (auto& w : s->workers) w->destroy();
+      for (void* p : s->slabs) (void)hipFree(p);
       s->builder.destroy();
     }
   } unbuild{s};
@@ -535,11 +587,32 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
   for (uint32_t k = 0; k < 3; k++)
     if ((r = build_circuit(s->builder, rc, circuit_seed(CIRCUIT_ROOT + k, 0), special[k], &s->special[k]))) return r;
   BPG_HIP(hipStreamSynchronize(s->builder.stream));
-  for (uint32_t i = 0; i < cfg->n_workers; i++) {
-    std::unique_ptr<Worker> w(new Worker());
-    if ((r = w->init(cfg->device, cfg->arena_bytes))) { w->destroy(); return r; }
-    s->idle.push_back(w.get());
-    s->workers.push_back(std::move(w));
+  {
+    // The arenas: one allocation cut into n_workers slices, so that neighbours can be leased as one piece of memory.
+    // Where the device does not grant one allocation of that size the run is halved until it does: a few slabs, each
+    // holding a whole run of slices (a slab of one slice is what every worker had before).
+    s->slice_stride = ((size_t)cfg->arena_bytes + 255) & ~(size_t)255;
+    std::vector<uint32_t> slab_of;
+    for (uint32_t done = 0, run = cfg->n_workers; done < cfg->n_workers;) {
+      run = std::min(run, cfg->n_workers - done);
+      void* slab = nullptr;
+      const hipError_t e = hipMalloc(&slab, (size_t)(run - 1) * s->slice_stride + cfg->arena_bytes);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (run == 1) return fail(BP_ERR_DEVICE, "hipMalloc of a prover arena (%zu MiB) failed: %s", (size_t)cfg->arena_bytes >> 20, hipGetErrorString(e));
+        run = (run + 1) / 2;
+        continue;
+      }
+      s->slabs.push_back(slab);
+      for (uint32_t k = 0; k < run; k++) {
+        std::unique_ptr<Worker> w(new Worker());
+        if ((r = w->init(cfg->device, cfg->arena_bytes, static_cast<char*>(slab) + (size_t)k * s->slice_stride))) { w->destroy(); return r; }
+        s->workers.push_back(std::move(w));
+        slab_of.push_back((uint32_t)s->slabs.size() - 1);
+      }
+      done += run;
+    }
+    s->table.reset(std::move(slab_of));
   }
   {
     // One prover = one HIP stream, and ROCm multiplexes a process's streams over GPU_MAX_HW_QUEUES hardware queues
@@ -548,6 +621,9 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
     // runtime has started, so it says so.
     const char* env = std::getenv("GPU_MAX_HW_QUEUES");
     const long queues = env && *env ? std::strtol(env, nullptr, 10) : 4;
+    // With fewer queues than streams the launches of a table proof are what the streams queue up behind: three
+    // transactions' table proofs in lock-step (tune.hpp has the measurement); with a queue per stream one at a time.
+    s->auto_txn_group = queues < (long)cfg->n_workers ? 3 : 1;
     if (queues < (long)cfg->n_workers) {
       char buf[512];
       std::snprintf(buf, sizeof(buf),
@@ -581,6 +657,7 @@ void bp_state_free(bp_state* s) {
   if (!s) return;
   (void)hipSetDevice(s->cfg.device);
   for (auto& w : s->workers) w->destroy();
+  for (void* p : s->slabs) (void)hipFree(p);
   s->builder.destroy();
   delete s;
 }
@@ -622,9 +699,14 @@ struct TableProofs {
 // generate_traces: the seven witnesses of a transaction in the worker's arena (d_trace[t]: n_cols x 2^log_n, column-major).
 // What is to be made, and the refusals of data that cannot form one statement, are plan_traces' (txn_tables.cpp); here
 // are the allocations, the staging and the launches.  Shared by the prover and the witness pre-flight.
+// stage (nullable): the pinned buffer the caller's items are staged through when it is not the worker's own (a group's
+// transactions use the buffers of the workers the group has leased); allocated: d_trace is the caller's already (a
+// group lays the equally shaped traces of its transactions one behind the other, as commit_batch wants them).
 static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES],
-                        uint64_t* d_trace[BP_NUM_TABLES]) {
+                        uint64_t* d_trace[BP_NUM_TABLES], const Worker* stage = nullptr, bool allocated = false) {
   int r;
+  uint64_t* const pinned = stage ? stage->pinned : w.pinned;
+  const size_t pinned_words = stage ? stage->pinned_words : w.pinned_words;
   bool given[BP_NUM_TABLES];
   size_t n_given[BP_NUM_TABLES];
   for (int t = 0; t < BP_NUM_TABLES; t++) {
@@ -636,7 +718,7 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
   const bool lookup_kf = plan.lookup[L_SPONGE_KECCAK], lookup_bm = plan.lookup[L_PACKING_MEMORY], lookup_sl = plan.lookup[L_SPONGE_LOGIC];
   // a looking table before the table it looks up (sponge before Keccak-f, byte packing before memory)
   static const int GEN_ORDER[BP_NUM_TABLES] = {T_KECCAK_SPONGE, T_ARITHMETIC, T_BYTE_PACKING, T_CPU, T_KECCAK, T_LOGIC, T_MEMORY};
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
+  for (int t = 0; t < BP_NUM_TABLES && !allocated; t++) {
     const uint64_t N = (uint64_t)1 << tcfg[t].log_n;
     d_trace[t] = w.arena.alloc_words((size_t)tcfg[t].n_cols * N);
     if (!d_trace[t]) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLES[t].name);
@@ -657,10 +739,10 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the logic table's operations");
       uint64_t* d_given = nullptr;
       if (n_ops) {
-        if (n_ops * wds > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "too many logic operations for the input staging buffer");
-        std::memcpy(w.pinned, wit->in[t], n_ops * wds * 8);
+        if (n_ops * wds > pinned_words) return fail(BP_ERR_UNSUPPORTED, "too many logic operations for the input staging buffer");
+        std::memcpy(pinned, wit->in[t], n_ops * wds * 8);
         d_given = d_in + (size_t)N * wds;
-        BPG_HIP(hipMemcpyAsync(d_given, w.pinned, n_ops * wds * 8, hipMemcpyHostToDevice, w.stream));
+        BPG_HIP(hipMemcpyAsync(d_given, pinned, n_ops * wds * 8, hipMemcpyHostToDevice, w.stream));
       }
       if ((r = launch_logic_inputs_from_sponge(d_sponge, sponge_log_n, plan.logic_covered, given[t] ? d_given : nullptr, (uint32_t)n_ops,
                                                d_in, (uint32_t)N, seed, w.stream))) return r;
@@ -672,9 +754,9 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
       const size_t words = cap * wds;
       d_in = w.arena.alloc_words(words);
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the witness data of table %s", TABLES[t].name);
-      if (words > w.pinned_words) return fail(BP_ERR_UNSUPPORTED, "table %s too tall for the input staging buffer", TABLES[t].name);
-      fill_table_inputs(t, N, wit->in[t], wit->n[t], w.pinned);
-      BPG_HIP(hipMemcpyAsync(d_in, w.pinned, words * 8, hipMemcpyHostToDevice, w.stream));
+      if (words > pinned_words) return fail(BP_ERR_UNSUPPORTED, "table %s too tall for the input staging buffer", TABLES[t].name);
+      fill_table_inputs(t, N, wit->in[t], wit->n[t], pinned);
+      BPG_HIP(hipMemcpyAsync(d_in, pinned, words * 8, hipMemcpyHostToDevice, w.stream));
     } else if (t == T_KECCAK && lookup_kf) {
       d_in = w.arena.alloc_words(cap * wds);
       if (!d_in) return fail(BP_ERR_DEVICE, "device arena exhausted for the Keccak-f table's inputs");
@@ -784,43 +866,35 @@ static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const T
   return check_lookups(tcfg, tp->proof);
 }
 
-static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
-                          const volatile uint8_t* abort_flag_u8, uint8_t** out, size_t* out_len,
-                          const TxnWitness* wit = nullptr, bool tables_only = false, RecPool* pool = nullptr, uint32_t node = 0) {
-  if (!s || !ir || ((!out || !out_len) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
-  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
-  const uint64_t* I = reinterpret_cast<const uint64_t*>(ir);
-  const bp_config& cfg = s->cfg;
-  TableProofs tp;
-  int r = parse_ir(s->cfg, I, wit, tp.tcfg, &tp.pv);
-  if (r) return r;
+// The seven table proofs as bp_generate_txn_table_proofs hands them out:
+// "BPGTABLS" | n_tables | public values | lookup challenges | per table: air_id, log_n, n_cols, n_words, proof words
+static int emit_tables(const TableProofs& tp, uint8_t** out, size_t* out_len) {
   const StarkCfg* tcfg = tp.tcfg;
   const std::vector<uint64_t>& pv = tp.pv;
-
-  (void)hipSetDevice(cfg.device);
-  WorkerLease lease(s);
-  Worker& w = *lease.w;
-  w.abort_flag = abort_flag;
-  w.abort_flag_u8 = abort_flag_u8;
-  if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
-  if ((r = prove_tables(s, w, I, wit, &tp))) return r;
-  if (tables_only) {
-    // "BPGTABLS" | n_tables | public values | lookup challenges | per table: air_id, log_n, n_cols, n_words, proof words
-    std::vector<uint64_t> o = {TABLES_MAGIC, BP_NUM_TABLES};
-    o.insert(o.end(), pv.begin(), pv.end());
-    o.insert(o.end(), tp.ctl.v, tp.ctl.v + 4);
-    for (int t = 0; t < BP_NUM_TABLES; t++) {
-      const uint64_t hdr[4] = {tcfg[t].air_id, tcfg[t].log_n, tcfg[t].n_cols, tp.proof[t].size()};
-      o.insert(o.end(), hdr, hdr + 4);
-      o.insert(o.end(), tp.proof[t].begin(), tp.proof[t].end());
-    }
-    uint64_t* buf = static_cast<uint64_t*>(std::malloc(o.size() * 8));
-    if (!buf) return fail(BP_ERR_DEVICE, "host allocation failed");
-    std::memcpy(buf, o.data(), o.size() * 8);
-    *out = reinterpret_cast<uint8_t*>(buf);
-    *out_len = o.size() * 8;
-    return BP_OK;
+  std::vector<uint64_t> o = {TABLES_MAGIC, BP_NUM_TABLES};
+  o.insert(o.end(), pv.begin(), pv.end());
+  o.insert(o.end(), tp.ctl.v, tp.ctl.v + 4);
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    const uint64_t hdr[4] = {tcfg[t].air_id, tcfg[t].log_n, tcfg[t].n_cols, tp.proof[t].size()};
+    o.insert(o.end(), hdr, hdr + 4);
+    o.insert(o.end(), tp.proof[t].begin(), tp.proof[t].end());
   }
+  uint64_t* buf = static_cast<uint64_t*>(std::malloc(o.size() * 8));
+  if (!buf) return fail(BP_ERR_DEVICE, "host allocation failed");
+  std::memcpy(buf, o.data(), o.size() * 8);
+  *out = reinterpret_cast<uint8_t*>(buf);
+  *out_len = o.size() * 8;
+  return BP_OK;
+}
+
+// What follows the table proofs of a transaction: the recursion chains over them and the root proof (or, with a pool,
+// the root posted as the job of `node`).  The traces are dead: the arena goes back to `arena_mark`.
+static int txn_recursion(const bp_state* s, Worker& w, size_t arena_mark, TableProofs& tp, uint8_t** out, size_t* out_len,
+                         RecPool* pool, uint32_t node) {
+  const bp_config& cfg = s->cfg;
+  const StarkCfg* tcfg = tp.tcfg;
+  const std::vector<uint64_t>& pv = tp.pv;
+  int r;
   // per child of a recursion circuit: its digest, and the Merkle path of its first trace opening (leaf digest, cap entry:
   // words of the parent's public-input list; position and siblings: witness of the parent's Merkle rows)
   uint64_t digest[BP_NUM_TABLES][4], leaf_cap[BP_NUM_TABLES][8];
@@ -833,7 +907,7 @@ static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   }
   std::vector<uint64_t> proof;
   if ((r = w.wait())) return r;
-  w.arena.release(lease.mark);  // traces are dead; the chains below only need digests
+  w.arena.release(arena_mark);  // traces are dead; the chains below only need digests
   // per-table recursion-shaped chains (wrap + shrinks).  The seven chains do not depend on each other and their
   // proofs have one shape: level k of all seven is ONE batch proved in lock-step (rec_prove_batch) -- seven
   // transcripts stepped together, every kernel launch and host wait shared --, then level k + 1.  (Until round 4 each
@@ -898,6 +972,197 @@ static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   if ((r = emit_box(0, CIRCUIT_ROOT, pi, proof, out, out_len))) return r;
   remember_proof(s, *out, *out_len);
   return BP_OK;
+}
+
+// ---- several transactions at a time (Tune::txn_group) ----------------------------------------------------------------
+// The seven tables of ONE transaction share a transcript and cannot be stepped together; table t of transaction A and
+// table t of transaction B have separate transcripts and, wherever their heights agree, one shape.  A prover that holds
+// a group of transactions therefore proves table t of all of them as lock-step batches (stark_prove_batch, the
+// machinery of the recursion chains), t = 0..6 in order, each transaction on its own transcript: the ~57 launches and
+// ~15 host waits of a table proof are paid once per batch instead of once per transaction.
+namespace {
+
+struct GroupTxn {  // one transaction of a group
+  const uint64_t* I = nullptr;
+  const TxnWitness* wit = nullptr;
+  TableProofs tp;
+};
+
+bool same_shape(const StarkCfg& a, const StarkCfg& b) {
+  return a.log_n == b.log_n && a.n_cols == b.n_cols && a.n_const == b.n_const && a.deg_pow == b.deg_pow && a.rate_bits == b.rate_bits &&
+         a.cap_height == b.cap_height && a.num_queries == b.num_queries && a.pow_bits == b.pow_bits && a.arity_bits == b.arity_bits &&
+         a.final_poly_bits == b.final_poly_bits && a.air_id == b.air_id;
+}
+// Table proofs of shape c one lock-step batch holds: every limit stark_prove_batch and commit_batch would refuse at,
+// taken up front so that a sub-batch is SPLIT and never failed -- MAX_BATCH, the query launches' index limit
+// (MAX_BATCH_QUERIES: 84 queries -> 3 proofs), and the mailbox (caps, openings, the last FRI layer; the query openings
+// fall back to the arena by themselves).  The kernels' argument blocks are BatchOf<...>, MAX_BATCH entries whatever the
+// batch: no limit of their own.
+uint32_t table_batch_cap(const StarkCfg& c, size_t pinned_words) {
+  const ProofLayout L = proof_layout(c);
+  const size_t open_words = ((size_t)c.n_const + c.n_cols + 2 * (size_t)L.n_aux + L.n_quot) * 4;
+  const size_t last_layer = (size_t)2 * ((size_t)L.final_len << c.rate_bits);
+  const size_t per_proof = std::max(std::max(open_words, last_layer), L.cap_words);
+  size_t cap = std::min<size_t>(MAX_BATCH, MAX_BATCH_QUERIES / std::max<uint32_t>(1, c.num_queries));
+  cap = std::min(cap, pinned_words / std::max<size_t>(1, per_proof));
+  return (uint32_t)std::max<size_t>(1, cap);
+}
+
+struct SubBatch {  // the transactions of a group whose table t has one shape, at most table_batch_cap of them
+  uint32_t n = 0;
+  uint32_t txn[MAX_BATCH];
+  uint64_t* d_traces = nullptr;  // [n][n_cols][N]
+};
+
+// prove_tables for g >= 2 transactions on the group's leading worker (its arena spans the group's slices)
+int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* const* tx, uint32_t g) {
+  int r;
+  // per table the sub-batches, in the order of their first transaction; a transaction's place in its sub-batch
+  std::vector<SubBatch> subs[BP_NUM_TABLES];
+  std::vector<std::array<uint64_t*, BP_NUM_TABLES>> d_trace(g);
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    for (uint32_t i = 0; i < g; i++) {
+      const StarkCfg& c = tx[i]->tp.tcfg[t];
+      const uint32_t cap = table_batch_cap(c, w.pinned_words);
+      SubBatch* sb = nullptr;
+      for (auto& cand : subs[t])
+        if (cand.n < cap && same_shape(tx[cand.txn[0]]->tp.tcfg[t], c)) { sb = &cand; break; }
+      if (!sb) { subs[t].emplace_back(); sb = &subs[t].back(); }
+      sb->txn[sb->n++] = i;
+    }
+    for (auto& sb : subs[t]) {
+      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
+      const size_t words = (size_t)c.n_cols << c.log_n;
+      sb.d_traces = w.arena.alloc_words(words * sb.n);
+      if (!sb.d_traces) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLES[t].name);
+      for (uint32_t k = 0; k < sb.n; k++) d_trace[sb.txn[k]][t] = sb.d_traces + k * words;
+    }
+  }
+  // generate_traces per transaction (its seed, plan and lookups), each staged through the pinned buffer of its own worker
+  for (uint32_t i = 0; i < g; i++)
+    if ((r = build_traces(w, tx[i]->I, tx[i]->wit, tx[i]->tp.tcfg, d_trace[i].data(), stage[i], true))) return r;
+  // trace commitments: one commit_batch per sub-batch
+  std::vector<std::array<Committed, BP_NUM_TABLES>> trace(g);
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    for (auto& sb : subs[t]) {
+      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
+      Committed cm[MAX_BATCH];
+      if ((r = commit_batch(w, sb.d_traces, c.n_cols, sb.n, c.log_n, c.rate_bits, c.cap_height, false, cm))) return r;
+      for (uint32_t k = 0; k < sb.n; k++) trace[sb.txn[k]][t] = std::move(cm[k]);
+    }
+  // every transaction's own transcript: its seven caps, its public values, its lookup challenges
+  std::vector<Challenger> ch(g);
+  for (uint32_t i = 0; i < g; i++) {
+    TableProofs& tp = tx[i]->tp;
+    for (int t = 0; t < BP_NUM_TABLES; t++) ch[i].observe(trace[i][t].cap.data(), trace[i][t].cap.size());
+    ch[i].observe(tp.pv.data(), tp.pv.size());
+    for (int k = 0; k < 4; k++) tp.ctl.v[k] = ch[i].challenge();
+  }
+  // the table proofs: t = 0..6 in order (one transcript per transaction runs through its seven), table t of the
+  // transactions of a sub-batch in lock-step
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    for (auto& sb : subs[t]) {
+      if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before table %s", TABLES[t].name);
+      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
+      const size_t mark = w.arena.mark();
+      Challenger before[MAX_BATCH], cur[MAX_BATCH];
+      Committed tr[MAX_BATCH];
+      const Committed* no_consts[MAX_BATCH] = {};
+      const uint64_t* d_tv[MAX_BATCH];
+      Ctl ctl[MAX_BATCH];
+      std::vector<uint64_t> proofs[MAX_BATCH];
+      uint64_t first_leaf[MAX_BATCH][4];
+      for (uint32_t k = 0; k < sb.n; k++) {
+        const uint32_t i = sb.txn[k];
+        before[k] = cur[k] = ch[i];
+        tr[k] = trace[i][t];
+        d_tv[k] = d_trace[i][t];
+        ctl[k] = tx[i]->tp.ctl;
+      }
+      if ((r = stark_prove_batch(w, c, sb.n, no_consts, tr, d_tv, ctl, cur, proofs, &first_leaf[0][0]))) return r;
+      for (uint32_t k = 0; k < sb.n; k++) {
+        const uint32_t i = sb.txn[k];
+        TableProofs& tp = tx[i]->tp;
+        ch[i] = cur[k];
+        tp.proof[t] = std::move(proofs[k]);
+        std::memcpy(tp.first_leaf[t], first_leaf[k], 32);
+        if (given_table(tx[i]->wit, tp.tcfg, t) &&  // (prove_tables: data that came from the caller is checked by the CPU verifier)
+            stark_verify(c, nullptr, tp.ctl, before[k], tp.proof[t].data(), tp.proof[t].size()) != BP_OK) {
+          const std::string why = bp_last_error();
+          return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: %s", TABLES[t].name, why.c_str());
+        }
+      }
+      w.arena.release(mark);
+    }
+  for (uint32_t i = 0; i < g; i++)
+    if ((r = check_lookups(tx[i]->tp.tcfg, tx[i]->tp.proof))) return r;
+  return BP_OK;
+}
+
+}  // namespace
+
+// Up to n transactions on one group lease: as many as the lease grants (>= 1; `granted` hears the number the moment the
+// lease is held, so that a scheduler can hand the others on), their table proofs in lock-step, then each transaction's
+// recursion chains and root as txn_proof_impl runs them, one transaction after the other on the group's stream.
+// outs / out_lens per transaction (tables_only: the table-proof blobs); with a pool the roots are posted as the jobs of
+// nodes[i] instead.  The first failing transaction's status and message are the call's.
+static int txn_group_impl(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const TxnWitness* const* wits,
+                          const volatile uint8_t* abort_flag, bool tables_only, RecPool* pool, const uint32_t* nodes,
+                          const std::function<void(uint32_t)>* granted, uint8_t** outs, size_t* out_lens, uint32_t* n_done) {
+  if (!s || !irs || !n || ((!outs || !out_lens) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
+  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
+  n = std::min<uint32_t>(n, MAX_BATCH);
+  std::vector<std::unique_ptr<GroupTxn>> tx;
+  (void)hipSetDevice(s->cfg.device);
+  GroupLease lease(s, n);
+  const uint32_t g = lease.size();
+  if (granted) (*granted)(g);
+  if (n_done) *n_done = g;
+  int r;
+  for (uint32_t i = 0; i < g; i++) {
+    if (!irs[i]) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
+    tx.emplace_back(new GroupTxn());
+    tx[i]->I = reinterpret_cast<const uint64_t*>(irs[i]);
+    tx[i]->wit = wits ? wits[i] : nullptr;
+    if ((r = parse_ir(s->cfg, tx[i]->I, tx[i]->wit, tx[i]->tp.tcfg, &tx[i]->tp.pv))) return r;
+  }
+  Worker& w = *lease.ws[0];
+  w.abort_flag = nullptr;
+  w.abort_flag_u8 = abort_flag;
+  if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
+  if (g == 1) {
+    if ((r = prove_tables(s, w, tx[0]->I, tx[0]->wit, &tx[0]->tp))) return r;
+  } else {
+    std::vector<GroupTxn*> p;
+    for (auto& t : tx) p.push_back(t.get());
+    if ((r = prove_tables_group(w, lease.ws, p.data(), g))) return r;
+  }
+  for (uint32_t i = 0; i < g; i++) {
+    if (tables_only) r = emit_tables(tx[i]->tp, &outs[i], &out_lens[i]);
+    else r = txn_recursion(s, w, lease.mark, tx[i]->tp, outs ? &outs[i] : nullptr, out_lens ? &out_lens[i] : nullptr, pool, nodes ? nodes[i] : 0);
+    if (r) return r;
+  }
+  return BP_OK;
+}
+
+static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
+                          const volatile uint8_t* abort_flag_u8, uint8_t** out, size_t* out_len,
+                          const TxnWitness* wit = nullptr, bool tables_only = false, RecPool* pool = nullptr, uint32_t node = 0) {
+  if (!s || !ir || ((!out || !out_len) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
+  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
+  const uint64_t* I = reinterpret_cast<const uint64_t*>(ir);
+  TableProofs tp;
+  int r = parse_ir(s->cfg, I, wit, tp.tcfg, &tp.pv);
+  if (r) return r;
+  (void)hipSetDevice(s->cfg.device);
+  WorkerLease lease(s);
+  Worker& w = *lease.w;
+  w.abort_flag = abort_flag;
+  w.abort_flag_u8 = abort_flag_u8;
+  if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
+  if ((r = prove_tables(s, w, I, wit, &tp))) return r;
+  if (tables_only) return emit_tables(tp, out, out_len);
+  return txn_recursion(s, w, lease.mark, tp, out, out_len, pool, node);
 }
 int bp_generate_txn_proof(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
                           uint8_t** out, size_t* out_len) try {
@@ -1064,6 +1329,36 @@ int bp_generate_txn_table_proofs(const bp_state* s, const uint8_t* ir, size_t ir
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit, true);
 }
 BPG_ABI_CATCH("bp_generate_txn_table_proofs")
+// The same for n transactions, table t of those whose shapes agree proved in lock-step (Tune::txn_group is not read: the
+// caller has formed the group).  One group lease at a time: as many transactions as it grants, then the next ones.
+// data: nullable, and so is every data[i].  outs[i] are the blobs bp_generate_txn_table_proofs gives, byte for byte; on
+// a failure nothing is handed out.
+int bp_generate_txn_table_proofs_group(const bp_state* s, const uint8_t* irs, size_t ir_stride, uint32_t n, const bp_txn_witness* const* data,
+                                       const volatile uint8_t* abort_flag, uint8_t** outs, size_t* out_lens) try {
+  if (!s || !irs || !outs || !out_lens || !n) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_table_proofs_group: null argument");
+  if (ir_stride < BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_table_proofs_group: ir_stride below %d bytes", BP_IR_WORDS * 8);
+  std::vector<TxnWitness> wit(n);
+  std::vector<const TxnWitness*> wp(n);
+  std::vector<const uint8_t*> ip(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (int r = witness_of(data ? data[i] : nullptr, &wit[i])) return r;
+    wp[i] = &wit[i];
+    ip[i] = irs + (size_t)i * ir_stride;
+    outs[i] = nullptr;
+    out_lens[i] = 0;
+  }
+  for (uint32_t done = 0; done < n;) {
+    uint32_t g = 0;
+    if (int r = txn_group_impl(s, n - done, ip.data() + done, BP_IR_WORDS * 8, wp.data() + done, abort_flag, true, nullptr, nullptr, nullptr,
+                               outs + done, out_lens + done, &g)) {
+      for (uint32_t i = 0; i < n; i++) { std::free(outs[i]); outs[i] = nullptr; out_lens[i] = 0; }
+      return r;
+    }
+    done += g;
+  }
+  return BP_OK;
+}
+BPG_ABI_CATCH("bp_generate_txn_table_proofs_group")
 
 // The host half of an aggregation: the children parsed, checked for contiguity and verified (or recognised as this
 // state's own), the public-input list and the two path witnesses of the aggregation circuit.  No device work.
@@ -1262,6 +1557,32 @@ int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const 
   TxnWitness wit;
   if (int r = witness_of(data, &wit)) return r;
   return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, &wit, false, pool, node);
+}
+
+uint32_t state_workers(const bp_state* s) { return s ? s->cfg.n_workers : 1; }
+uint32_t txn_group_of(const bp_state* s) {
+  const int knob = tune().txn_group.load(std::memory_order_relaxed);
+  return knob > 0 ? (uint32_t)knob : (s ? s->auto_txn_group : 1);
+}
+
+int txn_group_pooled(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const bp_txn_witness* const* data,
+                     const volatile uint8_t* abort_flag, RecPool* pool, const uint32_t* nodes, const std::function<void(uint32_t)>& granted,
+                     TreeBuf* outs) {
+  if (!n || n > MAX_BATCH || !nodes || (!pool && !outs)) return fail(BP_ERR_INVALID_INPUT, "txn_group_pooled: a group of %u", n);
+  TxnWitness wit[MAX_BATCH];
+  const TxnWitness* wp[MAX_BATCH];
+  for (uint32_t i = 0; i < n; i++) {
+    if (int r = witness_of(data ? data[i] : nullptr, &wit[i])) return r;
+    wp[i] = &wit[i];
+  }
+  uint8_t* o[MAX_BATCH] = {};
+  size_t ol[MAX_BATCH] = {};
+  const int r = txn_group_impl(s, n, irs, ir_len, wp, abort_flag, false, pool, nodes, &granted, pool ? nullptr : o, pool ? nullptr : ol, nullptr);
+  for (uint32_t i = 0; i < n && !pool; i++) {
+    if (r) std::free(o[i]);
+    else outs[i] = TreeBuf{o[i], ol[i]};
+  }
+  return r;
 }
 
 int agg_proof_prepare(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg, const uint8_t* rhs, size_t rhs_len,

@@ -295,12 +295,21 @@ int DeviceArena::init(size_t bytes) {
   BPG_HIP(hipMalloc(reinterpret_cast<void**>(&base_), bytes));
   cap_ = bytes;
   off_ = high_ = 0;
+  owned_ = true;
   return BP_OK;
 }
+void DeviceArena::adopt(void* base, size_t bytes) {
+  destroy();
+  base_ = static_cast<char*>(base);
+  cap_ = bytes;
+  off_ = high_ = 0;
+  owned_ = false;
+}
 void DeviceArena::destroy() {
-  if (base_) (void)hipFree(base_);
+  if (base_ && owned_) (void)hipFree(base_);
   base_ = nullptr;
   cap_ = off_ = 0;
+  owned_ = true;
 }
 uint64_t* DeviceArena::alloc_words(size_t words) {
   size_t bytes = (words * 8 + 255) & ~(size_t)255;
@@ -310,7 +319,7 @@ uint64_t* DeviceArena::alloc_words(size_t words) {
   high_ = std::max(high_, off_);
   return reinterpret_cast<uint64_t*>(p);
 }
-int Worker::init(int dev, size_t arena_bytes) {
+int Worker::init(int dev, size_t arena_bytes, void* slice) {
   device = dev;
   // The device's host-wait mode is chosen BEFORE this library makes its first stream on it and never changed after:
   // a worker whose stream and event were made under spinning waits and that is still alive when the device is
@@ -319,8 +328,11 @@ int Worker::init(int dev, size_t arena_bytes) {
   (void)bp_use_blocking_sync(dev);
   BPG_HIP(hipSetDevice(dev));
   BPG_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  int rc = arena.init(arena_bytes);
-  if (rc) return rc;
+  if (slice) {
+    arena.adopt(slice, arena_bytes);
+  } else if (int rc = arena.init(arena_bytes)) {
+    return rc;
+  }
   pinned_words = (size_t)1 << 22;  // 32 MiB staging
   BPG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned), pinned_words * 8, hipHostMallocDefault));
   BPG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0));

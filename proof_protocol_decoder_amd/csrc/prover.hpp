@@ -83,6 +83,10 @@ void proof_digest(const StarkCfg& c, const uint64_t* proof, uint64_t out[4]);
 class DeviceArena {
  public:
   int init(size_t bytes);
+  // a slice of memory someone else owns (a state's slab, proofgen.cpp): destroy() forgets it, never frees it
+  void adopt(void* base, size_t bytes);
+  // the slices that follow this one in the same slab belong to it for a while (a group lease): capacity only
+  void span(size_t bytes) { cap_ = bytes; }
   void destroy();
   // returns nullptr when exhausted (caller reports BP_ERR_DEVICE)
   uint64_t* alloc_words(size_t words);
@@ -94,6 +98,7 @@ class DeviceArena {
  private:
   char* base_ = nullptr;
   size_t cap_ = 0, off_ = 0, high_ = 0;
+  bool owned_ = true;
 };
 
 constexpr size_t HASH_ROWS_WORDS = (size_t)(air::plonk::HASH_ROWS_MAX + air::plonk::MERKLE_ROWS_MAX + air::plonk::LEAF_ROWS_MAX) * air::plonk::H_WIRES;  // per proof: list rows, Merkle rows, leaf rows
@@ -121,7 +126,8 @@ struct Worker {
   const volatile uint8_t* abort_flag_u8 = nullptr;  // AtomicBool::as_ptr() of the reference's Arc<AtomicBool>
   int device = 0;
 
-  int init(int device, size_t arena_bytes);
+  // slice (nullable): the arena is arena_bytes of memory the caller owns instead of an allocation of the worker's own
+  int init(int device, size_t arena_bytes, void* slice = nullptr);
   void destroy();
   int d2h(uint64_t* host_dst, const uint64_t* dev_src, size_t words);  // async copy + stream sync
   int wait();  // everything queued on the stream has completed; the thread sleeps meanwhile (prover.cpp, "Host waits")

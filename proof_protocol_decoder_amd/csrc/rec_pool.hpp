@@ -185,6 +185,13 @@ struct TreeOps {
   std::function<std::string()> last_error;
   uint32_t cap = 1;     // jobs a drained batch holds
   bool pooled = false;  // roots and aggregations are jobs (else every node is proved where it is started)
+  // Leaves ids[0..n) (ascending) started by ONE thread as a group (Tune::txn_group).  The callee may take fewer than it
+  // is offered: it calls granted(g), 1 <= g <= n, once and as soon as it knows -- the leaves ids[g..n) then go back to
+  // the queue at once, for other threads -- and starts ids[0..g): per leaf a container in outs[k], or with a pool the
+  // job posted.  A callee that returns without having called it has taken all n.
+  std::function<int(const uint32_t* ids, uint32_t n, RecPool* pool, const std::function<void(uint32_t)>& granted, TreeBuf* outs)> leaf_group;
+  uint32_t group = 1;   // leaves a thread may start at a time (1, or no leaf_group: one leaf per thread as ever)
+  uint32_t lanes = 0;   // provers the leaves' callee can lease at a time (a state's n_workers); read when group > 1
 };
 
 class TreeRun : public RecPool {
@@ -208,6 +215,7 @@ class TreeRun : public RecPool {
   // Runs the tree on n_threads threads (the caller's is one of them); all of them have been joined on return.
   int run(uint32_t n_threads) {
     n_threads = std::min<uint32_t>(std::min<uint32_t>(n_threads ? n_threads : 1, n_), 256);
+    n_threads_ = n_threads;
     std::vector<std::thread> pool;
     struct Joiner {
       std::vector<std::thread>& p;
@@ -253,7 +261,8 @@ class TreeRun : public RecPool {
   }
 
  private:
-  bool aborted() const { return abort_flag_ && *abort_flag_; }
+  // (the flag is the caller's AtomicBool, raised from another thread while the run is under way: an atomic load)
+  bool aborted() const { return abort_flag_ && __atomic_load_n(abort_flag_, __ATOMIC_RELAXED); }
   void fail_with(int rc, const std::string& own) noexcept {
     try {
       const std::string msg = !own.empty() ? own : (ops_.last_error ? ops_.last_error() : std::string());
@@ -267,23 +276,79 @@ class TreeRun : public RecPool {
     std::snprintf(buf, sizeof(buf), fmt, v);
     return buf;
   }
+  // Groups (ops_.group > 1).  A thread that would start a leaf starts up to `group` of them as one call of leaf_group.
+  // Every transaction of a group occupies one of the callee's `lanes` provers, so a thread takes leaves only while a
+  // lane is free (it waits here, where it can still prepare aggregations, and not inside the callee's lease), and it
+  // takes  min(group, free lanes, ceil(waiting leaves / threads that are not busy))  of them: while the shard is long
+  // that is `group`; over the last round it falls to 1, so that the tail spreads over all the provers' streams instead
+  // of leaving half of them idle behind a few groups.
+  bool grouped() const { return ops_.group > 1 && ops_.leaf_group && ops_.lanes > 0; }
+  bool leaf_startable() const { return !grouped() || lanes_used_ < ops_.lanes; }
+  bool runnable() const {
+    if (!queue_.empty()) return queue_.top().first == 0 || leaf_startable();
+    return !ready_.empty();
+  }
   void worker() noexcept {
     for (;;) {
       bool have = false;
-      uint32_t nid = 0;
+      uint32_t nid = 0, n_group = 0, lanes_held = 0;
+      uint32_t ids[kMaxGroup];
       std::vector<std::unique_ptr<RecJob>> batch;
       {
         std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || !queue_.empty() || !ready_.empty(); });
+        cv_.wait(lk, [&] { return stop_ || runnable(); });
         if (stop_) return;
         if (!queue_.empty()) {  // an aggregation to prepare (or prove), else the next leaf
           nid = queue_.top().second;
           queue_.pop();
           have = true;
+          if (nid < n_ && grouped()) {  // (the aggregations go first: what is left in the queue are leaves)
+            const uint32_t waiting = (uint32_t)queue_.size() + 1, idle_threads = std::max<uint32_t>(1, n_threads_ - std::min(busy_, n_threads_ - 1));
+            const uint32_t want = std::min(std::min<uint32_t>(std::min<uint32_t>(ops_.group, kMaxGroup), ops_.lanes - lanes_used_),
+                                           (waiting + idle_threads - 1) / idle_threads);
+            ids[n_group++] = nid;
+            while (n_group < want && !queue_.empty() && queue_.top().first == 1) {
+              ids[n_group++] = queue_.top().second;
+              queue_.pop();
+            }
+            lanes_used_ += lanes_held = n_group;
+          }
+          busy_++;
         } else if (take_locked(ops_.cap ? ops_.cap : 1, &batch) == 0) {
           return;  // (only a failure inside take_locked: the pool has stopped)
+        } else {
+          busy_++;
         }
       }
+      TreeBuf gouts[kMaxGroup];
+      uint32_t n_taken = n_group;
+      bool heard = false;
+      // the callee has its lease: what it did not take goes back to the queue, in index order, and the lanes with it
+      const std::function<void(uint32_t)> granted = [&](uint32_t g) {
+        if (heard) return;
+        heard = true;
+        g = std::min(std::max<uint32_t>(g, 1), n_group);
+        std::lock_guard<std::mutex> lk(mu_);
+        try {
+          for (uint32_t k = g; k < n_group; k++) queue_.push({1, ids[k]});
+        } catch (...) {
+          fail_locked(BP_ERR_DEVICE, "out of memory in the shard's bookkeeping");
+        }
+        lanes_used_ -= n_group - g;
+        lanes_held = n_taken = g;
+        cv_.notify_all();
+      };
+      // on every way out of this round: the thread is idle again, its lanes are free
+      struct Round {
+        TreeRun& t;
+        uint32_t& lanes;
+        ~Round() {
+          std::lock_guard<std::mutex> lk(t.mu_);
+          t.busy_--;
+          t.lanes_used_ -= lanes;
+          t.cv_.notify_all();
+        }
+      } round{*this, lanes_held};
       TreeBuf b;
       std::vector<TreeBuf> outs;
       int rc = BP_OK;
@@ -298,6 +363,12 @@ class TreeRun : public RecPool {
           if (rc == BP_OK && outs.size() != batch.size()) { rc = BP_ERR_DEVICE; own = "a batch of recursion jobs returned the wrong number of proofs"; }
           for (size_t k = 0; rc == BP_OK && k < outs.size(); k++)
             if (!outs[k].p) { rc = BP_ERR_DEVICE; own = text("node %u of the shard returned no proof", batch[k]->node); }
+        } else if (n_group) {
+          rc = ops_.leaf_group(ids, n_group, ops_.pooled ? this : nullptr, granted, gouts);
+          posted = ops_.pooled;
+          for (uint32_t k = 0; rc == BP_OK && !posted && k < n_taken; k++)
+            if (!gouts[k].p) { rc = BP_ERR_DEVICE; own = text("node %u of the shard returned no proof", ids[k]); }
+          if (rc == BP_OK && !posted) posted = true;  // (the containers are handed over below)
         } else if (nid < n_) {
           rc = ops_.leaf(nid, ops_.pooled ? this : nullptr, &b.p, &b.n, &posted);
         } else {
@@ -320,11 +391,16 @@ class TreeRun : public RecPool {
       if (rc) {
         std::free(b.p);
         for (auto& o : outs) std::free(o.p);
+        for (auto& o : gouts) std::free(o.p);
         fail_with(rc, own);
         return;
       }
       if (!have) {
         for (size_t k = 0; k < batch.size(); k++) complete(*batch[k], outs[k].p, outs[k].n);
+      } else if (n_group) {
+        std::lock_guard<std::mutex> lk(mu_);
+        for (uint32_t k = 0; k < n_taken; k++)
+          if (gouts[k].p) node_done_guarded(ids[k], gouts[k].p, gouts[k].n);
       } else if (b.p) {
         std::lock_guard<std::mutex> lk(mu_);
         node_done_guarded(nid, b.p, b.n);
@@ -332,6 +408,8 @@ class TreeRun : public RecPool {
     }
   }
 
+  static constexpr uint32_t kMaxGroup = 8;  // (the prover's MAX_BATCH)
+  uint32_t n_threads_ = 1, busy_ = 0, lanes_used_ = 0;  // under mu_
   const uint32_t n_;
   const std::vector<std::pair<uint32_t, uint32_t>> plan_;
   const TreeOps ops_;
@@ -359,6 +437,14 @@ int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const 
 // the host half of bp_generate_agg_proof: everything but the proving
 int agg_proof_prepare(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg, const uint8_t* rhs, size_t rhs_len,
                       int rhs_is_agg, RecJob* job);
+// up to n <= MAX_BATCH transactions on one group lease (proofgen.cpp: GroupLease, prove_tables_group): the first g the
+// lease grants -- granted(g) is called when it is held --, roots posted as the jobs of nodes[i], or without a pool the
+// containers in outs[i].  data nullable, and every data[i].
+int txn_group_pooled(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const bp_txn_witness* const* data,
+                     const volatile uint8_t* abort_flag, RecPool* pool, const uint32_t* nodes, const std::function<void(uint32_t)>& granted,
+                     TreeBuf* outs);
+uint32_t state_workers(const bp_state* s);
+uint32_t txn_group_of(const bp_state* s);  // Tune::txn_group, or what the state's queue count asks for (0 = automatic)
 // the jobs proved in lock-step on one leased prover; (*out)[k] = the container of jobs[k], remembered as this state's own
 int rec_prove_jobs(const bp_state* s, const std::vector<std::unique_ptr<RecJob>>& jobs, const volatile uint8_t* abort_flag,
                    std::vector<TreeBuf>* out);

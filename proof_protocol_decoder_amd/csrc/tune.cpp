@@ -38,6 +38,8 @@ void bp_tune_side_lanes(int n) { bpg::tune().side_lanes.store(n < 0 ? 0 : n); }
 // A switch between two schedules of the same proofs, not one of the kernel knobs that bp_debug_tune_state lists (its
 // lines are a fixed set); bp_tune_reset puts it back like the others.
 void bp_tune_rec_riders(int on) { bpg::tune().rec_riders.store(on != 0); }
+// Another schedule of the same proofs (tune.hpp): like rec_riders outside bp_debug_tune_state's fixed lines.
+void bp_tune_txn_group(int n) { bpg::tune().txn_group.store(n < 1 ? 0 : (n > (int)bpg::MAX_BATCH ? (int)bpg::MAX_BATCH : n)); }
 // The switch point between two forms of one kernel (range_mult.hip); like rec_riders outside bp_debug_tune_state's fixed
 // lines.  Out of range = the default.
 void bp_tune_range_lds_log(int log_range) {
@@ -51,6 +53,7 @@ void bp_tune_reset(void) {
   BPG_KNOBS(X)
 #undef X
   t.rec_riders.store(defaults.rec_riders.load());
+  t.txn_group.store(defaults.txn_group.load());
   t.range_lds_log.store(defaults.range_lds_log.load());
 }
 

@@ -70,6 +70,16 @@ struct Tune {
   // at the end of the tree is proved a batch at a time; 0 = every node is proved where it is started, one proof per
   // chain of launches (the scheduling up to this knob).  Read once per call.  Measurements: profiles/rec_riders_ab.txt.
   std::atomic<int> rec_riders{1};
+  // Transactions a thread of bp_prove_shard / bp_prove_shard_gi starts at a time: it leases that many provers whose
+  // arenas are neighbours (proofgen.cpp: GroupLease) and proves table t of all of them in lock-step batches wherever
+  // their shapes agree (prove_tables_group), t = 0..6, each transaction on its own transcript; the recursion chains
+  // follow one transaction after the other.  1 = one transaction per thread (the schedule up to this knob).  0 = by the
+  // state: 3 where bp_state_build saw fewer hardware queues than the state has prover streams, else 1.  Measured on the
+  // 256-txn block, 20 streams, three alternating runs each (profiles/txn_groups_ab.txt): at 4 queues 35.22 (1) / 35.39
+  // (2) / 37.97 (3) txn-proofs/s -- 3 is +7.8 %, 7.8 x the parent's spread, 2 is inside it --; at 32 queues, where every
+  // stream has a queue of its own, 40.04 (1) against 39.39 (3): halving the streams at work costs more there than the
+  // launches save.  Read once per call.
+  std::atomic<int> txn_group{0};
 
   // ---- range-check multiplicities (range_mult.hip)
   // bp_range_multiplicities counts in a per-workgroup LDS histogram up to 2^k values (1 .. 14: 32-bit counters, 64 KiB at

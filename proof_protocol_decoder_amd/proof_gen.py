@@ -388,6 +388,25 @@ def generate_txn_table_proofs(p_state, gen_inputs, keccak_inputs=None, witness=N
     return take_buffer(out, n)
 
 
+def generate_txn_table_proofs_group(p_state, gen_inputs_list):
+    """bp_generate_txn_table_proofs_group: generate_txn_table_proofs for several transactions at a time, table t of those
+    whose shapes agree proved in lock-step on one group of provers.  The blobs are the single call's, byte for byte."""
+    L = _bind()
+    irs = [g.to_bytes() if isinstance(g, TxnProofGenIR) else bytes(g) for g in gen_inputs_list]
+    n = len(irs)
+    if n < 1 or any(len(ir) != len(irs[0]) for ir in irs):
+        raise ValueError("one or more IRs of one length")
+    structs = [_witness_struct(g, None, None) if isinstance(g, TxnProofGenIR) else (None, []) for g in gen_inputs_list]
+    data = (C.c_void_p * n)(*[C.addressof(w) if w is not None else None for w, _ in structs])
+    outs, lens = (C.POINTER(C.c_uint8) * n)(), (C.c_size_t * n)()
+    L.bp_generate_txn_table_proofs_group.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
+    raw = b"".join(irs)
+    check(L.bp_generate_txn_table_proofs_group(p_state._h, raw, len(irs[0]), n, data, None, outs, lens))
+    del structs
+    return [take_buffer(outs[i], C.c_size_t(lens[i])) for i in range(n)]
+
+
 class WitnessTable(C.Structure):
     """bp_witness_table (include/bpg.h)"""
     from ._lib import AirViolation as _V

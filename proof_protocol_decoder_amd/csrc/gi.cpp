@@ -295,25 +295,27 @@ int chain_start(const std::vector<Entry>& es, bp_gi_chain* chain) {
   for (int i = 0; i < 4; i++) chain->state_root[i] = le64(h.data() + 8 * i) % gl::P;
   return BP_OK;
 }
-// pool (nullable): the shard's job pool -- the proof's root is then posted as the job of `node` instead of being proved here
-int prove_entry(const bp_state* s, const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, const volatile uint8_t* abort_flag,
-                uint8_t** out, size_t* out_len, bpg::RecPool* pool = nullptr, uint32_t node = 0) {
-  EntryWork w;
-  if (int rc = entry_work(e, o, chain, true, &w)) return rc;
-  if (!w.given[T_KECCAK]) {  // (every other table's work is that of the hashed bytes: entry_work)
-    if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), nullptr, abort_flag, pool, node);
-    return bp_generate_txn_proof_u8(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), abort_flag, out, out_len);
-  }
-  bp_txn_witness tw;
-  std::memset(&tw, 0, sizeof(tw));
+// the entry's own work as the witness of a transaction; null where the entry has none (every other table's work is that
+// of the hashed bytes: entry_work).  *tw points into w.
+const bp_txn_witness* witness_of_work(const EntryWork& w, bp_txn_witness* tw) {
+  if (!w.given[T_KECCAK]) return nullptr;
+  std::memset(tw, 0, sizeof(*tw));
   for (int t = 0; t < BP_NUM_TABLES; t++) {
     if (!w.given[t]) continue;
-    tw.*TABLES[t].data = w.items[t].data();
-    tw.*TABLES[t].n = w.items[t].size() / TABLES[t].item_words;
-    tw.*TABLES[t].has = 1;
+    tw->*TABLES[t].data = w.items[t].data();
+    tw->*TABLES[t].n = w.items[t].size() / TABLES[t].item_words;
+    tw->*TABLES[t].has = 1;
   }
-  if (pool) return bpg::txn_proof_pooled(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, pool, node);
-  return bp_generate_txn_proof_witness(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), &tw, abort_flag, out, out_len);
+  return tw;
+}
+int prove_entry(const bp_state* s, const Entry& e, const bp_gi_options& o, bp_gi_chain* chain, const volatile uint8_t* abort_flag,
+                uint8_t** out, size_t* out_len) {
+  EntryWork w;
+  if (int rc = entry_work(e, o, chain, true, &w)) return rc;
+  bp_txn_witness tw;
+  const bp_txn_witness* data = witness_of_work(w, &tw);
+  if (!data) return bp_generate_txn_proof_u8(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), abort_flag, out, out_len);
+  return bp_generate_txn_proof_witness(s, reinterpret_cast<const uint8_t*>(w.ir), sizeof(w.ir), data, abort_flag, out, out_len);
 }
 
 // ---------------------------------------------------------------- aggregation plan + scheduler
@@ -333,16 +335,14 @@ int make_plan(uint32_t n, uint32_t shape, std::vector<std::pair<uint32_t, uint32
 // what is ready a batch at a time -- the end of the tree, and all of bp_aggregate_proofs.  bp_run_shard's callbacks are
 // opaque: every node is proved where it is started.
 // leaf_is_agg (nullable): the kinds of the leaves when they are proofs made elsewhere (bp_aggregate_proofs); else txn proofs
-// pooled_leaf (nullable): the leaf callback of a run with jobs -- posts node i's root as a job instead of proving it
 // group_leaf (nullable): leaves ids[0..n) started as one group on the state's provers (TreeOps::leaf_group); with it and
-// Tune::txn_group > 1 a thread starts up to that many transactions at a time and proves their table proofs in lock-step
-using PooledLeaf = int (*)(void* ctx, uint32_t i, bpg::RecPool* pool);
+// Tune::txn_group > 1 a thread starts up to that many transactions at a time and proves their table proofs in lock-step.
+// In a run with jobs it is also the single leaf, as a group of one: node i's root is posted as a job instead of being proved
 using GroupLeaf = int (*)(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
                           bpg::TreeBuf* outs);
 int run_tree(uint32_t n, const bp_shard_options* opt, bp_shard_leaf_fn leaf, bp_shard_agg_fn agg, void* ctx,
              const volatile uint8_t* abort_flag, uint8_t** root_out, size_t* root_len, uint8_t** leaf_out, size_t* leaf_len,
-             const int* leaf_is_agg = nullptr, const bp_state* s = nullptr, PooledLeaf pooled_leaf = nullptr,
-             GroupLeaf group_leaf = nullptr) {
+             const int* leaf_is_agg = nullptr, const bp_state* s = nullptr, GroupLeaf group_leaf = nullptr) {
   if (!leaf || !agg || !root_out || !root_len) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: null argument");
   if ((leaf_out == nullptr) != (leaf_len == nullptr)) return fail(BP_ERR_INVALID_INPUT, "bp_run_shard: leaf_out and leaf_len go together");
   std::vector<std::pair<uint32_t, uint32_t>> plan;
@@ -352,9 +352,9 @@ int run_tree(uint32_t n, const bp_shard_options* opt, bp_shard_leaf_fn leaf, bp_
   ops.cap = ops.pooled ? bpg::rec_batch_cap(s) : 1;
   ops.last_error = [] { return std::string(bp_last_error()); };
   ops.leaf = [=](uint32_t i, bpg::RecPool* pool, uint8_t** out, size_t* out_len, bool* posted) {
-    if (pool && pooled_leaf) {
+    if (pool && group_leaf) {
       *posted = true;
-      return pooled_leaf(ctx, i, pool);
+      return group_leaf(ctx, &i, 1, pool, [](uint32_t) {}, nullptr);
     }
     return leaf(ctx, i, out, out_len);
   };
@@ -408,10 +408,6 @@ int ir_leaf(void* ctx, uint32_t i, uint8_t** out, size_t* out_len) {
   const IrShard* c = static_cast<const IrShard*>(ctx);
   return bp_generate_txn_proof_u8(c->s, c->irs + (size_t)i * c->stride, BP_IR_WORDS * 8, c->abort_flag, out, out_len);
 }
-int ir_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
-  const IrShard* c = static_cast<const IrShard*>(ctx);
-  return bpg::txn_proof_pooled(c->s, c->irs + (size_t)i * c->stride, BP_IR_WORDS * 8, nullptr, c->abort_flag, pool, i);
-}
 int ir_leaf_group(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
                   bpg::TreeBuf* outs) {
   const IrShard* c = static_cast<const IrShard*>(ctx);
@@ -435,11 +431,6 @@ int gi_leaf(void* ctx, uint32_t i, uint8_t** out, size_t* out_len) {
   bp_gi_chain ch = (*c->chain_before)[c->first + i];
   return prove_entry(c->s, (*c->es)[c->first + i], *c->o, &ch, c->abort_flag, out, out_len);
 }
-int gi_leaf_pooled(void* ctx, uint32_t i, bpg::RecPool* pool) {
-  const GiShard* c = static_cast<const GiShard*>(ctx);
-  bp_gi_chain ch = (*c->chain_before)[c->first + i];
-  return prove_entry(c->s, (*c->es)[c->first + i], *c->o, &ch, c->abort_flag, nullptr, nullptr, pool, i);
-}
 // a group of entries: the work of each as prove_entry makes it, then one call for the group
 int gi_leaf_group(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted,
                   bpg::TreeBuf* outs) {
@@ -452,15 +443,7 @@ int gi_leaf_group(void* ctx, const uint32_t* ids, uint32_t n, bpg::RecPool* pool
     bp_gi_chain ch = (*c->chain_before)[c->first + ids[k]];
     if (int rc = entry_work((*c->es)[c->first + ids[k]], *c->o, &ch, true, &w[k])) return rc;
     irs[k] = reinterpret_cast<const uint8_t*>(w[k].ir);
-    if (!w[k].given[T_KECCAK]) continue;  // (every other table's work is that of the hashed bytes: entry_work)
-    std::memset(&tw[k], 0, sizeof(tw[k]));
-    for (int t = 0; t < BP_NUM_TABLES; t++) {
-      if (!w[k].given[t]) continue;
-      tw[k].*TABLES[t].data = w[k].items[t].data();
-      tw[k].*TABLES[t].n = w[k].items[t].size() / TABLES[t].item_words;
-      tw[k].*TABLES[t].has = 1;
-    }
-    data[k] = &tw[k];
+    data[k] = witness_of_work(w[k], &tw[k]);
   }
   return bpg::txn_group_pooled(c->s, n, irs.data(), sizeof(w[0].ir), data.data(), c->abort_flag, pool, ids, granted, outs);
 }
@@ -564,11 +547,10 @@ int bp_prove_shard(const bp_state* s, const uint8_t* irs, size_t ir_stride, uint
   struct Ctx { const bp_state* s; IrShard sh; } c{s, {s, irs, ir_stride, abort_flag}};
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
   auto leaf = [](void* ctx, uint32_t i, uint8_t** out, size_t* out_len) { return ir_leaf(&static_cast<Ctx*>(ctx)->sh, i, out, out_len); };
-  auto pooled = [](void* ctx, uint32_t i, bpg::RecPool* pool) { return ir_leaf_pooled(&static_cast<Ctx*>(ctx)->sh, i, pool); };
   auto group = [](void* ctx, const uint32_t* ids, uint32_t k, bpg::RecPool* pool, const std::function<void(uint32_t)>& granted, bpg::TreeBuf* outs) {
     return ir_leaf_group(&static_cast<Ctx*>(ctx)->sh, ids, k, pool, granted, outs);
   };
-  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, pooled, group);
+  return run_tree(n, &o, leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, group);
 }
 BPG_ABI_CATCH("bp_prove_shard")
 
@@ -591,7 +573,7 @@ int bp_prove_shard_gi(const bp_state* s, const uint8_t* geni, size_t len, uint32
   }
   GiShard c{s, &es, gi, first, &before, abort_flag};
   bp_shard_options o{default_threads(s, opt), opt ? opt->tree_shape : 0};
-  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, gi_leaf_pooled, gi_leaf_group);
+  return run_tree(n, &o, gi_leaf, state_agg, &c, abort_flag, root_out, root_len, txn_out, txn_len, nullptr, s, gi_leaf_group);
 }
 BPG_ABI_CATCH("bp_prove_shard_gi")
 

@@ -78,7 +78,7 @@ struct bp_state {
   mutable std::vector<std::unique_ptr<Worker>> workers;
   // The workers' arenas are slices of a few large device allocations (one, where the device grants it): the slices of a
   // slab lie one behind the other, stride slice_stride, so a run of adjacent idle workers is one contiguous piece of
-  // memory (GroupLease).  table: who is idle, who is whose neighbour (worker_table.hpp); under mu.
+  // memory (ProverLease).  table: who is idle, who is whose neighbour (worker_table.hpp); under mu.
   std::vector<void*> slabs;
   size_t slice_stride = 0;
   mutable WorkerTable table;
@@ -98,66 +98,49 @@ struct bp_verifier_state {
 
 namespace {
 
-struct WorkerLease {
-  const bp_state* s;
-  Worker* w;
-  uint32_t index;
-  size_t mark;
-  explicit WorkerLease(const bp_state* st) : s(st) {
-    std::unique_lock<std::mutex> lk(s->mu);
-    s->cv.wait(lk, [&] { return s->table.any_idle(); });
-    index = (uint32_t)s->table.take_one();
-    w = s->workers[index].get();
-    mark = w->arena.mark();
-    prover_active(+1);
-  }
-  ~WorkerLease() {
-    prover_active(-1);
-    (void)hipStreamSynchronize(w->stream);
-    w->arena.release(mark);
-    w->abort_flag = nullptr;
-    w->abort_flag_u8 = nullptr;
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->table.give(index);
-    s->cv.notify_all();
-  }
-};
-
-// A RUN of workers whose arenas are neighbours, for the transactions a prover takes at a time (Tune::txn_group): up to
-// `want` adjacent idle workers, all or nothing under bp_state::mu -- the longest adjacent run there is when `want` are
-// not to be had, never a wait for adjacency; it blocks only while no worker is idle, as WorkerLease does, and holds
+// The prover(s) a call works on.  want == 1 (every call but a group of transactions): one worker by take_one's rule --
+// an idle worker with no idle neighbour first, else the one released last -- which spares the runs for groups.
+// want > 1 (the transactions a prover takes at a time, Tune::txn_group): a RUN of workers whose arenas are neighbours,
+// up to `want` adjacent idle workers, all or nothing under bp_state::mu -- the longest adjacent run there is when `want`
+// are not to be had, never a wait for adjacency.  Either way the lease blocks only while no worker is idle and holds
 // nothing while it waits.  The first worker of the run leads: its stream, its mailbox, and for the time of the lease an
 // arena that spans the run's slices.  The others lend their pinned buffers (witness staging); their streams stay idle.
 // A worker that kept something in its arena across leases (none does: every lease releases to the mark it found, which
 // is 0) would end the run in front of it: the spanning view covers clean slices only.
-struct GroupLease {
+struct ProverLease {
   const bp_state* s;
   std::vector<Worker*> ws;  // ws[0] leads
+  Worker* w;                // ws[0]
   uint32_t first = 0;
   size_t mark = 0, own_cap = 0;
-  GroupLease(const bp_state* st, uint32_t want) : s(st) {
+  explicit ProverLease(const bp_state* st, uint32_t want = 1) : s(st) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv.wait(lk, [&] { return s->table.any_idle(); });
-    uint32_t n = s->table.take_run(want, &first);
-    uint32_t clean = 1;
-    while (clean < n && s->workers[first + clean]->arena.mark() == 0) clean++;
-    for (uint32_t k = clean; k < n; k++) s->table.give(first + k);
-    n = clean;
+    uint32_t n = 1;
+    if (want > 1) {
+      n = s->table.take_run(want, &first);
+      uint32_t clean = 1;
+      while (clean < n && s->workers[first + clean]->arena.mark() == 0) clean++;
+      for (uint32_t k = clean; k < n; k++) s->table.give(first + k);
+      n = clean;
+    } else {
+      first = (uint32_t)s->table.take_one();
+    }
     for (uint32_t k = 0; k < n; k++) ws.push_back(s->workers[first + k].get());
-    Worker& lead = *ws[0];
-    mark = lead.arena.mark();
-    own_cap = lead.arena.capacity();
-    lead.arena.span((size_t)(n - 1) * s->slice_stride + own_cap);
+    w = ws[0];
+    mark = w->arena.mark();
+    own_cap = w->arena.capacity();
+    w->arena.span((size_t)(n - 1) * s->slice_stride + own_cap);
     prover_active((int)n);  // a group counts as the transactions it proves: the load-dependent choices see today's load
   }
   uint32_t size() const { return (uint32_t)ws.size(); }
-  ~GroupLease() {
+  ~ProverLease() {
     prover_active(-(int)ws.size());
-    (void)hipStreamSynchronize(ws[0]->stream);
-    ws[0]->arena.release(mark);
-    ws[0]->arena.span(own_cap);
-    ws[0]->abort_flag = nullptr;
-    ws[0]->abort_flag_u8 = nullptr;
+    (void)hipStreamSynchronize(w->stream);
+    w->arena.release(mark);
+    w->arena.span(own_cap);
+    w->abort_flag = nullptr;
+    w->abort_flag_u8 = nullptr;
     std::lock_guard<std::mutex> lk(s->mu);
     for (uint32_t k = 0; k < ws.size(); k++) s->table.give(first + k);
     s->cv.notify_all();
@@ -699,14 +682,13 @@ struct TableProofs {
 // generate_traces: the seven witnesses of a transaction in the worker's arena (d_trace[t]: n_cols x 2^log_n, column-major).
 // What is to be made, and the refusals of data that cannot form one statement, are plan_traces' (txn_tables.cpp); here
 // are the allocations, the staging and the launches.  Shared by the prover and the witness pre-flight.
-// stage (nullable): the pinned buffer the caller's items are staged through when it is not the worker's own (a group's
-// transactions use the buffers of the workers the group has leased); allocated: d_trace is the caller's already (a
-// group lays the equally shaped traces of its transactions one behind the other, as commit_batch wants them).
-static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES],
-                        uint64_t* d_trace[BP_NUM_TABLES], const Worker* stage = nullptr, bool allocated = false) {
+// d_trace: allocated by the caller (alloc_traces).  stage: the worker whose pinned buffer the caller's items are staged
+// through -- w itself, or for a group's transactions the worker each of them has leased.
+static int build_traces(Worker& w, const Worker& stage, const uint64_t* I, const TxnWitness* wit, const StarkCfg tcfg[BP_NUM_TABLES],
+                        uint64_t* const d_trace[BP_NUM_TABLES]) {
   int r;
-  uint64_t* const pinned = stage ? stage->pinned : w.pinned;
-  const size_t pinned_words = stage ? stage->pinned_words : w.pinned_words;
+  uint64_t* const pinned = stage.pinned;
+  const size_t pinned_words = stage.pinned_words;
   bool given[BP_NUM_TABLES];
   size_t n_given[BP_NUM_TABLES];
   for (int t = 0; t < BP_NUM_TABLES; t++) {
@@ -718,11 +700,6 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
   const bool lookup_kf = plan.lookup[L_SPONGE_KECCAK], lookup_bm = plan.lookup[L_PACKING_MEMORY], lookup_sl = plan.lookup[L_SPONGE_LOGIC];
   // a looking table before the table it looks up (sponge before Keccak-f, byte packing before memory)
   static const int GEN_ORDER[BP_NUM_TABLES] = {T_KECCAK_SPONGE, T_ARITHMETIC, T_BYTE_PACKING, T_CPU, T_KECCAK, T_LOGIC, T_MEMORY};
-  for (int t = 0; t < BP_NUM_TABLES && !allocated; t++) {
-    const uint64_t N = (uint64_t)1 << tcfg[t].log_n;
-    d_trace[t] = w.arena.alloc_words((size_t)tcfg[t].n_cols * N);
-    if (!d_trace[t]) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLES[t].name);
-  }
   const uint64_t* d_sponge = d_trace[T_KECCAK_SPONGE];
   const uint32_t sponge_log_n = tcfg[T_KECCAK_SPONGE].log_n;
   const uint64_t sponge_N = (uint64_t)1 << sponge_log_n;
@@ -788,82 +765,6 @@ static int build_traces(Worker& w, const uint64_t* I, const TxnWitness* wit, con
     }
   }
   return BP_OK;
-}
-
-// generate_traces + the seven table proofs on one transcript (plonky2_evm `prove`), on the leased worker
-static int prove_tables(const bp_state* s, Worker& w, const uint64_t* I, const TxnWitness* wit, TableProofs* tp) {
-  StarkCfg* tcfg = tp->tcfg;
-  int r;
-  // generate_traces + trace commitments for all tables, then the shared transcript prologue
-  uint64_t* d_trace[BP_NUM_TABLES];
-  Committed trace[BP_NUM_TABLES];
-  Challenger ch;
-  auto given = [&](int t) { return given_table(wit, tcfg, t); };
-  if ((r = build_traces(w, I, wit, tcfg, d_trace))) return r;
-  // The seven trace commitments do not depend on each other.  Under load they queue on this prover's stream like
-  // everything else (the chip is full); a prover that is ALONE on the device -- a lone transaction, the last one of a
-  // shard -- borrows the streams of up to three idle workers and the commitments overlap: the wide Keccak table's long
-  // sponge chains no longer have the chip to themselves (largest first, each to the lane with the least work so far).
-  std::vector<std::unique_ptr<SideLane>> sides;
-  if (s && provers_active() <= tune().side_lanes.load(std::memory_order_relaxed))
-    for (int k = 0; k < 3; k++) {
-      std::unique_ptr<SideLane> l = SideLane::try_acquire(s);
-      if (!l) break;
-      sides.push_back(std::move(l));
-    }
-  if (sides.empty()) {
-    for (int t = 0; t < BP_NUM_TABLES; t++)
-      if ((r = commit(w, d_trace[t], tcfg[t].n_cols, tcfg[t].log_n, tcfg[t].rate_bits, tcfg[t].cap_height, false, &trace[t]))) return r;
-  } else {
-    BPG_HIP(hipEventRecord(w.sync_event, w.stream));  // the witnesses are made on this prover's stream
-    std::vector<Worker*> lane = {&w};
-    for (auto& l : sides) {
-      BPG_HIP(hipStreamWaitEvent(l->w->stream, w.sync_event, 0));
-      lane.push_back(l->w);
-    }
-    std::vector<uint64_t> load(lane.size(), 0);
-    std::vector<size_t> slots(lane.size(), 0);
-    int order[BP_NUM_TABLES];
-    for (int t = 0; t < BP_NUM_TABLES; t++) order[t] = t;
-    auto cells = [&](int t) { return (uint64_t)tcfg[t].n_cols << tcfg[t].log_n; };
-    std::sort(order, order + BP_NUM_TABLES, [&](int a, int b) { return cells(a) != cells(b) ? cells(a) > cells(b) : a < b; });
-    PendingCommit pc[BP_NUM_TABLES];
-    for (int oi = 0; oi < BP_NUM_TABLES; oi++) {
-      const int t = order[oi];
-      const size_t k = std::min_element(load.begin(), load.end()) - load.begin();
-      if ((r = commit_launch(w, *lane[k], slots[k], d_trace[t], tcfg[t].n_cols, 1, tcfg[t].log_n, tcfg[t].rate_bits,
-                             tcfg[t].cap_height, false, &pc[t])))
-        return r;
-      load[k] += cells(t);
-      slots[k] += (size_t)4 << tcfg[t].cap_height;
-    }
-    for (int t = 0; t < BP_NUM_TABLES; t++)
-      if ((r = commit_finish(pc[t], &trace[t]))) return r;
-    sides.clear();  // the lanes are drained (commit_finish waited for each): back to their owners
-  }
-  for (int t = 0; t < BP_NUM_TABLES; t++) ch.observe(trace[t].cap.data(), trace[t].cap.size());
-  ch.observe(tp->pv.data(), tp->pv.size());
-  Ctl& ctl = tp->ctl;
-  for (int i = 0; i < 4; i++) ctl.v[i] = ch.challenge();
-  // table proofs: sequential, one transcript threaded through all of them (plonky2_evm prover)
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before table %s", TABLES[t].name);
-    const size_t mark = w.arena.mark();
-    Challenger before = ch;  // the transcript as the verifier of this table proof starts from it
-    if ((r = stark_prove(w, tcfg[t], nullptr, trace[t], d_trace[t], ctl, ch, tp->proof[t], tp->first_leaf[t]))) return r;
-    if (given(t)) {
-      // The prover does not check a witness, and nothing downstream of this call verifies the table proofs (upstream's
-      // root circuit would): data that came from the caller is therefore checked here, by the CPU verifier on the
-      // proof just made -- a log that is not a memory, a block that is not padded, ... ends the call.
-      if (stark_verify(tcfg[t], nullptr, ctl, before, tp->proof[t].data(), tp->proof[t].size()) != BP_OK) {
-        const std::string why = bp_last_error();
-        return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: %s", TABLES[t].name, why.c_str());
-      }
-    }
-    w.arena.release(mark);
-  }
-  // the tables must be ONE statement: what the sponge table hashes is what the Keccak-f table permutes
-  return check_lookups(tcfg, tp->proof);
 }
 
 // The seven table proofs as bp_generate_txn_table_proofs hands them out:
@@ -1013,43 +914,103 @@ struct SubBatch {  // the transactions of a group whose table t has one shape, a
   uint32_t txn[MAX_BATCH];
   uint64_t* d_traces = nullptr;  // [n][n_cols][N]
 };
-
-// prove_tables for g >= 2 transactions on the group's leading worker (its arena spans the group's slices)
-int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* const* tx, uint32_t g) {
-  int r;
-  // per table the sub-batches, in the order of their first transaction; a transaction's place in its sub-batch
-  std::vector<SubBatch> subs[BP_NUM_TABLES];
-  std::vector<std::array<uint64_t*, BP_NUM_TABLES>> d_trace(g);
+struct TraceLayout {
+  std::vector<SubBatch> subs[BP_NUM_TABLES];                      // per table, in the order of their first transaction
+  std::vector<std::array<uint64_t*, BP_NUM_TABLES>> d_trace;      // per transaction: its place in its sub-batches
+};
+// The traces of g transactions in w's arena (tcfg[i]: the seven shapes of transaction i): table by table, the equally
+// shaped traces of a sub-batch one behind the other, as commit_batch wants them.  A lone transaction's seven traces lie
+// in table order.
+int alloc_traces(Worker& w, const StarkCfg* const* tcfg, uint32_t g, TraceLayout* out) {
+  out->d_trace.resize(g);
   for (int t = 0; t < BP_NUM_TABLES; t++) {
+    std::vector<SubBatch>& subs = out->subs[t];
     for (uint32_t i = 0; i < g; i++) {
-      const StarkCfg& c = tx[i]->tp.tcfg[t];
+      const StarkCfg& c = tcfg[i][t];
       const uint32_t cap = table_batch_cap(c, w.pinned_words);
       SubBatch* sb = nullptr;
-      for (auto& cand : subs[t])
-        if (cand.n < cap && same_shape(tx[cand.txn[0]]->tp.tcfg[t], c)) { sb = &cand; break; }
-      if (!sb) { subs[t].emplace_back(); sb = &subs[t].back(); }
+      for (auto& cand : subs)
+        if (cand.n < cap && same_shape(tcfg[cand.txn[0]][t], c)) { sb = &cand; break; }
+      if (!sb) { subs.emplace_back(); sb = &subs.back(); }
       sb->txn[sb->n++] = i;
     }
-    for (auto& sb : subs[t]) {
-      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
+    for (auto& sb : subs) {
+      const StarkCfg& c = tcfg[sb.txn[0]][t];
       const size_t words = (size_t)c.n_cols << c.log_n;
       sb.d_traces = w.arena.alloc_words(words * sb.n);
       if (!sb.d_traces) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB) for table %s", w.arena.capacity() >> 20, TABLES[t].name);
-      for (uint32_t k = 0; k < sb.n; k++) d_trace[sb.txn[k]][t] = sb.d_traces + k * words;
+      for (uint32_t k = 0; k < sb.n; k++) out->d_trace[sb.txn[k]][t] = sb.d_traces + k * words;
     }
   }
-  // generate_traces per transaction (its seed, plan and lookups), each staged through the pinned buffer of its own worker
-  for (uint32_t i = 0; i < g; i++)
-    if ((r = build_traces(w, tx[i]->I, tx[i]->wit, tx[i]->tp.tcfg, d_trace[i].data(), stage[i], true))) return r;
-  // trace commitments: one commit_batch per sub-batch
-  std::vector<std::array<Committed, BP_NUM_TABLES>> trace(g);
-  for (int t = 0; t < BP_NUM_TABLES; t++)
-    for (auto& sb : subs[t]) {
-      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
-      Committed cm[MAX_BATCH];
-      if ((r = commit_batch(w, sb.d_traces, c.n_cols, sb.n, c.log_n, c.rate_bits, c.cap_height, false, cm))) return r;
-      for (uint32_t k = 0; k < sb.n; k++) trace[sb.txn[k]][t] = std::move(cm[k]);
+  return BP_OK;
+}
+
+// The trace commitments of a group (trace[i][t]: table t of transaction i): one commit_batch per sub-batch.
+// The seven commitments of a transaction do not depend on each other.  Under load they queue on the prover's stream like
+// everything else (the chip is full); a prover that is ALONE on the device with ONE transaction -- a lone call, the last
+// one of a shard -- borrows the streams of up to three idle workers and the commitments overlap: the wide Keccak table's
+// long sponge chains no longer have the chip to themselves (largest first, each to the lane with the least work so far).
+// A group never takes lanes, whatever Tune::side_lanes says (it counts as the provers it holds).
+int commit_traces(const bp_state* s, Worker& w, const StarkCfg* const* tcfg, const TraceLayout& lay,
+                  std::array<Committed, BP_NUM_TABLES>* trace) {
+  int r;
+  std::vector<std::unique_ptr<SideLane>> sides;
+  if (lay.d_trace.size() == 1 && provers_active() <= tune().side_lanes.load(std::memory_order_relaxed))
+    for (int k = 0; k < 3; k++) {
+      std::unique_ptr<SideLane> l = SideLane::try_acquire(s);
+      if (!l) break;
+      sides.push_back(std::move(l));
     }
+  if (sides.empty()) {
+    for (int t = 0; t < BP_NUM_TABLES; t++)
+      for (const SubBatch& sb : lay.subs[t]) {
+        const StarkCfg& c = tcfg[sb.txn[0]][t];
+        Committed cm[MAX_BATCH];
+        if ((r = commit_batch(w, sb.d_traces, c.n_cols, sb.n, c.log_n, c.rate_bits, c.cap_height, false, cm))) return r;
+        for (uint32_t k = 0; k < sb.n; k++) trace[sb.txn[k]][t] = std::move(cm[k]);
+      }
+    return BP_OK;
+  }
+  const StarkCfg* c = tcfg[0];
+  BPG_HIP(hipEventRecord(w.sync_event, w.stream));  // the witnesses are made on this prover's stream
+  std::vector<Worker*> lane = {&w};
+  for (auto& l : sides) {
+    BPG_HIP(hipStreamWaitEvent(l->w->stream, w.sync_event, 0));
+    lane.push_back(l->w);
+  }
+  std::vector<uint64_t> load(lane.size(), 0);
+  std::vector<size_t> slots(lane.size(), 0);
+  int order[BP_NUM_TABLES];
+  for (int t = 0; t < BP_NUM_TABLES; t++) order[t] = t;
+  auto cells = [&](int t) { return (uint64_t)c[t].n_cols << c[t].log_n; };
+  std::sort(order, order + BP_NUM_TABLES, [&](int a, int b) { return cells(a) != cells(b) ? cells(a) > cells(b) : a < b; });
+  PendingCommit pc[BP_NUM_TABLES];
+  for (int oi = 0; oi < BP_NUM_TABLES; oi++) {
+    const int t = order[oi];
+    const size_t k = std::min_element(load.begin(), load.end()) - load.begin();
+    if ((r = commit_launch(w, *lane[k], slots[k], lay.d_trace[0][t], c[t].n_cols, 1, c[t].log_n, c[t].rate_bits, c[t].cap_height, false, &pc[t])))
+      return r;
+    load[k] += cells(t);
+    slots[k] += (size_t)4 << c[t].cap_height;
+  }
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    if ((r = commit_finish(pc[t], &trace[0][t]))) return r;
+  return BP_OK;  // the lanes are drained (commit_finish waited for each): back to their owners
+}
+
+// generate_traces + the seven table proofs of each of g >= 1 transactions (plonky2_evm `prove`), on the lease's leading
+// worker (its arena spans the group's slices); stage[i]: the worker transaction i stages its witness data through
+int prove_tables(const bp_state* s, Worker& w, const std::vector<Worker*>& stage, GroupTxn* const* tx, uint32_t g) {
+  int r;
+  std::vector<const StarkCfg*> tcfg(g);
+  for (uint32_t i = 0; i < g; i++) tcfg[i] = tx[i]->tp.tcfg;
+  TraceLayout lay;
+  if ((r = alloc_traces(w, tcfg.data(), g, &lay))) return r;
+  // generate_traces per transaction (its seed, plan and lookups)
+  for (uint32_t i = 0; i < g; i++)
+    if ((r = build_traces(w, *stage[i], tx[i]->I, tx[i]->wit, tcfg[i], lay.d_trace[i].data()))) return r;
+  std::vector<std::array<Committed, BP_NUM_TABLES>> trace(g);
+  if ((r = commit_traces(s, w, tcfg.data(), lay, trace.data()))) return r;
   // every transaction's own transcript: its seven caps, its public values, its lookup challenges
   std::vector<Challenger> ch(g);
   for (uint32_t i = 0; i < g; i++) {
@@ -1061,11 +1022,11 @@ int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* c
   // the table proofs: t = 0..6 in order (one transcript per transaction runs through its seven), table t of the
   // transactions of a sub-batch in lock-step
   for (int t = 0; t < BP_NUM_TABLES; t++)
-    for (auto& sb : subs[t]) {
+    for (const SubBatch& sb : lay.subs[t]) {
       if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before table %s", TABLES[t].name);
-      const StarkCfg& c = tx[sb.txn[0]]->tp.tcfg[t];
+      const StarkCfg& c = tcfg[sb.txn[0]][t];
       const size_t mark = w.arena.mark();
-      Challenger before[MAX_BATCH], cur[MAX_BATCH];
+      Challenger before[MAX_BATCH], cur[MAX_BATCH];  // before: the transcript as the verifier of this table proof starts from it
       Committed tr[MAX_BATCH];
       const Committed* no_consts[MAX_BATCH] = {};
       const uint64_t* d_tv[MAX_BATCH];
@@ -1076,7 +1037,7 @@ int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* c
         const uint32_t i = sb.txn[k];
         before[k] = cur[k] = ch[i];
         tr[k] = trace[i][t];
-        d_tv[k] = d_trace[i][t];
+        d_tv[k] = lay.d_trace[i][t];
         ctl[k] = tx[i]->tp.ctl;
       }
       if ((r = stark_prove_batch(w, c, sb.n, no_consts, tr, d_tv, ctl, cur, proofs, &first_leaf[0][0]))) return r;
@@ -1086,14 +1047,17 @@ int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* c
         ch[i] = cur[k];
         tp.proof[t] = std::move(proofs[k]);
         std::memcpy(tp.first_leaf[t], first_leaf[k], 32);
-        if (given_table(tx[i]->wit, tp.tcfg, t) &&  // (prove_tables: data that came from the caller is checked by the CPU verifier)
-            stark_verify(c, nullptr, tp.ctl, before[k], tp.proof[t].data(), tp.proof[t].size()) != BP_OK) {
+        // The prover does not check a witness, and nothing downstream of this call verifies the table proofs (upstream's
+        // root circuit would): data that came from the caller is therefore checked here, by the CPU verifier on the
+        // proof just made -- a log that is not a memory, a block that is not padded, ... ends the call.
+        if (given_table(tx[i]->wit, tp.tcfg, t) && stark_verify(c, nullptr, tp.ctl, before[k], tp.proof[t].data(), tp.proof[t].size()) != BP_OK) {
           const std::string why = bp_last_error();
           return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: %s", TABLES[t].name, why.c_str());
         }
       }
       w.arena.release(mark);
     }
+  // the tables of a transaction must be ONE statement: what the sponge table hashes is what the Keccak-f table permutes
   for (uint32_t i = 0; i < g; i++)
     if ((r = check_lookups(tx[i]->tp.tcfg, tx[i]->tp.proof))) return r;
   return BP_OK;
@@ -1101,42 +1065,40 @@ int prove_tables_group(Worker& w, const std::vector<Worker*>& stage, GroupTxn* c
 
 }  // namespace
 
-// Up to n transactions on one group lease: as many as the lease grants (>= 1; `granted` hears the number the moment the
-// lease is held, so that a scheduler can hand the others on), their table proofs in lock-step, then each transaction's
-// recursion chains and root as txn_proof_impl runs them, one transaction after the other on the group's stream.
-// outs / out_lens per transaction (tables_only: the table-proof blobs); with a pool the roots are posted as the jobs of
-// nodes[i] instead.  The first failing transaction's status and message are the call's.
-static int txn_group_impl(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const TxnWitness* const* wits,
-                          const volatile uint8_t* abort_flag, bool tables_only, RecPool* pool, const uint32_t* nodes,
-                          const std::function<void(uint32_t)>* granted, uint8_t** outs, size_t* out_lens, uint32_t* n_done) {
+// Up to n transactions on one lease -- a lone transaction is a group of one: as many as the lease grants (>= 1;
+// `granted` hears the number the moment the lease is held, so that a scheduler can hand the others on), their table
+// proofs in lock-step, then each transaction's recursion chains and root, one transaction after the other on the
+// lease's stream.  outs / out_lens per transaction (tables_only: the table-proof blobs); with a pool the roots are
+// posted as the jobs of nodes[i] instead.  The first failing transaction's status and message are the call's.
+static int txn_proofs_impl(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const TxnWitness* const* wits,
+                           const volatile int32_t* abort_flag, const volatile uint8_t* abort_flag_u8, bool tables_only, RecPool* pool,
+                           const uint32_t* nodes, const std::function<void(uint32_t)>* granted, uint8_t** outs, size_t* out_lens,
+                           uint32_t* n_done) {
   if (!s || !irs || !n || ((!outs || !out_lens) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
-  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
   n = std::min<uint32_t>(n, MAX_BATCH);
-  std::vector<std::unique_ptr<GroupTxn>> tx;
+  for (uint32_t i = 0; i < n; i++)
+    if (!irs[i]) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
+  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
   (void)hipSetDevice(s->cfg.device);
-  GroupLease lease(s, n);
+  std::vector<std::unique_ptr<GroupTxn>> tx;
+  ProverLease lease(s, n);
   const uint32_t g = lease.size();
   if (granted) (*granted)(g);
   if (n_done) *n_done = g;
   int r;
+  std::vector<GroupTxn*> p;
   for (uint32_t i = 0; i < g; i++) {
-    if (!irs[i]) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
     tx.emplace_back(new GroupTxn());
+    p.push_back(tx[i].get());
     tx[i]->I = reinterpret_cast<const uint64_t*>(irs[i]);
     tx[i]->wit = wits ? wits[i] : nullptr;
     if ((r = parse_ir(s->cfg, tx[i]->I, tx[i]->wit, tx[i]->tp.tcfg, &tx[i]->tp.pv))) return r;
   }
-  Worker& w = *lease.ws[0];
-  w.abort_flag = nullptr;
-  w.abort_flag_u8 = abort_flag;
+  Worker& w = *lease.w;
+  w.abort_flag = abort_flag;
+  w.abort_flag_u8 = abort_flag_u8;
   if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
-  if (g == 1) {
-    if ((r = prove_tables(s, w, tx[0]->I, tx[0]->wit, &tx[0]->tp))) return r;
-  } else {
-    std::vector<GroupTxn*> p;
-    for (auto& t : tx) p.push_back(t.get());
-    if ((r = prove_tables_group(w, lease.ws, p.data(), g))) return r;
-  }
+  if ((r = prove_tables(s, w, lease.ws, p.data(), g))) return r;
   for (uint32_t i = 0; i < g; i++) {
     if (tables_only) r = emit_tables(tx[i]->tp, &outs[i], &out_lens[i]);
     else r = txn_recursion(s, w, lease.mark, tx[i]->tp, outs ? &outs[i] : nullptr, out_lens ? &out_lens[i] : nullptr, pool, nodes ? nodes[i] : 0);
@@ -1144,36 +1106,21 @@ static int txn_group_impl(const bp_state* s, uint32_t n, const uint8_t* const* i
   }
   return BP_OK;
 }
-
-static int txn_proof_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
-                          const volatile uint8_t* abort_flag_u8, uint8_t** out, size_t* out_len,
-                          const TxnWitness* wit = nullptr, bool tables_only = false, RecPool* pool = nullptr, uint32_t node = 0) {
-  if (!s || !ir || ((!out || !out_len) && !pool)) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof: null argument");
-  if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
-  const uint64_t* I = reinterpret_cast<const uint64_t*>(ir);
-  TableProofs tp;
-  int r = parse_ir(s->cfg, I, wit, tp.tcfg, &tp.pv);
-  if (r) return r;
-  (void)hipSetDevice(s->cfg.device);
-  WorkerLease lease(s);
-  Worker& w = *lease.w;
-  w.abort_flag = abort_flag;
-  w.abort_flag_u8 = abort_flag_u8;
-  if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
-  if ((r = prove_tables(s, w, I, wit, &tp))) return r;
-  if (tables_only) return emit_tables(tp, out, out_len);
-  return txn_recursion(s, w, lease.mark, tp, out, out_len, pool, node);
+// the calls that take one IR: a group of one
+static int txn_proof_of_one(const bp_state* s, const uint8_t* ir, size_t ir_len, const TxnWitness* wit, const volatile int32_t* abort_flag,
+                            const volatile uint8_t* abort_flag_u8, bool tables_only, uint8_t** out, size_t* out_len) {
+  return txn_proofs_impl(s, 1, &ir, ir_len, &wit, abort_flag, abort_flag_u8, tables_only, nullptr, nullptr, nullptr, out, out_len, nullptr);
 }
 int bp_generate_txn_proof(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile int32_t* abort_flag,
                           uint8_t** out, size_t* out_len) try {
-  return txn_proof_impl(s, ir, ir_len, abort_flag, nullptr, out, out_len);
+  return txn_proof_of_one(s, ir, ir_len, nullptr, abort_flag, nullptr, false, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof")
 // The same call with the reference's own flag type: Option<Arc<AtomicBool>> (proof_gen.rs:42) is one byte,
 // `flag.as_ptr()` binds directly.
 int bp_generate_txn_proof_u8(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile uint8_t* abort_flag,
                              uint8_t** out, size_t* out_len) try {
-  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len);
+  return txn_proof_of_one(s, ir, ir_len, nullptr, nullptr, abort_flag, false, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_u8")
 // generate_txn_proof where the transaction's Keccak table attests GIVEN hashing work: keccak_inputs = the states that
@@ -1184,7 +1131,7 @@ int bp_generate_txn_proof_keccak(const bp_state* s, const uint8_t* ir, size_t ir
   if (!keccak_inputs && n_perms) return fail(BP_ERR_INVALID_INPUT, "bp_generate_txn_proof_keccak: null inputs");
   TxnWitness wit;
   wit.give(T_KECCAK, keccak_inputs, n_perms);
-  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit);
+  return txn_proof_of_one(s, ir, ir_len, &wit, nullptr, abort_flag, false, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_keccak")
 // The general form: witness data for any of the tables that have an AIR (bp_txn_witness, include/bpg.h).
@@ -1192,7 +1139,7 @@ int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t i
                                   const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len) try {
   TxnWitness wit;
   if (int r = witness_of(data, &wit)) return r;
-  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit);
+  return txn_proof_of_one(s, ir, ir_len, &wit, nullptr, abort_flag, false, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof_witness")
 
@@ -1243,13 +1190,16 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   int r = parse_ir(s->cfg, I, wit, tcfg, &pv);
   if (r) return r;
   (void)hipSetDevice(s->cfg.device);
-  WorkerLease lease(s);
+  ProverLease lease(s);
   Worker& w = *lease.w;
   w.abort_flag = nullptr;
   w.abort_flag_u8 = nullptr;
-  uint64_t* d_trace[BP_NUM_TABLES];
   struct Release { Worker& w; size_t mark; ~Release() { (void)w.wait(); w.arena.release(mark); } } rel{w, lease.mark};
-  if ((r = build_traces(w, I, wit, tcfg, d_trace))) return r;
+  const StarkCfg* const one = tcfg;
+  TraceLayout lay;
+  if ((r = alloc_traces(w, &one, 1, &lay))) return r;
+  uint64_t* const* d_trace = lay.d_trace[0].data();
+  if ((r = build_traces(w, w, I, wit, tcfg, d_trace))) return r;
   if ((r = w.wait())) return r;
   // the AIRs, table by table (a seeded or derived table satisfies its AIR by construction; the prover checks the given ones)
   int status = BP_OK;
@@ -1326,7 +1276,7 @@ int bp_generate_txn_table_proofs(const bp_state* s, const uint8_t* ir, size_t ir
                                  const volatile uint8_t* abort_flag, uint8_t** out, size_t* out_len) try {
   TxnWitness wit;
   if (int r = witness_of(data, &wit)) return r;
-  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, out, out_len, &wit, true);
+  return txn_proof_of_one(s, ir, ir_len, &wit, nullptr, abort_flag, true, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_table_proofs")
 // The same for n transactions, table t of those whose shapes agree proved in lock-step (Tune::txn_group is not read: the
@@ -1349,7 +1299,7 @@ int bp_generate_txn_table_proofs_group(const bp_state* s, const uint8_t* irs, si
   }
   for (uint32_t done = 0; done < n;) {
     uint32_t g = 0;
-    if (int r = txn_group_impl(s, n - done, ip.data() + done, BP_IR_WORDS * 8, wp.data() + done, abort_flag, true, nullptr, nullptr, nullptr,
+    if (int r = txn_proofs_impl(s, n - done, ip.data() + done, BP_IR_WORDS * 8, wp.data() + done, nullptr, abort_flag, true, nullptr, nullptr, nullptr,
                                outs + done, out_lens + done, &g)) {
       for (uint32_t i = 0; i < n; i++) { std::free(outs[i]); outs[i] = nullptr; out_lens[i] = 0; }
       return r;
@@ -1436,7 +1386,7 @@ int bp_generate_agg_proof(const bp_state* s, const uint8_t* lhs, size_t lhs_len,
   int r = agg_prepare(s, lhs, lhs_len, lhs_is_agg, rhs, rhs_len, rhs_is_agg, &pi, &paths);
   if (r) return r;
   (void)hipSetDevice(s->cfg.device);
-  WorkerLease lease(s);
+  ProverLease lease(s);
   std::vector<uint64_t> proof;
   if ((r = rec_prove(*lease.w, s->rec_cfg, s->special[1], pi, proof, &paths))) return r;
   if ((r = emit_box(1, CIRCUIT_AGG, pi, proof, out, out_len))) return r;
@@ -1468,7 +1418,7 @@ int bp_generate_block_proof(const bp_state* s, const uint8_t* parent, size_t par
   first_query_trace_path(s->rec_cfg, A.stark, &pi[BLOCK_PATH_PI0], &pi[BLOCK_PATH_PI0 + 4], &paths[0]);
   std::memcpy(&pi[BLOCK_PATH_PI0 + 8], A.pv, BP_PV_WORDS * 8);
   (void)hipSetDevice(s->cfg.device);
-  WorkerLease lease(s);
+  ProverLease lease(s);
   std::vector<uint64_t> proof;
   if ((r = rec_prove(*lease.w, s->rec_cfg, s->special[2], pi, proof, &paths))) return r;
   if (b_height) *b_height = A.pv[12];  // block_metadata.block_number.low_u64(), proof_gen.rs:90-94
@@ -1551,14 +1501,6 @@ namespace bpg {
 
 uint32_t rec_batch_cap(const bp_state* s) { return s ? batch_cap(s->rec_cfg) : 1; }
 
-int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
-                     const volatile uint8_t* abort_flag, RecPool* pool, uint32_t node) {
-  if (!pool) return fail(BP_ERR_INVALID_INPUT, "txn_proof_pooled: no pool");
-  TxnWitness wit;
-  if (int r = witness_of(data, &wit)) return r;
-  return txn_proof_impl(s, ir, ir_len, nullptr, abort_flag, nullptr, nullptr, &wit, false, pool, node);
-}
-
 uint32_t state_workers(const bp_state* s) { return s ? s->cfg.n_workers : 1; }
 uint32_t txn_group_of(const bp_state* s) {
   const int knob = tune().txn_group.load(std::memory_order_relaxed);
@@ -1577,7 +1519,7 @@ int txn_group_pooled(const bp_state* s, uint32_t n, const uint8_t* const* irs, s
   }
   uint8_t* o[MAX_BATCH] = {};
   size_t ol[MAX_BATCH] = {};
-  const int r = txn_group_impl(s, n, irs, ir_len, wp, abort_flag, false, pool, nodes, &granted, pool ? nullptr : o, pool ? nullptr : ol, nullptr);
+  const int r = txn_proofs_impl(s, n, irs, ir_len, wp, nullptr, abort_flag, false, pool, nodes, &granted, pool ? nullptr : o, pool ? nullptr : ol, nullptr);
   for (uint32_t i = 0; i < n && !pool; i++) {
     if (r) std::free(o[i]);
     else outs[i] = TreeBuf{o[i], ol[i]};
@@ -1608,7 +1550,7 @@ int rec_prove_jobs(const bp_state* s, const std::vector<std::unique_ptr<RecJob>>
   }
   (void)hipSetDevice(s->cfg.device);
   {
-    WorkerLease lease(s);
+    ProverLease lease(s);
     Worker& w = *lease.w;
     w.abort_flag_u8 = abort_flag;
     if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before a batch of %zu recursion jobs", n);

@@ -430,16 +430,13 @@ class TreeRun : public RecPool {
 namespace bpg {
 // proofs one lock-step batch holds for this state's recursion shape (MAX_BATCH, Tune::rec_batch, the query limit)
 uint32_t rec_batch_cap(const bp_state* s);
-// bp_generate_txn_proof_witness up to the root's public-input list; the three chain batches carry ready jobs of `pool`
-// in their spare slots, and the root itself is posted as the job of `node`.  data nullable.
-int txn_proof_pooled(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data,
-                     const volatile uint8_t* abort_flag, RecPool* pool, uint32_t node);
 // the host half of bp_generate_agg_proof: everything but the proving
 int agg_proof_prepare(const bp_state* s, const uint8_t* lhs, size_t lhs_len, int lhs_is_agg, const uint8_t* rhs, size_t rhs_len,
                       int rhs_is_agg, RecJob* job);
-// up to n <= MAX_BATCH transactions on one group lease (proofgen.cpp: GroupLease, prove_tables_group): the first g the
-// lease grants -- granted(g) is called when it is held --, roots posted as the jobs of nodes[i], or without a pool the
-// containers in outs[i].  data nullable, and every data[i].
+// bp_generate_txn_proof_witness for up to n <= MAX_BATCH transactions on one lease (proofgen.cpp: ProverLease,
+// prove_tables; a lone transaction is a group of one): the first g the lease grants -- granted(g) is called when it is
+// held.  With a pool the chain batches carry its ready jobs in their spare slots and the roots are posted as the jobs of
+// nodes[i]; without one the containers land in outs[i].  data nullable, and every data[i].
 int txn_group_pooled(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const bp_txn_witness* const* data,
                      const volatile uint8_t* abort_flag, RecPool* pool, const uint32_t* nodes, const std::function<void(uint32_t)>& granted,
                      TreeBuf* outs);

@@ -71,8 +71,8 @@ struct Tune {
   // chain of launches (the scheduling up to this knob).  Read once per call.  Measurements: profiles/rec_riders_ab.txt.
   std::atomic<int> rec_riders{1};
   // Transactions a thread of bp_prove_shard / bp_prove_shard_gi starts at a time: it leases that many provers whose
-  // arenas are neighbours (proofgen.cpp: GroupLease) and proves table t of all of them in lock-step batches wherever
-  // their shapes agree (prove_tables_group), t = 0..6, each transaction on its own transcript; the recursion chains
+  // arenas are neighbours (proofgen.cpp: ProverLease) and proves table t of all of them in lock-step batches wherever
+  // their shapes agree (prove_tables), t = 0..6, each transaction on its own transcript; the recursion chains
   // follow one transaction after the other.  1 = one transaction per thread (the schedule up to this knob).  0 = by the
   // state: 3 where bp_state_build saw fewer hardware queues than the state has prover streams, else 1.  Measured on the
   // 256-txn block, 20 streams, three alternating runs each (profiles/txn_groups_ab.txt): at 4 queues 35.22 (1) / 35.39

@@ -4,7 +4,7 @@
 // of one slab lie one behind the other, so a prover that leases a RUN of adjacent idle workers owns one contiguous piece
 // of memory -- room for several transactions proved in lock-step (Tune::txn_group).  This is the bookkeeping of that:
 //
-//  * take_one: a single worker, as WorkerLease, SideLane and rec_prove_jobs take one.  An idle worker with no idle
+//  * take_one: a single worker, as a ProverLease of one (every call but a group of transactions) and SideLane take one.  An idle worker with no idle
 //    neighbour goes first (it is of no use to a group), else the one released last.
 //  * take_run: up to `want` adjacent idle workers, all or nothing of ONE run: the shortest run that holds `want`, else
 //    the longest run there is (>= 1 while any worker is idle).  It never waits for adjacency.

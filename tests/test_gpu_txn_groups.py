@@ -1,5 +1,5 @@
-"""Several transactions at a time (bp_tune_txn_group; csrc/proofgen.cpp: GroupLease, prove_tables_group; csrc/rec_pool.hpp:
-the scheduler's group rule): a thread of bp_prove_shard / bp_prove_shard_gi leases a run of neighbouring provers and proves
+"""Several transactions at a time (bp_tune_txn_group; csrc/proofgen.cpp: ProverLease, prove_tables -- the one path of
+every transaction, a lone one being a group of one; csrc/rec_pool.hpp: the scheduler's group rule): a thread of bp_prove_shard / bp_prove_shard_gi leases a run of neighbouring provers and proves
 table t of its transactions in lock-step wherever their shapes agree.  Every transaction keeps its own transcript, so not
 one byte may move: the reference is the same call with txn_group = 1 (and, once, the inline path and the oracle's
 verifier, as tests/test_gpu_rec_riders.py has them), the table-proof blobs of the single call for the group call.
@@ -198,17 +198,42 @@ AIR_CASES = [with_heights(BY_NAME["six_together"], LOWEST), with_heights(BY_NAME
 
 
 @pytest.mark.parametrize("case", AIR_CASES, ids=[c.name for c in AIR_CASES])
-def test_every_air_in_batches_of_two_and_three(pg, air_state, case):
+def test_every_air_in_batches_of_two_and_three(pg, bpg, air_state, case):
+    """... and in a batch of ONE, which is the single call: once with side_lanes at its default (the lone prover borrows the
+    streams of air_state's two idle workers for its trace commitments), once with the borrowing switched off."""
     singles = []
     for k in range(3):
         rc, msg, blob = tc.table_proofs(pg, air_state, case, case_words(case, k))
         assert rc == 0, msg
         singles.append(blob)
     assert len(set(singles)) == 3
-    for b in (2, 3):
+    for b in (1, 2, 3):
         rc, msg, blobs = group_call(pg, air_state, [(case, case_words(case, k)) for k in range(b)])
         assert rc == 0, msg
         assert blobs == singles[:b], (case.name, b)
+    with bpg.ops.tuned(side_lanes=0):
+        rc, msg, blobs = group_call(pg, air_state, [(case, case_words(case, 0))])
+    assert rc == 0, msg
+    assert blobs == singles[:1], case.name
+
+
+def test_side_lanes_belong_to_a_lone_transaction(pg, bpg, reference, group):
+    """side_lanes = 3 on four workers: a group of two counts as two provers and would pass the knob's test, but lanes are
+    for a group of ONE -- the two transactions are committed in lock-step and give the reference's bytes.  So do the same
+    two, one after the other on one thread, with the lanes switched off."""
+    irs, txns, roots = reference
+    st = build_state(pg, SMALL_PLONK, 4)
+    try:
+        with bpg.ops.tuned(side_lanes=3):
+            group(2)
+            root, got = prove_shard(pg, st, irs[:2], 1)
+        assert got == txns[:2] and root == roots[2]
+        with bpg.ops.tuned(side_lanes=0):
+            group(1)
+            root, got = prove_shard(pg, st, irs[:2], 1)
+        assert got == txns[:2] and root == roots[2]
+    finally:
+        st.close()
 
 
 def test_a_decoded_entry_with_its_own_witness_beside_seeded_ones(pg, air_state):

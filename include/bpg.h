@@ -672,6 +672,59 @@ int bp_stark_prove_table_set(const bp_set_table* tables, uint32_t n_tables, cons
                              uint32_t flags, int device, uint8_t** out, size_t* out_len);
 int bp_stark_verify_table_set(const bp_set_table* statement, uint32_t n_tables, const uint64_t* const* const_caps,
                               const bp_set_link* links, uint32_t n_links, const uint8_t* proof, size_t len);
+/* The pre-flight of a set: what is wrong with its witness, found without proving it (the analogue of
+ * bp_check_txn_witness).  The statement and its refusals are bp_stark_prove_table_set's, refused before a device is
+ * touched with the same statuses and texts under this entry's name; strides, constants and public inputs are read as the
+ * prover reads them.  Nothing is committed or proven; the call returns after the device has finished.
+ * BP_OK exactly when bp_stark_prove_table_set on the same arguments would return a container that
+ * bp_stark_verify_table_set accepts (up to the soundness error stated below); otherwise BP_ERR_VERIFY, and
+ * bp_last_error() names the first finding in this order: tables in index order (a member that violates its OWN AIR: row,
+ * constraint and family, in bp_check_txn_witness's words), then links in index order, a bad filter before an unbalanced
+ * tuple, both named by table, port and row.  Either way *out holds everything found: every table and every link is
+ * checked, not just the first that fails.
+ * table[t]: bp_air_check_trace's answer for the member (max_rows = max_viol = 8).
+ * link[k], with a port's (f, tuple) on a row being what its port unit computes (next row wrapping at the last row,
+ * x = w^i), or for a built-in member the filter and tuple listed above (Keccak-f's input read 23 rows up):
+ *   A TUPLE VALUE is the tuple with trailing zeros stripped: (a, b) and (a, b, 0) are one value, as they are to the
+ *     proof, whose compression sum_j beta^j t_j cannot tell them apart.  Ends of different tuple lengths may be linked.
+ *   BALANCE: for every tuple value, the sum of f over the looking rows that carry it is congruent mod p to the sum of f
+ *     over the looked rows that carry it -- the meaning of a log link above; on a product link the filters are bits, the
+ *     sums are counts below 2^31 and the congruence is the multiset equality.
+ *   n_unbalanced: the tuple values for which that fails.  first_looking_end / first_looking_row: the smallest (end index,
+ *     row), lexicographically, among the looking rows with f != 0 that carry an unbalanced value; first_looked_row: the
+ *     smallest such row of the looked end; -1 where there is none.  n_looking / n_looked: the rows with f != 0.
+ *   BAD FILTER: a row with f outside {0, 1} on an end whose port demands a bit -- a registered program's product port or
+ *     kind-1 log port; not a kind-2 port (a multiplicity), not a built-in member (its filter is its own AIR's matter,
+ *     reported under table[]).  The smallest (end, row) is reported with the value; the row enters the balance with its f.
+ *   holds: balanced and no bad filter.
+ * There are no poles here: the balance is over tuples, not over 1 / (gamma + v), so the pre-flight never fails the way
+ * bp_air_port_products can.
+ * How: the balance is computed on the device (csrc/set_check.hip).  Per call four fresh random challenges; a row's tuple
+ * is compressed to v_0, v_1 under two of them and accumulated in a hash table keyed by v_0 (S = sum of +-f,
+ * S_1 = sum of +-f v_1, exact integer sums: the report is a function of the inputs alone).  A value balances iff S = S_1 = 0.
+ * Two distinct tuple values collide in v_0 with probability about n_tuple N^2 / 2^64 (N rows in the link); a collision of
+ * balanced values leaves both sums zero, so there is NO false alarm at any size; a false pass (and a miscount of
+ * n_unbalanced by merging) needs that collision and, for the pass, S_1 = 0 on top of it: a second, independent
+ * 2^-64-sized coincidence.  Scratch: one allocation of 64 bytes x the power of two >= twice the rows of the largest
+ * link's ends; if the device cannot give it, BP_ERR_DEVICE naming the bytes. */
+typedef struct bp_set_table_report {
+  uint64_t n_violated_rows;      /* of the member's OWN constraints (bp_air_check_trace) */
+  uint32_t n_viol, reserved;
+  bp_air_violation viol[8];      /* the first rows', row order */
+} bp_set_table_report;
+typedef struct bp_set_link_report {
+  uint32_t holds;                /* balanced and no bad filter on any of its ends */
+  uint32_t is_log;
+  uint64_t n_looking, n_looked;  /* rows with f != 0 on each side */
+  uint64_t n_unbalanced;         /* tuple values whose two sides differ */
+  int32_t  first_looking_end;    /* index into link.looking; -1: none */
+  int32_t  bad_filter_end;       /* 0 .. n_looking-1: link.looking[i]; n_looking: the looked end; -1: none */
+  int64_t  first_looking_row, first_looked_row, bad_filter_row;   /* -1: none */
+  uint64_t bad_filter_value;
+} bp_set_link_report;
+typedef struct bp_set_report { bp_set_table_report table[8]; bp_set_link_report link[16]; } bp_set_report;
+int bp_check_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links,
+                       int device, bp_set_report* out);
 /* bp_stark_prove_synthetic keeps one worker (stream + device arena, up to ~100 GB for a 2^20 x 2432
  * table) parked per device between calls, because re-allocating it costs more than the proof.
  * This frees the parked workers. */

@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _PATH = os.environ.get("BPG_LIBBPG") or os.path.join(_HERE, "lib", "libbpg.so")
 
 BP_OK = 0
+BP_ERR_VERIFY = -5
 STATUS_NAMES = {0: "BP_OK", -1: "BP_ERR_ABORTED", -2: "BP_ERR_INVALID_INPUT", -3: "BP_ERR_RANGE",
                 -4: "BP_ERR_DEVICE", -5: "BP_ERR_VERIFY", -6: "BP_ERR_UNSUPPORTED"}
 
@@ -61,6 +62,24 @@ BP_SET_SKIP_LINK_CHECK = 1
 class AirViolation(C.Structure):
     """bp_air_violation: one constraint a row of a trace breaks (bp_air_check_trace)."""
     _fields_ = [(n, C.c_uint32) for n in ("row", "constraint", "family", "kind")] + [("value", C.c_uint64)]
+
+
+class SetTableReport(C.Structure):
+    """bp_set_table_report: a member's own constraints (bp_check_table_set)."""
+    _fields_ = [("n_violated_rows", C.c_uint64), ("n_viol", C.c_uint32), ("reserved", C.c_uint32), ("viol", AirViolation * 8)]
+
+
+class SetLinkReport(C.Structure):
+    """bp_set_link_report: the balance of one link (bp_check_table_set)."""
+    _fields_ = [("holds", C.c_uint32), ("is_log", C.c_uint32), ("n_looking", C.c_uint64), ("n_looked", C.c_uint64),
+                ("n_unbalanced", C.c_uint64), ("first_looking_end", C.c_int32), ("bad_filter_end", C.c_int32),
+                ("first_looking_row", C.c_int64), ("first_looked_row", C.c_int64), ("bad_filter_row", C.c_int64),
+                ("bad_filter_value", C.c_uint64)]
+
+
+class SetReport(C.Structure):
+    """bp_set_report."""
+    _fields_ = [("table", SetTableReport * 8), ("link", SetLinkReport * 16)]
 
 
 def take_buffer(ptr, length):
@@ -133,6 +152,7 @@ def lib():
                                            C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.bp_stark_verify_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(C.POINTER(u64)), C.POINTER(SetLink), u32,
                                             C.c_char_p, C.c_size_t]
+    L.bp_check_table_set.argtypes = [C.POINTER(SetTable), u32, C.POINTER(SetLink), u32, i, C.POINTER(SetReport)]
     L.bp_air_register.argtypes = [vp, C.c_size_t, C.POINTER(u32)]
     L.bp_air_unregister.argtypes = [u32]
     L.bp_air_program_digest.argtypes = [u32, C.c_char_p]

@@ -93,34 +93,15 @@ __global__ void __launch_bounds__(256) air_check_gather_kernel(const uint64_t* t
 }
 
 // The witness pre-flight's lookup check (proofgen.cpp): per row the term 1 + f (gamma + v - 1) of product column `col`
-// of the table (air::ctl::product_term: the same filter and column selection; challenge set 0 = (beta, gamma)).  A row
-// the filter leaves out gives 1, a tuple v gives gamma + v.  Keccak-f's looked tuple carries its input in the auxiliary
-// column h; here it is compressed from the trace, 23 rows up (the permutation's first row).   grid = (ceil(n / 256))
+// of the table (builtin_lookup_term, air_check_dev.cuh; challenge set 0 = (beta, gamma)).  A row the filter leaves out
+// gives 1, a tuple v gives gamma + v.   grid = (ceil(n / 256))
 template <uint32_t AIR>
 __global__ void __launch_bounds__(256) lookup_terms_kernel(const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta,
                                                            uint64_t gamma, uint64_t* out) {
   const uint64_t n = (uint64_t)1 << log_n;
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= n) return;
-  const CheckRow row{trace, nullptr, n, 0, pos, (pos + 1) & (n - 1), 0, nullptr};
-  uint64_t t = 1;
-  if constexpr (AIR == bpg::air::KECCAK_F) {
-    namespace kk = bpg::air::keccak;
-    const uint64_t g = row.loc(kk::COL_G);
-    if (g && pos >= 23) {
-      const CheckRow first{trace, nullptr, n, 0, pos - 23, pos - 22, 0, nullptr};
-      const uint64_t in = bpg::air::ctl::compress<uint64_t>([&](uint32_t j) { return first.loc(kk::COL_A + j); },
-                                                           bpg::air::ctl::TUPLE_LIMBS, beta);
-      const uint64_t o = bpg::air::ctl::compress<uint64_t>(
-          [&](uint32_t j) { return j < 2 ? row.loc(kk::COL_APPP + j) : row.loc(kk::COL_APP + j); }, bpg::air::ctl::TUPLE_LIMBS, beta);
-      const uint64_t v = gl::addc(in, gl::mulc(gl::pow(beta, bpg::air::ctl::TUPLE_LIMBS), o));
-      t = gl::addc(1, gl::mulc(g, gl::subc(gl::addc(gamma, v), 1)));
-    }
-  } else {
-    const uint64_t ctl[4] = {beta, gamma, beta, gamma};
-    t = bpg::air::ctl::product_term<uint64_t>(bpg::air::Shape{AIR, 0, 0, 1}, col, ctl, row);
-  }
-  out[pos] = t;
+  out[pos] = builtin_lookup_term<AIR>(trace, n, n, pos, col, beta, gamma);
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 #pragma once
 #include "air_check.hpp"
 #include "gl.hpp"
+#include "air.hpp"
 
 namespace bpg {
 namespace chk {
@@ -71,6 +72,34 @@ __device__ __forceinline__ CheckRow check_row(const CheckArgs& a, uint64_t pos, 
   return CheckRow{a.trace, a.consts, a.stride, n, pos, (pos + 1) & (n - 1),
                   with_x ? gl::pow(gl::root(a.log_n), pos) : 0, a.pub};
 }
+// The term 1 + f (gamma + v - 1) of product column `col` of a BUILT-IN table with a lookup side at row `pos` of its trace
+// (column stride `stride`), under the one challenge set (beta, gamma): air::ctl::product_term's filter and column
+// selection.  Keccak-f's looked tuple carries its input in the auxiliary column h; here it is compressed from the trace,
+// 23 rows up (the permutation's first row).
+template <uint32_t AIR>
+__device__ __forceinline__ uint64_t builtin_lookup_term(const uint64_t* trace, uint64_t stride, uint64_t n, uint64_t pos, uint32_t col,
+                                                        uint64_t beta, uint64_t gamma) {
+  const CheckRow row{trace, nullptr, stride, 0, pos, (pos + 1) & (n - 1), 0, nullptr};
+  uint64_t t = 1;
+  if constexpr (AIR == bpg::air::KECCAK_F) {
+    namespace kk = bpg::air::keccak;
+    const uint64_t g = row.loc(kk::COL_G);
+    if (g && pos >= 23) {
+      const CheckRow first{trace, nullptr, stride, 0, pos - 23, pos - 22, 0, nullptr};
+      const uint64_t in = bpg::air::ctl::compress<uint64_t>([&](uint32_t j) { return first.loc(kk::COL_A + j); },
+                                                           bpg::air::ctl::TUPLE_LIMBS, beta);
+      const uint64_t o = bpg::air::ctl::compress<uint64_t>(
+          [&](uint32_t j) { return j < 2 ? row.loc(kk::COL_APPP + j) : row.loc(kk::COL_APP + j); }, bpg::air::ctl::TUPLE_LIMBS, beta);
+      const uint64_t v = gl::addc(in, gl::mulc(gl::pow(beta, bpg::air::ctl::TUPLE_LIMBS), o));
+      t = gl::addc(1, gl::mulc(g, gl::subc(gl::addc(gamma, v), 1)));
+    }
+  } else {
+    const uint64_t ctl[4] = {beta, gamma, beta, gamma};
+    t = bpg::air::ctl::product_term<uint64_t>(bpg::air::Shape{AIR, 0, 0, 1}, col, ctl, row);
+  }
+  return t;
+}
+
 // bit `pos % 64` of word `pos / 64` = bad; lane 0 of each wave (its row is a multiple of 64) writes the wave's word.
 // Every lane of the wave must get here (no early return before it).
 __device__ __forceinline__ void flag_rows(const CheckArgs& a, uint64_t pos, bool bad) {

@@ -29,6 +29,7 @@
 #include <mutex>
 #include "air_check_dev.cuh"
 #include "air_program.hpp"
+#include "air_program_dev.cuh"
 #include "common.hpp"
 #include "quotient_dev.cuh"
 
@@ -37,21 +38,9 @@ namespace {
 using namespace bpg::k5;
 using namespace bpg::chk;
 namespace prog = bpg::air::prog;
-
-extern __shared__ uint64_t lds_regs[];  // [n_regs][256]
-
-struct LdsRegs {
-  uint64_t* lane;  // register 0 of this lane
-  uint64_t acc;    // the value of register `last`
-  uint32_t last;   // wave-uniform
-  __device__ __forceinline__ uint64_t get(uint32_t r) const { return r == last ? acc : lane[r * 256]; }
-  __device__ __forceinline__ void set(uint32_t r, uint64_t v) {
-    lane[r * 256] = v;
-    acc = v;
-    last = r;
-  }
-};
-__device__ __forceinline__ LdsRegs lds_regs_of_lane() { return LdsRegs{lds_regs + threadIdx.x, 0, ~0u}; }
+using bpg::progdev::BetaTab;
+using bpg::progdev::LdsRegs;
+using bpg::progdev::lds_regs_of_lane;
 
 // image: the program's unit offsets (n_air_units + 1 words), then its code (prog::Program::image).
 // grid = (rows / 256, workgroup rows, proofs) as quotient_air_kernel's; dynamic LDS = n_regs * 2 KiB.
@@ -157,9 +146,6 @@ struct PortTermsArgs {
   uint32_t log_n, n_units, n_code, n_ports;
   uint64_t ctl[4], pub[4];
   unsigned long long* pole;  // LOG only
-};
-struct BetaTab {
-  uint64_t v[2 * prog::MAX_TUPLE];
 };
 template <bool LOG>
 __global__ void __launch_bounds__(256) program_port_terms_kernel(PortTermsArgs a, BetaTab bt, const uint64_t* __restrict__ image) {

@@ -3,9 +3,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <random>
 #include <string>
 #include <vector>
 #include "prover.hpp"
+#include "set_check.hpp"
 
 using namespace bpg;
 
@@ -390,6 +392,134 @@ int bp_stark_verify_table_set(const bp_set_table* tables, uint32_t n_tables, con
   return check_links(sh, links, n_links, proof);
 }
 BPG_ABI_CATCH("bp_stark_verify_table_set")
+
+// The pre-flight of a set (include/bpg.h): every member's own constraints through bp_air_check_trace, every link's
+// balance on the device (set_check.hip).  Nothing is committed or proven; every table and every link is reported.
+int bp_check_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, int device,
+                       bp_set_report* out) try {
+  if (!out) return fail(BP_ERR_INVALID_INPUT, "bp_check_table_set: null argument");
+  SetShape sh;
+  int rc = check_set("bp_check_table_set", tables, n_tables, links, n_links, &sh);
+  if (rc) return rc;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const uint64_t N = (uint64_t)1 << sh.cfg[t].log_n;
+    if (!tables[t].d_trace || (sh.cfg[t].n_const && !tables[t].d_consts))
+      return fail(BP_ERR_INVALID_INPUT, "bp_check_table_set: table %u: null trace, or the AIR reads %u constant columns and none are given", t,
+                  sh.cfg[t].n_const);
+    if (tables[t].stride < N)
+      return fail(BP_ERR_INVALID_INPUT, "bp_check_table_set: table %u: column stride %llu is shorter than the %llu-row trace", t,
+                  (unsigned long long)tables[t].stride, (unsigned long long)N);
+  }
+  std::memset(out, 0, sizeof(*out));
+  int before = 0;
+  BPG_HIP(hipGetDevice(&before));
+  BPG_HIP(hipSetDevice(device));
+  struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{before};
+  hipStream_t st = nullptr;
+  int status = BP_OK;
+  std::string why;
+  char buf[384];
+  // the members' own constraints, as bp_check_txn_witness reports a table's
+  for (uint32_t t = 0; t < n_tables; t++) {
+    bp_set_table_report& o = out->table[t];
+    const bp_stark_cfg& c = tables[t].cfg;
+    uint32_t rows[8], nv = 0;
+    if ((rc = bp_air_check_trace(tables[t].air_id, &c, tables[t].d_trace, tables[t].stride, sh.cfg[t].n_const ? tables[t].d_consts : nullptr,
+                                 tables[t].pub, 8, &o.n_violated_rows, rows, o.viol, 8, &nv, st))) return rc;
+    o.n_viol = std::min<uint32_t>(nv, 8);
+    if (status == BP_OK && o.n_violated_rows) {
+      std::snprintf(buf, sizeof(buf), "table %u does not satisfy its AIR: row %u violates constraint %u (family %u), %llu rows in all", t,
+                    o.viol[0].row, o.viol[0].constraint, o.viol[0].family, (unsigned long long)o.n_violated_rows);
+      status = BP_ERR_VERIFY;
+      why = buf;
+    }
+  }
+  // the links: one scratch for the largest, reused link after link; a link's eight result words behind the slots
+  uint32_t log_slots[SET_MAX_LINKS], max_log = 0;
+  for (uint32_t k = 0; k < n_links; k++) {
+    uint64_t rows = 0;
+    for (uint32_t m = 0; m <= links[k].n_looking; m++)
+      rows += (uint64_t)1 << sh.cfg[(m < links[k].n_looking ? links[k].looking[m] : links[k].looked).table].log_n;
+    log_slots[k] = set_check_log_slots(rows);
+    max_log = std::max(max_log, log_slots[k]);
+  }
+  const size_t table_words = ((size_t)1 << max_log) * SET_SLOT_WORDS, bytes = (table_words + (size_t)SET_RESULT_WORDS * n_links) * 8;
+  uint64_t* d_s = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d_s), bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BP_ERR_DEVICE, "bp_check_table_set: the device has no %zu bytes for the balance of the largest link", bytes);
+  }
+  struct Free { void* p; ~Free() { (void)hipFree(p); } } guard{d_s};
+  std::random_device rd;
+  std::mt19937_64 g(((uint64_t)rd() << 32) ^ rd());
+  uint64_t ctl[4];
+  for (uint64_t& v : ctl) do v = g() % gl::P; while (v < 2);
+  auto end_of = [&](const bp_set_link& l, uint32_t m) {
+    const bp_set_port& e = m < l.n_looking ? l.looking[m] : l.looked;
+    const bp_set_table& tb = tables[e.table];
+    SetEnd se{};
+    se.air_id = tb.air_id; se.port = e.port;
+    se.trace = tb.d_trace; se.consts = sh.cfg[e.table].n_const ? tb.d_consts : nullptr; se.stride = tb.stride;
+    se.log_n = sh.cfg[e.table].log_n;
+    if (tb.pub) for (int j = 0; j < 4; j++) se.pub[j] = tb.pub[j];
+    se.end = m; se.looked = m == l.n_looking;
+    // a port that demands a bit: a registered program's product port or kind-1 log port (a built-in member's own AIR
+    // constrains its filter; a kind-2 filter is a multiplicity)
+    const auto program = air::prog::find(tb.air_id);
+    se.wants_bit = program && e.port < program->n_ports && program->port_kind[e.port] != air::prog::PORT_LOG_MULT;
+    return se;
+  };
+  for (uint32_t k = 0; k < n_links; k++) {
+    SetEnd ends[SET_MAX_LOOKING + 1];
+    for (uint32_t m = 0; m <= links[k].n_looking; m++) ends[m] = end_of(links[k], m);
+    if ((rc = launch_set_link(ends, links[k].n_looking + 1, ctl, d_s, log_slots[k], d_s + table_words + (size_t)SET_RESULT_WORDS * k, st))) return rc;
+  }
+  uint64_t res[SET_MAX_LINKS][SET_RESULT_WORDS];
+  BPG_HIP(hipMemcpyAsync(res, d_s + table_words, (size_t)SET_RESULT_WORDS * n_links * 8, hipMemcpyDeviceToHost, st));
+  BPG_HIP(hipStreamSynchronize(st));
+  const uint64_t row_mask = ((uint64_t)1 << SET_LOC_ROW_BITS) - 1;
+  for (uint32_t k = 0; k < n_links; k++) {
+    const bp_set_link& l = links[k];
+    bp_set_link_report& o = out->link[k];
+    const uint64_t* r = res[k];
+    if (r[SET_RES_OVERFLOW]) return fail(BP_ERR_DEVICE, "bp_check_table_set: link %u: the balance table overflowed", k);
+    o.is_log = sh.log_link[k];
+    o.n_looking = r[SET_RES_N_LOOKING];
+    o.n_looked = r[SET_RES_N_LOOKED];
+    o.n_unbalanced = r[SET_RES_UNBALANCED];
+    o.first_looking_end = o.bad_filter_end = -1;
+    o.first_looking_row = o.first_looked_row = o.bad_filter_row = -1;
+    if (r[SET_RES_MIN_LOOKING] != ~0ULL) {
+      o.first_looking_end = (int32_t)(r[SET_RES_MIN_LOOKING] >> SET_LOC_ROW_BITS);
+      o.first_looking_row = (int64_t)(r[SET_RES_MIN_LOOKING] & row_mask);
+    }
+    if (r[SET_RES_MIN_LOOKED] != ~0ULL) o.first_looked_row = (int64_t)r[SET_RES_MIN_LOOKED];
+    if (r[SET_RES_BAD_FILTER] != ~0ULL) {
+      o.bad_filter_end = (int32_t)(r[SET_RES_BAD_FILTER] >> SET_LOC_ROW_BITS);
+      o.bad_filter_row = (int64_t)(r[SET_RES_BAD_FILTER] & row_mask);
+      uint64_t* d_res = d_s + table_words + (size_t)SET_RESULT_WORDS * k;
+      if ((rc = launch_set_filter_at(end_of(l, (uint32_t)o.bad_filter_end), (uint64_t)o.bad_filter_row, ctl, d_res, st))) return rc;
+      BPG_HIP(hipMemcpyAsync(&o.bad_filter_value, d_res + SET_RES_BAD_VALUE, 8, hipMemcpyDeviceToHost, st));
+      BPG_HIP(hipStreamSynchronize(st));
+    }
+    o.holds = o.n_unbalanced == 0 && o.bad_filter_end < 0;
+    if (status != BP_OK || o.holds) continue;
+    status = BP_ERR_VERIFY;
+    if (o.bad_filter_end >= 0) {
+      const bp_set_port& e = (uint32_t)o.bad_filter_end < l.n_looking ? l.looking[o.bad_filter_end] : l.looked;
+      std::snprintf(buf, sizeof(buf), "link %u: the filter of port %u of table %u is no bit on row %lld: it is %llu", k, e.port, e.table,
+                    (long long)o.bad_filter_row, (unsigned long long)o.bad_filter_value);
+    } else {
+      const bp_set_port& e = l.looking[o.first_looking_end < 0 ? 0 : o.first_looking_end];
+      std::snprintf(buf, sizeof(buf), "link %u does not balance (%llu tuple values): first unmatched looking row %lld (port %u of table %u), "
+                    "looked row %lld (port %u of table %u)", k, (unsigned long long)o.n_unbalanced, (long long)o.first_looking_row, e.port, e.table,
+                    (long long)o.first_looked_row, l.looked.port, l.looked.table);
+    }
+    why = buf;
+  }
+  return status == BP_OK ? BP_OK : fail(status, "%s", why.c_str());
+}
+BPG_ABI_CATCH("bp_check_table_set")
 
 }  // extern "C"
 

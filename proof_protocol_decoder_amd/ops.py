@@ -488,6 +488,65 @@ def stark_prove_table_set(tables, links, skip_link_check=False, device=0):
     return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
 
 
+class SetLinkCheck:
+    """bp_set_link_report: does the link hold, and if not which rows unbalance it (include/bpg.h states every field)."""
+    FIELDS = ("holds", "is_log", "n_looking", "n_looked", "n_unbalanced", "first_looking_end", "first_looking_row",
+              "first_looked_row", "bad_filter_end", "bad_filter_row", "bad_filter_value")
+
+    def __init__(self, r):
+        for name in self.FIELDS:
+            setattr(self, name, bool(getattr(r, name)) if name in ("holds", "is_log") else int(getattr(r, name)))
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name in self.FIELDS}
+
+    def __repr__(self):
+        return "SetLinkCheck(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class SetCheck:
+    """What bp_check_table_set found: `tables` (an AirCheck per member: its own constraints, the first 8 rows and
+    violations), `links` (a SetLinkCheck per link), and the library's sentence about the first finding in `message`
+    ("" when the set is fine)."""
+
+    def __init__(self, tables, links, message):
+        self.tables = tables
+        self.links = links
+        self.message = message
+
+    @property
+    def ok(self):
+        return all(t.ok for t in self.tables) and all(l.holds for l in self.links)
+
+    def __repr__(self):
+        return "SetCheck(ok)" if self.ok else "SetCheck(%s)" % self.message
+
+
+def check_table_set(tables, links, device=0):
+    """bp_check_table_set: the pre-flight of stark_prove_table_set on the same arguments -- every member's own
+    constraints and every link's balance, computed on the device, nothing proven.  Nothing is raised for a set that would
+    not prove (BP_ERR_VERIFY is the answer: SetCheck.ok is False and .message names the first finding); every other status
+    raises BpgError."""
+    from ._lib import BP_ERR_VERIFY, BpgError, SetReport
+    ta, la, keep = _set_arguments(tables, links)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    rep = SetReport()
+    rc = lib().bp_check_table_set(ta, len(tables), la, len(links), device, C.byref(rep))
+    message = ""
+    if rc != 0:
+        message = lib().bp_last_error().decode("utf-8", "replace")
+        if rc != BP_ERR_VERIFY:
+            raise BpgError(rc, message)
+    checks = []
+    for t, m in zip(rep.table, tables):
+        k = min(t.n_viol, 8)
+        viol = [t.viol[i] for i in range(k)]
+        rows = sorted({v.row for v in viol})
+        checks.append(AirCheck(m["air_id"], t.n_violated_rows, rows, viol, t.n_viol))
+    return SetCheck(checks, [SetLinkCheck(rep.link[k]) for k in range(len(links))], message)
+
+
 def stark_verify_table_set(tables, links, proof, const_caps=None):
     """bp_stark_verify_table_set: the CPU verifier on a set's container.  The statement -- tables (air_id, cfg, pub; no
     traces), links, const_caps (per table the constants cap words or None) -- is the caller's own.  Raises

@@ -7,12 +7,11 @@
 // the per-index sum is a constraint's value.  Every non-zero index of the AIR's own list is a violation.
 #include <algorithm>
 #include <cstring>
-#include <random>
 #include <thread>
 #include <vector>
 #include "air_check.hpp"
 #include "air_program.hpp"
-#include "prover.hpp"
+#include "caller_table.hpp"
 
 using namespace bpg;
 using gl::Ext;
@@ -104,37 +103,24 @@ int make_checker(const char* who, uint32_t air_id, const bp_stark_cfg* shape, co
                  Checker* k) {
   if (!shape) return fail(BP_ERR_INVALID_INPUT, "%s: null shape", who);
   // the shape is validated exactly as bp_quotient_eval's
-  const StarkCfg c{shape->log_n, shape->n_cols, shape->n_const, shape->deg_pow, shape->rate_bits, shape->cap_height,
-                   shape->num_queries, shape->pow_bits, shape->arity_bits, shape->final_poly_bits, air_id};
+  const StarkCfg c = to_cfg(*shape, air_id);
   int rc = check_cfg(c);
   if (rc) return rc;
-  if (!trace || !n_violated_rows || !n_viol || (max_rows && !rows_out) || (max_viol && !viol_out))
+  if (!n_violated_rows || !n_viol || (max_rows && !rows_out) || (max_viol && !viol_out))
     return fail(BP_ERR_INVALID_INPUT, "%s: null argument", who);
-  if (stride < ((uint64_t)1 << c.log_n)) return fail(BP_ERR_INVALID_INPUT, "%s: column stride %llu is shorter than the %u-row trace",
-                                                     who, (unsigned long long)stride, 1u << c.log_n);
-  if (c.n_const && !consts) return fail(BP_ERR_INVALID_INPUT, "%s: the AIR reads %u constant columns: pass them", who, c.n_const);
-  k->program = air::prog::find(air_id);
-  if (air::prog::is_registered(air_id) && !k->program) return fail(BP_ERR_INVALID_INPUT, "%s: AIR program 0x%08x was unregistered", who, air_id);
-  if (air_id == air::PLONK || (k->program && k->program->n_public)) {
-    if (!pub) return fail(BP_ERR_INVALID_INPUT, "%s: the AIR reads public inputs (AIR 8: four, bound to its first row): pass four words", who);
-    for (int j = 0; j < 4; j++) {
-      if (pub[j] >= gl::P) return fail(BP_ERR_INVALID_INPUT, "%s: non-canonical public input", who);
-      k->pub[j] = pub[j];
-    }
-  }
+  CallerTable t = caller_table(c, trace, stride, consts, pub);
+  if (air::prog::is_registered(air_id) && !t.program) return fail(BP_ERR_INVALID_INPUT, "%s: AIR program 0x%08x was unregistered", who, air_id);
+  if (!t.reads_public()) t.pub = nullptr;  // public inputs the AIR does not read are not looked at
+  if ((rc = check_caller_table(who, "", t))) return rc;
+  k->program = t.program;
+  if (t.pub)
+    for (int j = 0; j < 4; j++) k->pub[j] = t.pub[j];
   k->shape = air::Shape{air_id, c.n_cols, c.n_const, c.deg_pow};
   k->log_n = c.log_n;
   k->T = air::any_n_constraints(k->shape);
   k->n_units = air::any_n_units(k->shape);
   if ((rc = bp_air_describe(air_id, c.n_cols, c.n_const, c.deg_pow, &k->desc))) return rc;
   return BP_OK;
-}
-
-uint64_t fresh_challenge(std::mt19937_64& g) {
-  uint64_t a;
-  do a = g() % gl::P;
-  while (a < 2);
-  return a;
 }
 
 }  // namespace
@@ -209,16 +195,15 @@ int bp_air_check_trace(uint32_t air_id, const bp_stark_cfg* shape, const uint64_
   a.trace = d_trace; a.consts = K ? d_consts : nullptr; a.stride = stride;
   a.air_id = air_id; a.log_n = k.log_n; a.n_cols = C; a.n_const = K; a.deg_pow = k.shape.deg_pow; a.T = k.T;
   for (int j = 0; j < 4; j++) a.pub[j] = k.pub[j];
-  std::random_device rd;
-  std::mt19937_64 g(((uint64_t)rd() << 32) ^ rd());
-  a.alpha0 = fresh_challenge(g);
-  a.alpha1 = fresh_challenge(g);
+  FreshChallenges fresh;
+  a.alpha0 = fresh();
+  a.alpha1 = fresh();
   const uint64_t partial = air_check_partial_words(a);
   // (a test / integration entry: its scratch is a buffer of its own) apow | count | bitmap | partial folds
   const uint64_t scratch_words = 2 * (uint64_t)k.T + 1 + words + partial;
-  uint64_t* d_s = nullptr;
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), scratch_words * 8));
-  struct Free { void* p; ~Free() { (void)hipFree(p); } } guard{d_s};
+  DeviceBuf scratch, rows_buf, out_buf;
+  BPG_HIP(hipMalloc(&scratch.p, scratch_words * 8));
+  uint64_t* d_s = scratch.as<uint64_t>();
   a.apow = d_s;
   a.count = reinterpret_cast<unsigned long long*>(d_s + 2 * (uint64_t)k.T);
   a.bitmap = d_s + 2 * (uint64_t)k.T + 1;
@@ -240,12 +225,10 @@ int bp_air_check_trace(uint32_t air_id, const bp_stark_cfg* shape, const uint64_
   constexpr uint32_t BATCH = 256;  // rows per gather (grid.y)
   std::vector<uint32_t> want;
   std::vector<uint64_t> got;
-  uint32_t* d_rows = nullptr;
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d_rows), 2 * BATCH * 4));
-  struct Free2 { void* p; ~Free2() { (void)hipFree(p); } } guard2{d_rows};
-  uint64_t* d_out = nullptr;
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)2 * BATCH * (C + K) * 8));
-  struct Free3 { void* p; ~Free3() { (void)hipFree(p); } } guard3{d_out};
+  BPG_HIP(hipMalloc(&rows_buf.p, 2 * BATCH * 4));
+  BPG_HIP(hipMalloc(&out_buf.p, (size_t)2 * BATCH * (C + K) * 8));
+  uint32_t* d_rows = rows_buf.as<uint32_t>();
+  uint64_t* d_out = out_buf.as<uint64_t>();
   for (size_t r0 = 0; r0 < rows.size(); r0 += BATCH) {
     const uint32_t m = (uint32_t)std::min<size_t>(BATCH, rows.size() - r0);
     want.clear();

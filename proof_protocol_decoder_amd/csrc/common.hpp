@@ -61,6 +61,17 @@ struct KernelTimer {
     else KERNEL<<<grid, block, lds, st>>>(__VA_ARGS__);                                                                 \
   } while (0)
 
+// A hipMalloc'd buffer of an entry that brings its own scratch (test / integration entries: the proving path has its
+// arena), freed on every way out of the scope, an exception included:  BPG_HIP(hipMalloc(&buf.p, bytes));
+struct DeviceBuf {
+  void* p = nullptr;
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { if (p) (void)hipFree(p); }
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline unsigned ceil_div(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 

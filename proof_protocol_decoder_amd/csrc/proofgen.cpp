@@ -15,7 +15,6 @@
 #include <thread>
 #include <deque>
 #include <functional>
-#include <random>
 #include <set>
 #include <unordered_map>
 #include "air_check.hpp"
@@ -1149,9 +1148,9 @@ namespace {
 int lookup_side_terms(Worker& w, uint32_t air_id, const uint64_t* d_trace, uint32_t log_n, uint32_t col0, uint32_t n_cols,
                       uint32_t stride, uint64_t beta, uint64_t gamma, std::vector<uint64_t>* out) {
   const uint64_t N = (uint64_t)1 << log_n;
-  uint64_t* d = nullptr;
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n_cols * N * 8));
-  struct Free { void* p; ~Free() { (void)hipFree(p); } } guard{d};
+  DeviceBuf terms;
+  BPG_HIP(hipMalloc(&terms.p, (size_t)n_cols * N * 8));
+  uint64_t* d = terms.as<uint64_t>();
   for (uint32_t m = 0; m < n_cols; m++)
     if (int r = launch_lookup_terms(air_id, d_trace, log_n, col0 + stride * m, beta, gamma, d + (size_t)m * N, w.stream)) return r;
   out->resize((size_t)n_cols * N);
@@ -1225,8 +1224,7 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     }
   }
   // the lookups, as multisets of compressed tuples under fresh challenges
-  std::random_device rd;
-  std::mt19937_64 g(((uint64_t)rd() << 32) ^ rd());
+  FreshChallenges fresh;
   const air::ctl::Pair* P = air::ctl::pairs();
   for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
     const air::ctl::Pair& p = P[i];
@@ -1234,9 +1232,7 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
     o.first_looking_row = o.first_looked_row = -1;
     if (!pair_active(tcfg, p)) continue;
     o.checked = 1;
-    uint64_t beta, gamma;
-    do beta = g() % gl::P; while (beta < 2);
-    do gamma = g() % gl::P; while (gamma < 2);
+    const uint64_t beta = fresh(), gamma = fresh();
     std::vector<uint64_t> a, b;
     const uint32_t la = tcfg[p.looking_table].log_n, lb = tcfg[p.looked_table].log_n;
     if ((r = lookup_side_terms(w, p.looking_air, d_trace[p.looking_table], la, p.looking_col, p.n_looking, p.stride, beta, gamma, &a))) return r;

@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstring>
+#include <random>
 #include <vector>
 #include "common.hpp"
 #include "gl.hpp"
@@ -60,6 +61,16 @@ class Challenger {
   }
   uint64_t state_[12], in_[8], out_[8];
   unsigned n_in_, n_out_;
+};
+
+// the challenges of a check that proves nothing (the pre-flights, the trace checker): fresh per call, never 0 or 1
+struct FreshChallenges {
+  std::mt19937_64 g{((uint64_t)std::random_device{}() << 32) ^ std::random_device{}()};
+  uint64_t operator()() {
+    uint64_t a;
+    do a = g() % gl::P; while (a < 2);
+    return a;
+  }
 };
 
 // ---- shapes ----

@@ -8,6 +8,7 @@ import pytest
 
 import air_program_cases as cases
 from air_program_cases import P
+from air_program_port_cases import LIMBS, SELF_LINK, cfg_of, count_limbs, range_program, range_witness, self_checked_table
 from proof_protocol_decoder_amd._lib import BpgError
 from proof_protocol_decoder_amd.air_program import ALL_ROWS, LAST_ROW, TRANSITION, Builder
 from test_gpu_air_program import constants_cap
@@ -307,58 +308,6 @@ def test_range_multiplicities_name_the_first_value_out_of_range(bpg):
 
 
 # ---------------------------------------------------------------------------------------------- 5. table sets
-
-LIMBS = 3
-
-
-def range_program(limb_kind_multiplicity=False, n_limbs=LIMBS, looked=True):
-    """A table that range-checks its own limbs.  Columns 0 .. n_limbs - 1: the limbs; column 3: which rows send (nothing
-    of the table's own constrains it: only the port's f f - f does); column 4: how often the table's constant column
-    (0 .. n - 1) is asked for each value; column 5: a counter; columns 6, 7: zero.  Ports 0 .. n_limbs - 1 send a limb each,
-    the last port exposes the constant column with the multiplicities as its filter."""
-    b = Builder(8, n_const=1 if looked else 0)
-    count = b.family(1, TRANSITION, 1)
-    zero = b.family(2, ALL_ROWS, 1)
-    b.unit()
-    b.emit(count, b.nxt(5) - b.loc(5) - 1)
-    b.emit(zero, b.loc(6))
-    b.emit(zero + 1, b.loc(7))
-    for k in range(n_limbs):
-        b.log_port(b.loc(3), [b.loc(k)], multiplicity=limb_kind_multiplicity)
-    if looked:
-        b.log_port(b.loc(4), [b.cst(0)], multiplicity=True)
-    return b
-
-
-def range_witness(log_n, limb_bound, rng, n_limbs=LIMBS):
-    """limbs below limb_bound on every row, sent by a seeded two thirds of the rows; multiplicities still zero"""
-    n = 1 << log_n
-    t = np.zeros((8, n), dtype=np.uint64)
-    t[:n_limbs] = rng.integers(0, limb_bound, size=(n_limbs, n), dtype=np.uint64)
-    t[3] = (rng.integers(0, 3, size=n) != 0).astype(np.uint64)
-    t[5] = np.arange(5, 5 + n, dtype=np.uint64)
-    return t
-
-
-def count_limbs(bpg, t, log_range, out=None, n_limbs=LIMBS):
-    return bpg.ops.range_multiplicities(to_dev(t)[:n_limbs], log_range, filter=to_dev(t[3]), out=out)
-
-
-def cfg_of(air_id, log_n):
-    return cases.cfg_for(air_id, log_n, num_queries=6, pow_bits=6)
-
-
-SELF_LINK = [([(0, k) for k in range(LIMBS)], (0, LIMBS))]
-
-
-def self_checked_table(bpg, limb_kind_multiplicity=False, seed=0x1D000):
-    """(registered id, trace with honest multiplicities, constants 0 .. 63, the one-table statement)"""
-    reg = bpg.ops.air_register(range_program(limb_kind_multiplicity).assemble())
-    t = range_witness(6, 64, np.random.default_rng(seed))
-    t[4] = to_host(count_limbs(bpg, t, 6))
-    consts = np.arange(64, dtype=np.uint64).reshape(1, 64)
-    return reg, t, consts, [{"air_id": reg, "cfg": cfg_of(reg, 6)}]
-
 
 def proven(bpg, tables, traces, consts, links, **kw):
     full = [dict(t, trace=to_dev(tr), **({"consts": to_dev(c)} if c is not None else {})) for t, tr, c in zip(tables, traces, consts)]

@@ -9,6 +9,7 @@ import pytest
 import air_program_cases as cases
 import air_program_port_cases as pc
 from air_program_cases import P
+from air_program_port_cases import LINK, WIDTH, balanced_pair, cfg_of, field, flagged, rows_of
 from proof_protocol_decoder_amd.air_program import ALL_ROWS, LAST_ROW, TRANSITION, Builder
 from util import to_dev, to_host
 
@@ -30,10 +31,6 @@ def random_lde(n_cols, rows, seed):
 def challenges(seed, k=4):
     rng = np.random.default_rng(seed)
     return [int(v) for v in rng.integers(2, P, size=k, dtype=np.uint64)]
-
-
-def field(rng, shape):
-    return rng.integers(0, P, size=shape, dtype=np.uint64)
 
 
 # ---------------------------------------------------------------------------------------------- 1. the products
@@ -304,37 +301,6 @@ def test_memory_transcription_with_a_port_gives_the_built_in_proof(bpg, log_n, n
 
 # ---------------------------------------------------------------------------------------------- 4 .. 6. table sets
 
-WIDTH = 3
-
-
-def cfg_of(air_id, log_n):
-    return cases.cfg_for(air_id, log_n, num_queries=6, pow_bits=6)
-
-
-def rows_of(log_n, rng, k):
-    return sorted(int(v) for v in rng.choice(1 << log_n, size=k, replace=False))
-
-
-def flagged(log_n, rows, tuples, rng, width=WIDTH, n_cols=8):
-    """a flag_witness whose rows `rows` are flagged and hold `tuples`; the other rows hold random tuples, unflagged"""
-    n = 1 << log_n
-    flags = [0] * n
-    body = [[int(v) for v in field(rng, width)] for _ in range(n)]
-    for row, tup in zip(rows, tuples):
-        flags[row], body[row] = 1, list(tup)
-    return pc.flag_witness(log_n, flags, body, width=width, n_cols=n_cols)
-
-
-def balanced_pair(seed=0xD000):
-    """A (2^5 rows) sends 9 tuples, one of them twice; B (2^7 rows) exposes a seeded permutation of the 10"""
-    rng = np.random.default_rng(seed)
-    sent = [[int(v) for v in field(rng, WIDTH)] for _ in range(9)]
-    sent.append(list(sent[3]))
-    a_rows, b_rows = rows_of(5, rng, 10), rows_of(7, rng, 10)
-    exposed = [sent[k] for k in rng.permutation(10)]
-    return flagged(5, a_rows, sent, rng), flagged(7, b_rows, exposed, rng), a_rows, b_rows
-
-
 def statement(bpg, reg, shapes):
     return [{"air_id": r, "cfg": cfg_of(r, log_n)} for r, log_n in zip(reg, shapes)]
 
@@ -354,9 +320,6 @@ def members(container, links):
         off += 4 + n_words
     assert off == container.size
     return out
-
-
-LINK = [([(0, 0)], (1, 0))]
 
 
 def rejected(bpg, tables, links, container, what=None, code=-5):
@@ -397,13 +360,8 @@ def test_a_balanced_set_proves_and_verifies_and_every_flipped_bit_is_rejected(bp
 
 def test_two_looking_ports_on_two_tables_into_one_looked_port(bpg):
     reg = bpg.ops.air_register(pc.flag_program().assemble())
-    rng = np.random.default_rng(0xD200)
-    s1 = [[int(v) for v in field(rng, WIDTH)] for _ in range(6)]
-    s2 = [[int(v) for v in field(rng, WIDTH)] for _ in range(11)] + [list(s1[0])]
-    exposed = [(s1 + s2)[k] for k in rng.permutation(18)]
-    traces = [flagged(5, rows_of(5, rng, 6), s1, rng), flagged(6, rows_of(6, rng, 12), s2, rng), flagged(7, rows_of(7, rng, 18), exposed, rng)]
+    traces, links = pc.two_looking_tables()
     tables = statement(bpg, [reg] * 3, [5, 6, 7])
-    links = [([(0, 0), (1, 0)], (2, 0))]
     container = bpg.ops.stark_prove_table_set(with_traces(tables, traces), links)
     bpg.ops.stark_verify_table_set(tables, links, container)
     assert [int(p[4]) for _, p in members(container, links)] == [2, 2, 2]
@@ -497,16 +455,8 @@ def test_the_statement_is_the_verifiers(bpg):
 
 def test_a_run_time_table_looks_words_up_in_the_built_in_memory_table(bpg):
     from proof_protocol_decoder_amd._lib import BpgError
-    from test_memory_air import random_log
-    reader = bpg.ops.air_register(pc.flag_program(width=11, n_cols=16).assemble())
-    log = random_log(64, 0xE000, n_addr=6)
-    rng = np.random.default_rng(0xE001)
-    asked = rows_of(6, rng, 9)
-    mem = bpg.ops.memory_trace(6, inputs=to_dev(log))
-    mem[pc.MEM_G, asked] = 1
-    words = [[int(v) for v in log[row]] for row in asked]
-    r = flagged(5, rows_of(5, rng, 9), [words[k] for k in rng.permutation(9)], rng, width=11, n_cols=16)
-    tables = [{"air_id": reader, "cfg": cfg_of(reader, 5)}, {"air_id": 3, "cfg": cfg_of(3, 6)}]
+    tables, (r, mem) = pc.memory_readers(bpg)
+    reader = tables[0]["air_id"]
     container = bpg.ops.stark_prove_table_set([dict(tables[0], trace=to_dev(r)), dict(tables[1], trace=mem)], LINK)
     bpg.ops.stark_verify_table_set(tables, LINK, container)
     assert [int(p[14]) for _, p in members(container, LINK)] == [reader, 3]

@@ -317,68 +317,59 @@ def keccak_f(lanes):
     return a
 
 
-def keccak_trace(log_n, seed=0, inputs=None):
-    """orc_keccak_trace: the AIR-1 witness [2431, 2^log_n] (the last column, the lookup's filter, zero)."""
-    out = np.zeros((KECCAK_COLS, 1 << log_n), dtype=np.uint64)
+# the built-in table AIRs by id: (name in orc_<name>_trace, trace width, shape of the inputs at 2^log_n rows)
+AIR_TRACES = {1: ("keccak", KECCAK_COLS, lambda log_n: (((1 << log_n) + 23) // 24, 25)),
+              2: ("logic", LOGIC_COLS, lambda log_n: (1 << log_n, 9)),
+              3: ("memory", MEMORY_COLS, lambda log_n: (1 << log_n, 11)),
+              4: ("arithmetic", ARITHMETIC_COLS, lambda log_n: (1 << log_n, 9)),
+              5: ("byte_packing", BYTE_PACKING_COLS, lambda log_n: (1 << log_n, 6)),
+              6: ("keccak_sponge", KECCAK_SPONGE_COLS, lambda log_n: (1 << log_n, 44)),
+              7: ("arithmetic_mul", ARITHMETIC_MUL_COLS, lambda log_n: (1 << log_n, 9))}
+
+
+def air_trace(air_id, log_n, seed=0, inputs=None):
+    """orc_<name>_trace of the built-in table AIR `air_id` (1..7): the witness [n_cols, 2^log_n] from `inputs` or seeded."""
+    name, n_cols, in_shape = AIR_TRACES[air_id]
+    out = np.zeros((n_cols, 1 << log_n), dtype=np.uint64)
     inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
     if inp is not None:
-        assert inp.shape == (((1 << log_n) + 23) // 24, 25)
-    lib().orc_keccak_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
+        assert inp.shape == in_shape(log_n)
+    getattr(lib(), "orc_%s_trace" % name)(seed, inp.ctypes.data if inp is not None else None, log_n, out)
     return out
+
+
+def keccak_trace(log_n, seed=0, inputs=None):
+    """orc_keccak_trace: the AIR-1 witness [2431, 2^log_n] (the last column, the lookup's filter, zero)."""
+    return air_trace(1, log_n, seed, inputs)
 
 
 def logic_trace(log_n, seed=0, inputs=None):
     """orc_logic_trace: the AIR-2 witness [524, 2^log_n]; inputs [2^log_n, 9] (code, operand 0, operand 1) or seeded."""
-    out = np.zeros((LOGIC_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 9)
-    lib().orc_logic_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(2, log_n, seed, inputs)
 
 
 def memory_trace(log_n, seed=0, inputs=None):
     """orc_memory_trace: the AIR-3 witness [45, 2^log_n] (the last column, the lookup's filter, zero); inputs [2^log_n, 11] (is_read, address, timestamp, value[8],
     sorted by address then timestamp) or a log drawn from the seed."""
-    out = np.zeros((MEMORY_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 11)
-    lib().orc_memory_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(3, log_n, seed, inputs)
 
 
 def arithmetic_trace(log_n, seed=0, inputs=None):
     """orc_arithmetic_trace: the AIR-4 witness [309, 2^log_n]; inputs [2^log_n, 9] (code 0 none / 1 add / 2 sub / 3 lt /
     4 gt, x, y as four u64 each) or seeded."""
-    out = np.zeros((ARITHMETIC_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 9)
-    lib().orc_arithmetic_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(4, log_n, seed, inputs)
 
 
 def byte_packing_trace(log_n, seed=0, inputs=None):
     """orc_byte_packing_trace: the AIR-5 witness [299, 2^log_n]; inputs [2^log_n, 6] (is_read, len, the 32 byte slots as
     four u64) or seeded."""
-    out = np.zeros((BYTE_PACKING_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 6)
-    lib().orc_byte_packing_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(5, log_n, seed, inputs)
 
 
 def arithmetic_mul_trace(log_n, seed=0, inputs=None):
     """orc_arithmetic_mul_trace: the AIR-7 witness [1217, 2^log_n]; inputs [2^log_n, 9] (is_mul, x, y as four u64 each)
     or seeded."""
-    out = np.zeros((ARITHMETIC_MUL_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 9)
-    lib().orc_arithmetic_mul_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(7, log_n, seed, inputs)
 
 
 def keccak_sponge_rows(msg: bytes):
@@ -392,12 +383,7 @@ def keccak_sponge_rows(msg: bytes):
 def keccak_sponge_trace(log_n, seed=0, inputs=None):
     """orc_keccak_sponge_trace: the AIR-6 witness [2414, 2^log_n]; inputs [2^log_n, 44] (keccak_sponge_rows, flags 0 =
     padding row) or seeded."""
-    out = np.zeros((KECCAK_SPONGE_COLS, 1 << log_n), dtype=np.uint64)
-    inp = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None else None
-    if inp is not None:
-        assert inp.shape == (1 << log_n, 44)
-    lib().orc_keccak_sponge_trace(seed, inp.ctypes.data if inp is not None else None, log_n, out)
-    return out
+    return air_trace(6, log_n, seed, inputs)
 
 
 class Committed:

@@ -120,8 +120,15 @@ ARITHMETIC_COLS = 309
 BYTE_PACKING_COLS = 299
 KECCAK_SPONGE_COLS = 2414
 ARITHMETIC_MUL_COLS = 1217
-AIR_COLS = {1: KECCAK_COLS, 2: LOGIC_COLS, 3: MEMORY_COLS, 4: ARITHMETIC_COLS, 5: BYTE_PACKING_COLS, 6: KECCAK_SPONGE_COLS,
-            7: ARITHMETIC_MUL_COLS}   # by AIR id
+# the built-in table AIRs by id: (name in bp_<name>_trace, trace width, shape of the caller's inputs at 2^log_n rows)
+AIR_TRACES = {1: ("keccak", KECCAK_COLS, lambda log_n: (((1 << log_n) + 23) // 24, 25)),
+              2: ("logic", LOGIC_COLS, lambda log_n: (1 << log_n, 9)),
+              3: ("memory", MEMORY_COLS, lambda log_n: (1 << log_n, 11)),
+              4: ("arithmetic", ARITHMETIC_COLS, lambda log_n: (1 << log_n, 9)),
+              5: ("byte_packing", BYTE_PACKING_COLS, lambda log_n: (1 << log_n, 6)),
+              6: ("keccak_sponge", KECCAK_SPONGE_COLS, lambda log_n: (1 << log_n, 44)),
+              7: ("arithmetic_mul", ARITHMETIC_MUL_COLS, lambda log_n: (1 << log_n, 9))}
+AIR_COLS = {air_id: n_cols for air_id, (_, n_cols, _) in AIR_TRACES.items()}
 
 
 def air_describe(air_id, n_cols=0, n_const=0, deg_pow=1):
@@ -154,12 +161,14 @@ def air_program_digest(air_id):
     return out.raw
 
 
-def _table_trace(name, n_cols, in_shape, log_n, seed, inputs, device):
-    """bp_<name>_trace: the [n_cols, 2^log_n] witness from `inputs` ([*in_shape] int64 on the device) or from `seed`."""
+def air_trace(air_id, log_n, seed=0, inputs=None, device="cuda"):
+    """bp_<name>_trace of the built-in table AIR `air_id` (1..7): the [n_cols, 2^log_n] witness from `inputs` (int64 on the
+    device, in the shape AIR_TRACES gives) or drawn from `seed`."""
+    name, n_cols, in_shape = AIR_TRACES[air_id]
     out = torch.empty((n_cols, 1 << log_n), dtype=torch.int64, device=device)
     if inputs is not None:
         _require_cuda(inputs)
-        assert inputs.shape == in_shape
+        assert inputs.shape == in_shape(log_n)
     check(getattr(lib(), "bp_%s_trace" % name)(inputs.data_ptr() if inputs is not None else None, seed, log_n, out.data_ptr(),
                                                _stream()))
     return out
@@ -168,43 +177,43 @@ def _table_trace(name, n_cols, in_shape, log_n, seed, inputs, device):
 def logic_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_logic_trace: the AIR-2 witness [524, 2^log_n]; inputs [2^log_n, 9] int64 on the device (operation code, the
     four words of operand 0, of operand 1), or drawn from `seed`."""
-    return _table_trace("logic", LOGIC_COLS, (1 << log_n, 9), log_n, seed, inputs, device)
+    return air_trace(2, log_n, seed, inputs, device)
 
 
 def memory_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_memory_trace: the AIR-3 witness [45, 2^log_n]; inputs [2^log_n, 11] int64 on the device (is_read, address,
     timestamp, eight value limbs; sorted by address then timestamp), or a log drawn from `seed`."""
-    return _table_trace("memory", MEMORY_COLS, (1 << log_n, 11), log_n, seed, inputs, device)
+    return air_trace(3, log_n, seed, inputs, device)
 
 
 def arithmetic_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_arithmetic_trace: the AIR-4 witness [309, 2^log_n]; inputs [2^log_n, 9] int64 on the device (operation code
     0 none / 1 add / 2 sub / 3 lt / 4 gt, the four words of x, of y), or drawn from `seed`."""
-    return _table_trace("arithmetic", ARITHMETIC_COLS, (1 << log_n, 9), log_n, seed, inputs, device)
+    return air_trace(4, log_n, seed, inputs, device)
 
 
 def byte_packing_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_byte_packing_trace: the AIR-5 witness [299, 2^log_n]; inputs [2^log_n, 6] int64 on the device (is_read, len,
     the 32 byte slots as four words), or drawn from `seed`."""
-    return _table_trace("byte_packing", BYTE_PACKING_COLS, (1 << log_n, 6), log_n, seed, inputs, device)
+    return air_trace(5, log_n, seed, inputs, device)
 
 
 def keccak_sponge_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_sponge_trace: the AIR-6 witness [2414, 2^log_n]; inputs [2^log_n, 44] int64 on the device (flags, message
     bytes in the block, the block as absorbed, the state before it: proof_gen.keccak256_sponge_rows), or seeded."""
-    return _table_trace("keccak_sponge", KECCAK_SPONGE_COLS, (1 << log_n, 44), log_n, seed, inputs, device)
+    return air_trace(6, log_n, seed, inputs, device)
 
 
 def arithmetic_mul_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_arithmetic_mul_trace: the AIR-7 witness [1217, 2^log_n]; inputs [2^log_n, 9] int64 on the device (is_mul, the
     four words of x, of y), or drawn from `seed`."""
-    return _table_trace("arithmetic_mul", ARITHMETIC_MUL_COLS, (1 << log_n, 9), log_n, seed, inputs, device)
+    return air_trace(7, log_n, seed, inputs, device)
 
 
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""
-    return _table_trace("keccak", KECCAK_COLS, (((1 << log_n) + 23) // 24, 25), log_n, seed, inputs, device)
+    return air_trace(1, log_n, seed, inputs, device)
 
 
 def quotient_eval(cfg, trace_lde, aux_lde, const_lde, ctl, alphas, air_id=AIR_SYNTHETIC):

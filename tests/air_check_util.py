@@ -5,12 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-P = 0xFFFFFFFF00000001
-ORACLE_CONSTRAINTS = {1: "orc_keccak_constraints_base", 2: "orc_logic_constraints_base", 3: "orc_memory_constraints_base",
-                      4: "orc_arithmetic_constraints_base", 5: "orc_byte_packing_constraints_base",
-                      6: "orc_keccak_sponge_constraints_base", 7: "orc_arithmetic_mul_constraints_base"}
-# describe()'s family list of each AIR starts with its own families in this order (tests/test_*_air.py's names)
-FAMILY_PREFIX = {1: "F", 2: "L", 3: "M", 4: "A", 5: "P", 6: "K", 7: "U"}
+from builtin_airs import AIRS, P
 
 
 class OrcConsumer(C.Structure):
@@ -26,7 +21,7 @@ def oracle_fn(oracle, air_id):
     """a handle of its own on liboracle.so (argument types set here do not touch pyoracle's)"""
     if air_id not in _ORC:
         L = C.CDLL(oracle._LIB_PATH)
-        f = getattr(L, ORACLE_CONSTRAINTS[air_id])
+        f = getattr(L, AIRS[air_id].constraints)
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(OrcConsumer)]
         f.restype = None
         _ORC[air_id] = f

@@ -132,10 +132,10 @@ def two_looking_tables(seed=0xD200):
 def memory_readers(bpg):
     """(statement, [reader trace (numpy), memory trace (device)]): a 2^5-row flag table of 11-word tuples that looks nine
     rows of a 2^6-row operation log up in the built-in memory table made from that log"""
-    from test_memory_air import random_log
+    from builtin_airs import memory
     from util import to_dev
     reader = bpg.ops.air_register(flag_program(width=11, n_cols=16).assemble())
-    log = random_log(64, 0xE000, n_addr=6)
+    log = memory.random_log(64, 0xE000, n_addr=6)
     rng = np.random.default_rng(0xE001)
     asked = rows_of(6, rng, 9)
     mem = bpg.ops.memory_trace(6, inputs=to_dev(log))

@@ -8,11 +8,10 @@ import re
 import numpy as np
 import pytest
 
-from air_check_util import FAMILY_PREFIX, P, oracle_constraint_values, oracle_violated_rows, selectors
+from air_check_util import P, oracle_constraint_values, oracle_violated_rows, selectors
+from builtin_airs import AIRS, checker_breaks, memory
 
 LOG_N = 6
-TRACES = {1: "keccak_trace", 2: "logic_trace", 3: "memory_trace", 4: "arithmetic_trace", 5: "byte_packing_trace",
-          6: "keccak_sponge_trace", 7: "arithmetic_mul_trace"}
 
 
 def ops():
@@ -22,14 +21,15 @@ def ops():
 
 
 def seeded(oracle, air_id, log_n=LOG_N, seed=0xC0DE):
-    return getattr(oracle, TRACES[air_id])(log_n, seed=seed)
+    return oracle.air_trace(air_id, log_n, seed=seed)
 
 
 def family_name(air_id, family):
-    return "%s%d" % (FAMILY_PREFIX[air_id], family)
+    """describe()'s family list of each AIR starts with its own families, in the order of their names"""
+    return "%s%d" % (AIRS[air_id].prefix, family)
 
 
-@pytest.mark.parametrize("air_id", sorted(TRACES))
+@pytest.mark.parametrize("air_id", sorted(AIRS))
 def test_seeded_traces_satisfy_their_air(oracle, air_id):
     for seed in (1, 0xC0DE):
         r = ops().check_air_trace_host(air_id, seeded(oracle, air_id, seed=seed))
@@ -56,23 +56,9 @@ def test_synthetic_trace_with_constants_satisfies_its_air(oracle):
     assert r.rows == [19] and {(v.constraint, v.family, v.kind) for v in r.violations} == {(4, 1, 1)}
 
 
-# (air, column, row, value or None for "xor 1", the families any of which may be named) -- the cell breaks of
-# tests/test_keccak_air.py, test_logic_air.py, test_memory_air.py, test_arithmetic_air.py, test_arithmetic_mul_air.py and
-# test_byte_packing_air.py whose target is the AIR itself (the lookup filters' constraints are not the AIR's)
-K_STEP, K_A, K_C, K_CP, K_AP, K_APP, K_APP0, K_APPP = 0, 24, 74, 394, 714, 2314, 2364, 2428
-BREAKS = [
-    (1, K_STEP + 3, 3, None, "F0 F1"), (1, K_C + 64 * 2 + 17, 9, None, "F3 F5"), (1, K_CP + 64 * 4 + 63, 30, None, "F3 F4"),
-    (1, K_AP + 64 * 13 + 5, 12, None, "F4 F5 F6"), (1, K_A + 2 * 7 + 1, 25, None, "F5 F9"), (1, K_APP + 2 * 11, 40, None, "F6 F9"),
-    (1, K_APP0 + 31, 2, None, "F7 F8"), (1, K_APPP + 1, 7, None, "F8 F9"),
-    (2, 0, 3, 2, "L0"), (2, 1, 5, None, "L1 L3"), (2, 3 + 77, 9, 2, "L2"), (2, 259 + 200, 11, None, "L3"), (2, 515 + 4, 20, None, "L3"),
-    (3, 0, 3, 2, "M0"), (3, 11, 9, 2, "M1"), (3, 12 + 5, 20, 3, "M2"), (3, 11, 17, None, "M3 M4"),
-    (4, 2, 3, 2, "A0"), (4, 0, 5, None, "A1 A4"), (4, 36 + 100, 9, 2, "A2"), (4, 292 + 7, 11, None, "A3 A4"), (4, 4 + 3, 13, None, "A4"),
-    (4, 36 + 255, 17, None, "A4"), (4, 308, 19, None, "A5"),
-    (5, 1 + 4, 3, 2, "P1"), (5, 33 + 70, 9, 2, "P3"), (5, 289, 13, 0x100, "P5"), (5, 0, 2, 3, "P0"),
-    (7, 0, 3, 2, "U0"), (7, 33 + 77, 5, 2, "U1"), (7, 289 + 200, 7, 2, "U2"), (7, 545 + 21 * 9 + 4, 9, 2, "U3"),
-    (7, 1 + 6, 11, None, "U4"), (7, 33, 13, None, "U4"), (7, 289 + 255, 15, None, "U4"), (7, 545 + 21 * 20 + 3, 17, None, "U4"),
-    (7, 545 + 21 * 31, 19, None, "U4 U5"),
-]
+# (air, column, row, value or None for "xor 1", the families any of which may be named): the cell breaks of
+# tests/builtin_airs.py whose target is the AIR itself (the lookup filters' constraints are not the AIR's)
+BREAKS = checker_breaks()
 
 
 @pytest.mark.parametrize("air_id,col,row,val,fams", BREAKS, ids=["%d-%s@%d" % (b[0], b[4].replace(" ", "/"), b[2]) for b in BREAKS])
@@ -93,8 +79,7 @@ def test_a_corrupted_cell_is_named_at_its_row_with_its_family(oracle, air_id, co
 
 
 def test_a_stale_memory_read_is_named_at_the_row_before(oracle):
-    from test_memory_air import random_log
-    log = random_log(64, 11, n_addr=6)
+    log = memory.random_log(64, 11, n_addr=6)
     r0 = next(i for i in range(1, 64) if log[i, 0] == 1 and log[i, 1] == log[i - 1, 1])
     log[r0, 3 + 2] ^= np.uint64(5)
     r = ops().check_air_trace_host(3, oracle.memory_trace(6, inputs=log))
@@ -109,7 +94,7 @@ def _corrupt(t, k, rng):
     return rows
 
 
-@pytest.mark.parametrize("air_id", sorted(TRACES))
+@pytest.mark.parametrize("air_id", sorted(AIRS))
 def test_rows_agree_with_the_oracle(oracle, air_id):
     """The rows the host entry reports are exactly those whose oracle fold (orc_*_constraints_base with the trace
     domain's selectors) is non-zero; for the AIRs of at most ~600 constraints the values too, constraint by constraint."""

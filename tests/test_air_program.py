@@ -10,6 +10,7 @@ import pytest
 
 import air_program_cases as cases
 import air_program_random as rnd
+import builtin_airs as ba
 from air_program_cases import P
 from proof_protocol_decoder_amd.air_program import (ALL_ROWS, FIRST_ROW, LAST_ROW, OP_EMIT, OP_IMM, OP_LOC, OP_MUL, TRANSITION,
                                                     Builder)
@@ -555,20 +556,16 @@ def test_validator_accepts_exactly_what_the_header_comment_says():
 
 # ---------------------------------------------------------------------------------------------- 4. against the built-ins
 
-TRACES = {3: "memory_trace", 4: "arithmetic_trace", 7: "arithmetic_mul_trace"}
-
-
 @pytest.mark.parametrize("air_id", sorted(TRANSCRIPTIONS))
 def test_a_valid_witness_has_no_violation_under_its_transcription(oracle, air_id):
     reg = cases.register(TRANSCRIPTIONS[air_id]())
     for seed in (1, 0xC0DE):
-        r = ops().check_air_trace_host(reg, getattr(oracle, TRACES[air_id])(6, seed=seed))
+        r = ops().check_air_trace_host(reg, oracle.air_trace(air_id, 6, seed=seed))
         assert r.ok and r.rows == [] and r.violations == [], r
 
 
 def _breaks():
-    from test_air_check import BREAKS
-    return [b[:4] for b in BREAKS if b[0] in TRANSCRIPTIONS]
+    return [b[:4] for b in ba.checker_breaks() if b[0] in TRANSCRIPTIONS]
 
 
 def both_checks(reg, air_id, t):
@@ -585,7 +582,7 @@ def test_a_corrupted_cell_gives_the_built_ins_violations(oracle, air_id, col, ro
     """one cell per constraint family (the cells tests/test_air_check.py breaks): the same (row, constraint, family,
     kind, value) list from the transcription and from the built-in id"""
     reg = cases.register(TRANSCRIPTIONS[air_id]())
-    t = getattr(oracle, TRACES[air_id])(6, seed=0xC0DE)
+    t = oracle.air_trace(air_id, 6, seed=0xC0DE)
     t[col, row] = np.uint64(val) if val is not None else t[col, row] ^ np.uint64(1)
     both_checks(reg, air_id, t)
 
@@ -614,11 +611,10 @@ def test_the_memory_airs_value_families_give_the_built_ins_violations(oracle):
 def test_oracle_proof_verifies_under_the_registered_id(oracle, air_id, log_n):
     """An oracle proof of the built-in AIR, header word 14 rewritten to the registered id (the id is in no transcript),
     is accepted under the transcription and rejected under a transcription with 65536 -> 65535 in the carry equations."""
-    mod = __import__("test_arithmetic_air" if air_id == 4 else "test_arithmetic_mul_air")
     make = TRANSCRIPTIONS[air_id]
-    cfg = mod.small_cfg(oracle, log_n)
-    trace = getattr(oracle, TRACES[air_id])(log_n, seed=0xA11CE + log_n)
-    proof, _, _ = mod.prove(oracle, cfg, trace)
+    cfg = ba.small_cfg(oracle, ba.AIRS[air_id], log_n)
+    trace = oracle.air_trace(air_id, log_n, seed=0xA11CE + log_n)
+    proof, _, _ = ba.prove(oracle, cfg, trace)
     assert int(proof[14]) == air_id
     good, wrong = cases.register(make()), cases.register(make(carry_weight=65535))
     assert good != wrong

@@ -594,13 +594,13 @@ def test_memory_and_byte_packing_work_of_a_decoded_transaction():
     sequences of an entry are the traffic of exactly the bytes its Keccak table hashes -- the sequences spell the
     32-byte chunks big-endian, the log replays as a memory whose reads return the words those chunks spell, each read
     being the operation (address, timestamp) its sequence names (the lookup byte_packing -> memory), and the oracle's
-    witnesses of both (padded to the table heights the IR asks for) satisfy what tests/test_memory_air.py and
-    tests/test_byte_packing_air.py check (host only)."""
+    witnesses of both (padded to the table heights the IR asks for) satisfy the row models of
+    tests/builtin_airs.py (host only)."""
     import numpy as np
     from oracle import pyoracle
     from proof_protocol_decoder_amd.block_driver import (hashed_preimages_of_generation_inputs, irs_from_generation_inputs,
                                                          memory_and_byte_packing_work_of_preimages)
-    import test_memory_air as tm
+    import builtin_airs as ba
     pyoracle.build()
     m = fresh_model()
     infos = [t for t, _ in block(m)]
@@ -642,12 +642,12 @@ def test_memory_and_byte_packing_work_of_a_decoded_transaction():
         for i in range(len(log), n_rows):
             last[2] += np.uint64(1)
             padded[i] = last
-        tm.check_trace_is_a_memory(pyoracle.memory_trace(ir.table_log_n[6], inputs=padded))
+        ba.memory.check_trace_is_a_memory(pyoracle.memory_trace(ir.table_log_n[6], inputs=padded))
         bp_rows = 1 << ir.table_log_n[1]
         bp = np.zeros((bp_rows, 6), dtype=np.uint64)
         bp[:len(seqs)] = seqs
         t = pyoracle.byte_packing_trace(ir.table_log_n[1], inputs=bp)
         for r, c in enumerate(chunks):
-            assert sum(int(t[289 + k, r]) << (32 * k) for k in range(8)) == int.from_bytes(c, "big")
-            assert (int(t[297, r]), int(t[298, r])) == (r, r + 2)
+            assert sum(int(t[ba.byte_packing.COL_VAL + k, r]) << (32 * k) for k in range(8)) == int.from_bytes(c, "big")
+            assert (int(t[ba.byte_packing.COL_ADDR, r]), int(t[ba.byte_packing.COL_TS, r])) == (r, r + 2)
     assert busy >= 2

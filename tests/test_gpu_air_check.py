@@ -8,19 +8,18 @@ import numpy as np
 import pytest
 
 from air_check_util import P, oracle_violated_rows
+from builtin_airs import AIRS, memory
 from util import to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 
-TRACE_FN = {1: "keccak_trace", 2: "logic_trace", 3: "memory_trace", 4: "arithmetic_trace", 5: "byte_packing_trace",
-            6: "keccak_sponge_trace", 7: "arithmetic_mul_trace"}
 # one reference height per table: Keccak-f 2^14, memory 2^17, the others at upstream's lower bounds (constants.rs;
 # arithmetic_mul is the arithmetic table's other half)
 REF_LOG_N = {1: 14, 2: 12, 3: 17, 4: 16, 5: 9, 6: 9, 7: 16}
 
 
 def dev_trace(bpg, air_id, log_n, seed):
-    return getattr(bpg.ops, TRACE_FN[air_id])(log_n, seed=seed)
+    return bpg.ops.air_trace(air_id, log_n, seed=seed)
 
 
 def corrupt(t, k, rng):
@@ -34,7 +33,7 @@ def corrupt(t, k, rng):
     return rows
 
 
-@pytest.mark.parametrize("air_id", sorted(TRACE_FN))
+@pytest.mark.parametrize("air_id", sorted(AIRS))
 def test_device_witnesses_satisfy_their_air(bpg, air_id):
     for log_n in (6, REF_LOG_N[air_id]):
         r = bpg.ops.check_air_trace(air_id, dev_trace(bpg, air_id, log_n, 0xA1 + log_n))
@@ -42,8 +41,7 @@ def test_device_witnesses_satisfy_their_air(bpg, air_id):
 
 
 def test_given_memory_log_satisfies_its_air(bpg):
-    from test_memory_air import random_log
-    log = random_log(256, 5)
+    log = memory.random_log(256, 5)
     t = bpg.ops.memory_trace(8, inputs=to_dev(log))
     assert bpg.ops.check_air_trace(3, t).ok
     log[40, 3] ^= np.uint64(1)   # a value limb of one operation: whatever it breaks, host and device see the same rows
@@ -52,7 +50,7 @@ def test_given_memory_log_satisfies_its_air(bpg):
     assert r.rows == bpg.ops.check_air_trace_host(3, to_host(bad), max_rows=256).rows
 
 
-@pytest.mark.parametrize("air_id", sorted(TRACE_FN))
+@pytest.mark.parametrize("air_id", sorted(AIRS))
 def test_device_rows_equal_the_host_entry_and_the_oracle(bpg, oracle, air_id):
     log_n = 6 + (air_id % 5)     # 2^6 .. 2^10
     rng = np.random.default_rng(0x700 + air_id)

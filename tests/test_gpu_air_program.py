@@ -16,7 +16,6 @@ from util import to_dev, to_host
 pytestmark = pytest.mark.gpu
 
 PROGRAM = {3: cases.memory_program, 4: cases.arithmetic_program, 7: cases.arithmetic_mul_program}
-TRACE = {3: "memory_trace", 4: "arithmetic_trace", 7: "arithmetic_mul_trace"}
 SEED = 0x5EED00000000A1F0
 
 
@@ -75,7 +74,7 @@ def test_prove_trace_with_a_built_in_id_is_prove_air(bpg, air_id, log_n, nq, pb)
     import torch
     cfg = cases.cfg_for(air_id, log_n, num_queries=nq, pow_bits=pb)
     want = bpg.ops.stark_prove_air(air_id, cfg, SEED + log_n)
-    trace = getattr(bpg.ops, TRACE[air_id])(log_n, seed=SEED + log_n)
+    trace = bpg.ops.air_trace(air_id, log_n, seed=SEED + log_n)
     got = bpg.ops.stark_prove_trace(air_id, cfg, trace)
     assert got.shape == want.shape and (got == want).all() and int(got[14]) == air_id
     if log_n <= 9:
@@ -111,7 +110,7 @@ def test_a_registered_transcription_gives_the_built_ins_proof(bpg, air_id, log_n
     tests/test_gpu_arithmetic*_air.py prove (2^16 / 2^14 rows); it verifies under its id only."""
     reg = cases.register(PROGRAM[air_id]())
     cfg = cases.cfg_for(air_id, log_n, num_queries=nq, pow_bits=pb)
-    trace = getattr(bpg.ops, TRACE[air_id])(log_n, seed=SEED + log_n)
+    trace = bpg.ops.air_trace(air_id, log_n, seed=SEED + log_n)
     with bpg.ops.tuned(assume_loaded=loaded):
         want = bpg.ops.stark_prove_trace(air_id, cfg, trace)
         got = bpg.ops.stark_prove_trace(reg, cfg, trace)
@@ -129,7 +128,7 @@ def test_a_registered_transcription_gives_the_built_ins_proof(bpg, air_id, log_n
 def test_a_corrupted_trace_yields_a_rejected_proof(bpg, air_id, col, row):
     reg = cases.register(PROGRAM[air_id]())
     cfg = cases.cfg_for(air_id, 5, num_queries=6, pow_bits=6)
-    trace = getattr(bpg.ops, TRACE[air_id])(5, seed=SEED)
+    trace = bpg.ops.air_trace(air_id, 5, seed=SEED)
     assert cases.verify(reg, cfg, bpg.ops.stark_prove_trace(reg, cfg, trace)) == 0
     set_cell(trace, col, row, cell(trace, col, row) ^ 1)
     assert not bpg.ops.check_air_trace(reg, trace).ok
@@ -180,9 +179,9 @@ def test_device_checker_agrees_with_the_host_pass(bpg, log_n):
 
 
 def test_a_stale_read_is_rejected_by_the_verifier(bpg):
-    from test_memory_air import random_log
+    from builtin_airs import memory
     reg = cases.register(cases.memory_program())
-    log = random_log(64, 11, n_addr=6)
+    log = memory.random_log(64, 11, n_addr=6)
     cfg = cases.cfg_for(reg, 6, num_queries=6, pow_bits=6)
     assert cases.verify(reg, cfg, bpg.ops.stark_prove_trace(reg, cfg, bpg.ops.memory_trace(6, inputs=to_dev(log)))) == 0
     r0 = next(i for i in range(1, 64) if log[i, 0] == 1 and log[i, 1] == log[i - 1, 1])

@@ -1,90 +1,8 @@
-"""AIR 7 (multiplication, csrc/air.hpp) on the GPU against the oracle's independent statement of it (oracle/arithmetic_mul_air.c): the
-witness generator, K5 alone through bp_quotient_eval(air_id = 7, ...), and whole table proofs byte for byte."""
-import ctypes as C
+"""AIR 7 (multiplication, csrc/air.hpp) on the GPU against the oracle's independent statement of it
+(oracle/arithmetic_mul_air.c): the witness generator, K5 alone through bp_quotient_eval, and whole table proofs byte
+for byte.  The tests are builtin_airs.gpu_tests, the same for all seven AIRs, over this AIR's record (its shapes,
+seeds and spot checks, with a note on why those heights)."""
+from builtin_airs import arithmetic_mul, gpu_tests
 
-import numpy as np
-import pytest
-
-from util import P, coset_major_to_natural, rand_field, to_dev, to_host
-
-pytestmark = pytest.mark.gpu
-SEED = 0x5EED00000000000B
-
-
-@pytest.mark.parametrize("log_n", [4, 9, 13])
-def test_witness_matches_oracle(bpg, oracle, log_n):
-    want = oracle.arithmetic_mul_trace(log_n, seed=SEED + log_n)
-    got = to_host(bpg.ops.arithmetic_mul_trace(log_n, seed=SEED + log_n))
-    assert got.shape == want.shape == (1217, 1 << log_n) and (got == want).all()
-    rng = np.random.default_rng(log_n)
-    inputs = rng.integers(0, 1 << 64, size=(1 << log_n, 9), dtype=np.uint64)
-    inputs[3, 0] = 1
-    want = oracle.arithmetic_mul_trace(log_n, inputs=inputs)
-    got = to_host(bpg.ops.arithmetic_mul_trace(log_n, inputs=to_dev(inputs)))
-    assert (got == want).all()
-    x = sum(int(inputs[3, 1 + w]) << (64 * w) for w in range(4))
-    y = sum(int(inputs[3, 5 + w]) << (64 * w) for w in range(4))
-    z = sum(int(got[33 + i, 3]) << i for i in range(256))
-    w = sum(int(got[289 + i, 3]) << i for i in range(256))
-    assert z + (w << 256) == x * y
-
-
-@pytest.mark.parametrize("log_n", [5, 10, 14])
-def test_quotient_eval_matches_oracle(bpg, oracle, log_n):
-    """K5 alone on AIR 4: random LDE matrices (on the coset the 'bit' columns are arbitrary field elements), fixed
-    challenges.  2^5 / 2^10 rows spread the eight units and the CTL part over grid.y, 2^14 is closer to one pass."""
-    rng = np.random.default_rng(900 + log_n)
-    rows = (1 << log_n) << 1
-    trace = rand_field(rng, (1217, rows))
-    aux = rand_field(rng, (1, rows))
-    ctl, alphas = rand_field(rng, (4,)), rand_field(rng, (2,))
-    want = oracle.quotient_values(oracle.make_cfg(log_n, 1217, air_id=7), None, trace, aux, ctl, alphas[0], alphas[1])
-    idx = coset_major_to_natural(log_n, 1)
-
-    def to_cm(mat):
-        cm = np.empty_like(mat)
-        cm[:, idx] = mat
-        return to_dev(cm)
-    got = bpg.ops.quotient_eval(bpg.ops.stark_cfg(log_n, 1217), to_cm(trace), to_cm(aux), None, ctl, alphas, air_id=7)
-    assert (to_host(got)[:, idx] == want).all()
-
-
-def oracle_proof(oracle, log_n, nq, pb, seed):
-    cfg = oracle.make_cfg(log_n, 1217, num_queries=nq, pow_bits=pb, air_id=7)
-    tr = oracle.arithmetic_mul_trace(log_n, seed=seed)
-    tc = oracle.Committed.from_values(tr, 1, 4)
-    ch = oracle.PyChallenger()
-    ch.observe(tc.cap())
-    ctl = np.array([ch.challenge() for _ in range(4)], dtype=np.uint64)
-    chv = ch.clone()
-    return cfg, oracle.stark_prove(cfg, tr, ctl, ch, None, tc), ctl, chv
-
-
-def product_verify(bpg, pc, proof):
-    raw = np.ascontiguousarray(proof, dtype="<u8").tobytes()
-    return bpg.lib().bp_stark_verify_air(7, C.byref(pc), None, raw, len(raw))
-
-
-@pytest.mark.parametrize("log_n,nq,pb,loaded", [(5, 6, 6, 0), (9, 20, 10, 1), (12, 84, 16, 0), (12, 84, 16, 1), (14, 84, 16, 0)])
-def test_table_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
-    """prove -> verify, bit-flip rejection, HIP bytes == oracle bytes, up to 2^14 rows.  loaded: K5 in ONE pass, as the library runs it while provers share the device."""
-    cfg, want, ctl, chv = oracle_proof(oracle, log_n, nq, pb, SEED)
-    pc = bpg.ops.stark_cfg(log_n, 1217, num_queries=nq, pow_bits=pb)
-    with bpg.ops.tuned(assume_loaded=loaded):
-        got = bpg.ops.stark_prove_air(7, pc, SEED)
-    assert got.shape == want.shape and int(got[14]) == 7
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)
-    assert oracle.stark_verify(cfg, got, ctl, chv, None) == 0
-    assert product_verify(bpg, pc, got) == 0
-    flipped = got.copy()
-    flipped[got.size // 2] ^= np.uint64(1 << 21)
-    assert product_verify(bpg, pc, flipped) != 0
-
-
-def test_wrong_shapes_for_the_air_are_refused(bpg):
-    from proof_protocol_decoder_amd._lib import BpgError
-    for kw in (dict(n_cols=1220), dict(n_cols=1217, n_const=2), dict(n_cols=1217, deg_pow=3, rate_bits=3)):
-        cfg = bpg.ops.stark_cfg(6, kw.pop("n_cols"), num_queries=6, pow_bits=6, **kw)
-        with pytest.raises(BpgError, match="arithmetic_mul"):
-            bpg.ops.stark_prove_air(7, cfg, 1)
+pytestmark, test_witness_matches_oracle, test_quotient_eval_matches_oracle, test_table_proof_bit_exact, \
+    test_wrong_shapes_for_the_air_are_refused = gpu_tests(arithmetic_mul)

@@ -1,90 +1,8 @@
 """AIR 2 (logic, csrc/air.hpp) on the GPU against the oracle's independent statement of it (oracle/logic_air.c): the
-witness generator, K5 alone through bp_quotient_eval(air_id = 2, ...), and whole table proofs byte for byte."""
-import ctypes as C
+witness generator, K5 alone through bp_quotient_eval, and whole table proofs byte for byte.  The tests are
+builtin_airs.gpu_tests, the same for all seven AIRs, over this AIR's record (its shapes, seeds and spot checks, with a
+note on why those heights)."""
+from builtin_airs import gpu_tests, logic
 
-import numpy as np
-import pytest
-
-from util import P, coset_major_to_natural, rand_field, to_dev, to_host
-
-pytestmark = pytest.mark.gpu
-SEED = 0x5EED000000000006
-
-
-@pytest.mark.parametrize("log_n", [4, 9, 13])
-def test_witness_matches_oracle(bpg, oracle, log_n):
-    want = oracle.logic_trace(log_n, seed=SEED + log_n)
-    got = to_host(bpg.ops.logic_trace(log_n, seed=SEED + log_n))
-    assert got.shape == want.shape == (524, 1 << log_n) and (got == want).all()
-    rng = np.random.default_rng(log_n)
-    inputs = rng.integers(0, 1 << 64, size=(1 << log_n, 9), dtype=np.uint64)   # codes: the low two bits of any word
-    want = oracle.logic_trace(log_n, inputs=inputs)
-    got = to_host(bpg.ops.logic_trace(log_n, inputs=to_dev(inputs)))
-    assert (got == want).all()
-    r = 5
-    a = sum(int(inputs[r, 1 + w]) << (64 * w) for w in range(4))
-    b = sum(int(inputs[r, 5 + w]) << (64 * w) for w in range(4))
-    res = sum(int(got[515 + k, r]) << (32 * k) for k in range(8))
-    assert res == {0: 0, 1: a & b, 2: a | b, 3: a ^ b}[int(inputs[r, 0]) & 3]
-
-
-@pytest.mark.parametrize("log_n", [5, 10, 14])
-def test_quotient_eval_matches_oracle(bpg, oracle, log_n):
-    """K5 alone on AIR 2: random LDE matrices (on the coset the 'bit' columns are arbitrary field elements), fixed
-    challenges.  2^5 / 2^10 rows spread the eight units and the CTL part over grid.y, 2^14 is closer to one pass."""
-    rng = np.random.default_rng(900 + log_n)
-    rows = (1 << log_n) << 1
-    trace = rand_field(rng, (524, rows))
-    aux = rand_field(rng, (2, rows))    # z_0, z_1 of keccak_sponge -> logic
-    ctl, alphas = rand_field(rng, (4,)), rand_field(rng, (2,))
-    want = oracle.quotient_values(oracle.make_cfg(log_n, 524, air_id=2), None, trace, aux, ctl, alphas[0], alphas[1])
-    idx = coset_major_to_natural(log_n, 1)
-
-    def to_cm(mat):
-        cm = np.empty_like(mat)
-        cm[:, idx] = mat
-        return to_dev(cm)
-    got = bpg.ops.quotient_eval(bpg.ops.stark_cfg(log_n, 524), to_cm(trace), to_cm(aux), None, ctl, alphas, air_id=2)
-    assert (to_host(got)[:, idx] == want).all()
-
-
-def oracle_proof(oracle, log_n, nq, pb, seed):
-    cfg = oracle.make_cfg(log_n, 524, num_queries=nq, pow_bits=pb, air_id=2)
-    tr = oracle.logic_trace(log_n, seed=seed)
-    tc = oracle.Committed.from_values(tr, 1, 4)
-    ch = oracle.PyChallenger()
-    ch.observe(tc.cap())
-    ctl = np.array([ch.challenge() for _ in range(4)], dtype=np.uint64)
-    chv = ch.clone()
-    return cfg, oracle.stark_prove(cfg, tr, ctl, ch, None, tc), ctl, chv
-
-
-def product_verify(bpg, pc, proof):
-    raw = np.ascontiguousarray(proof, dtype="<u8").tobytes()
-    return bpg.lib().bp_stark_verify_air(2, C.byref(pc), None, raw, len(raw))
-
-
-@pytest.mark.parametrize("log_n,nq,pb,loaded", [(5, 6, 6, 0), (9, 20, 10, 1), (12, 84, 16, 0), (12, 84, 16, 1), (15, 84, 16, 0)])
-def test_table_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
-    """prove -> verify, bit-flip rejection, HIP bytes == oracle bytes.  2^12 rows is the bottom of the reference's
-    logic range (constants.rs:14).  loaded: K5 in ONE pass, as the library runs it while provers share the device."""
-    cfg, want, ctl, chv = oracle_proof(oracle, log_n, nq, pb, SEED)
-    pc = bpg.ops.stark_cfg(log_n, 524, num_queries=nq, pow_bits=pb)
-    with bpg.ops.tuned(assume_loaded=loaded):
-        got = bpg.ops.stark_prove_air(2, pc, SEED)
-    assert got.shape == want.shape and int(got[14]) == 2
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)
-    assert oracle.stark_verify(cfg, got, ctl, chv, None) == 0
-    assert product_verify(bpg, pc, got) == 0
-    flipped = got.copy()
-    flipped[got.size // 2] ^= np.uint64(1 << 21)
-    assert product_verify(bpg, pc, flipped) != 0
-
-
-def test_wrong_shapes_for_the_air_are_refused(bpg):
-    from proof_protocol_decoder_amd._lib import BpgError
-    for kw in (dict(n_cols=523), dict(n_cols=524, n_const=2), dict(n_cols=524, deg_pow=3, rate_bits=3)):
-        cfg = bpg.ops.stark_cfg(6, kw.pop("n_cols"), num_queries=6, pow_bits=6, **kw)
-        with pytest.raises(BpgError, match="logic"):
-            bpg.ops.stark_prove_air(2, cfg, 1)
+pytestmark, test_witness_matches_oracle, test_quotient_eval_matches_oracle, test_table_proof_bit_exact, \
+    test_wrong_shapes_for_the_air_are_refused = gpu_tests(logic)

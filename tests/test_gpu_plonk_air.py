@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from builtin_airs import product_verify
 from util import P, coset_major_to_natural, rand_field, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -121,14 +122,6 @@ def oracle_proof(oracle, log_n, nq, pb, seed, cseed):
     return cfg, oracle.stark_prove(cfg, tr, ctl, ch, cc, tc), ctl, chv, cc.cap().copy(), pub
 
 
-def product_verify(bpg, pc, proof, cap, pub):
-    L = bpg.lib()
-    L.bp_stark_verify_air_pub.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
-    raw = np.ascontiguousarray(proof, dtype="<u8").tobytes()
-    capa = np.ascontiguousarray(cap, dtype=np.uint64)
-    return L.bp_stark_verify_air_pub(8, C.byref(pc), capa.ctypes.data_as(C.POINTER(C.c_uint64)), (C.c_uint64 * 4)(*[int(x) for x in pub]), raw, len(raw))
-
-
 @pytest.mark.parametrize("log_n,nq,pb,loaded", [(5, 6, 6, 0), (9, 20, 10, 1), (13, 28, 16, 0), (13, 28, 16, 1)])
 def test_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
     cfg, want, ctl, chv, cap, pub = oracle_proof(oracle, log_n, nq, pb, SEED, CSEED)
@@ -139,13 +132,13 @@ def test_proof_bit_exact(bpg, oracle, log_n, nq, pb, loaded):
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, "first mismatch at word %d of %d" % (bad[0], want.size)
     assert oracle.stark_verify(cfg, got, ctl, chv, cap) == 0
-    assert product_verify(bpg, pc, got, cap, pub) == 0
+    assert product_verify(pc, 8, got, cap, pub) == 0
     flipped = got.copy()
     flipped[got.size // 2] ^= np.uint64(1 << 21)
-    assert product_verify(bpg, pc, flipped, cap, pub) != 0
+    assert product_verify(pc, 8, flipped, cap, pub) != 0
     wrong = [int(x) for x in pub]
     wrong[0] ^= 2
-    assert product_verify(bpg, pc, got, cap, wrong) != 0
+    assert product_verify(pc, 8, got, cap, wrong) != 0
 
 
 def test_wrong_shapes_for_the_air_are_refused(bpg):

@@ -119,8 +119,8 @@ def two_looking_range_tables(bpg):
 
 def memory_reader(bpg):
     """a run-time table looking words up in the built-in memory table (AIR 3)"""
-    from test_memory_air import random_log
-    log = random_log(64, 0xE000, n_addr=6)
+    from builtin_airs import memory
+    log = memory.random_log(64, 0xE000, n_addr=6)
     rng = np.random.default_rng(0xE001)
     asked = rows_of(6, rng, 9)
     mem = bpg.ops.memory_trace(6, inputs=to_dev(log))

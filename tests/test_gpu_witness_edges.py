@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import witness_edges as we
-from test_memory_air import prove
+from builtin_airs import AIRS, product_verify, prove
 from util import P, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -24,18 +24,12 @@ _CACHE = {}
 def device_trace(bpg, table):
     """the device generator's trace of the table (device tensor), made once"""
     if table.name not in _CACHE:
-        _CACHE[table.name] = getattr(bpg.ops, we.TRACE_FN[table.air_id])(table.log_n, inputs=to_dev(table.inputs))
+        _CACHE[table.name] = bpg.ops.air_trace(table.air_id, table.log_n, inputs=to_dev(table.inputs))
     return _CACHE[table.name]
 
 
 def oracle_trace(oracle, table):
-    return getattr(oracle, we.TRACE_FN[table.air_id])(table.log_n, inputs=table.inputs)
-
-
-def product_verify(bpg, air_id, pc, proof):
-    import ctypes as C
-    raw = np.ascontiguousarray(proof, dtype="<u8").tobytes()
-    return bpg.lib().bp_stark_verify_air(air_id, C.byref(pc), None, raw, len(raw))
+    return oracle.air_trace(table.air_id, table.log_n, inputs=table.inputs)
 
 
 # ------------------------------------------------------------------------------------------------ a. the trace
@@ -76,7 +70,7 @@ def test_device_checker_on_the_device_trace(bpg, table):
 def test_proof_from_the_device_trace_is_the_oracle_s(bpg, oracle, table):
     """valid tables: bytes equal, both verifiers accept, one flipped bit is rejected; false logs: the proof is produced
     (the prover does not judge its witness), equals the oracle's, and both verifiers reject it"""
-    n_cols = we.N_COLS[table.air_id]
+    n_cols = AIRS[table.air_id].n_cols
     cfg = oracle.make_cfg(table.log_n, n_cols, num_queries=6, pow_bits=6, air_id=table.air_id)
     want, ctl, chv = prove(oracle, cfg, oracle_trace(oracle, table))
     pc = bpg.ops.stark_cfg(table.log_n, n_cols, num_queries=6, pow_bits=6)
@@ -86,13 +80,13 @@ def test_proof_from_the_device_trace_is_the_oracle_s(bpg, oracle, table):
     assert bad.size == 0, "%s: first mismatch at word %d of %d" % (table.name, bad[0], want.size)
     if table.kind == we.VALID:
         assert oracle.stark_verify(cfg, got, ctl, chv, None) == 0
-        assert product_verify(bpg, table.air_id, pc, got) == 0
+        assert product_verify(pc, table.air_id, got) == 0
         flipped = got.copy()
         flipped[got.size // 2] ^= np.uint64(1 << 21)
-        assert product_verify(bpg, table.air_id, pc, flipped) != 0
+        assert product_verify(pc, table.air_id, flipped) != 0
     else:
         assert oracle.stark_verify(cfg, got, ctl, chv, None) != 0
-        assert product_verify(bpg, table.air_id, pc, got) != 0
+        assert product_verify(pc, table.air_id, got) != 0
 
 
 # ------------------------------------------------------------------------------------------------ d. seeded == caller's
@@ -104,14 +98,14 @@ def test_seeded_and_caller_trace_proofs_are_the_same_bytes(bpg, air_id, loaded):
     """what include/bpg.h promises of bp_stark_prove_trace(built-in id, bp_*_trace(seed)); 2^5 rows (AIR 1: one
     permutation and a part of the next)"""
     seed = 0x5EED0E00 + air_id
-    pc = bpg.ops.stark_cfg(5, we.N_COLS[air_id], num_queries=6, pow_bits=6)
-    trace = getattr(bpg.ops, we.TRACE_FN[air_id])(5, seed=seed)
+    pc = bpg.ops.stark_cfg(5, AIRS[air_id].n_cols, num_queries=6, pow_bits=6)
+    trace = bpg.ops.air_trace(air_id, 5, seed=seed)
     with bpg.ops.tuned(assume_loaded=loaded):
         want = bpg.ops.stark_prove_air(air_id, pc, seed)
         got = bpg.ops.stark_prove_trace(air_id, pc, trace)
     bad = np.nonzero(got != want)[0] if got.shape == want.shape else [-1]
     assert len(bad) == 0, "AIR %d: first mismatch at word %d of %d" % (air_id, bad[0], want.size)
-    assert product_verify(bpg, air_id, pc, got) == 0
+    assert product_verify(pc, air_id, got) == 0
 
 
 # ------------------------------------------------------------------------------------------------ e. lookup products
@@ -154,9 +148,9 @@ def test_lookup_products_with_a_filter_set_against_python_integers(bpg, air_id, 
     n = 1 << log_n
     if log_n == 4:                         # the first sixteen rows of the edge table
         table = next(t for t in TABLES if t.air_id == air_id and t.kind == we.VALID)
-        trace = getattr(bpg.ops, we.TRACE_FN[air_id])(4, inputs=to_dev(table.inputs[:16]))
+        trace = bpg.ops.air_trace(air_id, 4, inputs=to_dev(table.inputs[:16]))
     else:
-        trace = getattr(bpg.ops, we.TRACE_FN[air_id])(log_n, seed=0xA0C5 + 16 * air_id + log_n)
+        trace = bpg.ops.air_trace(air_id, log_n, seed=0xA0C5 + 16 * air_id + log_n)
     tup, _ = we.lookup_tuple(air_id, to_host(trace))
     v = [we.compress(tup, CTL[0]), we.compress(tup, CTL[2])]   # the compressed tuple does not depend on the filter
     assert len(set(v[0])) > 1

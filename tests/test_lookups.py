@@ -6,14 +6,14 @@ constraints) both accept; tables that are each valid alone but disagree with eac
 import numpy as np
 import pytest
 
+from builtin_airs import table_air
 from pg_common import LOG_N, SMALL, WIDTH, ir_words
 
-REAL_WIDTH = {0: 309, 1: 299, 3: 2431, 4: 2414, 5: 524, 6: 45}
 REAL_FLAG = {3: 0x100, 5: 0x200, 6: 0x400, 0: 0x800, 1: 0x1000, 4: 0x2000}
 
 
 def real_ir(tables, seed=0x5EED0C71, log_n=LOG_N):
-    w = [REAL_WIDTH[t] if t in tables else WIDTH[t] for t in range(7)]
+    w = [table_air(t).n_cols if t in tables else WIDTH[t] for t in range(7)]
     ir = ir_words(9, 0, seed, log_n=log_n, width=tuple(w))
     for t in tables:
         ir[1] |= REAL_FLAG[t]

@@ -5,12 +5,12 @@ the oracle's proofs pass the oracle's verifier and the PRODUCT's CPU verifier (c
 oracle ties the copy classes as explicit sets and inverts every chunk, the product computes "the next member" in closed
 form and folds by Horner), one broken copy constraint / gate / public input gives a rejected proof.  GPU side:
 tests/test_gpu_plonk_air.py."""
-import ctypes as C
-
 import os
 
 import numpy as np
 import pytest
+
+import builtin_airs as ba
 
 P = 0xFFFFFFFF00000001
 SEED, CSEED = 0x5EED0080, 0xC0DE0080
@@ -21,27 +21,9 @@ def small_cfg(oracle, log_n, pub, **kw):
 
 
 def prove(oracle, cfg, consts, trace):
-    cc = oracle.Committed.from_values(consts, cfg.rate_bits, cfg.cap_height)
-    tc = oracle.Committed.from_values(trace, cfg.rate_bits, cfg.cap_height)
-    ch = oracle.PyChallenger()
-    ch.observe(cc.cap())
-    ch.observe(tc.cap())
-    ctl = np.array([ch.challenge() for _ in range(4)], dtype=np.uint64)
-    chv = ch.clone()
-    return oracle.stark_prove(cfg, trace, ctl, ch, cc, tc), ctl, chv, cc.cap().copy()
-
-
-def product_verify(cfg, proof, const_cap, pub):
-    import proof_protocol_decoder_amd as pkg
-    L = pkg.lib()
-    L.bp_stark_verify_air_pub.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
-    pc = pkg.ops.stark_cfg(cfg.log_n, cfg.n_cols, n_const=cfg.n_const, deg_pow=cfg.deg_pow, rate_bits=cfg.rate_bits,
-                           cap_height=cfg.cap_height, num_queries=cfg.num_queries, pow_bits=cfg.pow_bits,
-                           arity_bits=cfg.arity_bits, final_poly_bits=cfg.final_poly_bits)
-    raw = np.ascontiguousarray(proof, dtype="<u8").tobytes()
-    cap = np.ascontiguousarray(const_cap, dtype=np.uint64)
-    pb = (C.c_uint64 * 4)(*[int(x) for x in pub])
-    return L.bp_stark_verify_air_pub(8, C.byref(pc), cap.ctypes.data_as(C.POINTER(C.c_uint64)), pb, raw, len(raw))
+    """builtin_airs.prove with the constants committed first, and their cap, which the verifiers take beside the proof"""
+    cap = oracle.Committed.from_values(consts, cfg.rate_bits, cfg.cap_height).cap().copy()
+    return ba.prove(oracle, cfg, trace, consts) + (cap,)
 
 
 def mul(a, b):
@@ -225,14 +207,14 @@ def test_oracle_proof_is_accepted_by_both_verifiers_and_tampering_is_not(oracle,
     proof, ctl, chv, cap = prove(oracle, cfg, k, t)
     assert int(proof[14]) == 8 and int(proof[4]) == 20            # the AIR, its 20 auxiliary columns
     assert oracle.stark_verify(cfg, proof, ctl, chv.clone(), cap) == 0
-    assert product_verify(cfg, proof, cap, pub) == 0
+    assert ba.product_verify(cfg, 8, proof, cap, pub) == 0
     for word in (20, proof.size // 2, proof.size - 5):
         bad = proof.copy()
         bad[word] ^= np.uint64(1 << 9)
-        assert product_verify(cfg, bad, cap, pub) != 0
+        assert ba.product_verify(cfg, 8, bad, cap, pub) != 0
     wrong = [int(x) for x in pub]
     wrong[2] ^= 1
-    assert product_verify(cfg, proof, cap, wrong) != 0            # the public inputs are part of the statement
+    assert ba.product_verify(cfg, 8, proof, cap, wrong) != 0            # the public inputs are part of the statement
     assert oracle.stark_verify(small_cfg(oracle, log_n, wrong), proof, ctl, chv.clone(), cap) != 0
 
 
@@ -268,7 +250,7 @@ def test_a_witness_that_breaks_one_rule_yields_a_rejected_proof(oracle, col, row
     except RuntimeError:
         return          # the prover itself noticed (a violated constraint leaves a FRI tail): rejected early
     assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0
-    assert product_verify(cfg, proof, cap, pub) != 0
+    assert ba.product_verify(cfg, 8, proof, cap, pub) != 0
 
 
 # a circuit that walks two paths of five levels (rows 17..26; the list's path words at 10..25): one wrong cell each
@@ -295,14 +277,14 @@ def test_a_wrong_merkle_path_yields_a_rejected_proof(oracle, col, row, what):
     t = oracle.plonk_trace(log_n, 78, pi, k, *layout[1:], wit)
     if col == 130 and what.startswith("the position bit"):
         proof, ctl, chv, cap = prove(oracle, cfg, k, t)          # the untouched witness first
-        assert oracle.stark_verify(cfg, proof, ctl, chv, cap) == 0 and product_verify(cfg, proof, cap, pub) == 0
+        assert oracle.stark_verify(cfg, proof, ctl, chv, cap) == 0 and ba.product_verify(cfg, 8, proof, cap, pub) == 0
         # the other side of the same level, consistently (bit and deltas): every gate of the row holds, the path does not arrive
         wit2 = list(wit)
         wit2[0] ^= 1 << 1
         t2 = oracle.plonk_trace(log_n, 78, pi, k, *layout[1:], wit2)
         assert int(t2[130, 18]) == 1 - int(t[130, 18])
         proof, ctl, chv, cap = prove(oracle, cfg, k, t2)
-        assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and product_verify(cfg, proof, cap, pub) != 0
+        assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and ba.product_verify(cfg, 8, proof, cap, pub) != 0
         t[col, row] = np.uint64(2)
     else:
         t[col, row] = np.uint64((int(t[col, row]) + 1) % P)
@@ -311,7 +293,7 @@ def test_a_wrong_merkle_path_yields_a_rejected_proof(oracle, col, row, what):
     except RuntimeError:
         return
     assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0
-    assert product_verify(cfg, proof, cap, pub) != 0
+    assert ba.product_verify(cfg, 8, proof, cap, pub) != 0
 
 
 def test_a_leaf_row_that_is_not_the_leaf_s_preimage_yields_a_rejected_proof(oracle):
@@ -329,16 +311,16 @@ def test_a_leaf_row_that_is_not_the_leaf_s_preimage_yields_a_rejected_proof(orac
     k = oracle.plonk_constants(log_n, CSEED, *layout)
     t = oracle.plonk_trace(log_n, 79, pi, k, layout[1], layout[2], layout[3], wit, 135)
     proof, ctl, chv, cap = prove(oracle, cfg, k, t)
-    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) == 0 and product_verify(cfg, proof, cap, pub) == 0
+    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) == 0 and ba.product_verify(cfg, 8, proof, cap, pub) == 0
     wit2 = list(wit)
     wit2[1 + 4 * 7 + 60] ^= 1                       # word 60 of the opened row
     t2 = oracle.plonk_trace(log_n, 79, pi, k, layout[1], layout[2], layout[3], wit2, 135)
     proof, ctl, chv, cap = prove(oracle, cfg, k, t2)
-    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and product_verify(cfg, proof, cap, pub) != 0
+    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and ba.product_verify(cfg, 8, proof, cap, pub) != 0
     t3 = t.copy()
     t3[9, MROW0 + 7 + 3] = np.uint64((int(t3[9, MROW0 + 7 + 3]) + 1) % P)   # a carried capacity word of leaf row 3
     proof, ctl, chv, cap = prove(oracle, cfg, k, t3)
-    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and product_verify(cfg, proof, cap, pub) != 0
+    assert oracle.stark_verify(cfg, proof, ctl, chv, cap) != 0 and ba.product_verify(cfg, 8, proof, cap, pub) != 0
 
 
 def test_air_registry_describes_the_plonk_air():

@@ -10,15 +10,14 @@ import pytest
 
 import witness_edges as we
 from air_check_util import oracle_violated_rows
-from test_keccak_air import sha3_256_by_hand
-from test_memory_air import product_verify, prove
+from builtin_airs import AIRS, keccak, product_verify, prove
 
 TABLES = we.all_tables()
 IDS = [t.name for t in TABLES]
 
 
 def oracle_trace(oracle, table):
-    return getattr(oracle, we.TRACE_FN[table.air_id])(table.log_n, inputs=table.inputs)
+    return oracle.air_trace(table.air_id, table.log_n, inputs=table.inputs)
 
 
 def host_rows(table, trace):
@@ -34,7 +33,7 @@ def test_the_keccak_model_is_keccak():
     def permute(st):
         return np.array(we.keccak_f(st), dtype=np.uint64)
     for msg in (b"", b"abc", b"q" * 135, b"r" * 136, b"witness edges" * 30):
-        assert sha3_256_by_hand(permute, msg)[0] == hashlib.sha3_256(msg).digest()
+        assert keccak.sha3_256_by_hand(permute, msg)[0] == hashlib.sha3_256(msg).digest()
     assert we.keccak_f([0] * 25)[:2] == [0xF1258F7940E1DDE7, 0x84D5CCF933C0478A]
 
 
@@ -92,10 +91,10 @@ def test_the_outside_memory_log_is_rejected_where_the_true_gap_does_not_fit(orac
 @pytest.mark.parametrize("table", [t for t in TABLES if t.kind != we.OUTSIDE], ids=[t.name for t in TABLES if t.kind != we.OUTSIDE])
 def test_oracle_proof_of_a_table(oracle, table):
     """valid tables: accepted by the oracle's verifier and by bp_stark_verify_air; false logs: rejected by both"""
-    cfg = oracle.make_cfg(table.log_n, we.N_COLS[table.air_id], num_queries=6, pow_bits=6, air_id=table.air_id)
+    cfg = oracle.make_cfg(table.log_n, AIRS[table.air_id].n_cols, num_queries=6, pow_bits=6, air_id=table.air_id)
     proof, ctl, chv = prove(oracle, cfg, oracle_trace(oracle, table))
     assert int(proof[14]) == table.air_id
     if table.kind == we.VALID:
-        assert oracle.stark_verify(cfg, proof, ctl, chv, None) == 0 and product_verify(cfg, proof) == 0
+        assert oracle.stark_verify(cfg, proof, ctl, chv, None) == 0 and product_verify(cfg, table.air_id, proof) == 0
     else:
-        assert oracle.stark_verify(cfg, proof, ctl, chv, None) != 0 and product_verify(cfg, proof) != 0
+        assert oracle.stark_verify(cfg, proof, ctl, chv, None) != 0 and product_verify(cfg, table.air_id, proof) != 0

@@ -10,20 +10,15 @@ AIR 1 a permutation):
 `Table` adds the AIR, a name, the table's kind (false if any row is, else outside if any row is, else valid) and, for
 false and outside MEMORY logs, the rows the model says the AIR must reject.
 
-The models reuse the row checkers of tests/test_*_air.py and extend them to the columns those leave out (memory:
+The models reuse the row checkers of tests/builtin_airs.py and extend them to the columns those leave out (memory:
 address_changed and the 32 gap bits; multiplication: the 32 x 21 carry bits; arithmetic: all 16 carries; byte packing:
 address and timestamp; Keccak-f and the sponge: every column, from a Keccak-f written here and held against hashlib)."""
 from collections import namedtuple
 
 import numpy as np
 
-import test_arithmetic_air as ar
-import test_arithmetic_mul_air as am
-import test_byte_packing_air as bpk
-import test_keccak_air as kk
-import test_keccak_sponge_air as sp
-import test_logic_air as lg
-import test_memory_air as mm
+from builtin_airs import (AIRS, arithmetic as ar, arithmetic_mul as am, byte_packing as bpk, keccak as kk, keccak_sponge as sp,
+                          logic as lg, memory as mm)
 
 P = 0xFFFFFFFF00000001
 M = 1 << 256
@@ -32,9 +27,6 @@ U32 = (1 << 32) - 1
 VALID, FALSE, OUTSIDE = "valid", "false", "outside"
 
 Table = namedtuple("Table", "air_id name kind log_n inputs labels violated")
-TRACE_FN = {1: "keccak_trace", 2: "logic_trace", 3: "memory_trace", 4: "arithmetic_trace", 5: "byte_packing_trace",
-            6: "keccak_sponge_trace", 7: "arithmetic_mul_trace"}
-N_COLS = {1: 2431, 2: 524, 3: 45, 4: 309, 5: 299, 6: 2414, 7: 1217}
 # a 256-bit operand with no structure: every byte different, top bit set
 X = int.from_bytes(bytes(range(7, 39)), "little") | (1 << 255)
 Y = int.from_bytes(bytes((37 * i + 11) & 0xFF for i in range(32)), "little")
@@ -331,7 +323,7 @@ def check_byte_packing(t, inputs):
         w0, w1 = int(inputs[r, 0]), int(inputs[r, 1])
         data = b"".join(int(inputs[r, 2 + w]).to_bytes(8, "little") for w in range(4))
         bpk.check_row(t, r, w0 & 1, min(w1 & 0xFF, 32), data)
-        assert int(t[297, r]) == (w1 >> 8) & U32 and int(t[298, r]) == (w0 >> 8) & U32, r
+        assert int(t[bpk.COL_ADDR, r]) == (w1 >> 8) & U32 and int(t[bpk.COL_TS, r]) == (w0 >> 8) & U32, r
         assert (t[:bpk.COL_VAL, r] <= 1).all(), r
 
 
@@ -386,7 +378,7 @@ def check_sponge(t, inputs):
 
 
 def check_sponge_digests(t, first_rows, msgs):
-    """the digest check of tests/test_keccak_sponge_air.py: a message's last row leaves its Keccak-256"""
+    """the digest check of tests/test_keccak_sponge_air.py and tests/test_gpu_keccak_sponge_air.py: a message's last row leaves its Keccak-256"""
     from proof_protocol_decoder_amd import compact
     for r0, m in zip(first_rows, msgs):
         last = r0 + len(m) // 136
@@ -468,7 +460,7 @@ def all_tables():
 
 def check_model(table, t):
     """the Python-integer model of the table's AIR on a trace of its inputs (the oracle's or the device's)"""
-    assert t.shape == (N_COLS[table.air_id], 1 << table.log_n) and (t < np.uint64(P)).all()
+    assert t.shape == (AIRS[table.air_id].n_cols, 1 << table.log_n) and (t < np.uint64(P)).all()
     if table.air_id == 1:
         check_keccak(t, table.inputs)
     elif table.air_id == 2:
@@ -521,7 +513,7 @@ def lookup_tuple(air_id, t):
         return [col(c) for c in range(11)], col(44)
     if air_id == 5:     # is_read, address, timestamp, 8 value limbs; filter = the row has a length
         flags = [int(v) for v in t[1:33].sum(axis=0)]
-        return [col(0), col(297), col(298)] + [col(289 + k) for k in range(8)], flags
+        return [col(bpk.COL_READ), col(bpk.COL_ADDR), col(bpk.COL_TS)] + [col(bpk.COL_VAL + k) for k in range(8)], flags
     raise ValueError(air_id)
 
 

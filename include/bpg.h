@@ -864,11 +864,24 @@ int bp_verify_txn_table_proofs_for(const bp_config* cfg, const uint8_t* ir, size
 /* The transaction witness pre-flight: what bp_generate_txn_proof_witness would say about the same inputs, without
  * committing or proving anything.  The seven traces are built by the prover's own code (the same refusals, statuses
  * BP_ERR_INVALID_INPUT / BP_ERR_RANGE); every table proven by its AIR is checked row by row (bp_air_check_trace), and
- * the three lookups (keccak_sponge -> keccak_f, byte_packing -> memory, keccak_sponge -> logic) as multisets of tuples,
- * compressed on the device with fresh challenges (the columns air::ctl selects) and compared on the host.  Status: BP_OK
- * when the prover would accept the data, BP_ERR_VERIFY when it would not -- a given table that violates its AIR (its
- * row and constraint in the message), else the first lookup that does not hold (its first unmatched rows) -- and out
- * holds everything found either way.  Takes one of the state's workers, as a proof call does. */
+ * the lookups that exist between them (keccak_sponge -> keccak_f, byte_packing -> memory, keccak_sponge -> logic) as
+ * links: the tables proven by an AIR are the members, as contiguous traces, and the balance is bp_check_table_set's, by
+ * its code (csrc/set_check.hip, one set of fresh challenges per call) and with its soundness.  A bp_witness_lookup's
+ * fields are the bp_set_link_report's of the same names, as "Table sets" above defines them; the looking ends of
+ * keccak_sponge -> logic are the sponge table's ports 1 .. 5 in order, and first_looking_row is the row of the smallest
+ * (end, row) -- the end is not reported.  Status: BP_OK when the prover would accept the data, BP_ERR_VERIFY when it would
+ * not -- a given table that violates its AIR (its row and constraint in the message), else the first lookup that does
+ * not hold (its first unmatched rows) -- and out holds everything found either way.  Takes one of the state's workers,
+ * as a proof call does, on whose stream everything runs.  Scratch: one allocation of 64 bytes x the power of two >= twice
+ * the rows of the largest lookup's ends, beside the worker's arena; if the device cannot give it, BP_ERR_DEVICE naming the
+ * bytes.
+ * Until the lookups were checked as links, their terms were downloaded and matched greedily in a map on the host.  A
+ * report differs from that one in two places only.  (1) A tuple value that a looking rows and b looked rows carry with
+ * 0 < b < a: the greedy match named the (b + 1)-th looking row (with 0 < a < b: the (a + 1)-th looked row), the balance
+ * names the value's first row on both sides.  Where a value is on one side only, or everything balances, the two agree.  (2) keccak_sponge -> logic:
+ * first_looking_row was the smallest row over the five ends and is the row of the smallest (end, row); through this
+ * entry that lookup balances by construction (the logic table's first rows are derived from the sponge trace), so no
+ * input shows it. */
 typedef struct bp_witness_table {
   uint32_t checked;            /* 1: the table is proven by its AIR and was checked */
   uint32_t given;              /* 1: made from the caller's data (0: drawn from the seed or derived) */
@@ -879,7 +892,7 @@ typedef struct bp_witness_table {
 typedef struct bp_witness_lookup {
   uint32_t checked;            /* 1: both tables are proven by their AIRs */
   uint32_t holds;
-  uint64_t n_looking, n_looked;  /* tuples on each side */
+  uint64_t n_looking, n_looked;  /* rows with f != 0 on each side (keccak_sponge -> logic: over the five ends) */
   int64_t first_looking_row;   /* first looking row whose tuple the looked table does not expose; -1: none */
   int64_t first_looked_row;    /* first looked row nobody asks for; -1: none */
 } bp_witness_lookup;

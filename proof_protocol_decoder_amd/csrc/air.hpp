@@ -1580,7 +1580,77 @@ GL_HD T compress(const Col& col, uint32_t n, T beta) {
   for (uint32_t j = n - 1; j-- > 0;) acc = F::add(F::mul(acc, beta), col(j));
   return acc;
 }
-// term of product column `col` (an aux column index) of the table: 1 + f (gamma + v - 1)
+// The filter f and the tuple of product column `col` of a table with a lookup side (DESC[].in_pair), read off row `row`:
+// sink(t) for every tuple element from the LAST to the first (Horner's order), f returned.  Keccak-f: the 50 output limbs
+// only -- its 50 input limbs stand on the permutation's first row (the prover carries their compression in h).
+template <class T, class Row, class Sink>
+GL_HD T port_tuple(const Shape& s, uint32_t col, const Row& row, Sink&& sink) {
+  typedef Ops<T> F;
+  auto limb = [&](uint32_t bits0) {  // 32 bit columns, lowest first
+    T v = F::k(0);
+#pragma unroll 1
+    for (uint32_t z = 32; z-- > 0;) v = F::add(F::dbl(v), row.loc(bits0 + z));
+    return v;
+  };
+  if (s.air_id == KECCAK_F) {
+    // output limb j of the row: the iota output for lane 0, else the chi output (what constraint family F9 hands on)
+#pragma unroll 1
+    for (uint32_t j = TUPLE_LIMBS; j-- > 0;) sink(j < 2 ? row.loc(keccak::COL_APPP + j) : row.loc(keccak::COL_APP + j));
+    return row.loc(keccak::COL_G);
+  }
+  if (s.air_id == KECCAK_SPONGE && col >= SPONGE_LZ) {
+    // keccak_sponge -> logic: the XOR of limbs 8m .. 8m + 7 of the rate with the block is one operation of the logic
+    // table: (0, 0, 1 | rate-before limbs | block limbs | xored limbs), limbs past the 34th zero
+    const uint32_t m = (col - SPONGE_LZ) >> 1;
+#pragma unroll 1
+    for (uint32_t j = 8; j-- > 0;) sink(8 * m + j < 34 ? row.loc(keccak_sponge::COL_XORED + 8 * m + j) : F::k(0));
+#pragma unroll 1
+    for (uint32_t part = 0; part < 2; part++) {  // part 0: the block (input 1), part 1: the rate before (input 0)
+      const uint32_t bits0 = part == 0 ? keccak_sponge::COL_BLOCK : keccak_sponge::COL_RATE;
+#pragma unroll 1
+      for (uint32_t j = 8; j-- > 0;) sink(8 * m + j < 34 ? limb(bits0 + 32 * (8 * m + j)) : F::k(0));
+    }
+    sink(F::k(1));  // is_xor
+    sink(F::k(0));  // is_or
+    sink(F::k(0));  // is_and
+    return F::add(row.loc(keccak_sponge::COL_FULL), row.loc(keccak_sponge::COL_FINAL));
+  }
+  if (s.air_id == LOGIC) {
+#pragma unroll 1
+    for (uint32_t j = 8; j-- > 0;) sink(row.loc(logic::COL_RES + j));
+#pragma unroll 1
+    for (uint32_t part = 0; part < 2; part++) {
+      const uint32_t bits0 = part == 0 ? logic::COL_IN1 : logic::COL_IN0;
+#pragma unroll 1
+      for (uint32_t j = 8; j-- > 0;) sink(limb(bits0 + 32 * j));
+    }
+#pragma unroll 1
+    for (uint32_t j = 3; j-- > 0;) sink(row.loc(logic::COL_OP + j));
+    return row.loc(logic::COL_G);
+  }
+  if (s.air_id == KECCAK_SPONGE) {
+    // tuple order: xored rate (34 limbs), capacity (16), updated state (50)
+#pragma unroll 1
+    for (uint32_t j = 2 * TUPLE_LIMBS; j-- > 0;)
+      sink(j < 34 ? row.loc(keccak_sponge::COL_XORED + j)
+           : j < 50 ? row.loc(keccak_sponge::COL_CAP + j - 34)
+                    : row.loc(keccak_sponge::COL_UPDATED + j - 50));
+    return F::add(row.loc(keccak_sponge::COL_FULL), row.loc(keccak_sponge::COL_FINAL));
+  }
+  // byte packing and memory: is_read, address, timestamp, eight value limbs
+  const bool pack = s.air_id == BYTE_PACKING;
+#pragma unroll 1
+  for (uint32_t j = WORD_TUPLE; j-- > 3;) sink(row.loc((pack ? byte_packing::COL_VAL : memory::COL_VAL) + j - 3));
+  sink(row.loc(pack ? byte_packing::COL_TS : memory::COL_TS));
+  sink(row.loc(pack ? byte_packing::COL_ADDR : memory::COL_ADDR));
+  sink(row.loc(pack ? byte_packing::COL_READ : memory::COL_READ));
+  if (!pack) return row.loc(memory::COL_G);
+  T f = F::k(0);  // the row has a length: it moves a word
+#pragma unroll 1
+  for (uint32_t j = 0; j < 32; j++) f = F::add(f, row.loc(byte_packing::COL_LEN + j));
+  return f;
+}
+// term of product column `col` (an aux column index) of the table: 1 + f (gamma + v - 1), v = sum_j beta^j t_j
 template <class T, class Row>
 GL_HD T product_term(const Shape& s, uint32_t col, const uint64_t ctl[4], const Row& row) {
   typedef Ops<T> F;
@@ -1590,105 +1660,13 @@ GL_HD T product_term(const Shape& s, uint32_t col, const uint64_t ctl[4], const 
     const T beta = F::k(ctl[2 * (col & 1)]), gamma = F::k(ctl[2 * (col & 1) + 1]);
     return F::add(F::add(gamma, row.loc(8 * col)), F::mul(beta, row.loc(8 * col + 1)));
   }
-  if (s.air_id == KECCAK_F) {
-    const uint32_t c = col - KECCAK_Z;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]), b50 = F::k(gl::pow(ctl[2 * c], TUPLE_LIMBS));
-    // output limb j of the row: the iota output for lane 0, else the chi output (what constraint family F9 hands on)
-    const T out = compress<T>([&](uint32_t j) { return j < 2 ? row.loc(keccak::COL_APPP + j) : row.loc(keccak::COL_APP + j); },
-                              TUPLE_LIMBS, beta);
-    const T v = F::add(row.aux(KECCAK_H + c), F::mul(b50, out));
-    return F::add(F::k(1), F::mul(row.loc(keccak::COL_G), F::sub(F::add(gamma, v), F::k(1))));
-  }
-  if (s.air_id == KECCAK_SPONGE && col >= SPONGE_LZ) {
-    // keccak_sponge -> logic: the XOR of limbs 8m .. 8m + 7 of the rate with the block is one operation of the logic
-    // table: (0, 0, 1 | rate-before limbs | block limbs | xored limbs), limbs past the 34th zero
-    const uint32_t m = (col - SPONGE_LZ) >> 1, c = (col - SPONGE_LZ) & 1;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
-    T acc = F::k(0);  // Horner from the top: result limbs, input-1 limbs, input-0 limbs, then the flags (0, 0, 1)
-#pragma unroll 1
-    for (uint32_t j = 8; j-- > 0;) {
-      const uint32_t l = 8 * m + j;
-      acc = F::mul(acc, beta);
-      if (l < 34) acc = F::add(acc, row.loc(keccak_sponge::COL_XORED + l));
-    }
-#pragma unroll 1
-    for (uint32_t part = 0; part < 2; part++) {  // part 0: the block (input 1), part 1: the rate before (input 0)
-      const uint32_t bits0 = part == 0 ? keccak_sponge::COL_BLOCK : keccak_sponge::COL_RATE;
-#pragma unroll 1
-      for (uint32_t j = 8; j-- > 0;) {
-        const uint32_t l = 8 * m + j;
-        T limb = F::k(0);
-        if (l < 34) {
-#pragma unroll 1
-          for (uint32_t z = 32; z-- > 0;) limb = F::add(F::dbl(limb), row.loc(bits0 + 32 * l + z));
-        }
-        acc = F::add(F::mul(acc, beta), limb);
-      }
-    }
-    acc = F::add(F::mul(acc, beta), F::k(1));  // is_xor
-    acc = F::mul(F::mul(acc, beta), beta);      // is_or = is_and = 0
-    const T f = F::add(row.loc(keccak_sponge::COL_FULL), row.loc(keccak_sponge::COL_FINAL));
-    return F::add(F::k(1), F::mul(f, F::sub(F::add(gamma, acc), F::k(1))));
-  }
-  if (s.air_id == LOGIC) {
-    const uint32_t c = col - LOGIC_Z;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
-    T acc = F::k(0);
-#pragma unroll 1
-    for (uint32_t j = 8; j-- > 0;) acc = F::add(F::mul(acc, beta), row.loc(logic::COL_RES + j));
-#pragma unroll 1
-    for (uint32_t part = 0; part < 2; part++) {
-      const uint32_t bits0 = part == 0 ? logic::COL_IN1 : logic::COL_IN0;
-#pragma unroll 1
-      for (uint32_t j = 8; j-- > 0;) {
-        T limb = F::k(0);
-#pragma unroll 1
-        for (uint32_t z = 32; z-- > 0;) limb = F::add(F::dbl(limb), row.loc(bits0 + 32 * j + z));
-        acc = F::add(F::mul(acc, beta), limb);
-      }
-    }
-#pragma unroll 1
-    for (uint32_t j = 3; j-- > 0;) acc = F::add(F::mul(acc, beta), row.loc(logic::COL_OP + j));
-    return F::add(F::k(1), F::mul(row.loc(logic::COL_G), F::sub(F::add(gamma, acc), F::k(1))));
-  }
-  if (s.air_id == KECCAK_SPONGE) {
-    const uint32_t c = col - SPONGE_Z;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
-    // tuple order: xored rate (34 limbs), capacity (16), updated state (50)
-    const T v = compress<T>([&](uint32_t j) {
-      return j < 34 ? row.loc(keccak_sponge::COL_XORED + j)
-             : j < 50 ? row.loc(keccak_sponge::COL_CAP + j - 34)
-                      : row.loc(keccak_sponge::COL_UPDATED + j - 50);
-    }, 2 * TUPLE_LIMBS, beta);
-    const T f = F::add(row.loc(keccak_sponge::COL_FULL), row.loc(keccak_sponge::COL_FINAL));
-    return F::add(F::k(1), F::mul(f, F::sub(F::add(gamma, v), F::k(1))));
-  }
-  if (s.air_id == BYTE_PACKING) {
-    const uint32_t c = col - PACK_Z;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
-    const T v = compress<T>([&](uint32_t j) {
-      return j == 0 ? row.loc(byte_packing::COL_READ)
-             : j == 1 ? row.loc(byte_packing::COL_ADDR)
-             : j == 2 ? row.loc(byte_packing::COL_TS)
-                      : row.loc(byte_packing::COL_VAL + j - 3);
-    }, WORD_TUPLE, beta);
-    T f = F::k(0);  // the row has a length: it moves a word
-#pragma unroll 1
-    for (uint32_t j = 0; j < 32; j++) f = F::add(f, row.loc(byte_packing::COL_LEN + j));
-    return F::add(F::k(1), F::mul(f, F::sub(F::add(gamma, v), F::k(1))));
-  }
-  if (s.air_id == MEMORY) {
-    const uint32_t c = col - MEM_Z;
-    const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
-    const T v = compress<T>([&](uint32_t j) {
-      return j == 0 ? row.loc(memory::COL_READ)
-             : j == 1 ? row.loc(memory::COL_ADDR)
-             : j == 2 ? row.loc(memory::COL_TS)
-                      : row.loc(memory::COL_VAL + j - 3);
-    }, WORD_TUPLE, beta);
-    return F::add(F::k(1), F::mul(row.loc(memory::COL_G), F::sub(F::add(gamma, v), F::k(1))));
-  }
-  return F::k(1);
+  if (s.air_id >= COUNT || !DESC[s.air_id].in_pair) return F::k(1);
+  const uint32_t c = (col - DESC[s.air_id].first_product) & 1;  // the challenge set
+  const T beta = F::k(ctl[2 * c]), gamma = F::k(ctl[2 * c + 1]);
+  T v = F::k(0);
+  const T f = port_tuple<T>(s, col, row, [&](T t) { v = F::add(F::mul(v, beta), t); });
+  if (s.air_id == KECCAK_F) v = F::add(row.aux(KECCAK_H + c), F::mul(F::k(gl::pow(ctl[2 * c], TUPLE_LIMBS)), v));
+  return F::add(F::k(1), F::mul(f, F::sub(F::add(gamma, v), F::k(1))));
 }
 // What ctl::eval keeps of a product's term when the table's AIR units emit the limb shares of the tuple themselves
 // (keccak_sponge -> logic, both sides: logic::eval_unit, keccak_sponge::eval_unit): the flags' part.  Every other
@@ -1783,20 +1761,24 @@ GL_HD void eval(const Shape& s, uint32_t base, uint32_t k0, uint32_t k1, const u
 // columns, for challenge set c.  Tables by their position in a transaction (prover_state.rs:85-93).
 struct Pair {
   const char* name;
-  // the looking side: n_looking aux columns of challenge set 0, `stride` apart (set c is column + c): their first-row
-  // values are multiplied together
-  uint32_t looking_table, looking_air, looking_col, n_looking, stride;
-  uint32_t looked_table, looked_air, looked_col;
+  // the looking side: ports looking_port .. looking_port + n_looking - 1 of its table, whose first-row values are
+  // multiplied together; the looked side: one port.  Port l of a table is its product columns first_product + 2 l + c
+  // (challenge set c), as a table set numbers a built-in member's ports (include/bpg.h, "Table sets").
+  uint32_t looking_table, looking_air, looking_port, n_looking;
+  uint32_t looked_table, looked_air, looked_port;
 };
 constexpr uint32_t N_PAIRS = 3;
 inline const Pair* pairs() {
   static const Pair P[N_PAIRS] = {
-      {"keccak_sponge -> keccak_f", 4, KECCAK_SPONGE, SPONGE_Z, 1, 2, 3, KECCAK_F, KECCAK_Z},
-      {"byte_packing -> memory", 1, BYTE_PACKING, PACK_Z, 1, 2, 6, MEMORY, MEM_Z},
-      {"keccak_sponge -> logic", 4, KECCAK_SPONGE, SPONGE_LZ, SPONGE_LOGIC_OPS, 2, 5, LOGIC, LOGIC_Z},
+      {"keccak_sponge -> keccak_f", 4, KECCAK_SPONGE, 0, 1, 3, KECCAK_F, 0},
+      {"byte_packing -> memory", 1, BYTE_PACKING, 0, 1, 6, MEMORY, 0},
+      {"keccak_sponge -> logic", 4, KECCAK_SPONGE, 1, SPONGE_LOGIC_OPS, 5, LOGIC, 0},
   };
   return P;
 }
+static_assert(SPONGE_Z == DESC[KECCAK_SPONGE].first_product && SPONGE_LZ == SPONGE_Z + 2, "the sponge table's port 0 is z, ports 1 .. 5 the logic products");
+static_assert(KECCAK_Z == DESC[KECCAK_F].first_product && PACK_Z == DESC[BYTE_PACKING].first_product &&
+              MEM_Z == DESC[MEMORY].first_product && LOGIC_Z == DESC[LOGIC].first_product, "port 0 is the table's first product column");
 }  // namespace ctl
 
 }  // namespace air

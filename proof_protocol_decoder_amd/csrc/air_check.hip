@@ -92,18 +92,6 @@ __global__ void __launch_bounds__(256) air_check_gather_kernel(const uint64_t* t
   out[(uint64_t)blockIdx.y * n_cols + c] = trace[(uint64_t)c * stride + rows[blockIdx.y]];
 }
 
-// The witness pre-flight's lookup check (proofgen.cpp): per row the term 1 + f (gamma + v - 1) of product column `col`
-// of the table (builtin_lookup_term, air_check_dev.cuh; challenge set 0 = (beta, gamma)).  A row the filter leaves out
-// gives 1, a tuple v gives gamma + v.   grid = (ceil(n / 256))
-template <uint32_t AIR>
-__global__ void __launch_bounds__(256) lookup_terms_kernel(const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta,
-                                                           uint64_t gamma, uint64_t* out) {
-  const uint64_t n = (uint64_t)1 << log_n;
-  const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (pos >= n) return;
-  out[pos] = builtin_lookup_term<AIR>(trace, n, n, pos, col, beta, gamma);
-}
-
 }  // namespace
 
 namespace bpg {
@@ -144,17 +132,6 @@ int launch_air_check(const CheckArgs& a, hipStream_t st) {
     air_check_reduce_kernel<<<ceil_div(n, 256), 256, 0, st>>>(a, a.wg_rows + (a.air_id == air::PLONK ? 1 : 0));
     BPG_LAUNCH_CHECK();
   }
-  return BP_OK;
-}
-
-int launch_lookup_terms(uint32_t air_id, const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta, uint64_t gamma,
-                        uint64_t* out, hipStream_t st) {
-  const unsigned g = ceil_div((uint64_t)1 << log_n, 256);
-  if (air_id >= air::COUNT || !air::DESC[air_id].in_pair) return fail(BP_ERR_INVALID_INPUT, "no lookup is built for AIR %u", air_id);
-  air::dispatch(air_id, [&](auto A) {
-    if constexpr (air::DESC[A.value].in_pair) lookup_terms_kernel<A.value><<<g, 256, 0, st>>>(trace, log_n, col, beta, gamma, out);
-  });
-  BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 

@@ -28,9 +28,4 @@ int launch_air_check_program(const CheckArgs& a, dim3 grid, hipStream_t st);
 int launch_gather_rows(const uint64_t* trace, uint64_t stride, uint32_t n_cols, const uint32_t* d_rows, uint32_t n_rows,
                        uint64_t* out, hipStream_t st);
 
-// out[i] = the term of product column `col` (air::ctl::product_term, challenge set (beta, gamma)) at row i of a trace of
-// air_id (stride 2^log_n): 1 where the lookup's filter leaves the row out, gamma + the compressed tuple where it does not
-int launch_lookup_terms(uint32_t air_id, const uint64_t* trace, uint32_t log_n, uint32_t col, uint64_t beta, uint64_t gamma,
-                        uint64_t* out, hipStream_t st);
-
 }  // namespace bpg

@@ -72,32 +72,33 @@ __device__ __forceinline__ CheckRow check_row(const CheckArgs& a, uint64_t pos, 
   return CheckRow{a.trace, a.consts, a.stride, n, pos, (pos + 1) & (n - 1),
                   with_x ? gl::pow(gl::root(a.log_n), pos) : 0, a.pub};
 }
-// The term 1 + f (gamma + v - 1) of product column `col` of a BUILT-IN table with a lookup side at row `pos` of its trace
-// (column stride `stride`), under the one challenge set (beta, gamma): air::ctl::product_term's filter and column
-// selection.  Keccak-f's looked tuple carries its input in the auxiliary column h; here it is compressed from the trace,
-// 23 rows up (the permutation's first row).
+// The filter f and the tuple of product column `col` of a BUILT-IN table with a lookup side at row `pos` of its trace
+// (column stride `stride`), the tuple compressed under two challenges in ONE pass over it: v_k = sum_j beta_k^j t_j
+// (air::ctl::port_tuple, what air::ctl::product_term compresses under one).  Keccak-f's looked tuple is its 50 input limbs,
+// which the prover carries in the auxiliary column h and which are read here from the trace 23 rows up (the permutation's
+// first row), then its 50 output limbs; a row with no permutation above it exposes nothing.
 template <uint32_t AIR>
-__device__ __forceinline__ uint64_t builtin_lookup_term(const uint64_t* trace, uint64_t stride, uint64_t n, uint64_t pos, uint32_t col,
-                                                        uint64_t beta, uint64_t gamma) {
+__device__ __forceinline__ void builtin_port_keys(const uint64_t* trace, uint64_t stride, uint64_t n, uint64_t pos, uint32_t col,
+                                                  uint64_t beta0, uint64_t beta1, uint64_t* f, uint64_t* v0, uint64_t* v1) {
+  namespace ctl = bpg::air::ctl;
   const CheckRow row{trace, nullptr, stride, 0, pos, (pos + 1) & (n - 1), 0, nullptr};
-  uint64_t t = 1;
+  uint64_t a0 = 0, a1 = 0;
+  auto both = [&](uint64_t t) {
+    a0 = gl::addc(gl::mulc(a0, beta0), t);
+    a1 = gl::addc(gl::mulc(a1, beta1), t);
+  };
   if constexpr (AIR == bpg::air::KECCAK_F) {
-    namespace kk = bpg::air::keccak;
-    const uint64_t g = row.loc(kk::COL_G);
-    if (g && pos >= 23) {
-      const CheckRow first{trace, nullptr, stride, 0, pos - 23, pos - 22, 0, nullptr};
-      const uint64_t in = bpg::air::ctl::compress<uint64_t>([&](uint32_t j) { return first.loc(kk::COL_A + j); },
-                                                           bpg::air::ctl::TUPLE_LIMBS, beta);
-      const uint64_t o = bpg::air::ctl::compress<uint64_t>(
-          [&](uint32_t j) { return j < 2 ? row.loc(kk::COL_APPP + j) : row.loc(kk::COL_APP + j); }, bpg::air::ctl::TUPLE_LIMBS, beta);
-      const uint64_t v = gl::addc(in, gl::mulc(gl::pow(beta, bpg::air::ctl::TUPLE_LIMBS), o));
-      t = gl::addc(1, gl::mulc(g, gl::subc(gl::addc(gamma, v), 1)));
-    }
-  } else {
-    const uint64_t ctl[4] = {beta, gamma, beta, gamma};
-    t = bpg::air::ctl::product_term<uint64_t>(bpg::air::Shape{AIR, 0, 0, 1}, col, ctl, row);
+    *f = *v0 = *v1 = 0;
+    if (pos < 23 || !gl::canon(row.loc(bpg::air::keccak::COL_G))) return;
   }
-  return t;
+  *f = gl::canon(ctl::port_tuple<uint64_t>(bpg::air::Shape{AIR, 0, 0, 1}, col, row, both));
+  if constexpr (AIR == bpg::air::KECCAK_F) {
+    const CheckRow first{trace, nullptr, stride, 0, pos - 23, pos - 22, 0, nullptr};
+#pragma unroll 1
+    for (uint32_t j = ctl::TUPLE_LIMBS; j-- > 0;) both(first.loc(bpg::air::keccak::COL_A + j));
+  }
+  *v0 = a0;
+  *v1 = a1;
 }
 
 // bit `pos % 64` of word `pos / 64` = bad; lane 0 of each wave (its row is a multiple of 64) writes the wave's word.

@@ -12,6 +12,10 @@ inline StarkCfg to_cfg(const bp_stark_cfg& c, uint32_t air_id) {
   return StarkCfg{c.log_n, c.n_cols, c.n_const, c.deg_pow, c.rate_bits, c.cap_height, c.num_queries, c.pow_bits, c.arity_bits,
                   c.final_poly_bits, air_id};
 }
+inline bp_stark_cfg abi_cfg(const StarkCfg& c) {  // to_cfg's inverse (the id travels beside it)
+  return bp_stark_cfg{c.log_n, c.n_cols, c.n_const, c.deg_pow, c.rate_bits, c.cap_height, c.num_queries, c.pow_bits, c.arity_bits,
+                      c.final_poly_bits};
+}
 
 struct CallerTable {
   StarkCfg cfg;           // cfg.air_id: a built-in AIR or a registered program
@@ -67,5 +71,23 @@ int emit(const std::vector<uint64_t>& words, uint8_t** out, size_t* out_len);
 int finish(Worker& w, int rc, uint8_t** out, size_t* out_len);
 
 inline const bp_set_port& link_end(const bp_set_link& l, uint32_t m) { return m < l.n_looking ? l.looking[m] : l.looked; }  // m == n_looking: the looked port
+
+// ---- tables tied port to port: a set's links, a transaction's active lookups (txn::links_of) -- table_set.cpp ----
+// A link names its ends by (index into the tables, port); log_link[k]: link k is a link of log ports, whose identity is
+// a sum (null: every link is a product link).  Neither function refuses anything about the statement: an unlinked port
+// is legal for a transaction; what a public set refuses is check_set's.
+//
+// The identity on the first-row openings: for both challenge sets the product (a log link: the sum) of the looking
+// ports' first-row values is the looked port's.  cfg[t], proof[t]: table t's shape and proof words.  True when a link
+// fails: *link and *set name the first one and its challenge set.
+bool first_failing_link(const StarkCfg* cfg, const std::vector<uint64_t>* proof, const bp_set_link* links, const bool* log_link,
+                        uint32_t n_links, uint32_t* link, uint32_t* set);
+// The pre-flight of tables and links: table[t] = bp_air_check_trace's answer for tables[t] (max_rows = max_viol = 8;
+// a table without a trace is no member and is left alone), link[k] = the balance of link k on the device (set_check.hip)
+// under one set of fresh challenges, as include/bpg.h defines bp_set_link_report.  Scratch: one hipMalloc of 64 bytes x
+// the power of two >= twice the rows of the largest link's ends; BP_ERR_DEVICE under `who` when the device cannot give
+// it.  Everything is checked; wording the first finding is the caller's.  Returns after `st` has finished.
+int check_tables_and_links(const char* who, const CallerTable* tables, uint32_t n_tables, const bp_set_link* links, const bool* log_link,
+                           uint32_t n_links, hipStream_t st, bp_set_table_report* table, bp_set_link_report* link);
 
 }  // namespace bpg

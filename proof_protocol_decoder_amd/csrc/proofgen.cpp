@@ -16,8 +16,7 @@
 #include <deque>
 #include <functional>
 #include <set>
-#include <unordered_map>
-#include "air_check.hpp"
+#include "caller_table.hpp"
 #include "mpt.hpp"
 #include "prover.hpp"
 #include "rec_pool.hpp"
@@ -1143,42 +1142,6 @@ int bp_generate_txn_proof_witness(const bp_state* s, const uint8_t* ir, size_t i
 BPG_ABI_CATCH("bp_generate_txn_proof_witness")
 
 // ---- the transaction witness pre-flight (bp_check_txn_witness) ----------------------------------------------------
-namespace {
-// the terms of one side of a lookup on the device (launch_lookup_terms), downloaded: tuples = the terms other than 1
-int lookup_side_terms(Worker& w, uint32_t air_id, const uint64_t* d_trace, uint32_t log_n, uint32_t col0, uint32_t n_cols,
-                      uint32_t stride, uint64_t beta, uint64_t gamma, std::vector<uint64_t>* out) {
-  const uint64_t N = (uint64_t)1 << log_n;
-  DeviceBuf terms;
-  BPG_HIP(hipMalloc(&terms.p, (size_t)n_cols * N * 8));
-  uint64_t* d = terms.as<uint64_t>();
-  for (uint32_t m = 0; m < n_cols; m++)
-    if (int r = launch_lookup_terms(air_id, d_trace, log_n, col0 + stride * m, beta, gamma, d + (size_t)m * N, w.stream)) return r;
-  out->resize((size_t)n_cols * N);
-  BPG_HIP(hipMemcpyAsync(out->data(), d, out->size() * 8, hipMemcpyDeviceToHost, w.stream));
-  BPG_HIP(hipStreamSynchronize(w.stream));
-  return BP_OK;
-}
-// the first row of side `a` (terms [n_cols][N], row-major over rows, then columns) whose tuple `b` does not have left
-int64_t first_unmatched(const std::vector<uint64_t>& a, uint32_t na, uint64_t Na, const std::vector<uint64_t>& b, uint64_t* n_tuples) {
-  std::unordered_map<uint64_t, int64_t> left;
-  for (uint64_t v : b)
-    if (v != 1) left[v]++;
-  int64_t first = -1;
-  uint64_t n = 0;
-  for (uint64_t i = 0; i < Na; i++)
-    for (uint32_t m = 0; m < na; m++) {
-      const uint64_t v = a[(size_t)m * Na + i];
-      if (v == 1) continue;
-      n++;
-      auto it = left.find(v);
-      if (it != left.end() && it->second > 0) it->second--;
-      else if (first < 0) first = (int64_t)i;
-    }
-  *n_tuples = n;
-  return first;
-}
-}  // namespace
-
 static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, const TxnWitness* wit, bp_witness_report* out) {
   if (!s || !ir || !out) return fail(BP_ERR_INVALID_INPUT, "bp_check_txn_witness: null argument");
   if (ir_len != BP_IR_WORDS * 8) return fail(BP_ERR_INVALID_INPUT, "IR must be %d bytes", BP_IR_WORDS * 8);
@@ -1200,56 +1163,54 @@ static int check_txn_impl(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   uint64_t* const* d_trace = lay.d_trace[0].data();
   if ((r = build_traces(w, w, I, wit, tcfg, d_trace))) return r;
   if ((r = w.wait())) return r;
-  // the AIRs, table by table (a seeded or derived table satisfies its AIR by construction; the prover checks the given ones)
-  int status = BP_OK;
-  std::string why;
+  // The tables proven by an AIR as contiguous caller tables (a synthetic table has no trace here: it is left alone), the
+  // active lookups as links, on the worker's stream.  A seeded or derived table satisfies its AIR by construction; the
+  // prover checks the given ones, so only those fail the call.
+  CallerTable tables[BP_NUM_TABLES] = {};
+  for (int t = 0; t < BP_NUM_TABLES; t++)
+    if (tcfg[t].air_id != air::SYNTHETIC) tables[t] = caller_table(tcfg[t], d_trace[t], (uint64_t)1 << tcfg[t].log_n, nullptr, nullptr);
+  bp_set_link links[air::ctl::N_PAIRS];
+  uint32_t pair[air::ctl::N_PAIRS];
+  const uint32_t n_links = links_of(tcfg, links, pair);
+  bp_set_report found{};
+  if ((r = check_tables_and_links("bp_check_txn_witness", tables, BP_NUM_TABLES, links, nullptr, n_links, w.stream, found.table, found.link)))
+    return r;
   for (int t = 0; t < BP_NUM_TABLES; t++) {
     bp_witness_table& o = out->table[t];
-    if (tcfg[t].air_id == air::SYNTHETIC) continue;
+    if (!tables[t].trace) continue;
     o.checked = 1;
     o.given = given_table(wit, tcfg, t);
-    const bp_stark_cfg c{tcfg[t].log_n, tcfg[t].n_cols, tcfg[t].n_const, tcfg[t].deg_pow, tcfg[t].rate_bits, tcfg[t].cap_height,
-                         tcfg[t].num_queries, tcfg[t].pow_bits, tcfg[t].arity_bits, tcfg[t].final_poly_bits};
-    uint32_t rows[8], nv = 0;
-    if ((r = bp_air_check_trace(tcfg[t].air_id, &c, d_trace[t], (uint64_t)1 << tcfg[t].log_n, nullptr, nullptr, 8, &o.n_violated_rows,
-                                rows, o.viol, 8, &nv, w.stream))) return r;
-    o.n_viol = std::min<uint32_t>(nv, 8);
-    if (status == BP_OK && o.given && o.n_violated_rows) {
-      char buf[256];
-      std::snprintf(buf, sizeof(buf), "the witness data given for table %s does not satisfy its AIR: row %u violates constraint %u "
-                    "(family %u), %llu rows in all", TABLES[t].name, o.viol[0].row, o.viol[0].constraint, o.viol[0].family,
-                    (unsigned long long)o.n_violated_rows);
-      status = BP_ERR_VERIFY;
-      why = buf;
-    }
+    o.n_violated_rows = found.table[t].n_violated_rows;
+    o.n_viol = found.table[t].n_viol;
+    std::memcpy(o.viol, found.table[t].viol, sizeof(o.viol));
   }
-  // the lookups, as multisets of compressed tuples under fresh challenges
-  FreshChallenges fresh;
-  const air::ctl::Pair* P = air::ctl::pairs();
-  for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
-    const air::ctl::Pair& p = P[i];
-    bp_witness_lookup& o = out->lookup[i];
-    o.first_looking_row = o.first_looked_row = -1;
-    if (!pair_active(tcfg, p)) continue;
+  for (bp_witness_lookup& o : out->lookup) o.first_looking_row = o.first_looked_row = -1;
+  for (uint32_t k = 0; k < n_links; k++) {
+    bp_witness_lookup& o = out->lookup[pair[k]];
+    const bp_set_link_report& f = found.link[k];
     o.checked = 1;
-    const uint64_t beta = fresh(), gamma = fresh();
-    std::vector<uint64_t> a, b;
-    const uint32_t la = tcfg[p.looking_table].log_n, lb = tcfg[p.looked_table].log_n;
-    if ((r = lookup_side_terms(w, p.looking_air, d_trace[p.looking_table], la, p.looking_col, p.n_looking, p.stride, beta, gamma, &a))) return r;
-    if ((r = lookup_side_terms(w, p.looked_air, d_trace[p.looked_table], lb, p.looked_col, 1, 0, beta, gamma, &b))) return r;
-    o.first_looking_row = first_unmatched(a, p.n_looking, (uint64_t)1 << la, b, &o.n_looking);
-    o.first_looked_row = first_unmatched(b, 1, (uint64_t)1 << lb, a, &o.n_looked);
-    o.holds = o.first_looking_row < 0 && o.first_looked_row < 0;
-    if (status == BP_OK && !o.holds) {
-      char buf[256];
-      std::snprintf(buf, sizeof(buf), "cross-table lookup %s does not hold: first unmatched looking row %lld (table %s), looked row "
-                    "%lld (table %s)", p.name, (long long)o.first_looking_row, TABLES[p.looking_table].name, (long long)o.first_looked_row,
-                    TABLES[p.looked_table].name);
-      status = BP_ERR_VERIFY;
-      why = buf;
-    }
+    o.holds = f.holds;
+    o.n_looking = f.n_looking;
+    o.n_looked = f.n_looked;
+    o.first_looking_row = f.first_looking_row;
+    o.first_looked_row = f.first_looked_row;
   }
-  return status == BP_OK ? BP_OK : fail(status, "%s", why.c_str());
+  for (int t = 0; t < BP_NUM_TABLES; t++) {
+    const bp_witness_table& o = out->table[t];
+    if (o.given && o.n_violated_rows)
+      return fail(BP_ERR_VERIFY, "the witness data given for table %s does not satisfy its AIR: row %u violates constraint %u "
+                  "(family %u), %llu rows in all", TABLES[t].name, o.viol[0].row, o.viol[0].constraint, o.viol[0].family,
+                  (unsigned long long)o.n_violated_rows);
+  }
+  for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
+    const air::ctl::Pair& p = air::ctl::pairs()[i];
+    const bp_witness_lookup& o = out->lookup[i];
+    if (o.checked && !o.holds)
+      return fail(BP_ERR_VERIFY, "cross-table lookup %s does not hold: first unmatched looking row %lld (table %s), looked row "
+                  "%lld (table %s)", p.name, (long long)o.first_looking_row, TABLES[p.looking_table].name, (long long)o.first_looked_row,
+                  TABLES[p.looked_table].name);
+  }
+  return BP_OK;
 }
 int bp_check_txn_witness(const bp_state* s, const uint8_t* ir, size_t ir_len, const bp_txn_witness* data, bp_witness_report* out) try {
   TxnWitness wit;

@@ -1,12 +1,12 @@
-// set_check.hip -- the device side of bp_check_table_set (include/bpg.h): does a link of a table set balance, and if
+// set_check.hip -- the device side of bp_check_table_set and bp_check_txn_witness (include/bpg.h): does a link balance, and if
 // not, which rows unbalance it -- computed where the traces are, a handful of words back to the host.
 //
 // Keys.  A lane owns a row of one end of the link and computes the port's filter f and its tuple compressed by two
 // fresh challenges, v_0 = sum_j beta_0^j t_j and v_1 = sum_j beta_1^j t_j (trailing zeros of a tuple drop out of both).
 // A registered program's port unit is interpreted exactly as program_port_terms_kernel interprets it (prog::run_port into
 // a PortAcc; registers in LDS [reg][lane], the code and the beta table read wave-uniformly: air_program_dev.cuh).  A
-// built-in member's come from builtin_lookup_term (air_check_dev.cuh: air::ctl::product_term, Keccak-f's input 23 rows
-// up): term(gamma) = 1 + f (gamma + v - 1), so f = term(2) - term(1) and f v = term(1) - 1.
+// built-in member's come from builtin_port_keys (air_check_dev.cuh): one pass over the filter and tuple that
+// air::ctl::product_term reads (air::ctl::port_tuple), Keccak-f's input 23 rows up.
 //
 // Balance.  Rows with f != 0 insert into an open-addressed table in HBM keyed by v_0: a slot is claimed by ONE 64-bit
 // compare-and-swap on its key word (empty = all ones, which is no canonical field element; 0 is a key like any other),
@@ -147,21 +147,8 @@ __global__ void __launch_bounds__(256) set_keys_builtin_kernel(KeyArgs a) {
   bool active;
   uint64_t pos;
   if (!wave_rows(a, n, &active, &pos)) return;
-  uint64_t t0 = 0, t1 = 0, t2 = 0;  // 1 + f v_0, 1 + f v_1, 1 + f (1 + v_0)
-#pragma unroll 1
-  for (uint32_t k = 0; k < 3; k++) {
-    const uint64_t t = builtin_lookup_term<AIR>(a.trace, a.stride, n, pos, a.port, a.beta[k == 1], k == 2 ? 2 : 1);
-    if (k == 0) t0 = t;
-    else if (k == 1) t1 = t;
-    else t2 = t;
-  }
-  const uint64_t f = gl::subc(t2, t0);
-  uint64_t v0 = gl::subc(t0, 1), v1 = gl::subc(t1, 1);
-  if (f > 1) {  // (only a trace that breaks the table's own filter constraint gets here)
-    const uint64_t fi = gl::inv(f);
-    v0 = gl::mulc(v0, fi);
-    v1 = gl::mulc(v1, fi);
-  }
+  uint64_t f, v0, v1;
+  builtin_port_keys<AIR>(a.trace, a.stride, n, pos, a.port, a.beta[0], a.beta[1], &f, &v0, &v1);
   accumulate(a, active, pos, f, v0, v1);
 }
 

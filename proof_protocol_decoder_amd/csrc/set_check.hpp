@@ -1,4 +1,4 @@
-// set_check.hpp -- the device side of bp_check_table_set (set_check.hip): the balance of one link of a table set.
+// set_check.hpp -- the device side of both pre-flights (set_check.hip; check_tables_and_links, table_set.cpp): the balance of one link.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1,6 +1,8 @@
 // table_set.cpp -- table sets: several caller traces linked port to port, proven on one transcript (include/bpg.h):
-// the statement and its refusals (check_set), what both sides observe of it (observe_set), the links on the first-row
-// openings (check_links), and the entries bp_stark_prove_table_set, bp_stark_verify_table_set, bp_check_table_set.
+// the statement and its refusals (check_set), what both sides observe of it (observe_set), and the entries
+// bp_stark_prove_table_set, bp_stark_verify_table_set, bp_check_table_set.  Below the statement, and shared with a
+// transaction's seven tables (txn_tables.cpp, proofgen.cpp): the links on the first-row openings (first_failing_link) and
+// the pre-flight of tables and links (check_tables_and_links).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -16,12 +18,10 @@ constexpr uint32_t SET_MAX_TABLES = 8, SET_MAX_LINKS = 16, SET_MAX_LOOKING = 8;
 
 // the lookup ports of a member: a registered program's own, a built-in's product columns in air::DESC order
 // (port l = columns first_product + 2l + c); 0: the id is no side of any lookup
-uint32_t set_ports_of(uint32_t air_id, uint32_t* first_product) {
-  *first_product = 0;
+uint32_t set_ports_of(uint32_t air_id) {
   if (const auto p = air::prog::find(air_id)) return p->n_ports;
   const air::Desc* d = air::info(air_id);
   if (!d || !d->in_pair) return 0;
-  *first_product = d->first_product;
   return (d->n_aux - d->first_product) / 2;
 }
 struct Where {  // "table %u: " in front of what is refused about a member
@@ -30,8 +30,9 @@ struct Where {  // "table %u: " in front of what is refused about a member
 };
 struct SetShape {
   CallerTable table[SET_MAX_TABLES];  // (the verifier's statement leaves the device pointers alone)
-  const StarkCfg& cfg(uint32_t t) const { return table[t].cfg; }
-  uint32_t n_ports[SET_MAX_TABLES], first_product[SET_MAX_TABLES];
+  StarkCfg cfgs[SET_MAX_TABLES];      // table[t].cfg, side by side as first_failing_link reads them
+  const StarkCfg& cfg(uint32_t t) const { return cfgs[t]; }
+  uint32_t n_ports[SET_MAX_TABLES];
   uint32_t log_ports[SET_MAX_TABLES];  // bit l: port l of the table is a log port (a registered "BPGAIRP3" program's)
   bool log_link[SET_MAX_LINKS];        // the link's ports are log ports: its identity is a sum
 };
@@ -44,11 +45,12 @@ int check_set(const char* who, const bp_set_table* tables, uint32_t n_tables, co
   for (uint32_t t = 0; t < n_tables; t++) {
     const bp_set_table& m = tables[t];
     const CallerTable& tb = out->table[t] = caller_table(to_cfg(m.cfg, m.air_id), m.d_trace, m.stride, m.d_consts, m.pub);
+    out->cfgs[t] = tb.cfg;
     if (int rc = check_cfg(tb.cfg)) {
       const std::string why = bp_last_error();
       return fail(rc, "%s: table %u: %s", who, t, why.c_str());
     }
-    out->n_ports[t] = set_ports_of(m.air_id, &out->first_product[t]);
+    out->n_ports[t] = set_ports_of(m.air_id);
     out->log_ports[t] = tb.program ? tb.program->log_ports() : 0;  // a built-in member's ports are product ports
     if (!out->n_ports[t])
       return fail(BP_ERR_INVALID_INPUT, "%s: table %u: air_id %u (0x%08x) has no lookup port: a member is a registered program with ports or "
@@ -118,29 +120,128 @@ int observe_set(Challenger& ch, const bp_set_table* tables, uint32_t n_tables, c
   }
   return BP_OK;
 }
-// Every link on the first-row openings: for both challenge sets the product of the looking ports' values is the looked
-// port's (check_lookups' identity, txn_tables.cpp, with a looking count); for a link of log ports, their sum.
+// Every link on the first-row openings (first_failing_link), in a set's words
 int check_links(const SetShape& sh, const bp_set_link* links, uint32_t n_links, const std::vector<uint64_t>* proof) {
+  uint32_t k, c;
+  if (!first_failing_link(sh.cfgs, proof, links, sh.log_link, n_links, &k, &c)) return BP_OK;
+  const bp_set_link& l = links[k];
+  return fail(BP_ERR_VERIFY, "link %u does not hold (challenge set %u): port %u of table %u%s asks for tuples that port %u of table %u "
+              "does not expose", k, c, l.looking[0].port, l.looking[0].table, l.n_looking > 1 ? " (and the link's other looking ports)" : "",
+              l.looked.port, l.looked.table);
+}
+}  // namespace
+
+namespace bpg {
+
+bool first_failing_link(const StarkCfg* cfg, const std::vector<uint64_t>* proof, const bp_set_link* links, const bool* log_link,
+                        uint32_t n_links, uint32_t* link, uint32_t* set) {
   for (uint32_t k = 0; k < n_links; k++) {
     const bp_set_link& l = links[k];
+    const bool is_log = log_link && log_link[k];
     for (uint32_t c = 0; c < 2; c++) {
-      auto first_row = [&](const bp_set_port& e) {
-        const ProofLayout L = proof_layout(sh.cfg(e.table));
-        const uint64_t* v = proof[e.table].data() + L.open_first + 2 * (size_t)(sh.first_product[e.table] + 2 * e.port + c);
+      auto first_row = [&](const bp_set_port& e) {  // (a registered program's products start at column 0)
+        const uint64_t* v = proof[e.table].data() + proof_layout(cfg[e.table]).open_first +
+                            2 * (size_t)(air::ctl::first_product(cfg[e.table].air_id) + 2 * e.port + c);
         return gl::Ext{v[0], v[1]};
       };
-      gl::Ext a = gl::ext(sh.log_link[k] ? 0 : 1);
-      for (uint32_t m = 0; m < l.n_looking; m++) a = sh.log_link[k] ? gl::add(a, first_row(l.looking[m])) : gl::mul(a, first_row(l.looking[m]));
+      gl::Ext a = gl::ext(is_log ? 0 : 1);
+      for (uint32_t m = 0; m < l.n_looking; m++) a = is_log ? gl::add(a, first_row(l.looking[m])) : gl::mul(a, first_row(l.looking[m]));
       const gl::Ext b = first_row(l.looked);
-      if (a.c0 != b.c0 || a.c1 != b.c1)
-        return fail(BP_ERR_VERIFY, "link %u does not hold (challenge set %u): port %u of table %u%s asks for tuples that port %u of table %u "
-                    "does not expose", k, c, l.looking[0].port, l.looking[0].table, l.n_looking > 1 ? " (and the link's other looking ports)" : "",
-                    l.looked.port, l.looked.table);
+      if (a.c0 != b.c0 || a.c1 != b.c1) {
+        *link = k;
+        *set = c;
+        return true;
+      }
     }
+  }
+  return false;
+}
+
+int check_tables_and_links(const char* who, const CallerTable* tables, uint32_t n_tables, const bp_set_link* links, const bool* log_link,
+                           uint32_t n_links, hipStream_t st, bp_set_table_report* table, bp_set_link_report* link) {
+  int rc;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const CallerTable& tb = tables[t];
+    if (!tb.trace) continue;
+    bp_set_table_report& o = table[t];
+    const bp_stark_cfg shape = abi_cfg(tb.cfg);
+    uint32_t rows[8], nv = 0;
+    if ((rc = bp_air_check_trace(tb.cfg.air_id, &shape, tb.trace, tb.stride, tb.consts, tb.pub, 8, &o.n_violated_rows, rows, o.viol, 8, &nv,
+                                 st))) return rc;
+    o.n_viol = std::min<uint32_t>(nv, 8);
+  }
+  if (!n_links) return BP_OK;
+  // the links: one scratch for the largest, reused link after link; a link's eight result words behind the slots
+  uint32_t log_slots[SET_MAX_LINKS], max_log = 0;
+  for (uint32_t k = 0; k < n_links; k++) {
+    uint64_t rows = 0;
+    for (uint32_t m = 0; m <= links[k].n_looking; m++)
+      rows += (uint64_t)1 << tables[link_end(links[k], m).table].cfg.log_n;
+    log_slots[k] = set_check_log_slots(rows);
+    max_log = std::max(max_log, log_slots[k]);
+  }
+  const size_t table_words = ((size_t)1 << max_log) * SET_SLOT_WORDS, bytes = (table_words + (size_t)SET_RESULT_WORDS * n_links) * 8;
+  DeviceBuf scratch;
+  if (hipMalloc(&scratch.p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BP_ERR_DEVICE, "%s: the device has no %zu bytes for the balance of the largest link", who, bytes);
+  }
+  uint64_t* d_s = scratch.as<uint64_t>();
+  FreshChallenges fresh;
+  uint64_t ctl[4];
+  for (uint64_t& v : ctl) v = fresh();
+  auto end_of = [&](const bp_set_link& l, uint32_t m) {
+    const bp_set_port& e = link_end(l, m);
+    const CallerTable& tb = tables[e.table];
+    SetEnd se{};
+    se.air_id = tb.cfg.air_id; se.port = e.port;
+    se.trace = tb.trace; se.consts = tb.consts; se.stride = tb.stride;
+    se.log_n = tb.cfg.log_n;
+    if (tb.pub) for (int j = 0; j < 4; j++) se.pub[j] = tb.pub[j];
+    se.end = m; se.looked = m == l.n_looking;
+    // a port that demands a bit: a registered program's product port or kind-1 log port (a built-in member's own AIR
+    // constrains its filter; a kind-2 filter is a multiplicity)
+    se.wants_bit = tb.program && e.port < tb.program->n_ports && tb.program->port_kind[e.port] != air::prog::PORT_LOG_MULT;
+    return se;
+  };
+  for (uint32_t k = 0; k < n_links; k++) {
+    SetEnd ends[SET_MAX_LOOKING + 1];
+    for (uint32_t m = 0; m <= links[k].n_looking; m++) ends[m] = end_of(links[k], m);
+    if ((rc = launch_set_link(ends, links[k].n_looking + 1, ctl, d_s, log_slots[k], d_s + table_words + (size_t)SET_RESULT_WORDS * k, st))) return rc;
+  }
+  uint64_t res[SET_MAX_LINKS][SET_RESULT_WORDS];
+  BPG_HIP(hipMemcpyAsync(res, d_s + table_words, (size_t)SET_RESULT_WORDS * n_links * 8, hipMemcpyDeviceToHost, st));
+  BPG_HIP(hipStreamSynchronize(st));
+  const uint64_t row_mask = ((uint64_t)1 << SET_LOC_ROW_BITS) - 1;
+  for (uint32_t k = 0; k < n_links; k++) {
+    bp_set_link_report& o = link[k];
+    const uint64_t* r = res[k];
+    if (r[SET_RES_OVERFLOW]) return fail(BP_ERR_DEVICE, "%s: link %u: the balance table overflowed", who, k);
+    o.is_log = log_link && log_link[k];
+    o.n_looking = r[SET_RES_N_LOOKING];
+    o.n_looked = r[SET_RES_N_LOOKED];
+    o.n_unbalanced = r[SET_RES_UNBALANCED];
+    o.first_looking_end = o.bad_filter_end = -1;
+    o.first_looking_row = o.first_looked_row = o.bad_filter_row = -1;
+    if (r[SET_RES_MIN_LOOKING] != ~0ULL) {
+      o.first_looking_end = (int32_t)(r[SET_RES_MIN_LOOKING] >> SET_LOC_ROW_BITS);
+      o.first_looking_row = (int64_t)(r[SET_RES_MIN_LOOKING] & row_mask);
+    }
+    if (r[SET_RES_MIN_LOOKED] != ~0ULL) o.first_looked_row = (int64_t)r[SET_RES_MIN_LOOKED];
+    if (r[SET_RES_BAD_FILTER] != ~0ULL) {
+      o.bad_filter_end = (int32_t)(r[SET_RES_BAD_FILTER] >> SET_LOC_ROW_BITS);
+      o.bad_filter_row = (int64_t)(r[SET_RES_BAD_FILTER] & row_mask);
+      uint64_t* d_res = d_s + table_words + (size_t)SET_RESULT_WORDS * k;
+      if ((rc = launch_set_filter_at(end_of(links[k], (uint32_t)o.bad_filter_end), (uint64_t)o.bad_filter_row, ctl, d_res, st))) return rc;
+      BPG_HIP(hipMemcpyAsync(&o.bad_filter_value, d_res + SET_RES_BAD_VALUE, 8, hipMemcpyDeviceToHost, st));
+      BPG_HIP(hipStreamSynchronize(st));
+    }
+    o.holds = o.n_unbalanced == 0 && o.bad_filter_end < 0;
   }
   return BP_OK;
 }
-}  // namespace
+
+}  // namespace bpg
 
 extern "C" {
 
@@ -279,8 +380,8 @@ int bp_stark_verify_table_set(const bp_set_table* tables, uint32_t n_tables, con
 }
 BPG_ABI_CATCH("bp_stark_verify_table_set")
 
-// The pre-flight of a set (include/bpg.h): every member's own constraints through bp_air_check_trace, every link's
-// balance on the device (set_check.hip).  Nothing is committed or proven; every table and every link is reported.
+// The pre-flight of a set (include/bpg.h): check_tables_and_links behind the statement's refusals, on the null stream.
+// Nothing is committed or proven; every table and every link is reported.
 int bp_check_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_set_link* links, uint32_t n_links, int device,
                        bp_set_report* out) try {
   if (!out) return fail(BP_ERR_INVALID_INPUT, "bp_check_table_set: null argument");
@@ -293,107 +394,30 @@ int bp_check_table_set(const bp_set_table* tables, uint32_t n_tables, const bp_s
   BPG_HIP(hipGetDevice(&before));
   BPG_HIP(hipSetDevice(device));
   struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{before};
-  hipStream_t st = nullptr;
-  int status = BP_OK;
-  std::string why;
-  char buf[384];
-  // the members' own constraints, as bp_check_txn_witness reports a table's
+  if ((rc = check_tables_and_links("bp_check_table_set", sh.table, n_tables, links, sh.log_link, n_links, nullptr, out->table, out->link)))
+    return rc;
+  // the first finding: tables in index order (as bp_check_txn_witness words a table's), then links
   for (uint32_t t = 0; t < n_tables; t++) {
-    bp_set_table_report& o = out->table[t];
-    const CallerTable& tb = sh.table[t];
-    uint32_t rows[8], nv = 0;
-    if ((rc = bp_air_check_trace(tb.cfg.air_id, &tables[t].cfg, tb.trace, tb.stride, tb.consts, tb.pub, 8, &o.n_violated_rows, rows, o.viol, 8,
-                                 &nv, st))) return rc;
-    o.n_viol = std::min<uint32_t>(nv, 8);
-    if (status == BP_OK && o.n_violated_rows) {
-      std::snprintf(buf, sizeof(buf), "table %u does not satisfy its AIR: row %u violates constraint %u (family %u), %llu rows in all", t,
-                    o.viol[0].row, o.viol[0].constraint, o.viol[0].family, (unsigned long long)o.n_violated_rows);
-      status = BP_ERR_VERIFY;
-      why = buf;
-    }
+    const bp_set_table_report& o = out->table[t];
+    if (o.n_violated_rows)
+      return fail(BP_ERR_VERIFY, "table %u does not satisfy its AIR: row %u violates constraint %u (family %u), %llu rows in all", t,
+                  o.viol[0].row, o.viol[0].constraint, o.viol[0].family, (unsigned long long)o.n_violated_rows);
   }
-  // the links: one scratch for the largest, reused link after link; a link's eight result words behind the slots
-  uint32_t log_slots[SET_MAX_LINKS], max_log = 0;
-  for (uint32_t k = 0; k < n_links; k++) {
-    uint64_t rows = 0;
-    for (uint32_t m = 0; m <= links[k].n_looking; m++)
-      rows += (uint64_t)1 << sh.cfg(link_end(links[k], m).table).log_n;
-    log_slots[k] = set_check_log_slots(rows);
-    max_log = std::max(max_log, log_slots[k]);
-  }
-  const size_t table_words = ((size_t)1 << max_log) * SET_SLOT_WORDS, bytes = (table_words + (size_t)SET_RESULT_WORDS * n_links) * 8;
-  DeviceBuf scratch;
-  if (hipMalloc(&scratch.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(BP_ERR_DEVICE, "bp_check_table_set: the device has no %zu bytes for the balance of the largest link", bytes);
-  }
-  uint64_t* d_s = scratch.as<uint64_t>();
-  FreshChallenges fresh;
-  uint64_t ctl[4];
-  for (uint64_t& v : ctl) v = fresh();
-  auto end_of = [&](const bp_set_link& l, uint32_t m) {
-    const bp_set_port& e = link_end(l, m);
-    const CallerTable& tb = sh.table[e.table];
-    SetEnd se{};
-    se.air_id = tb.cfg.air_id; se.port = e.port;
-    se.trace = tb.trace; se.consts = tb.consts; se.stride = tb.stride;
-    se.log_n = tb.cfg.log_n;
-    if (tb.pub) for (int j = 0; j < 4; j++) se.pub[j] = tb.pub[j];
-    se.end = m; se.looked = m == l.n_looking;
-    // a port that demands a bit: a registered program's product port or kind-1 log port (a built-in member's own AIR
-    // constrains its filter; a kind-2 filter is a multiplicity)
-    se.wants_bit = tb.program && e.port < tb.program->n_ports && tb.program->port_kind[e.port] != air::prog::PORT_LOG_MULT;
-    return se;
-  };
-  for (uint32_t k = 0; k < n_links; k++) {
-    SetEnd ends[SET_MAX_LOOKING + 1];
-    for (uint32_t m = 0; m <= links[k].n_looking; m++) ends[m] = end_of(links[k], m);
-    if ((rc = launch_set_link(ends, links[k].n_looking + 1, ctl, d_s, log_slots[k], d_s + table_words + (size_t)SET_RESULT_WORDS * k, st))) return rc;
-  }
-  uint64_t res[SET_MAX_LINKS][SET_RESULT_WORDS];
-  BPG_HIP(hipMemcpyAsync(res, d_s + table_words, (size_t)SET_RESULT_WORDS * n_links * 8, hipMemcpyDeviceToHost, st));
-  BPG_HIP(hipStreamSynchronize(st));
-  const uint64_t row_mask = ((uint64_t)1 << SET_LOC_ROW_BITS) - 1;
   for (uint32_t k = 0; k < n_links; k++) {
     const bp_set_link& l = links[k];
-    bp_set_link_report& o = out->link[k];
-    const uint64_t* r = res[k];
-    if (r[SET_RES_OVERFLOW]) return fail(BP_ERR_DEVICE, "bp_check_table_set: link %u: the balance table overflowed", k);
-    o.is_log = sh.log_link[k];
-    o.n_looking = r[SET_RES_N_LOOKING];
-    o.n_looked = r[SET_RES_N_LOOKED];
-    o.n_unbalanced = r[SET_RES_UNBALANCED];
-    o.first_looking_end = o.bad_filter_end = -1;
-    o.first_looking_row = o.first_looked_row = o.bad_filter_row = -1;
-    if (r[SET_RES_MIN_LOOKING] != ~0ULL) {
-      o.first_looking_end = (int32_t)(r[SET_RES_MIN_LOOKING] >> SET_LOC_ROW_BITS);
-      o.first_looking_row = (int64_t)(r[SET_RES_MIN_LOOKING] & row_mask);
-    }
-    if (r[SET_RES_MIN_LOOKED] != ~0ULL) o.first_looked_row = (int64_t)r[SET_RES_MIN_LOOKED];
-    if (r[SET_RES_BAD_FILTER] != ~0ULL) {
-      o.bad_filter_end = (int32_t)(r[SET_RES_BAD_FILTER] >> SET_LOC_ROW_BITS);
-      o.bad_filter_row = (int64_t)(r[SET_RES_BAD_FILTER] & row_mask);
-      uint64_t* d_res = d_s + table_words + (size_t)SET_RESULT_WORDS * k;
-      if ((rc = launch_set_filter_at(end_of(l, (uint32_t)o.bad_filter_end), (uint64_t)o.bad_filter_row, ctl, d_res, st))) return rc;
-      BPG_HIP(hipMemcpyAsync(&o.bad_filter_value, d_res + SET_RES_BAD_VALUE, 8, hipMemcpyDeviceToHost, st));
-      BPG_HIP(hipStreamSynchronize(st));
-    }
-    o.holds = o.n_unbalanced == 0 && o.bad_filter_end < 0;
-    if (status != BP_OK || o.holds) continue;
-    status = BP_ERR_VERIFY;
+    const bp_set_link_report& o = out->link[k];
+    if (o.holds) continue;
     if (o.bad_filter_end >= 0) {
       const bp_set_port& e = link_end(l, (uint32_t)o.bad_filter_end);
-      std::snprintf(buf, sizeof(buf), "link %u: the filter of port %u of table %u is no bit on row %lld: it is %llu", k, e.port, e.table,
-                    (long long)o.bad_filter_row, (unsigned long long)o.bad_filter_value);
-    } else {
-      const bp_set_port& e = l.looking[o.first_looking_end < 0 ? 0 : o.first_looking_end];
-      std::snprintf(buf, sizeof(buf), "link %u does not balance (%llu tuple values): first unmatched looking row %lld (port %u of table %u), "
-                    "looked row %lld (port %u of table %u)", k, (unsigned long long)o.n_unbalanced, (long long)o.first_looking_row, e.port, e.table,
-                    (long long)o.first_looked_row, l.looked.port, l.looked.table);
+      return fail(BP_ERR_VERIFY, "link %u: the filter of port %u of table %u is no bit on row %lld: it is %llu", k, e.port, e.table,
+                  (long long)o.bad_filter_row, (unsigned long long)o.bad_filter_value);
     }
-    why = buf;
+    const bp_set_port& e = l.looking[o.first_looking_end < 0 ? 0 : o.first_looking_end];
+    return fail(BP_ERR_VERIFY, "link %u does not balance (%llu tuple values): first unmatched looking row %lld (port %u of table %u), "
+                "looked row %lld (port %u of table %u)", k, (unsigned long long)o.n_unbalanced, (long long)o.first_looking_row, e.port, e.table,
+                (long long)o.first_looked_row, l.looked.port, l.looked.table);
   }
-  return status == BP_OK ? BP_OK : fail(status, "%s", why.c_str());
+  return BP_OK;
 }
 BPG_ABI_CATCH("bp_check_table_set")
 

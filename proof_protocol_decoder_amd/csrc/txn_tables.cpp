@@ -1,6 +1,7 @@
 // txn_tables.cpp -- the host-only code over the descriptor of a transaction's seven tables (txn_tables.hpp).
 #include <algorithm>
 #include <string>
+#include "caller_table.hpp"
 #include "txn_tables.hpp"
 
 namespace bpg {
@@ -144,29 +145,31 @@ int plan_traces(const StarkCfg tcfg[BP_NUM_TABLES], const bool given[BP_NUM_TABL
   return BP_OK;
 }
 
-// The cross-table lookups of a transaction's table proofs (air::ctl::pairs): for both challenge sets the first-row
-// value of the looking running product equals that of the looked one.  Shared by the prover (which refuses to go on with
-// tables that do not form one statement: upstream's root circuit checks this in-circuit) and bp_verify_txn_table_proofs.
-int check_lookups(const StarkCfg tcfg[BP_NUM_TABLES], const std::vector<uint64_t> proof[BP_NUM_TABLES]) {
+uint32_t links_of(const StarkCfg tcfg[BP_NUM_TABLES], bp_set_link links[air::ctl::N_PAIRS], uint32_t pair[air::ctl::N_PAIRS]) {
   const air::ctl::Pair* P = air::ctl::pairs();
+  uint32_t n = 0;
   for (uint32_t i = 0; i < air::ctl::N_PAIRS; i++) {
     const air::ctl::Pair& p = P[i];
     if (!pair_active(tcfg, p)) continue;
-    const ProofLayout La = proof_layout(tcfg[p.looking_table]), Lb = proof_layout(tcfg[p.looked_table]);
-    for (uint32_t c = 0; c < 2; c++) {
-      // the first-row values of the looking side's product columns, multiplied together, against the looked side's
-      gl::Ext a = gl::ext(1);
-      for (uint32_t m = 0; m < p.n_looking; m++) {
-        const uint64_t* v = proof[p.looking_table].data() + La.open_first + 2 * (p.looking_col + p.stride * m + c);
-        a = gl::mul(a, gl::Ext{v[0], v[1]});
-      }
-      const uint64_t* b = proof[p.looked_table].data() + Lb.open_first + 2 * (p.looked_col + c);
-      if (a.c0 != b[0] || a.c1 != b[1])
-        return fail(BP_ERR_VERIFY, "cross-table lookup %s does not hold (challenge set %u): the %s table asks for tuples the %s table "
-                    "does not expose", p.name, c, TABLES[p.looking_table].name, TABLES[p.looked_table].name);
-    }
+    bp_set_link& l = links[n] = bp_set_link{};
+    l.n_looking = p.n_looking;
+    for (uint32_t m = 0; m < p.n_looking; m++) l.looking[m] = bp_set_port{p.looking_table, p.looking_port + m};
+    l.looked = bp_set_port{p.looked_table, p.looked_port};
+    pair[n++] = i;
   }
-  return BP_OK;
+  return n;
+}
+
+// The cross-table lookups of a transaction's table proofs, on the first-row openings (first_failing_link).  Shared by the
+// prover (which refuses to go on with tables that do not form one statement: upstream's root circuit checks this
+// in-circuit) and bp_verify_txn_table_proofs.
+int check_lookups(const StarkCfg tcfg[BP_NUM_TABLES], const std::vector<uint64_t> proof[BP_NUM_TABLES]) {
+  bp_set_link links[air::ctl::N_PAIRS];
+  uint32_t pair[air::ctl::N_PAIRS], k, c;
+  if (!first_failing_link(tcfg, proof, links, nullptr, links_of(tcfg, links, pair), &k, &c)) return BP_OK;
+  const air::ctl::Pair& p = air::ctl::pairs()[pair[k]];
+  return fail(BP_ERR_VERIFY, "cross-table lookup %s does not hold (challenge set %u): the %s table asks for tuples the %s table "
+              "does not expose", p.name, c, TABLES[p.looking_table].name, TABLES[p.looked_table].name);
 }
 
 namespace {

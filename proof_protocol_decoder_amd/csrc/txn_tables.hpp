@@ -95,6 +95,10 @@ struct TracePlan {
 };
 int plan_traces(const StarkCfg tcfg[BP_NUM_TABLES], const bool given[BP_NUM_TABLES], const size_t n_given[BP_NUM_TABLES], TracePlan* out);
 
+// The active lookups as links over the table indices 0 .. 6 -- the form a table set's links have (caller_table.hpp) --
+// in pairs() order; pair[k]: the pair that link k is.  Returns how many.  (A lookup that is not active leaves its
+// sponge ports unlinked: legal here, refused for a public set.)
+uint32_t links_of(const StarkCfg tcfg[BP_NUM_TABLES], bp_set_link links[air::ctl::N_PAIRS], uint32_t pair[air::ctl::N_PAIRS]);
 int check_lookups(const StarkCfg tcfg[BP_NUM_TABLES], const std::vector<uint64_t> proof[BP_NUM_TABLES]);
 
 }  // namespace txn

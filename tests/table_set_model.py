@@ -1,13 +1,14 @@
 """The reference of bp_check_table_set (include/bpg.h) over Python integers: from builders, traces and links the whole
 link report -- balance per tuple value, the first rows, the counts, the bad-filter scan -- as the header defines it.  A
 registered member's ports are Builder.evaluate_ports (next row wrapping at the last row, x = w^i); a built-in member's
-are read off the trace columns as AIRS.md section 3 lists them (memory, AIR 3, and byte packing, AIR 5).  It shares
-nothing with the library: no challenges, no compression, no hash table -- a dictionary from tuple value to the
+are read off the trace columns as include/bpg.h lists them under "Table sets" (AIRs 1, 2, 3, 5 and 6), the column
+offsets of AIRs 1, 2 and 6 from the records of tests/builtin_airs.py.  It shares nothing with the library: no challenges, no compression, no hash table -- a dictionary from tuple value to the
 difference of the two sides mod p.
 
-A member is a dict: "builder" (a Builder) or "air_id" (3 or 5), "trace" ([n_cols, n] uint64), optionally "consts", "pub".
+A member is a dict: "builder" (a Builder) or "air_id" (1, 2, 3, 5 or 6), "trace" ([n_cols, n] uint64), optionally "consts", "pub".
 A link is (looking [(table, port), ...], looked (table, port)), as ops.stark_prove_table_set takes it."""
 from air_program_cases import P
+from builtin_airs import keccak as KF, keccak_sponge as SP, logic as LG
 from proof_protocol_decoder_amd.air_program import PORT_LOG_MULT, PORT_PRODUCT
 
 FIELDS = ("holds", "is_log", "n_looking", "n_looked", "n_unbalanced", "first_looking_end", "first_looking_row",
@@ -34,7 +35,28 @@ def builtin_ports(air_id, trace):
     if air_id == 5:      # byte packing: the row has a length; the same tuple from its own columns
         return [[(sum(col(PACK_LEN + j, i) for j in range(32)) % P,
                   [col(0, i), col(PACK_ADDR, i), col(PACK_TS, i)] + [col(PACK_VAL + k, i) for k in range(8)]) for i in range(n)]]
-    raise ValueError("the model reads AIR 3 and AIR 5 only")
+    limb = lambda c0, i: sum(col(c0 + z, i) << z for z in range(32)) % P        # 32 bit columns, lowest first
+    if air_id == 1:      # Keccak-f: filter g; 50 input limbs, read 23 rows up (the permutation's first row), 50 output limbs
+        out = lambda j, i: col((KF.COL_APPP if j < 2 else KF.COL_APP) + j, i)    # lane 0 after iota, the others after chi
+        return [[(col(KF.COL_FILTER, i), [col(KF.COL_A + j, i - 23) for j in range(50)] + [out(j, i) for j in range(50)])
+                 if i >= 23 else (0, []) for i in range(n)]]                     # no permutation ends above row 23
+    if air_id == 2:      # logic: filter g; is_and, is_or, is_xor, eight limbs of input 0, of input 1, of the result
+        return [[(col(LG.COL_FILTER, i), [col(LG.COL_OP + j, i) for j in range(3)] + [limb(LG.COL_IN0 + 32 * j, i) for j in range(8)]
+                  + [limb(LG.COL_IN1 + 32 * j, i) for j in range(8)] + [col(LG.COL_RES + j, i) for j in range(8)]) for i in range(n)]]
+    if air_id == 6:      # Keccak sponge: every port's filter is is_full + is_final
+        f = lambda i: (col(SP.COL_FULL, i) + col(SP.COL_FINAL, i)) % P
+        # port 0: 34 xored rate limbs, 16 capacity limbs, 50 updated state limbs
+        ports = [[(f(i), [col(SP.COL_XORED + j, i) for j in range(34)] + [col(SP.COL_CAP + j, i) for j in range(16)]
+                   + [col(SP.COL_UPDATED + j, i) for j in range(50)]) for i in range(n)]]
+        # ports 1 .. 5, limb group m = port - 1: 0, 0, 1, limbs 8m .. 8m + 7 of the rate before, of the block, of the xored
+        # rate; limbs past the 34th are zero
+        for m in range(5):
+            group = [l for l in range(8 * m, 8 * m + 8)]
+            ports.append([(f(i), [0, 0, 1] + [limb(SP.COL_RATE + 32 * l, i) if l < 34 else 0 for l in group]
+                           + [limb(SP.COL_BLOCK + 32 * l, i) if l < 34 else 0 for l in group]
+                           + [col(SP.COL_XORED + l, i) if l < 34 else 0 for l in group]) for i in range(n)])
+        return ports
+    raise ValueError("the model reads AIRs 1, 2, 3, 5 and 6")
 
 
 def member_ports(m):

@@ -10,6 +10,7 @@ import air_program_cases as cases
 import air_program_port_cases as pc
 import table_set_model as model
 from air_program_cases import P
+from builtin_airs import keccak as KF, keccak_sponge as SP, logic as LG
 from proof_protocol_decoder_amd._lib import BpgError
 from proof_protocol_decoder_amd.air_program import ALL_ROWS, TRANSITION, Builder
 from test_gpu_air_program import constants_cap
@@ -442,6 +443,69 @@ def test_two_built_in_members_are_read_as_the_header_lists_them(bpg):
     assert not got.ok and got.tables[0].ok and not got.tables[1].ok and "table 1 " in got.message
     assert want["n_looking"] == len(sending) and want["n_looked"] == 22 and want["n_unbalanced"] >= len(sending) - 4
     assert got.links[0].first_looking_row == sending[4] and got.links[0].first_looked_row == 12 and got.links[0].bad_filter_end == -1
+
+
+# the three tables a transaction's sponge ties together, as a set: every port of the sponge table (AIR 6) is in a link
+SPONGE_LINKS = [([(0, 0)], (1, 0)), ([(0, 1 + m) for m in range(5)], (2, 0))]
+
+
+def sponge_keccak_logic(bpg):
+    """seeded 2^5-row tables of AIRs 6, 1 and 2 on the host (the seeded looked tables expose nothing: their g is zero), and
+    the sponge rows that send"""
+    sponge, keccak, logic = (to_host(bpg.ops.air_trace(a, 5, seed=s)) for a, s in ((6, 3), (1, 4), (2, 5)))
+    assert not keccak[KF.COL_FILTER].any() and not logic[LG.COL_FILTER].any()
+    sending = [i for i in range(32) if int(sponge[SP.COL_FULL, i]) + int(sponge[SP.COL_FINAL, i])]
+    assert len(sending) >= 5
+    return sponge, keccak, logic, sending
+
+
+def test_the_sponge_and_keccak_f_tables_are_read_as_the_header_lists_them(bpg):
+    """sponge port 0 (AIR 6) looking into Keccak-f (AIR 1): 2^5 rows hold one whole permutation, rows 0 .. 23; the tuple of
+    one sponge row is written over its input limbs (row 0, read 23 rows up) and its output limbs (row 23), with g set on
+    row 23 -- that row balances, every other sending sponge row does not.  (The overwritten Keccak-f table breaks its own
+    AIR: table 1's report.)"""
+    sponge, keccak, logic, sending = sponge_keccak_logic(bpg)
+    r = sending[1]
+    _, tup = model.builtin_ports(6, sponge[:, r:r + 1])[0][0]
+    keccak[KF.COL_A:KF.COL_A + 50, 0] = tup[:50]
+    keccak[KF.COL_APPP:KF.COL_APPP + 2, 23], keccak[KF.COL_APP + 2:KF.COL_APP + 50, 23] = tup[50:52], tup[52:]
+    keccak[KF.COL_FILTER, 23] = 1
+    members = [member(bpg, None, sponge, air_id=6), member(bpg, None, keccak, air_id=1), member(bpg, None, logic, air_id=2)]
+    got, want = checked(bpg, members, SPONGE_LINKS)
+    assert not got.ok and got.tables[0].ok and not got.tables[1].ok
+    assert want[0]["n_looking"] == len(sending) and want[0]["n_looked"] == 1 and 1 <= want[0]["n_unbalanced"] <= len(sending) - 1
+    assert got.links[0].first_looking_row == sending[0] and got.links[0].first_looked_row == -1
+    assert want[1]["n_looking"] == 5 * len(sending) and want[1]["n_looked"] == 0
+
+
+def test_the_sponge_and_logic_tables_are_read_as_the_header_lists_them(bpg):
+    """sponge ports 1 .. 5 (AIR 6) looking into logic (AIR 2): the five XORs of the first four sending sponge rows are
+    written over logic rows 0 .. 19 (row 5k + m: limb group m of the k-th of them), then one result limb of logic row 0 is
+    flipped: limb group 0 of the first sending row.  Those twenty tuples less one balance, nothing else does, and the
+    first unmatched looking row is that row at end 0, the flipped limb's group.  The end alone does not show that the flip
+    was seen -- the uncovered rows are unmatched at end 0 too, and a flip in another group would hide behind them: the
+    smallest (end, row) is at end 0 either way -- the ROW does (without the flip it is the fifth sending row, the looked
+    row 2), and so does the comparison with the model, field for field."""
+    sponge, keccak, logic, sending = sponge_keccak_logic(bpg)
+    ports = model.builtin_ports(6, sponge)
+    for k, i in enumerate(sending[:4]):
+        for m in range(5):
+            _, tup = ports[1 + m][i]
+            row = 5 * k + m
+            logic[LG.COL_OP:LG.COL_OP + 3, row] = tup[:3]
+            for j in range(8):
+                logic[LG.COL_IN0 + 32 * j:LG.COL_IN0 + 32 * j + 32, row] = [(tup[3 + j] >> z) & 1 for z in range(32)]
+                logic[LG.COL_IN1 + 32 * j:LG.COL_IN1 + 32 * j + 32, row] = [(tup[11 + j] >> z) & 1 for z in range(32)]
+            logic[LG.COL_RES:LG.COL_RES + 8, row] = tup[19:]
+            logic[LG.COL_FILTER, row] = 1
+    logic[LG.COL_RES + 1, 0] ^= np.uint64(0x40)
+    members = [member(bpg, None, sponge, air_id=6), member(bpg, None, keccak, air_id=1), member(bpg, None, logic, air_id=2)]
+    got, want = checked(bpg, members, SPONGE_LINKS)
+    assert not got.ok and got.tables[0].ok
+    assert want[1]["n_looking"] == 5 * len(sending) and want[1]["n_looked"] == 20
+    assert 2 <= want[1]["n_unbalanced"] <= 5 * len(sending) - 19 + 1      # at most: every uncovered tuple, the flipped one on both sides
+    lk = got.links[1]
+    assert (lk.first_looking_end, lk.first_looking_row, lk.first_looked_row) == (0, sending[0], 0) and lk.bad_filter_end == -1
 
 
 # ---------------------------------------------------------------------------------------------- 7. seeded differential run

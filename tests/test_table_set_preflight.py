@@ -185,7 +185,9 @@ def test_set_check_kernels_have_no_scratch_and_no_spill(tmp_path):
 def test_set_check_kernels_have_no_carry_mask_hazard(tmp_path):
     from test_build import device_assembly, scan_carry_mask_hazards
     bad, n = scan_carry_mask_hazards(device_assembly("set_check.hip", tmp_path))
-    assert n > 1000 and not bad, bad[:10]
+    # n: the scan saw the kernels' field arithmetic (the floor of tests/test_air_program.py's scan; it was 1000 while a
+    # built-in port's term was inlined three times per key kernel, with an inversion: one pass over the tuple is less code)
+    assert n > 100 and not bad, bad[:10]
 
 
 def test_set_check_kernels_have_no_dpp_read_of_a_fresh_asm_result(tmp_path):

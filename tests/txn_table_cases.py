@@ -174,8 +174,8 @@ def txn_proof(pg, st, case, words=None):
     return _call(pg, st, "bp_generate_txn_proof_witness", case, words, 1)
 
 
-def preflight(pg, st, case, words=None):
-    """(status, message) of bp_check_txn_witness"""
+def preflight_report(pg, st, case, words=None):
+    """(status, message, the pg.WitnessReport) of bp_check_txn_witness"""
     import ctypes as C
     import struct
     L = pg._bind()
@@ -185,4 +185,9 @@ def preflight(pg, st, case, words=None):
     rep = pg.WitnessReport()
     rc = L.bp_check_txn_witness(st._h, ir, len(ir), C.byref(w) if w is not None else None, C.byref(rep))
     del keep
-    return rc, L.bp_last_error().decode() if rc else ""
+    return rc, L.bp_last_error().decode() if rc else "", rep
+
+
+def preflight(pg, st, case, words=None):
+    """(status, message) of bp_check_txn_witness"""
+    return preflight_report(pg, st, case, words)[:2]

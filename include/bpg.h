@@ -529,6 +529,29 @@ int bp_keccak_sponge_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log
  * 0xFFFEF, out of column 15 of (2^256 - 1)^2, so bit 20 of every carry is zero): n = 2^log_n rows x 1217 columns, column-major.
  * d_inputs: [n][9] = is_mul (bit 0 of the word; 0 = a padding row), the four 64-bit words of x and of y; or NULL to draw them from `seed`. */
 int bp_arithmetic_mul_trace(const uint64_t* d_inputs, uint64_t seed, uint32_t log_n, uint64_t* d_trace_out, void* stream);
+/* Witness of the DIVISION table: DIV and MOD on 256-bit words, one operation per row.  The table has no built-in air_id:
+ * its AIR is a constraint program shipped with the Python package (proof_protocol_decoder_amd/arithmetic_div.py, which
+ * registers it with bp_air_register; AIRS.md section 2, "Division (a shipped program)", lists the columns).  Every row
+ * proves: there are q, r in [0, 2^256) with q y + r = x OVER THE INTEGERS (no wrap modulo 2^256); r < y unless y = 0; res = 0
+ * when y = 0 (the EVM's x / 0 = x % 0 = 0), else q under is_div and r under is_mod; at most one flag is set, a row with
+ * neither is a padding row (res = 0), and the filter g of the table's one product port, which exposes (is_div, is_mod, the
+ * sixteen 16-bit limbs of x, of y, of res), may be 1 only on a row with a flag.
+ * n = 2^log_n rows (log_n 4 .. 26, as bp_arithmetic_mul_trace) x 1650 columns, column-major.  d_inputs: [n][9] = word 0:
+ * the operation in its low byte (1 div, 2 mod, anything else a padding row, whose other words are ignored) | exposed << 8
+ * (bit 8: the row's g; bits 9 .. 63 are ignored); then the four 64-bit words of x and of y, least significant first.  Any
+ * u64 is accepted and every 256-bit operand is a valid one: this table has no input a verifier must reject.  There is no
+ * seeded draw: d_inputs == NULL is BP_ERR_INVALID_INPUT.
+ * Carries: product column k (16-bit limbs) is sum_{i+j=k} q_i y_j + r_k + c_{k-1} = x_k + 2^16 c_k.  q y <= x < 2^256 lets
+ * q and y have at most 17 limbs between them, so a column holds at most 8 products that are not zero and c_k <
+ * (8 (2^16 - 1)^2 + 2^16 - 1) / (2^16 - 1) = 8 (2^16 - 1) + 1 < 2^19: 19 bits a carry, all of them needed (q = y =
+ * 2^128 - 1, r = y - 1 reaches 0x7FFF7 out of column 7).  Only c_0 .. c_14 are columns: c_15 = floor((q y + r) / 2^256) = 0, and columns 16 .. 30 are
+ * the one constraint sum_{i+j>=16} q_i y_j = 0 (a sum of non-negative integers below 2^39). */
+int bp_arithmetic_div_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* d_trace_out, void* stream);
+/* The column map bp_arithmetic_div_trace stores by, 18 words (n_words: the room in `out`, at least 18): n_cols, then the
+ * first column of is_div, is_mod, g, z, inv, the x / y / res / q limbs, the x / y / q / r / d bits, the carry bits, the
+ * bits per carry, the first column of the r + d + 1 carry bits.  No device is needed.  The program in arithmetic_div.py
+ * states the same map a second time; its register() compares the two and refuses to go on when they differ. */
+int bp_arithmetic_div_layout(uint32_t* out, size_t n_words);
 
 /* AIR 8 (plonk): the 85 preprocessed constant columns of the fixed circuit (selectors, gate constants drawn from `seed`,
  * the Poseidon-row selector, the 80 sigmas of its copy permutation), n = 2^log_n rows, column-major, for a circuit that

@@ -210,6 +210,21 @@ def arithmetic_mul_trace(log_n, seed=0, inputs=None, device="cuda"):
     return air_trace(7, log_n, seed, inputs, device)
 
 
+def arithmetic_div_trace(log_n, inputs, device="cuda"):
+    """bp_arithmetic_div_trace: the witness [1650, 2^log_n] of the division table (arithmetic_div.py: a shipped program,
+    no built-in air_id); inputs [2^log_n, 9] int64 on the device (op 1 div / 2 mod / else padding | exposed << 8, the four
+    words of x, of y: arithmetic_div.pack_inputs).  There is no seeded draw: inputs=None is refused by the library."""
+    from .arithmetic_div import N_COLS
+    if inputs is not None:
+        _require_cuda(inputs)
+        if tuple(inputs.shape) != (1 << log_n, 9):
+            raise ValueError("arithmetic_div_trace: inputs are [%d, 9]: got %s" % (1 << log_n, tuple(inputs.shape)))
+        device = inputs.device
+    out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=device)
+    check(lib().bp_arithmetic_div_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
+    return out
+
+
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""

@@ -186,11 +186,22 @@ void bp_tune_rec_riders(int on);
  * A thread that takes n transactions leases n provers whose arenas are neighbours in device memory -- fewer when fewer
  * neighbours are idle at that moment, never waiting for them -- and proves table t of all its transactions as lock-step
  * batches wherever their shapes agree, t = 0..6, every transaction on its own transcript; the recursion chains and the
- * root follow, one transaction after the other.  bp_config.arena_bytes remains the memory of ONE transaction: a group
+ * roots follow (bp_tune_rec_group).  bp_config.arena_bytes remains the memory of ONE transaction: a group
  * uses the arenas of the provers it leases, and nothing that is provable alone fails because it was grouped (a batch
  * that would pass a limit is split).  Read once per call.  Results are identical, byte for byte.  (Not listed by
  * bp_debug_tune_state; bp_tune_reset puts it back.) */
 void bp_tune_txn_group(int n);
+/* How a group's recursion follows its table proofs: 0 (default) = level k of the seven chains of ALL the transactions the
+ * lease granted is one lock-step batch -- 7 g proofs on 7 g transcripts, and the riders that fit, 24 at most; a batch
+ * that would pass a limit (24 proofs, 672 query indices, the mailbox) is split, never failed --, then level k + 1, then
+ * each transaction's root; 1 = one transaction's recursion after the other (batches of seven and a rider: the schedule
+ * before this knob, kept for A/B runs).  A lone transaction is the same either way.  Read once per call.  Results are
+ * identical, byte for byte.  (Not listed by bp_debug_tune_state; bp_tune_reset puts it back.) */
+void bp_tune_rec_group(int mode);
+/* Host only: out[b] (b < n) = how many lock-step batches of exactly b recursion-shaped proofs this process has proved
+ * since the last reset (sizes beyond n - 1 are not reported; 25 words hold every size); reset != 0 clears the counters
+ * after reading them.  out may be null when n is 0 (reset only). */
+int bp_debug_rec_batch_histogram(uint64_t* out, uint32_t n, int reset);
 /* The witness of a recursion circuit's Poseidon rows (the sponge over its public-input list, its children's Merkle paths,
  * the sponges over their opened rows: independent pieces) is made on the host; a prover that is alone on the device makes
  * the pieces of a lock-step batch on up to n threads (default 7; 1 = on the prover's own thread).  Results are identical. */

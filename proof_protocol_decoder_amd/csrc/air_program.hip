@@ -48,10 +48,11 @@ using bpg::progdev::lds_regs_of_lane;
 // PORTS: the program has lookup ports; without them the kernel is the one it was before ports existed.
 // LOG: one of them is a log port; the kinds (n_ports words) follow the port units' offsets in the image.
 template <bool PORTS, bool LOG = false>
-__global__ void __launch_bounds__(256) quotient_program_kernel(bpg::BatchOf<bpg::QuotArgs> batch, const uint64_t* __restrict__ image,
+__global__ void __launch_bounds__(256) quotient_program_kernel(bpg::ArgPtr<bpg::QuotArgs> args, const uint64_t* __restrict__ image,
                                                                uint32_t n_code) {
+  BPG_ARG_BATCH(bpg::QuotArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::QuotArgs& q = batch.a[blockIdx.z];
+  const bpg::QuotArgs& q = batch[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
@@ -124,8 +125,9 @@ __global__ void __launch_bounds__(256) air_check_program_kernel(bpg::CheckArgs a
 
 // beta_c^j, j < 128, c < 2, behind the per-coset words of every proof's alpha-power table.  One workgroup of 256 lanes
 // per proof of the batch.
-__global__ void __launch_bounds__(256) beta_table_kernel(bpg::BatchOf<bpg::QuotArgs> batch) {
-  const bpg::QuotArgs& q = batch.a[blockIdx.x];
+__global__ void __launch_bounds__(256) beta_table_kernel(bpg::ArgPtr<bpg::QuotArgs> args) {
+  BPG_ARG_BATCH(bpg::QuotArgs, args);
+  const bpg::QuotArgs& q = batch[blockIdx.x];
   const uint32_t t = threadIdx.x;
   const_cast<uint64_t*>(q.apow)[2 * (size_t)q.n_constraints + 48 + t] = gl::pow(q.ctl.v[t >> 7 ? 2 : 0], t & (prog::MAX_TUPLE - 1));
 }
@@ -211,22 +213,21 @@ int program_of(uint32_t air_id, uint32_t n_units, std::shared_ptr<const prog::Pr
 namespace bpg {
 
 // The evaluation launch of launch_quotient (stark_kernels.hip) for a registered id: same grid, same argument blocks.
-int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer& kt, hipStream_t st) {
-  const QuotArgs& q = qb.a[0];
+int launch_quotient_program(const QuotArgs* qb, const QuotArgs& q, dim3 grid, KernelTimer& kt, hipStream_t st) {
   std::shared_ptr<const prog::Program> p;
   const uint64_t* d_image = nullptr;
   if (int rc = program_of(q.air_id, q.n_air_units, &p, &d_image)) return rc;
   if (q.n_ports != p->n_ports) return bpg::fail(BP_ERR_INVALID_INPUT, "AIR program 0x%08x: the launch was sized for another program", q.air_id);
-  if (p->log_ports()) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(quotient_program_kernel<true, true>), grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
-  else if (q.n_ports) BPG_LAUNCH_TIMED(kt, quotient_program_kernel<true>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
-  else BPG_LAUNCH_TIMED(kt, quotient_program_kernel<false>, grid, 256, p->n_regs * 256 * 8, st, qb, d_image, p->n_code);
+  if (p->log_ports()) BPG_LAUNCH_TIMED(kt, HIP_KERNEL_NAME(quotient_program_kernel<true, true>), grid, 256, p->n_regs * 256 * 8, st, arg_ptr(qb), d_image, p->n_code);
+  else if (q.n_ports) BPG_LAUNCH_TIMED(kt, quotient_program_kernel<true>, grid, 256, p->n_regs * 256 * 8, st, arg_ptr(qb), d_image, p->n_code);
+  else BPG_LAUNCH_TIMED(kt, quotient_program_kernel<false>, grid, 256, p->n_regs * 256 * 8, st, arg_ptr(qb), d_image, p->n_code);
   return BP_OK;
 }
 
 // The beta powers of every proof of a batch, beside its alpha powers: launch_quotient issues this with the alpha tables,
 // before the evaluation launch and its timer.
-int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t st) {
-  beta_table_kernel<<<batch, 256, 0, st>>>(qb);
+int launch_beta_tables(const QuotArgs* qb, uint32_t batch, hipStream_t st) {
+  beta_table_kernel<<<batch, 256, 0, st>>>(arg_ptr(qb));
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

@@ -708,7 +708,7 @@ int merkle_upper_levels(uint64_t* d_digests, uint32_t log_leaves, uint32_t cap_h
   uint64_t* lvl = d_digests;
   uint32_t l = log_leaves;
   if (mirrored) *mirrored = false;
-  if (batch == 0 || batch > MAX_BATCH) return fail(BP_ERR_INVALID_INPUT, "merkle: batch of %u trees", batch);
+  if (batch == 0 || batch > MAX_LOCKSTEP) return fail(BP_ERR_INVALID_INPUT, "merkle: batch of %u trees", batch);
   // `batch` trees of this shape are in every launch (grid.z): the choice of kernel form goes by the work of the
   // whole launch, the fusing limits by one tree (a workgroup never spans two trees)
   while (l > cap_height) {
@@ -869,7 +869,7 @@ int merkle_commit_cols(const uint64_t* d_lde, uint64_t lde_stride, uint32_t n_co
     return fail(BP_ERR_INVALID_INPUT,
                 "bp_merkle_commit: bad shape (log_n=%u rate_bits=%u cap_height=%u n_cols=%u stride=%llu)", log_n,
                 rate_bits, cap_height, n_cols, (unsigned long long)lde_stride);
-  if (batch == 0 || batch > MAX_BATCH) return fail(BP_ERR_INVALID_INPUT, "merkle: batch of %u trees", batch);
+  if (batch == 0 || batch > MAX_LOCKSTEP) return fail(BP_ERR_INVALID_INPUT, "merkle: batch of %u trees", batch);
   uint64_t rows = (uint64_t)1 << log_leaves;
   {
     // integer-ALU-bound family: the "bytes" slot of the profiler carries permutations

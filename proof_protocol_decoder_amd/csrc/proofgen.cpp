@@ -227,31 +227,58 @@ uint32_t batch_cap(const StarkCfg& rc) {
   return std::min<uint32_t>(std::min<uint32_t>(MAX_BATCH, std::max<uint32_t>(1, tune().rec_batch.load(std::memory_order_relaxed))),
                             std::max<uint32_t>(1, MAX_BATCH_QUERIES / std::max<uint32_t>(1, rc.num_queries)));
 }
+// What the mailbox holds of a lock-step batch of shape c: every proof's caps, its openings, its last FRI layer (the
+// query openings fall back to the arena by themselves).
+size_t mailbox_cap(const StarkCfg& c, size_t pinned_words) {
+  const ProofLayout L = proof_layout(c);
+  const size_t open_words = ((size_t)c.n_const + c.n_cols + 2 * (size_t)L.n_aux + L.n_quot) * 4;
+  const size_t last_layer = (size_t)2 * ((size_t)L.final_len << c.rate_bits);
+  const size_t per_proof = std::max(std::max(open_words, last_layer), L.cap_words);
+  return pinned_words / std::max<size_t>(1, per_proof);
+}
+// ... and one sub-batch of rec_prove_batch for a caller that brings the levels of n_txn transactions: n_txn times what
+// one transaction's level takes (batch_cap: the arena of a transaction is sized for that, and a group holds n_txn of
+// them), within what a launch accepts -- MAX_LOCKSTEP blocks, MAX_BATCH_QUERIES indices -- and the mailbox holds.
+uint32_t lockstep_cap(const StarkCfg& rc, size_t pinned_words, uint32_t n_txn) {
+  size_t cap = std::min<size_t>(MAX_LOCKSTEP, MAX_BATCH_QUERIES / std::max<uint32_t>(1, rc.num_queries));
+  cap = std::min(cap, mailbox_cap(rc, pinned_words));
+  cap = std::min(cap, (size_t)batch_cap(rc) * std::max<uint32_t>(1, n_txn));
+  return (uint32_t)std::max<size_t>(1, cap);
+}
+// rec_prove_batch's sub-batches by size (bp_debug_rec_batch_histogram)
+std::atomic<uint64_t>* rec_batch_sizes() {
+  static std::atomic<uint64_t> n[MAX_LOCKSTEP + 1];
+  return n;
+}
 // Recursion-shaped proofs; transcript of each = circuit digest, hash of the public inputs, trace cap.  `n` proofs of
 // the state's one recursion shape are proved in lock-step, up to Tune::rec_batch at a time (stark_prove_batch: every
 // launch and every host wait is shared; circuits, public inputs and transcripts are each proof's own).
 // paths (nullable): per proof the witness of the Merkle paths its circuit walks (Circuit::lay.n_paths of them)
 // first_leaf (nullable, 4 words per proof): the digest of the trace leaf each proof's first query opens
+// n_txn: the transactions whose levels the caller brings (a group's recursion: lockstep_cap) -- a batch that would pass
+// a limit is split, never failed
 int rec_prove_batch(Worker& w, const StarkCfg& rc, uint32_t n, const Circuit* const* circ, const std::vector<uint64_t>* pi,
-                    std::vector<uint64_t>* proofs, const std::vector<PathWitness>* paths = nullptr, uint64_t* first_leaf = nullptr) {
-  const uint32_t cap = batch_cap(rc);
+                    std::vector<uint64_t>* proofs, const std::vector<PathWitness>* paths = nullptr, uint64_t* first_leaf = nullptr,
+                    uint32_t n_txn = 1) {
+  const uint32_t cap = lockstep_cap(rc, w.pinned_words, n_txn);
   const uint64_t N = (uint64_t)1 << rc.log_n;
   for (uint32_t first = 0; first < n; first += cap) {
     const uint32_t B = std::min(cap, n - first);
+    rec_batch_sizes()[B].fetch_add(1, std::memory_order_relaxed);
     const size_t mark = w.arena.mark();
     uint64_t* d_trace = w.arena.alloc_words((size_t)B * rc.n_cols * N);
     if (!d_trace) return fail(BP_ERR_DEVICE, "device arena exhausted (%zu MiB)", w.arena.capacity() >> 20);
-    Challenger ch[MAX_BATCH];
-    SynthTraceArgs sa[MAX_BATCH];
-    PlonkTraceArgs pa[MAX_BATCH];
-    Ctl ctl[MAX_BATCH];
-    const uint64_t* d_tv[MAX_BATCH];
-    const Committed* consts[MAX_BATCH];
+    Challenger ch[MAX_LOCKSTEP];
+    SynthTraceArgs sa[MAX_LOCKSTEP];
+    PlonkTraceArgs pa[MAX_LOCKSTEP];
+    Ctl ctl[MAX_LOCKSTEP];
+    const uint64_t* d_tv[MAX_LOCKSTEP];
+    const Committed* consts[MAX_LOCKSTEP];
     // The witness of every proof's Poseidon rows is made on the host (prover.hpp): per proof the sponge over its list, per
     // path the Merkle rows and -- where the circuit hashes its leaves -- the sponge over the opened row.  The pieces are
     // independent; a prover that is alone on the device (a lone transaction: this is its critical path) makes them on up
     // to seven threads.
-    uint64_t pi_hashes[MAX_BATCH][4];
+    uint64_t pi_hashes[MAX_LOCKSTEP][4];
     struct Job {
       uint32_t b, kind, p;  // kind 0: the list's rows, 1: path p's Merkle rows, 2: path p's leaf rows
     };
@@ -340,7 +367,7 @@ int rec_prove_batch(Worker& w, const StarkCfg& rc, uint32_t n, const Circuit* co
     int r = rc.air_id == air::PLONK ? launch_plonk_trace(pa, B, rc.log_n, w.stream)
                                     : launch_synth_trace(sa, B, rc.log_n, rc.n_cols, rc.n_const, rc.deg_pow, w.stream);
     if (r) return r;
-    Committed trace[MAX_BATCH];
+    Committed trace[MAX_LOCKSTEP];
     if ((r = commit_batch(w, d_trace, rc.n_cols, B, rc.log_n, rc.rate_bits, rc.cap_height, false, trace))) return r;
     for (uint32_t b = 0; b < B; b++) {
       ch[b].observe(trace[b].cap.data(), trace[b].cap.size());
@@ -786,90 +813,104 @@ static int emit_tables(const TableProofs& tp, uint8_t** out, size_t* out_len) {
   return BP_OK;
 }
 
-// What follows the table proofs of a transaction: the recursion chains over them and the root proof (or, with a pool,
-// the root posted as the job of `node`).  The traces are dead: the arena goes back to `arena_mark`.
-static int txn_recursion(const bp_state* s, Worker& w, size_t arena_mark, TableProofs& tp, uint8_t** out, size_t* out_len,
-                         RecPool* pool, uint32_t node) {
+// What follows the table proofs of the g transactions of a group (g = 1: a lone transaction): the recursion chains over
+// them and each transaction's root proof (or, with a pool, the root posted as the job of nodes[i]).  The traces are
+// dead: the arena goes back to `arena_mark`.
+static int group_recursion(const bp_state* s, Worker& w, size_t arena_mark, TableProofs* const* tps, uint32_t g, uint8_t** outs,
+                           size_t* out_lens, RecPool* pool, const uint32_t* nodes) {
   const bp_config& cfg = s->cfg;
-  const StarkCfg* tcfg = tp.tcfg;
-  const std::vector<uint64_t>& pv = tp.pv;
+  constexpr uint32_t T = BP_NUM_TABLES;
+  const uint32_t n_chains = T * g;
   int r;
   // per child of a recursion circuit: its digest, and the Merkle path of its first trace opening (leaf digest, cap entry:
-  // words of the parent's public-input list; position and siblings: witness of the parent's Merkle rows)
-  uint64_t digest[BP_NUM_TABLES][4], leaf_cap[BP_NUM_TABLES][8];
-  std::vector<PathWitness> child_path[BP_NUM_TABLES];
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    proof_digest(tcfg[t], tp.proof[t].data(), digest[t]);
-    child_path[t].resize(1);
-    first_query_trace_path(tcfg[t], tp.proof[t].data(), leaf_cap[t], leaf_cap[t] + 4, &child_path[t][0], tp.first_leaf[t]);
-    std::vector<uint64_t>().swap(tp.proof[t]);
+  // words of the parent's public-input list; position and siblings: witness of the parent's Merkle rows).  Slot T i + t:
+  // chain t of transaction i.
+  struct Child {
+    uint64_t digest[4], leaf_cap[8];
+  };
+  std::vector<Child> child(n_chains);
+  std::vector<std::vector<PathWitness>> slot_path(n_chains);
+  for (uint32_t i = 0; i < g; i++) {
+    TableProofs& tp = *tps[i];
+    for (uint32_t t = 0; t < T; t++) {
+      Child& c = child[T * i + t];
+      proof_digest(tp.tcfg[t], tp.proof[t].data(), c.digest);
+      slot_path[T * i + t].resize(1);
+      first_query_trace_path(tp.tcfg[t], tp.proof[t].data(), c.leaf_cap, c.leaf_cap + 4, &slot_path[T * i + t][0], tp.first_leaf[t]);
+      std::vector<uint64_t>().swap(tp.proof[t]);
+    }
   }
-  std::vector<uint64_t> proof;
   if ((r = w.wait())) return r;
   w.arena.release(arena_mark);  // traces are dead; the chains below only need digests
-  // per-table recursion-shaped chains (wrap + shrinks).  The seven chains do not depend on each other and their
-  // proofs have one shape: level k of all seven is ONE batch proved in lock-step (rec_prove_batch) -- seven
-  // transcripts stepped together, every kernel launch and host wait shared --, then level k + 1.  (Until round 4 each
-  // chain was its own sequence of 6..16-column launches: 88 of a transaction's 118 LDE launches and most of its
-  // 1,620 kernel launches.)  Level 0 is proved by the circuit of the table's height (its child is the table's STARK
-  // proof), the levels above by the table's shrink circuit.
+  // per-table recursion-shaped chains (wrap + shrinks).  The chains do not depend on each other and their proofs have
+  // one shape: level k of all seven chains of all g transactions is ONE batch proved in lock-step (rec_prove_batch) --
+  // 7 g transcripts stepped together, every kernel launch and host wait shared, every grid g times as large --, then
+  // level k + 1.  (Until round 4 each chain was its own sequence of 6..16-column launches: 88 of a transaction's 118 LDE
+  // launches and most of its 1,620 kernel launches; until Tune::rec_group each transaction of a group ran its levels
+  // alone, the group's other provers idle.)  Level 0 is proved by the circuit of the table's height (its child is the
+  // table's STARK proof), the levels above by the table's shrink circuit.
   // With a pool (a shard's scheduler, gi.cpp) each of these batches also carries ready jobs of the pool -- other
-  // transactions' root proofs, the tree's aggregation proofs -- in the slots the seven chains leave free: one more
-  // circuit, list and transcript in launches that are made anyway.  A rider's container is handed back the moment its
-  // batch is done; a state whose batches hold seven proofs or fewer carries none.
+  // transactions' root proofs, the tree's aggregation proofs -- in the slots the chains leave free: one more circuit,
+  // list and transcript in launches that are made anyway.  A rider's container is handed back the moment its batch is
+  // done; a state whose batches have no room beyond the chains carries none.
   {
-    const Circuit* circ[MAX_BATCH];
-    std::vector<uint64_t> pis[MAX_BATCH], chain_proof[MAX_BATCH];
-    std::vector<PathWitness> slot_path[MAX_BATCH];
-    for (int t = 0; t < BP_NUM_TABLES; t++) slot_path[t] = std::move(child_path[t]);
-    const uint32_t cap = batch_cap(s->rec_cfg);
+    const uint32_t cap = lockstep_cap(s->rec_cfg, w.pinned_words, g);
+    std::vector<const Circuit*> circ(n_chains);
+    std::vector<std::vector<uint64_t>> pis(n_chains), chain_proof;
     for (uint32_t depth = 0; depth < cfg.shrink_depth; depth++) {
       if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted in the recursion chains (level %u)", depth);
-      for (int t = 0; t < BP_NUM_TABLES; t++) {
-        circ[t] = depth == 0 ? &s->table_circuits[s->table_offset[t] + (tcfg[t].log_n - cfg.table_log_lo[t])] : &s->shrink_circuits[t];
-        pis[t] = {digest[t][0], digest[t][1], digest[t][2], digest[t][3], (uint64_t)t, depth};
-        pis[t].insert(pis[t].end(), leaf_cap[t], leaf_cap[t] + 8);
-      }
+      for (uint32_t i = 0; i < g; i++)
+        for (uint32_t t = 0; t < T; t++) {
+          const Child& c = child[T * i + t];
+          circ[T * i + t] = depth == 0 ? &s->table_circuits[s->table_offset[t] + (tps[i]->tcfg[t].log_n - cfg.table_log_lo[t])] : &s->shrink_circuits[t];
+          pis[T * i + t] = {c.digest[0], c.digest[1], c.digest[2], c.digest[3], (uint64_t)t, depth};
+          pis[T * i + t].insert(pis[T * i + t].end(), c.leaf_cap, c.leaf_cap + 8);
+        }
       std::vector<std::unique_ptr<RecJob>> riders;
-      if (pool && cap > BP_NUM_TABLES) pool->take(cap - BP_NUM_TABLES, &riders);
+      if (pool && cap > n_chains) pool->take(cap - n_chains, &riders);
+      const uint32_t n = n_chains + (uint32_t)riders.size();
+      circ.resize(n); pis.resize(n); slot_path.resize(n);
       for (size_t k = 0; k < riders.size(); k++) {
-        circ[BP_NUM_TABLES + k] = static_cast<const Circuit*>(riders[k]->circuit);
-        pis[BP_NUM_TABLES + k] = riders[k]->pi;
-        slot_path[BP_NUM_TABLES + k] = std::move(riders[k]->paths);
+        circ[n_chains + k] = static_cast<const Circuit*>(riders[k]->circuit);
+        pis[n_chains + k] = riders[k]->pi;
+        slot_path[n_chains + k] = std::move(riders[k]->paths);
       }
-      uint64_t first_leaf[MAX_BATCH][4];
-      if ((r = rec_prove_batch(w, s->rec_cfg, BP_NUM_TABLES + (uint32_t)riders.size(), circ, pis, chain_proof, slot_path, &first_leaf[0][0]))) return r;
+      chain_proof.assign(n, {});
+      std::vector<uint64_t> first_leaf(4 * (size_t)n);
+      if ((r = rec_prove_batch(w, s->rec_cfg, n, circ.data(), pis.data(), chain_proof.data(), slot_path.data(), first_leaf.data(), g))) return r;
       for (size_t k = 0; k < riders.size(); k++)
-        if ((r = finish_job(s, *riders[k], chain_proof[BP_NUM_TABLES + k], pool))) return r;
-      for (int t = 0; t < BP_NUM_TABLES; t++) {
-        proof_digest(s->rec_cfg, chain_proof[t].data(), digest[t]);
-        first_query_trace_path(s->rec_cfg, chain_proof[t].data(), leaf_cap[t], leaf_cap[t] + 4, &slot_path[t][0], first_leaf[t]);
+        if ((r = finish_job(s, *riders[k], chain_proof[n_chains + k], pool))) return r;
+      for (uint32_t k = 0; k < n_chains; k++) {
+        proof_digest(s->rec_cfg, chain_proof[k].data(), child[k].digest);
+        first_query_trace_path(s->rec_cfg, chain_proof[k].data(), child[k].leaf_cap, child[k].leaf_cap + 4, &slot_path[k][0], &first_leaf[4 * k]);
       }
     }
-    for (int t = 0; t < BP_NUM_TABLES; t++) child_path[t] = std::move(slot_path[t]);
   }
-  // root proof: the seven chains' digests, their seven (leaf digest, cap entry) pairs, the public values
-  std::vector<uint64_t> pi;
-  std::vector<PathWitness> root_paths(BP_NUM_TABLES);
-  for (int t = 0; t < BP_NUM_TABLES; t++) pi.insert(pi.end(), digest[t], digest[t] + 4);
-  for (int t = 0; t < BP_NUM_TABLES; t++) {
-    pi.insert(pi.end(), leaf_cap[t], leaf_cap[t] + 8);
-    root_paths[t] = std::move(child_path[t][0]);
+  // root proofs: a transaction's seven chain digests, their seven (leaf digest, cap entry) pairs, its public values
+  for (uint32_t i = 0; i < g; i++) {
+    std::vector<uint64_t> pi;
+    std::vector<PathWitness> root_paths(T);
+    for (uint32_t t = 0; t < T; t++) pi.insert(pi.end(), child[T * i + t].digest, child[T * i + t].digest + 4);
+    for (uint32_t t = 0; t < T; t++) {
+      pi.insert(pi.end(), child[T * i + t].leaf_cap, child[T * i + t].leaf_cap + 8);
+      root_paths[t] = std::move(slot_path[T * i + t][0]);
+    }
+    pi.insert(pi.end(), tps[i]->pv.begin(), tps[i]->pv.end());
+    if (pool) {  // the root rides in another transaction's batch, or in a batch of the jobs that are left at the end
+      std::unique_ptr<RecJob> job(new RecJob());
+      job->node = nodes ? nodes[i] : 0;
+      job->kind = 0;
+      job->circuit = &s->special[0];
+      job->pi = std::move(pi);
+      job->paths = std::move(root_paths);
+      pool->post(std::move(job));
+      continue;
+    }
+    std::vector<uint64_t> proof;
+    if ((r = rec_prove(w, s->rec_cfg, s->special[0], pi, proof, &root_paths))) return r;
+    if ((r = emit_box(0, CIRCUIT_ROOT, pi, proof, &outs[i], &out_lens[i]))) return r;
+    remember_proof(s, outs[i], out_lens[i]);
   }
-  pi.insert(pi.end(), pv.begin(), pv.end());
-  if (pool) {  // the root rides in another transaction's batch, or in a batch of the jobs that are left at the end
-    std::unique_ptr<RecJob> job(new RecJob());
-    job->node = node;
-    job->kind = 0;
-    job->circuit = &s->special[0];
-    job->pi = std::move(pi);
-    job->paths = std::move(root_paths);
-    pool->post(std::move(job));
-    return BP_OK;
-  }
-  if ((r = rec_prove(w, s->rec_cfg, s->special[0], pi, proof, &root_paths))) return r;
-  if ((r = emit_box(0, CIRCUIT_ROOT, pi, proof, out, out_len))) return r;
-  remember_proof(s, *out, *out_len);
   return BP_OK;
 }
 
@@ -893,17 +934,11 @@ bool same_shape(const StarkCfg& a, const StarkCfg& b) {
          a.final_poly_bits == b.final_poly_bits && a.air_id == b.air_id;
 }
 // Table proofs of shape c one lock-step batch holds: every limit stark_prove_batch and commit_batch would refuse at,
-// taken up front so that a sub-batch is SPLIT and never failed -- MAX_BATCH, the query launches' index limit
-// (MAX_BATCH_QUERIES: 84 queries -> 3 proofs), and the mailbox (caps, openings, the last FRI layer; the query openings
-// fall back to the arena by themselves).  The kernels' argument blocks are BatchOf<...>, MAX_BATCH entries whatever the
-// batch: no limit of their own.
+// taken up front so that a sub-batch is SPLIT and never failed -- MAX_BATCH (a group holds eight transactions at
+// most), the query launches' index limit (MAX_BATCH_QUERIES: 84 queries -> 8 proofs), and the mailbox (mailbox_cap).
 uint32_t table_batch_cap(const StarkCfg& c, size_t pinned_words) {
-  const ProofLayout L = proof_layout(c);
-  const size_t open_words = ((size_t)c.n_const + c.n_cols + 2 * (size_t)L.n_aux + L.n_quot) * 4;
-  const size_t last_layer = (size_t)2 * ((size_t)L.final_len << c.rate_bits);
-  const size_t per_proof = std::max(std::max(open_words, last_layer), L.cap_words);
   size_t cap = std::min<size_t>(MAX_BATCH, MAX_BATCH_QUERIES / std::max<uint32_t>(1, c.num_queries));
-  cap = std::min(cap, pinned_words / std::max<size_t>(1, per_proof));
+  cap = std::min(cap, mailbox_cap(c, pinned_words));
   return (uint32_t)std::max<size_t>(1, cap);
 }
 
@@ -1065,8 +1100,8 @@ int prove_tables(const bp_state* s, Worker& w, const std::vector<Worker*>& stage
 
 // Up to n transactions on one lease -- a lone transaction is a group of one: as many as the lease grants (>= 1;
 // `granted` hears the number the moment the lease is held, so that a scheduler can hand the others on), their table
-// proofs in lock-step, then each transaction's recursion chains and root, one transaction after the other on the
-// lease's stream.  outs / out_lens per transaction (tables_only: the table-proof blobs); with a pool the roots are
+// proofs in lock-step, then the recursion chains of all of them level by level in lock-step and each transaction's root
+// (Tune::rec_group 1: each transaction's recursion and root, one transaction after the other), on the lease's stream.  outs / out_lens per transaction (tables_only: the table-proof blobs); with a pool the roots are
 // posted as the jobs of nodes[i] instead.  The first failing transaction's status and message are the call's.
 static int txn_proofs_impl(const bp_state* s, uint32_t n, const uint8_t* const* irs, size_t ir_len, const TxnWitness* const* wits,
                            const volatile int32_t* abort_flag, const volatile uint8_t* abort_flag_u8, bool tables_only, RecPool* pool,
@@ -1097,11 +1132,16 @@ static int txn_proofs_impl(const bp_state* s, uint32_t n, const uint8_t* const* 
   w.abort_flag_u8 = abort_flag_u8;
   if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted before start");
   if ((r = prove_tables(s, w, lease.ws, p.data(), g))) return r;
-  for (uint32_t i = 0; i < g; i++) {
-    if (tables_only) r = emit_tables(tx[i]->tp, &outs[i], &out_lens[i]);
-    else r = txn_recursion(s, w, lease.mark, tx[i]->tp, outs ? &outs[i] : nullptr, out_lens ? &out_lens[i] : nullptr, pool, nodes ? nodes[i] : 0);
-    if (r) return r;
+  if (tables_only) {
+    for (uint32_t i = 0; i < g; i++)
+      if ((r = emit_tables(tx[i]->tp, &outs[i], &out_lens[i]))) return r;
+    return BP_OK;
   }
+  std::vector<TableProofs*> tps;
+  for (uint32_t i = 0; i < g; i++) tps.push_back(&tx[i]->tp);
+  if (tune().rec_group.load(std::memory_order_relaxed) != 1) return group_recursion(s, w, lease.mark, tps.data(), g, outs, out_lens, pool, nodes);
+  for (uint32_t i = 0; i < g; i++)  // one transaction's recursion after the other
+    if ((r = group_recursion(s, w, lease.mark, &tps[i], 1, outs ? outs + i : nullptr, out_lens ? out_lens + i : nullptr, pool, nodes ? nodes + i : nullptr))) return r;
   return BP_OK;
 }
 // the calls that take one IR: a group of one
@@ -1114,6 +1154,18 @@ int bp_generate_txn_proof(const bp_state* s, const uint8_t* ir, size_t ir_len, c
   return txn_proof_of_one(s, ir, ir_len, nullptr, abort_flag, nullptr, false, out, out_len);
 }
 BPG_ABI_CATCH("bp_generate_txn_proof")
+// rec_prove_batch's sub-batches by the proofs they held (include/bpg.h)
+int bp_debug_rec_batch_histogram(uint64_t* out, uint32_t n, int reset) try {
+  if (!out && n) return fail(BP_ERR_INVALID_INPUT, "bp_debug_rec_batch_histogram: null argument");
+  std::atomic<uint64_t>* sizes = rec_batch_sizes();
+  for (uint32_t b = 0; b <= MAX_LOCKSTEP; b++) {
+    const uint64_t v = reset ? sizes[b].exchange(0) : sizes[b].load();
+    if (b < n) out[b] = v;
+  }
+  for (uint32_t b = MAX_LOCKSTEP + 1; b < n; b++) out[b] = 0;
+  return BP_OK;
+}
+BPG_ABI_CATCH("bp_debug_rec_batch_histogram")
 // The same call with the reference's own flag type: Option<Arc<AtomicBool>> (proof_gen.rs:42) is one byte,
 // `flag.as_ptr()` binds directly.
 int bp_generate_txn_proof_u8(const bp_state* s, const uint8_t* ir, size_t ir_len, const volatile uint8_t* abort_flag,

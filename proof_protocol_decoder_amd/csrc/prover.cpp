@@ -15,6 +15,8 @@
 #include <immintrin.h>
 #endif
 #include <memory>
+#include <mutex>
+#include <unordered_map>
 #include <thread>
 
 namespace bpg {
@@ -336,9 +338,16 @@ int Worker::init(int dev, size_t arena_bytes, void* slice) {
   pinned_words = (size_t)1 << 22;  // 32 MiB staging
   BPG_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned), pinned_words * 8, hipHostMallocDefault));
   BPG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&pinned_dev), pinned, 0));
-  BPG_HIP(hipHostMalloc(reinterpret_cast<void**>(&hash_rows), MAX_BATCH * HASH_ROWS_WORDS * 8, hipHostMallocDefault));
+  BPG_HIP(hipHostMalloc(reinterpret_cast<void**>(&hash_rows), MAX_LOCKSTEP * HASH_ROWS_WORDS * 8, hipHostMallocDefault));
   BPG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&hash_rows_dev), hash_rows, 0));
-  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d_pow_result), 8 * MAX_BATCH));
+  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d_pow_result), 8 * MAX_LOCKSTEP));
+  {
+    void* dev = nullptr;
+    BPG_HIP(hipHostMalloc(&args_mem, ARG_RING_BYTES, hipHostMallocDefault));
+    BPG_HIP(hipHostGetDevicePointer(&dev, args_mem, 0));
+    args.adopt(args_mem, dev, ARG_RING_BYTES);
+    arg_ring_register(stream, &args);
+  }
   // many prover threads share few host cores: wait on a blocking event (the thread sleeps) rather
   // than spin in hipStreamSynchronize
   BPG_HIP(hipEventCreateWithFlags(&sync_event, hipEventBlockingSync | hipEventDisableTiming));
@@ -346,6 +355,10 @@ int Worker::init(int dev, size_t arena_bytes, void* slice) {
 }
 void Worker::destroy() {
   if (stream) (void)hipStreamSynchronize(stream);
+  if (stream) arg_ring_unregister(stream);
+  args.forget();
+  if (args_mem) (void)hipHostFree(args_mem);
+  args_mem = nullptr;
   arena.destroy();
   if (pinned) (void)hipHostFree(pinned);
   if (hash_rows) (void)hipHostFree(hash_rows);
@@ -397,7 +410,103 @@ int Worker::wait_recorded() {
 }
 int Worker::wait() {
   BPG_HIP(hipEventRecord(sync_event, stream));
-  return wait_recorded();
+  TRY(wait_recorded());
+  args.rewind();  // every launch that read a block of the ring has completed
+  return BP_OK;
+}
+
+// ---- argument rings by stream ----
+// A worker registers its ring when it is made and takes it out when it is destroyed (bp_state_build / bp_state_free:
+// rare, under `mu`).  The launchers look a stream up on every batched launch, so the lookup takes no lock: each thread
+// keeps the streams it found last, valid while `generation` is what it was when they were found.
+namespace {
+constexpr int MAX_DEVICES = 16;
+struct SharedRing {  // the ring of one device's streams that belong to no worker: used under its `mu`
+  std::mutex mu;
+  ArgRing ring;
+  void* mem = nullptr;
+};
+struct ArgRings {
+  std::mutex mu;
+  std::unordered_map<hipStream_t, ArgRing*> of;
+  std::atomic<uint64_t> generation{1};
+  SharedRing shared[MAX_DEVICES];
+};
+ArgRings& arg_rings() {
+  static ArgRings* r = new ArgRings();  // never destroyed: pinned memory is not freed behind the runtime's back at exit
+  return *r;
+}
+struct FoundRings {  // per thread: its worker's stream and the lanes it borrowed
+  uint64_t generation = 0;
+  int n = 0;
+  hipStream_t st[4];
+  ArgRing* ring[4];
+};
+ArgRing* ring_of(hipStream_t st) {
+  thread_local FoundRings found;
+  ArgRings& r = arg_rings();
+  const uint64_t gen = r.generation.load(std::memory_order_acquire);
+  if (found.generation != gen) { found.generation = gen; found.n = 0; }
+  for (int k = 0; k < found.n; k++)
+    if (found.st[k] == st) return found.ring[k];
+  ArgRing* ring = nullptr;
+  bool current = true;
+  {
+    std::lock_guard<std::mutex> lk(r.mu);
+    current = r.generation.load(std::memory_order_relaxed) == gen;
+    auto it = r.of.find(st);
+    if (it != r.of.end()) ring = it->second;
+  }
+  if (ring && current) {  // found under another generation: right now, but not to be kept  // (a stream that is nobody's is looked up again each time: it may be registered later)
+    const int k = found.n < 4 ? found.n++ : 0;
+    found.st[k] = st;
+    found.ring[k] = ring;
+  }
+  return ring;
+}
+int arg_ring_status(ArgRing::Status s, size_t bytes, size_t cap) {
+  switch (s) {
+    case ArgRing::OK: return BP_OK;
+    case ArgRing::TOO_LARGE: return fail(BP_ERR_UNSUPPORTED, "argument blocks of %zu bytes do not fit the argument ring (%zu bytes)", bytes, cap);
+    case ArgRing::WAIT_FAILED: return fail(BP_ERR_DEVICE, "waiting for the stream of a full argument ring failed");
+    default: return fail(BP_ERR_DEVICE, "the stream's argument ring has no memory");
+  }
+}
+}  // namespace
+void arg_ring_register(hipStream_t st, ArgRing* ring) {
+  ArgRings& r = arg_rings();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.of[st] = ring;
+  r.generation.fetch_add(1, std::memory_order_release);
+}
+void arg_ring_unregister(hipStream_t st) {
+  ArgRings& r = arg_rings();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.of.erase(st);
+  r.generation.fetch_add(1, std::memory_order_release);
+}
+int arg_ring_put(hipStream_t st, const void* blocks, size_t bytes, const void** dev) {
+  if (ArgRing* own = ring_of(st))  // the thread that holds the worker (or the lane) is the only one that launches on its stream
+    return arg_ring_status(own->put(blocks, bytes, dev, [&] { return hipStreamSynchronize(st) == hipSuccess ? 0 : 1; }), bytes, own->capacity());
+  // A caller's own stream (the single-launch entries): the ring of the device the launch goes to.  Whichever of that
+  // device's streams its live blocks were launched on: once the device has drained, so have they.
+  int device = 0;
+  BPG_HIP(hipGetDevice(&device));
+  if (device < 0 || device >= MAX_DEVICES) return fail(BP_ERR_UNSUPPORTED, "device %d: argument rings are kept for devices 0..%d", device, MAX_DEVICES - 1);
+  SharedRing& sh = arg_rings().shared[device];
+  std::lock_guard<std::mutex> lk(sh.mu);
+  if (!sh.mem) {
+    void *m = nullptr, *d = nullptr;
+    BPG_HIP(hipHostMalloc(&m, ARG_RING_BYTES, hipHostMallocDefault));
+    const hipError_t e = hipHostGetDevicePointer(&d, m, 0);
+    if (e != hipSuccess) {
+      (void)hipHostFree(m);
+      return fail(BP_ERR_DEVICE, "hipHostGetDevicePointer failed for the argument ring: %s", hipGetErrorString(e));
+    }
+    sh.mem = m;
+    sh.ring.adopt(m, d, ARG_RING_BYTES);
+  }
+  return arg_ring_status(sh.ring.put(blocks, bytes, dev, [] { return hipDeviceSynchronize() == hipSuccess ? 0 : 1; }), bytes, sh.ring.capacity());
 }
 int Worker::d2h(uint64_t* host_dst, const uint64_t* dev_src, size_t words) {
   for (size_t off = 0; off < words; off += pinned_words) {
@@ -436,7 +545,7 @@ int commit_batch(Worker& w, const uint64_t* d_in, uint32_t n_cols, uint32_t batc
 int commit_launch(Worker& mem, Worker& lane, size_t mailbox_word, const uint64_t* d_in, uint32_t n_cols, uint32_t batch,
                   uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, bool from_coeffs, PendingCommit* pc) {
   Worker& w = mem;
-  if (batch == 0 || batch > MAX_BATCH) return fail(BP_ERR_INVALID_INPUT, "commit: batch of %u", batch);
+  if (batch == 0 || batch > MAX_LOCKSTEP) return fail(BP_ERR_INVALID_INPUT, "commit: batch of %u", batch);
   const uint64_t n = (uint64_t)1 << log_n, m = n << rate_bits;
   const size_t all_cols = (size_t)n_cols * batch;
   ARENA_ALLOC(lde, all_cols * m);
@@ -564,15 +673,15 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
                       const Committed* trace, const uint64_t* const* d_tv, const Ctl* ctl, Challenger* ch,
                       std::vector<uint64_t>* proofs, uint64_t* first_trace_leaf) {
   TRY(check_cfg(cfg));
-  if (B == 0 || B > MAX_BATCH || (size_t)B * cfg.num_queries > MAX_BATCH_QUERIES)
+  if (B == 0 || B > MAX_LOCKSTEP || (size_t)B * cfg.num_queries > MAX_BATCH_QUERIES)
     return fail(BP_ERR_INVALID_INPUT, "stark_prove_batch: %u proofs x %u queries (at most %u proofs, %u queries in all)", B,
-                cfg.num_queries, MAX_BATCH, MAX_BATCH_QUERIES);
+                cfg.num_queries, MAX_LOCKSTEP, MAX_BATCH_QUERIES);
   const ProofLayout L = proof_layout(cfg);
   const uint32_t log_n = cfg.log_n, r = cfg.rate_bits, h = cfg.cap_height, R = 1u << r;
   const uint64_t N = (uint64_t)1 << log_n, M = N << r;
   const uint32_t C = cfg.n_cols, K = cfg.n_const, A = L.n_aux, Q = L.n_quot;
   hipStream_t st = w.stream;
-  uint64_t* P[MAX_BATCH];
+  uint64_t* P[MAX_LOCKSTEP];
   for (uint32_t b = 0; b < B; b++) {
     if (K && !(consts && consts[b])) return fail(BP_ERR_INVALID_INPUT, "constants commitment missing");
     proofs[b].assign(L.total, 0);
@@ -594,14 +703,14 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   // 1. auxiliary columns -- the table's lookups (air::ctl): helper columns and running products -- and their commitment
   ARENA_ALLOC(d_auxv, (size_t)B * A * N);
   {
-    AuxArgs aa[MAX_BATCH];
+    AuxArgs aa[MAX_LOCKSTEP];
     for (uint32_t b = 0; b < B; b++) {
       aa[b] = AuxArgs{d_tv[b], d_auxv + (size_t)b * A * N, ctl[b]};
       if (K) aa[b].consts = consts[b]->values;
     }
     TRY(launch_aux(aa, B, cfg.air_id, C, log_n, st));
   }
-  Committed aux[MAX_BATCH];
+  Committed aux[MAX_LOCKSTEP];
   TRY(commit_batch(w, d_auxv, A, B, log_n, r, h, false, aux));
   for (uint32_t b = 0; b < B; b++) {
     std::memcpy(P[b] + L.aux_cap, aux[b].cap.data(), L.cap_words * 8);
@@ -609,7 +718,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   }
 
   // 2. alphas;  3. quotient on the LDE coset -> per-coset iNTT -> chunk coefficients -> commitment
-  QuotArgs qa[MAX_BATCH] = {};
+  QuotArgs qa[MAX_LOCKSTEP] = {};
   QuotCoset coset{};
   const int loaded = device_loaded();  // one answer for the whole batch: the proofs share one grid
   for (uint32_t b = 0; b < B; b++) {
@@ -629,7 +738,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
     }
     TRY(launch_quotient(qa, B, coset, st));
     TRY(intt_nat2br(d_qvals, N, d_qvals, N, log_n, B * 2 * R, true, st));  // 2 challenges x 2^r cosets per proof, in place
-    ChunkArgs ca[MAX_BATCH] = {};
+    ChunkArgs ca[MAX_LOCKSTEP] = {};
     const uint64_t wr_inv = gl::inv(gl::root(r)), sn_inv = gl::inv(gl::pow(gl::GENERATOR, N)), r_inv = gl::inv(R);
     for (uint32_t b = 0; b < B; b++) {
       ChunkArgs& c = ca[b];
@@ -644,7 +753,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   }
   // the temporaries are dead once the chunk kernel has run; stream order makes reuse safe
   w.arena.release(mark_tmp);
-  Committed quot[MAX_BATCH];
+  Committed quot[MAX_LOCKSTEP];
   TRY(commit_batch(w, d_qc, Q, B, log_n, r, h, true, quot));
   for (uint32_t b = 0; b < B; b++) {
     std::memcpy(P[b] + L.quot_cap, quot[b].cap.data(), L.cap_words * 8);
@@ -653,7 +762,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   if (w.aborted()) return fail(BP_ERR_ABORTED, "aborted after quotient commitment");
 
   // 4. zeta
-  gl::Ext zeta[MAX_BATCH], zeta_next[MAX_BATCH];
+  gl::Ext zeta[MAX_LOCKSTEP], zeta_next[MAX_LOCKSTEP];
   for (uint32_t b = 0; b < B; b++) {
     zeta[b] = ch[b].challenge_ext();
     if (gl::eq(gl::pow(zeta[b], N), gl::ext(1))) return fail(BP_ERR_INVALID_INPUT, "Opening point is in the subgroup.");
@@ -663,7 +772,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   // 5. openings: dot products of bit-reversed coefficient columns with zeta^bitrev(pos)
   ARENA_ALLOC(d_pw, (size_t)B * 6 * N);  // zeta, g zeta and 1 of every proof in one launch
   {
-    PowerVecArgs pv[MAX_BATCH];
+    PowerVecArgs pv[MAX_LOCKSTEP];
     for (uint32_t b = 0; b < B; b++) pv[b] = PowerVecArgs{d_pw + (size_t)b * 6 * N, {zeta[b], zeta_next[b], gl::ext(1)}};
     TRY(launch_power_vectors(pv, B, log_n, 3, st));
   }
@@ -672,7 +781,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   {
     // one launch for the five opening sets of every proof (they used to be five launches in a row on the critical
     // path); the kernels write the openings straight into host-visible memory
-    OpenMulti om[MAX_BATCH] = {};
+    OpenMulti om[MAX_LOCKSTEP] = {};
     for (uint32_t b = 0; b < B; b++) {
       OpenMulti& o = om[b];
       o.stride = N; o.log_n = log_n;
@@ -710,17 +819,17 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   }
 
   // 6. FRI.  Batches: (zeta: all), (g*zeta: trace, aux), (1: aux);  final = ((q0*a^k1 + q1)*a^k2 + q2)
-  gl::Ext alpha[MAX_BATCH];
+  gl::Ext alpha[MAX_LOCKSTEP];
   for (uint32_t b = 0; b < B; b++) alpha[b] = ch[b].challenge_ext();
   const uint32_t k0 = L.n_zeta, k1 = L.n_next, k2 = A;
   ARENA_ALLOC(d_apow, (size_t)B * 2 * k0);
   {
-    AlphaPowArgs ap[MAX_BATCH];
+    AlphaPowArgs ap[MAX_LOCKSTEP];
     for (uint32_t b = 0; b < B; b++) ap[b] = AlphaPowArgs{d_apow + (size_t)b * 2 * k0, alpha[b]};
     TRY(launch_alpha_pows(ap, B, k0, st));
   }
   struct OracleRef { const Committed* c; int32_t e[3]; };
-  OracleRef refs[MAX_BATCH][4];
+  OracleRef refs[MAX_LOCKSTEP][4];
   int n_or = 0;
   for (uint32_t b = 0; b < B; b++) {
     n_or = 0;
@@ -740,9 +849,9 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
       ARENA_ALLOC(cp, (size_t)B * total_chunks * 6 * N);
       d_cpart = cp;
     }
-    CombineMulti cm[MAX_BATCH] = {};
-    uint64_t* gp[MAX_BATCH];
-    CombineReduceArgs cr[MAX_BATCH];
+    CombineMulti cm[MAX_LOCKSTEP] = {};
+    uint64_t* gp[MAX_LOCKSTEP];
+    CombineReduceArgs cr[MAX_LOCKSTEP];
     for (uint32_t b = 0; b < B; b++) {
       uint32_t chunk_base = 0;
       uint64_t* part = d_cpart ? d_cpart + (size_t)b * total_chunks * 6 * N : nullptr;
@@ -768,7 +877,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
   TRY(ntt_br2nat(d_g, N, d_glde, M, N, log_n, 6 * B, R, coset_scale, false, st));
   ARENA_ALLOC(d_v0, (size_t)B * 2 * M);
   {
-    FriInitArgs fi[MAX_BATCH] = {};
+    FriInitArgs fi[MAX_LOCKSTEP] = {};
     for (uint32_t b = 0; b < B; b++) {
       FriInitArgs& f = fi[b];
       f.glde = d_glde + (size_t)b * 6 * M; f.tw_n = tw_n; f.log_n = log_n; f.rate_bits = r;
@@ -804,7 +913,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
     const size_t dw = bp_merkle_digest_words(log_leaves, h), next_words = (size_t)2 << log_leaves;
     ARENA_ALLOC(d_dig, dw * B);
     ARENA_ALLOC(d_next, next_words * B);
-    FriLayerArgs fa[MAX_BATCH] = {};
+    FriLayerArgs fa[MAX_LOCKSTEP] = {};
     TRY(fri_layer_args(log_nl, r, ab, shift, &fa[0]));
     for (uint32_t b = 0; b < B; b++) {
       if (b) fa[b] = fa[0];
@@ -872,12 +981,12 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
 
   // proof of work: smallest witness
   {
-    PowArgs pa[MAX_BATCH] = {};
+    PowArgs pa[MAX_LOCKSTEP] = {};
     for (uint32_t b = 0; b < B; b++) {
       ch[b].pow_state(pa[b].state, &pa[b].pos);
       pa[b].bits = cfg.pow_bits;
     }
-    unsigned long long res[MAX_BATCH];
+    unsigned long long res[MAX_LOCKSTEP];
     for (uint32_t b = 0; b < B; b++) res[b] = 0;
     if (cfg.pow_bits) {
       // The smallest witness is geometric with mean 2^pow_bits and every candidate costs a whole permutation, so
@@ -887,7 +996,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
       // extra launches are latency on one of 24 streams.  After 8 misses the batch grows (tiny bit counts, bad luck).
       const uint32_t batch0 = (uint32_t)std::min<uint64_t>(1u << 20, std::max<uint64_t>(1u << 12, (uint64_t)1 << (cfg.pow_bits ? cfg.pow_bits - 1 : 0)));
       uint32_t batch = batch0, n_batches = 0;
-      BPG_HIP(hipMemsetAsync(w.d_pow_result, 0xFF, 8 * MAX_BATCH, st));
+      BPG_HIP(hipMemsetAsync(w.d_pow_result, 0xFF, 8 * MAX_LOCKSTEP, st));
       // Batches are launched four at a time before the host looks: a batch whose predecessors already found a
       // witness leaves at once (pow_grind_mx_kernel), so the speculation costs four tiny launches and saves the
       // device->host round trip after every batch (2.5 -> 1.2 round trips per proof at 16 bits).  The proofs of a
@@ -923,7 +1032,7 @@ int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t B, const Committe
 
   // query phase: indices from the transcript, rows + Merkle paths gathered on the device
   {
-    // (heap: the two argument blocks are 3 KiB each)
+    // (heap: the two argument blocks are 9 and 10 KiB)
     std::unique_ptr<QueryArgs> qa2(new QueryArgs());
     std::unique_ptr<QueryLayerArgs> ql(new QueryLayerArgs());
     const size_t q_words = (size_t)cfg.num_queries * L.query_words;

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "gl.hpp"
 #include "stark_kernels.hpp"
+#include "arg_ring.hpp"
 #include "air_program.hpp"
 
 namespace bpg {
@@ -131,7 +132,11 @@ struct Worker {
   // the hash-row witnesses of a batch of recursion-shaped proofs (AIR 8), made on the host, read by the witness kernel:
   // pinned memory of its own (the mailbox above belongs to the kernels that mirror caps and openings into it)
   uint64_t *hash_rows = nullptr, *hash_rows_dev = nullptr;
-  unsigned long long* d_pow_result = nullptr;  // MAX_BATCH words: one witness per proof of a batch
+  unsigned long long* d_pow_result = nullptr;  // MAX_LOCKSTEP words: one witness per proof of a batch
+  // the argument blocks of the launches queued on `stream` (arg_ring.hpp): host-pinned, device-mapped memory of its own,
+  // written by the host alone, empty again whenever wait() returns.  Launchers find it by the stream (arg_ring_put).
+  ArgRing args;
+  void* args_mem = nullptr;
   hipEvent_t sync_event = nullptr;  // blocking-sync event: waiting threads sleep instead of spinning
   const volatile int32_t* abort_flag = nullptr;
   const volatile uint8_t* abort_flag_u8 = nullptr;  // AtomicBool::as_ptr() of the reference's Arc<AtomicBool>
@@ -150,7 +155,7 @@ struct Worker {
 // bit-reversed coefficients when from_coeffs; then the commitment aliases d_in as its coefficients).
 int commit(Worker& w, const uint64_t* d_in, uint32_t n_cols, uint32_t log_n, uint32_t rate_bits,
            uint32_t cap_height, bool from_coeffs, Committed* out);
-// `batch` (<= MAX_BATCH) commitments of one shape, every launch covering all of them: d_in = [batch][n_cols][n]
+// `batch` (<= MAX_LOCKSTEP) commitments of one shape, every launch covering all of them: d_in = [batch][n_cols][n]
 int commit_batch(Worker& w, const uint64_t* d_in, uint32_t n_cols, uint32_t batch, uint32_t log_n, uint32_t rate_bits,
                  uint32_t cap_height, bool from_coeffs, Committed* out);
 
@@ -177,13 +182,20 @@ int commit_finish(const PendingCommit& pc, Committed* out);
 int stark_prove(Worker& w, const StarkCfg& cfg, const Committed* consts, const Committed& trace,
                 const uint64_t* d_trace_values, const Ctl& ctl, Challenger& ch, std::vector<uint64_t>& proof,
                 uint64_t* first_trace_leaf = nullptr);
-// The same for `batch` (<= MAX_BATCH, batch * num_queries <= MAX_BATCH_QUERIES) proofs of ONE shape in lock-step:
+// The same for `batch` (<= MAX_LOCKSTEP, batch * num_queries <= MAX_BATCH_QUERIES) proofs of ONE shape in lock-step:
 // independent transcripts, every kernel launch and every host wait shared (the seven per-table recursion chains of
 // a transaction, proofgen.cpp).  Proof b's bytes are those stark_prove would give for (consts[b], trace[b], ...).
 // consts: per proof, may be null when the shape has no constant columns.
 int stark_prove_batch(Worker& w, const StarkCfg& cfg, uint32_t batch, const Committed* const* consts,
                       const Committed* trace, const uint64_t* const* d_trace_values, const Ctl* ctl, Challenger* ch,
                       std::vector<uint64_t>* proofs, uint64_t* first_trace_leaf = nullptr);
+
+// A stream's argument ring, found by the launchers (arg_ring_put, stark_kernels.hpp).  A worker registers its own; a
+// stream nobody registered (a caller's, at the single-launch entry points) is served by one ring of the library's,
+// which waits for the whole device when it is full.
+constexpr size_t ARG_RING_BYTES = (size_t)1 << 20;
+void arg_ring_register(hipStream_t st, ArgRing* ring);
+void arg_ring_unregister(hipStream_t st);
 
 // hash_kernels.hip: +1 / -1 as a prover starts / finishes (the Poseidon kernel choice follows the load)
 void prover_active(int delta);

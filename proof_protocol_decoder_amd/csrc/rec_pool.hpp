@@ -3,7 +3,9 @@
 // A transaction's three lock-step batches hold seven proofs each and a batch has room for eight (MAX_BATCH): the root
 // proof of a transaction and the aggregation proofs of the tree are proofs of the same shape whose inputs are host data,
 // so any prover can carry one of them as the eighth slot of a batch it launches anyway.  A chain of one costs the same
-// ~57 launches and host round trips as a chain of seven; riding, it costs none.
+// ~57 launches and host round trips as a chain of seven; riding, it costs none.  A group of g transactions proves a level
+// of all its chains as one batch (proofgen.cpp: group_recursion, Tune::rec_group): 7 g proofs, and the slots a batch of
+// MAX_LOCKSTEP = 24 leaves free -- three at g = 3 -- carry riders the same way.
 //
 //  * RecJob: one such proof to be made -- circuit, public-input list, path witnesses -- and the tree node it is for.
 //  * RecPool: post a job, take up to k ready jobs (aggregations before roots, each in node order), hand back the

@@ -16,6 +16,7 @@
 #include "poseidon.cuh"
 #include "poseidon_mx.cuh"
 #include "stark_kernels.hpp"
+#include "arg_ring.hpp"
 #include "quotient_dev.cuh"
 #include "air_program.hpp"
 
@@ -45,12 +46,13 @@ synth_const_kernel(uint64_t* out, uint32_t log_n, uint32_t n_const, uint64_t see
 }
 // grid = (rows/256, groups + 1, proofs): group g < G fills columns 4g..4g+3; blockIdx.y == G fills the tail.
 __global__ void __launch_bounds__(256)
-synth_trace_kernel(bpg::BatchOf<bpg::SynthTraceArgs> batch, uint32_t log_n, uint32_t n_cols, uint32_t n_const,
+synth_trace_kernel(bpg::ArgPtr<bpg::SynthTraceArgs> args, uint32_t log_n, uint32_t n_cols, uint32_t n_const,
                    uint32_t deg_pow) {
+  BPG_ARG_BATCH(bpg::SynthTraceArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  uint64_t* __restrict__ t = batch.a[blockIdx.z].trace;
-  const uint64_t* __restrict__ consts = batch.a[blockIdx.z].consts;
-  const uint64_t seed = batch.a[blockIdx.z].seed;
+  uint64_t* __restrict__ t = batch[blockIdx.z].trace;
+  const uint64_t* __restrict__ consts = batch[blockIdx.z].consts;
+  const uint64_t seed = batch[blockIdx.z].seed;
   const uint32_t n = 1u << log_n, G = n_cols / 4;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -506,11 +508,12 @@ struct TraceRow {
 // different cache line, 16x the algorithmic HBM reads on the 2^14..2^17-row tables by PMC.)
 template <uint32_t AIR>
 __global__ void __launch_bounds__(1024)
-aux_suffix_product_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, uint32_t n_cols) {
+aux_suffix_product_kernel(bpg::ArgPtr<bpg::AuxArgs> args, uint32_t log_n, uint32_t n_cols) {
+  BPG_ARG_BATCH(bpg::AuxArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const uint64_t* __restrict__ trace = batch.a[blockIdx.z].trace;
-  uint64_t* __restrict__ aux = batch.a[blockIdx.z].aux;
-  const bpg::Ctl& ctl = batch.a[blockIdx.z].ctl;
+  const uint64_t* __restrict__ trace = batch[blockIdx.z].trace;
+  uint64_t* __restrict__ aux = batch[blockIdx.z].aux;
+  const bpg::Ctl& ctl = batch[blockIdx.z].ctl;
   __shared__ uint64_t part[1024];
   const bpg::air::Shape shape{AIR, n_cols, 0, 1};
   const uint32_t n = 1u << log_n, T = blockDim.x, t = threadIdx.x;
@@ -609,22 +612,24 @@ __device__ __forceinline__ void suffix_scan_in_column(uint64_t* __restrict__ z, 
   }
 }
 __global__ void __launch_bounds__(1024)
-port_running_columns_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, uint32_t log_ports) {
+port_running_columns_kernel(bpg::ArgPtr<bpg::AuxArgs> args, uint32_t log_n, uint32_t log_ports) {
+  BPG_ARG_BATCH(bpg::AuxArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
   __shared__ uint64_t part[1024];
   const uint32_t n = 1u << log_n;
-  uint64_t* z = batch.a[blockIdx.z].aux + (uint64_t)blockIdx.x * n;
+  uint64_t* z = batch[blockIdx.z].aux + (uint64_t)blockIdx.x * n;
   if ((log_ports >> (blockIdx.x >> 1)) & 1) suffix_scan_in_column<true>(z, n, part);
   else suffix_scan_in_column<false>(z, n, part);
 }
 // The helper columns of the Keccak-f table's lookup (air::ctl): h_0 / h_1, the permutation's input compressed by beta_0 /
 // beta_1 and carried along its rows.  A lane owns a row; it reads the 50 input limbs of its permutation's first row.
 __global__ void __launch_bounds__(256)
-keccak_ctl_helpers_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n) {
+keccak_ctl_helpers_kernel(bpg::ArgPtr<bpg::AuxArgs> args, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::AuxArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
   namespace kk = bpg::air::keccak;
   namespace ct = bpg::air::ctl;
-  const bpg::AuxArgs& a = batch.a[blockIdx.z];
+  const bpg::AuxArgs& a = batch[blockIdx.z];
   const uint32_t n = 1u << log_n, i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t first = (i / 24) * 24;
@@ -702,17 +707,18 @@ plonk_constants_kernel(uint64_t* __restrict__ out, uint32_t log_n, uint64_t seed
 // seed.  No lane keeps more than a handful of values: nothing lives in scratch.  grid.x covers (n / 4) x 20 lanes,
 // groups fastest.
 __global__ void __launch_bounds__(256)
-plonk_trace_kernel(bpg::BatchOf<bpg::PlonkTraceArgs> batch, uint32_t log_n) {
+plonk_trace_kernel(bpg::ArgPtr<bpg::PlonkTraceArgs> args, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::PlonkTraceArgs, args);
   namespace pk = bpg::air::plonk;
   if (gridDim.x * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
   const uint32_t n = 1u << log_n, groups = n >> 2, id = blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= groups * pk::N_SLOTS) return;
   const uint32_t g = id % groups, s = id / groups, r0 = 4 * g;
-  uint64_t* __restrict__ t = batch.a[blockIdx.z].trace;
-  const uint64_t* __restrict__ cs = batch.a[blockIdx.z].consts;
-  const uint64_t seed = batch.a[blockIdx.z].seed;
+  uint64_t* __restrict__ t = batch[blockIdx.z].trace;
+  const uint64_t* __restrict__ cs = batch[blockIdx.z].consts;
+  const uint64_t seed = batch[blockIdx.z].seed;
   const uint32_t sn = (s + 1) % pk::N_SLOTS;  // the neighbour slot whose output this slot's b input copies
-  const uint64_t pub_s = s < 4 ? batch.a[blockIdx.z].pub[s] : 0, pub_n = sn < 4 ? batch.a[blockIdx.z].pub[sn] : 0;
+  const uint64_t pub_s = s < 4 ? batch[blockIdx.z].pub[s] : 0, pub_n = sn < 4 ? batch[blockIdx.z].pub[sn] : 0;
   const bool unit = s < pk::N_SBOX;
   const uint32_t u = pk::COL_SBOX + 5 * s;  // the slot's S-box unit (slots 0..10)
 #define PUT(col, row, v) t[(uint64_t)(col) * n + (row)] = (v)
@@ -724,10 +730,10 @@ plonk_trace_kernel(bpg::BatchOf<bpg::PlonkTraceArgs> batch, uint32_t log_n) {
         for (uint32_t w = 0; w < 5; w++) PUT(u + w, r, rnd(seed, u + w, r));
     }
     if (s == 0)
-      for (uint32_t j = 0; j < 4; j++) PUT(j, 0, batch.a[blockIdx.z].pub[j]);
+      for (uint32_t j = 0; j < 4; j++) PUT(j, 0, batch[blockIdx.z].pub[j]);
     return;
   }
-  const uint32_t a0 = batch.a[blockIdx.z].arith_row0;
+  const uint32_t a0 = batch[blockIdx.z].arith_row0;
   if (r0 < a0) return;  // rows 4 .. a0 - 1: the hash rows and the Merkle rows, written by plonk_hash_rows_kernel
   const bool first_group = r0 == a0;  // its c inputs are the public inputs
   if (unit)  // the advice wires of the three arithmetic rows are free
@@ -769,10 +775,11 @@ plonk_trace_kernel(bpg::BatchOf<bpg::PlonkTraceArgs> batch, uint32_t log_n) {
 // profiles/r5_transcript_latency.txt), 8 <= h < 8 + n_merkle_rows while it walked the children's Merkle paths
 // (bpg::poseidon_merkle_rows); every other row of the region is free.  grid = (1, rows of the region, proofs) x 135 lanes.
 __global__ void __launch_bounds__(256)
-plonk_hash_rows_kernel(bpg::BatchOf<bpg::PlonkTraceArgs> batch, uint32_t log_n) {
+plonk_hash_rows_kernel(bpg::ArgPtr<bpg::PlonkTraceArgs> args, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::PlonkTraceArgs, args);
   namespace pk = bpg::air::plonk;
   __builtin_amdgcn_s_setprio(3);
-  const bpg::PlonkTraceArgs& a = batch.a[blockIdx.z];
+  const bpg::PlonkTraceArgs& a = batch[blockIdx.z];
   const uint32_t n = 1u << log_n, c = threadIdx.x, h = blockIdx.y, row = pk::HASH_ROW0 + h;
   if (c >= pk::N_COLS || row >= a.arith_row0) return;
   const bool given = h < a.n_hash_rows || (h >= pk::HASH_ROWS_MAX && h < pk::HASH_ROWS_MAX + a.n_merkle_rows);
@@ -782,11 +789,12 @@ plonk_hash_rows_kernel(bpg::BatchOf<bpg::PlonkTraceArgs> batch, uint32_t log_n) 
 // the denominators are inverted together) as cumulative products P_k = prod_{k' <= k} num / den: P_1..P_9 into the
 // partial-product columns, the row's total P_10 into the Z column.  grid = (rows/256, 2, proofs).
 __global__ void __launch_bounds__(256)
-plonk_chunk_ratios_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, const uint64_t* __restrict__ tw_n) {
+plonk_chunk_ratios_kernel(bpg::ArgPtr<bpg::AuxArgs> args, uint32_t log_n, const uint64_t* __restrict__ tw_n) {
+  BPG_ARG_BATCH(bpg::AuxArgs, args);
   namespace pk = bpg::air::plonk;
   namespace ct = bpg::air::ctl;
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
-  const bpg::AuxArgs& a = batch.a[blockIdx.z];
+  const bpg::AuxArgs& a = batch[blockIdx.z];
   const uint32_t n = 1u << log_n, i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
   if (i >= n) return;
   const uint64_t beta = a.ctl.v[2 * c], gamma = a.ctl.v[2 * c + 1];
@@ -826,9 +834,10 @@ plonk_chunk_ratios_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n, cons
 }
 // step 3 of 3 (step 2, the suffix products of the row totals in the two Z columns, is aux_suffix_product_kernel):
 // partial product k of row i = Z(i + 1) P_k(i), the wrap from the last row to the first included.  grid = (rows/256, 18, proofs).
-__global__ void __launch_bounds__(256) plonk_partial_products_kernel(bpg::BatchOf<bpg::AuxArgs> batch, uint32_t log_n) {
+__global__ void __launch_bounds__(256) plonk_partial_products_kernel(bpg::ArgPtr<bpg::AuxArgs> args, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::AuxArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
-  const bpg::AuxArgs& a = batch.a[blockIdx.z];
+  const bpg::AuxArgs& a = batch[blockIdx.z];
   const uint32_t n = 1u << log_n, i = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y / 9, k = 1 + blockIdx.y % 9;
   if (i >= n) return;
   const uint64_t z_next = a.aux[(uint64_t)(10 * c) * n + ((i + 1) & (n - 1))];
@@ -853,9 +862,10 @@ __global__ void __launch_bounds__(256) plonk_partial_products_kernel(bpg::BatchO
 #endif
 template <uint32_t AIR>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AIR == bpg::air::KECCAK_F ? 3 : 1)))
-quotient_air_kernel(bpg::BatchOf<bpg::QuotArgs> batch) {
+quotient_air_kernel(bpg::ArgPtr<bpg::QuotArgs> args) {
+  BPG_ARG_BATCH(bpg::QuotArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::QuotArgs& q = batch.a[blockIdx.z];
+  const bpg::QuotArgs& q = batch[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
@@ -893,9 +903,10 @@ quotient_air_kernel(bpg::BatchOf<bpg::QuotArgs> batch) {
 // register budget (the twelve-word state and the layer's accumulators), hence its own kernel: the chunk units keep three
 // waves per SIMD.   grid = (rows / 256, 1, batch)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BPG_PLONK_HASH_WAVES)))
-quotient_plonk_hash_kernel(bpg::BatchOf<bpg::QuotArgs> batch, uint32_t wg_row) {
+quotient_plonk_hash_kernel(bpg::ArgPtr<bpg::QuotArgs> args, uint32_t wg_row) {
+  BPG_ARG_BATCH(bpg::QuotArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::QuotArgs& q = batch.a[blockIdx.z];
+  const bpg::QuotArgs& q = batch[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
@@ -911,9 +922,10 @@ quotient_plonk_hash_kernel(bpg::BatchOf<bpg::QuotArgs> batch, uint32_t wg_row) {
   q.partial[((uint64_t)wg_row * 2 + 1) * rows + pos] = gl::mulc(out.result(1), qh);
 }
 // qvals = (sum of the workgroup rows' partial sums) / Z_H.   grid = (rows / 256, 2 challenges)
-__global__ void __launch_bounds__(256) quotient_sum_kernel(bpg::BatchOf<bpg::QuotArgs> batch, uint32_t n_wg_rows) {
+__global__ void __launch_bounds__(256) quotient_sum_kernel(bpg::ArgPtr<bpg::QuotArgs> args, uint32_t n_wg_rows) {
+  BPG_ARG_BATCH(bpg::QuotArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::QuotArgs& q = batch.a[blockIdx.z];
+  const bpg::QuotArgs& q = batch[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
@@ -931,10 +943,11 @@ struct AlphaTabArgs {
   uint64_t a0, a1;
 };
 __global__ void __launch_bounds__(256)
-alpha_table_kernel(bpg::BatchOf<AlphaTabArgs> batch, uint32_t T, CosetTab ct) {
+alpha_table_kernel(bpg::ArgPtr<AlphaTabArgs> args, uint32_t T, CosetTab ct) {
+  BPG_ARG_BATCH(AlphaTabArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  uint64_t* __restrict__ out = batch.a[blockIdx.z].out;
-  const uint64_t a0 = batch.a[blockIdx.z].a0, a1 = batch.a[blockIdx.z].a1;
+  uint64_t* __restrict__ out = batch[blockIdx.z].out;
+  const uint64_t a0 = batch[blockIdx.z].a0, a1 = batch[blockIdx.z].a1;
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.y == 0 && e < 48) out[2 * (uint64_t)T + e] = ct.v[e];
   if (e >= T) return;
@@ -942,9 +955,10 @@ alpha_table_kernel(bpg::BatchOf<AlphaTabArgs> batch, uint32_t T, CosetTab ct) {
 }
 // After the per-coset inverse NTT: E_t[pos] (bit-reversed n0).  c_{n0 + n*n1} =
 // (s^n)^(-n1) / 2^r * sum_t w_{2^r}^(-t n1) * E_t[pos] * g_t^(-n0).   grid = (n/256, 2 challenges)
-__global__ void __launch_bounds__(256) quotient_chunks_kernel(bpg::BatchOf<bpg::ChunkArgs> batch) {
+__global__ void __launch_bounds__(256) quotient_chunks_kernel(bpg::ArgPtr<bpg::ChunkArgs> args) {
+  BPG_ARG_BATCH(bpg::ChunkArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::ChunkArgs& c = batch.a[blockIdx.z];
+  const bpg::ChunkArgs& c = batch[blockIdx.z];
   const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << c.log_n;
   if (pos >= n) return;
   const uint32_t j = blockIdx.y, R = 1u << c.rate_bits;
@@ -961,21 +975,23 @@ __global__ void __launch_bounds__(256) quotient_chunks_kernel(bpg::BatchOf<bpg::
 // ---------------------------------------------------------------- K8 openings
 // pw[0..n) = zeta^bitrev(pos) (c0 plane), pw[n..2n) c1 plane; same for the second point at 2n.
 __global__ void __launch_bounds__(256)
-power_vector_kernel(bpg::BatchOf<bpg::PowerVecArgs> batch, uint32_t log_n) {
+power_vector_kernel(bpg::ArgPtr<bpg::PowerVecArgs> args, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::PowerVecArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
   const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << log_n;
   if (pos >= n) return;
   const uint32_t e = gl::bitrev(pos, log_n);
-  const Ext z = batch.a[blockIdx.z].z[blockIdx.y];
+  const Ext z = batch[blockIdx.z].z[blockIdx.y];
   const Ext r = gl::pow(z, e);
-  uint64_t* o = batch.a[blockIdx.z].out + (uint64_t)blockIdx.y * 2 * n;
+  uint64_t* o = batch[blockIdx.z].out + (uint64_t)blockIdx.y * 2 * n;
   o[pos] = r.c0;
   o[n + pos] = r.c1;
 }
-__global__ void __launch_bounds__(256) alpha_pows_kernel(bpg::BatchOf<bpg::AlphaPowArgs> batch, uint32_t count) {
+__global__ void __launch_bounds__(256) alpha_pows_kernel(bpg::ArgPtr<bpg::AlphaPowArgs> args, uint32_t count) {
+  BPG_ARG_BATCH(bpg::AlphaPowArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  uint64_t* __restrict__ out = batch.a[blockIdx.z].out;
-  const Ext alpha = batch.a[blockIdx.z].alpha;
+  uint64_t* __restrict__ out = batch[blockIdx.z].out;
+  const Ext alpha = batch[blockIdx.z].alpha;
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count) return;
   const Ext r = gl::pow(alpha, j);
@@ -1020,9 +1036,10 @@ openings_kernel(const uint64_t* __restrict__ coeffs, uint64_t stride, uint32_t l
 }
 // every opening set of a proof (constants, trace, aux, quotient at zeta [/ g zeta], aux at 1) in ONE launch: the
 // five launches it replaces sat one behind the other on the proof's critical path
-__global__ void __launch_bounds__(256) openings_multi_kernel(bpg::BatchOf<bpg::OpenMulti> batch) {
+__global__ void __launch_bounds__(256) openings_multi_kernel(bpg::ArgPtr<bpg::OpenMulti> args) {
+  BPG_ARG_BATCH(bpg::OpenMulti, args);
   if (gridDim.x * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
-  const bpg::OpenMulti& m = batch.a[blockIdx.z];
+  const bpg::OpenMulti& m = batch[blockIdx.z];
   uint32_t s = 0;
 #pragma unroll
   for (int k = 1; k < 5; k++)
@@ -1084,11 +1101,12 @@ __device__ __forceinline__ void fri_combine_partial_body(const bpg::CombineArgs&
 // Every column of every oracle in one pass, straight into g[6][n]: no partial sums, no reduce launch.  For a
 // device that several provers share (nothing needs filling); the sums are exact, so the bytes are the same.
 struct GPtrs {
-  uint64_t* g[bpg::MAX_BATCH];
+  uint64_t* g[bpg::MAX_LOCKSTEP];
 };
-__global__ void __launch_bounds__(256) fri_combine_all_kernel(bpg::BatchOf<bpg::CombineMulti> batch, GPtrs gp) {
+__global__ void __launch_bounds__(256) fri_combine_all_kernel(bpg::ArgPtr<bpg::CombineMulti> args, GPtrs gp) {
+  BPG_ARG_BATCH(bpg::CombineMulti, args);
   if (gridDim.x * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
-  const bpg::CombineMulti& m = batch.a[blockIdx.z];
+  const bpg::CombineMulti& m = batch[blockIdx.z];
   uint64_t* __restrict__ g = gp.g[blockIdx.z];
   const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << m.a[0].log_n;
   if (pos >= n) return;
@@ -1102,9 +1120,10 @@ __global__ void __launch_bounds__(256) fri_combine_partial_kernel(bpg::CombineAr
   fri_combine_partial_body(a, blockIdx.y);
 }
 // all oracles of a proof (constants, trace, aux, quotient) in one launch: grid.y runs over the chunks of all of them
-__global__ void __launch_bounds__(256) fri_combine_partial_multi_kernel(bpg::BatchOf<bpg::CombineMulti> batch) {
+__global__ void __launch_bounds__(256) fri_combine_partial_multi_kernel(bpg::ArgPtr<bpg::CombineMulti> args) {
+  BPG_ARG_BATCH(bpg::CombineMulti, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);
-  const bpg::CombineMulti& m = batch.a[blockIdx.z];
+  const bpg::CombineMulti& m = batch[blockIdx.z];
   uint32_t o = 0;
 #pragma unroll
   for (int k = 1; k < 4; k++)
@@ -1113,10 +1132,11 @@ __global__ void __launch_bounds__(256) fri_combine_partial_multi_kernel(bpg::Bat
 }
 // g[6][n] = sum over chunks.  grid = (n/256, 6)
 __global__ void __launch_bounds__(256)
-fri_combine_reduce_kernel(bpg::BatchOf<bpg::CombineReduceArgs> batch, uint32_t n_chunks, uint32_t log_n) {
+fri_combine_reduce_kernel(bpg::ArgPtr<bpg::CombineReduceArgs> args, uint32_t n_chunks, uint32_t log_n) {
+  BPG_ARG_BATCH(bpg::CombineReduceArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const uint64_t* __restrict__ partial = batch.a[blockIdx.z].partial;
-  uint64_t* __restrict__ g = batch.a[blockIdx.z].g;
+  const uint64_t* __restrict__ partial = batch[blockIdx.z].partial;
+  uint64_t* __restrict__ g = batch[blockIdx.z].g;
   const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << log_n;
   if (pos >= n) return;
   uint64_t acc = 0;
@@ -1125,9 +1145,10 @@ fri_combine_reduce_kernel(bpg::BatchOf<bpg::CombineReduceArgs> batch, uint32_t n
 }
 // Layer-0 FRI values: V(x) = sum_b alpha^(e_b) * (G_b(x) - y_b) / (x - z_b), x on the LDE coset.
 // glde: [6][rows] coset-major; out: AoS ext [rows].
-__global__ void __launch_bounds__(256) fri_quotient_values_kernel(bpg::BatchOf<bpg::FriInitArgs> batch) {
+__global__ void __launch_bounds__(256) fri_quotient_values_kernel(bpg::ArgPtr<bpg::FriInitArgs> args) {
+  BPG_ARG_BATCH(bpg::FriInitArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::FriInitArgs& a = batch.a[blockIdx.z];
+  const bpg::FriInitArgs& a = batch[blockIdx.z];
   const uint64_t rows = (uint64_t)1 << (a.log_n + a.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
@@ -1156,9 +1177,10 @@ __global__ void __launch_bounds__(256) fri_quotient_values_kernel(bpg::BatchOf<b
 // x0 * w_a^j', j' = 0..a-1 at positions t*n_l + m0 + j'*(n_l/a).  Its Merkle leaf (upstream:
 // bit-reversed values chunked by arity) is those values in bitrev_a(j) order, leaf index
 // bitrev(t + 2^r*m0).
-__global__ void __launch_bounds__(256) fri_layer_leaf_kernel(bpg::BatchOf<bpg::FriLayerArgs> batch) {
+__global__ void __launch_bounds__(256) fri_layer_leaf_kernel(bpg::ArgPtr<bpg::FriLayerArgs> args) {
+  BPG_ARG_BATCH(bpg::FriLayerArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::FriLayerArgs& a = batch.a[blockIdx.z];
+  const bpg::FriLayerArgs& a = batch[blockIdx.z];
   const uint32_t log_q = a.log_nl - a.arity_bits;  // log2(n_l / arity)
   const uint64_t n_leaves = (uint64_t)1 << (log_q + a.rate_bits);
   const uint64_t id = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -1185,9 +1207,10 @@ __global__ void __launch_bounds__(256) fri_layer_leaf_kernel(bpg::BatchOf<bpg::F
 }
 // Quad-cooperative form of the same leaf hash: lane q of a quad carries state words q and q+4, i.e.
 // component (q & 1) of ext elements (q >> 1) and 2 + (q >> 1) of every 4-element absorb.
-__global__ void __launch_bounds__(256) fri_layer_leaf_quad_kernel(bpg::BatchOf<bpg::FriLayerArgs> batch) {
+__global__ void __launch_bounds__(256) fri_layer_leaf_quad_kernel(bpg::ArgPtr<bpg::FriLayerArgs> args) {
+  BPG_ARG_BATCH(bpg::FriLayerArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::FriLayerArgs& a = batch.a[blockIdx.z];
+  const bpg::FriLayerArgs& a = batch[blockIdx.z];
   __shared__ uint64_t rc[360];
   for (uint32_t i = threadIdx.x; i < 360; i += blockDim.x) rc[i] = poseidon::RC[i];
   __syncthreads();
@@ -1213,9 +1236,10 @@ __global__ void __launch_bounds__(256) fri_layer_leaf_quad_kernel(bpg::BatchOf<b
 // Matrix-core form (poseidon_mx.cuh): a wave takes 16 * NS leaves; lane (n, kb) of set m carries state words kb and
 // kb + 4 of leaf 16m + n, i.e. component (kb & 1) of ext elements (kb >> 1) and 2 + (kb >> 1) of every absorb.
 template <int NS>
-__global__ void __launch_bounds__(256) fri_layer_leaf_mx_kernel(bpg::BatchOf<bpg::FriLayerArgs> batch) {
+__global__ void __launch_bounds__(256) fri_layer_leaf_mx_kernel(bpg::ArgPtr<bpg::FriLayerArgs> args) {
+  BPG_ARG_BATCH(bpg::FriLayerArgs, args);
   if (gridDim.x * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::FriLayerArgs& a = batch.a[blockIdx.z];
+  const bpg::FriLayerArgs& a = batch[blockIdx.z];
   __shared__ __attribute__((aligned(16))) uint32_t cin[poseidon::mx::CIN_WORDS];
   poseidon::mx::build_cin(cin);
   __syncthreads();
@@ -1253,9 +1277,10 @@ __global__ void __launch_bounds__(256) fri_layer_leaf_mx_kernel(bpg::BatchOf<bpg
   }
 }
 // P'(x0^a) = sum_i (beta/x0)^i u_i,  u_i = 1/a * sum_j' w_a^(-i j') P(x0 w_a^j')
-__global__ void __launch_bounds__(256) fri_fold_kernel(bpg::BatchOf<bpg::FriLayerArgs> batch) {
+__global__ void __launch_bounds__(256) fri_fold_kernel(bpg::ArgPtr<bpg::FriLayerArgs> args) {
+  BPG_ARG_BATCH(bpg::FriLayerArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
-  const bpg::FriLayerArgs& a = batch.a[blockIdx.z];
+  const bpg::FriLayerArgs& a = batch[blockIdx.z];
   const uint32_t log_q = a.log_nl - a.arity_bits;
   const uint64_t n_out = (uint64_t)1 << (log_q + a.rate_bits);
   const uint64_t id = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -1328,8 +1353,9 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(bpg::BatchOf<bpg::FriLaye
 // ---------------------------------------------------------------- K9 proof of work
 // Smallest witness w >= base with leading pow_bits zero in state[7] after the duplex
 // (fri_proof_of_work; upstream takes any winner, we take the minimum so results are reproducible).
-__global__ void __launch_bounds__(256) pow_grind_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result) {
-  const bpg::PowArgs& a = batch.a[blockIdx.z];
+__global__ void __launch_bounds__(256) pow_grind_kernel(bpg::ArgPtr<bpg::PowArgs> args, unsigned long long* result) {
+  BPG_ARG_BATCH(bpg::PowArgs, args);
+  const bpg::PowArgs& a = batch[blockIdx.z];
   result += blockIdx.z;
   // a witness below this workgroup's first candidate is already known: see pow_grind_mx_kernel (here every lane works
   // for itself, so lanes may leave one by one)
@@ -1348,8 +1374,9 @@ __global__ void __launch_bounds__(256) pow_grind_kernel(bpg::BatchOf<bpg::PowArg
 // tables, as in hash_kernels.hip).
 template <bool GR>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
-pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result, const uint32_t* __restrict__ gtab) {
-  const bpg::PowArgs& a = batch.a[blockIdx.z];
+pow_grind_mx_kernel(bpg::ArgPtr<bpg::PowArgs> args, unsigned long long* result, const uint32_t* __restrict__ gtab) {
+  BPG_ARG_BATCH(bpg::PowArgs, args);
+  const bpg::PowArgs& a = batch[blockIdx.z];
   result += blockIdx.z;  // one witness word per proof of the batch
   // A witness below this batch is already known (an earlier batch of the same speculative group found it: batches
   // run one after the other on the stream, so the value is stable and the same for every thread): nothing here can
@@ -1395,8 +1422,9 @@ pow_grind_mx_kernel(bpg::BatchOf<bpg::PowArgs> batch, unsigned long long* result
 // ---------------------------------------------------------------- query openings
 // grid = (num_queries x proofs, n_oracles).  Writes row values and the Merkle path of leaf x into the
 // query record (layout: DESIGN.md section 6).
-__global__ void __launch_bounds__(256) query_initial_kernel(bpg::QueryArgs a) {
+__global__ void __launch_bounds__(256) query_initial_kernel(bpg::ArgPtr<bpg::QueryArgs> args) {
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
+  const bpg::QueryArgs& a = *(const bpg::QueryArgs*)args;
   const uint32_t b = blockIdx.x / a.n_queries, q = blockIdx.x % a.n_queries, o = blockIdx.y;
   const uint64_t x = a.x_index[blockIdx.x];
   const bpg::QueryOracle& orc = a.proof[b].oracle[o];
@@ -1421,8 +1449,9 @@ __global__ void __launch_bounds__(256) query_initial_kernel(bpg::QueryArgs a) {
   if (q == 0 && o == a.leaf_oracle && a.proof[b].first_leaf && threadIdx.x < 4) a.proof[b].first_leaf[threadIdx.x] = orc.digests[x * 4 + threadIdx.x];
 }
 // grid = (num_queries x proofs, n_layers)
-__global__ void __launch_bounds__(64) query_layers_kernel(bpg::QueryLayerArgs a) {
+__global__ void __launch_bounds__(64) query_layers_kernel(bpg::ArgPtr<bpg::QueryLayerArgs> args) {
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
+  const bpg::QueryLayerArgs& a = *(const bpg::QueryLayerArgs*)args;
   const uint32_t b = blockIdx.x / a.n_queries, q = blockIdx.x % a.n_queries, l = blockIdx.y;
   const bpg::QueryLayer& L = a.proof[b].layer[l];
   const uint32_t arity = 1u << a.arity_bits;
@@ -1457,14 +1486,26 @@ int launch_synth_constants(uint64_t* d_out, uint32_t log_n, uint32_t n_const, ui
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
+// the argument blocks of a launch into the ring of its stream: `var` is what the kernel reads
+#define BPG_ARG_BLOCKS(var, a, n, st)                                               \
+  const std::remove_cv_t<std::remove_reference_t<decltype((a)[0])>>* var##_dev = nullptr; \
+  if (int rc_ = arg_put(st, &(a)[0], n, &var##_dev)) return rc_;                    \
+  const auto var = arg_ptr(var##_dev)
+template <class... A>
+constexpr bool blocks_fit() { return ((sizeof(A) <= ARG_BLOCK_MAX) && ...); }
+static_assert(blocks_fit<SynthTraceArgs, PlonkTraceArgs, AuxArgs, QuotArgs, AlphaTabArgs, ChunkArgs, PowerVecArgs, AlphaPowArgs, OpenMulti,
+                         CombineMulti, CombineReduceArgs, FriInitArgs, FriLayerArgs, PowArgs>(),
+              "arg_ring.hpp: ARG_BLOCK_MAX bounds every per-proof argument block");
+static_assert(sizeof(QueryArgs) <= ARG_WHOLE_MAX && sizeof(QueryLayerArgs) <= ARG_WHOLE_MAX, "arg_ring.hpp: ARG_WHOLE_MAX");
 static int check_batch(uint32_t batch) {
-  return batch >= 1 && batch <= MAX_BATCH ? BP_OK : fail(BP_ERR_INVALID_INPUT, "batch of %u proofs: 1..%u can be proved in lock-step", batch, MAX_BATCH);
+  return batch >= 1 && batch <= MAX_LOCKSTEP ? BP_OK : fail(BP_ERR_INVALID_INPUT, "batch of %u proofs: 1..%u can be proved in lock-step", batch, MAX_LOCKSTEP);
 }
 int launch_synth_trace(const SynthTraceArgs* a, uint32_t batch, uint32_t log_n, uint32_t n_cols, uint32_t n_const,
                        uint32_t deg_pow, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   dim3 grid(ceil_div((uint64_t)1 << log_n, 256), n_cols / 4 + 1, batch);
-  synth_trace_kernel<<<grid, 256, 0, st>>>(batch_of(a, batch), log_n, n_cols, n_const, deg_pow);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  synth_trace_kernel<<<grid, 256, 0, st>>>(ab, log_n, n_cols, n_const, deg_pow);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1549,9 +1590,10 @@ int launch_plonk_trace(const PlonkTraceArgs* a, uint32_t batch, uint32_t log_n, 
       return fail(BP_ERR_INVALID_INPUT, "launch_plonk_trace: %u Merkle rows and first arithmetic row %u do not fit 2^%u rows", a[b].n_merkle_rows, a[b].arith_row0, log_n);
     region = std::max(region, a[b].arith_row0 - air::plonk::HASH_ROW0);
   }
-  plonk_trace_kernel<<<dim3(ceil_div((((uint64_t)1 << log_n) / 4) * air::plonk::N_SLOTS, 256), 1, batch), 256, 0, st>>>(batch_of(a, batch), log_n);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  plonk_trace_kernel<<<dim3(ceil_div((((uint64_t)1 << log_n) / 4) * air::plonk::N_SLOTS, 256), 1, batch), 256, 0, st>>>(ab, log_n);
   BPG_LAUNCH_CHECK();
-  plonk_hash_rows_kernel<<<dim3(1, region, batch), 256, 0, st>>>(batch_of(a, batch), log_n);
+  plonk_hash_rows_kernel<<<dim3(1, region, batch), 256, 0, st>>>(ab, log_n);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1566,8 +1608,9 @@ int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint
   if (!log_ports) {
     for (uint32_t b = 0; b < batch; b++)
       if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, nullptr, st)) return rc;
+    BPG_ARG_BLOCKS(ab, a, batch, st);
     KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
-    BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ctl::TERMS_IN_COLUMN>, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, 0u);
+    BPG_LAUNCH_TIMED(kt, aux_suffix_product_kernel<air::ctl::TERMS_IN_COLUMN>, dim3(n_aux, 1, batch), threads, 0, st, ab, log_n, 0u);
     BPG_LAUNCH_CHECK();
     return BP_OK;
   }
@@ -1584,11 +1627,12 @@ int launch_port_products(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint
   for (uint32_t b = 0; b < batch; b++)
     if (int rc = launch_port_terms(a[b], air_id, log_n, trace_stride, pole.d + b * words, st)) return rc;
   {
+    BPG_ARG_BLOCKS(ab, a, batch, st);
     KernelTimer kt(PROF_AUX, st, 16.0 * (double)((uint64_t)1 << log_n) * n_aux * batch, true);
-    BPG_LAUNCH_TIMED(kt, port_running_columns_kernel, dim3(n_aux, 1, batch), threads, 0, st, batch_of(a, batch), log_n, log_ports);
+    BPG_LAUNCH_TIMED(kt, port_running_columns_kernel, dim3(n_aux, 1, batch), threads, 0, st, ab, log_n, log_ports);
     BPG_LAUNCH_CHECK();
   }
-  uint64_t found[MAX_BATCH * 2 * air::prog::MAX_PORTS];
+  uint64_t found[MAX_LOCKSTEP * 2 * air::prog::MAX_PORTS];
   BPG_HIP(hipMemcpyAsync(found, pole.d, batch * words * 8, hipMemcpyDeviceToHost, st));
   BPG_HIP(hipStreamSynchronize(st));
   for (uint32_t b = 0; b < batch; b++)
@@ -1603,8 +1647,8 @@ int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_col
   const uint32_t n_aux = air::any_n_aux(shape), p0 = air::ctl::first_product(air_id);
   if (!n_aux) return BP_OK;
   if (int rc = check_batch(batch)) return rc;
-  const BatchOf<AuxArgs> ab = batch_of(a, batch);
   if (air::prog::is_registered(air_id) && n_aux > 1) return launch_port_products(a, batch, air_id, log_n, (uint64_t)1 << log_n, st);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
   if (air_id == air::KECCAK_F) {  // the helper columns first: the products read them
     keccak_ctl_helpers_kernel<<<dim3(ceil_div((uint64_t)1 << log_n, 256), 1, batch), 256, 0, st>>>(ab, log_n);
     BPG_LAUNCH_CHECK();
@@ -1646,20 +1690,21 @@ int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, 
   // the alpha-power table of every proof's two challenges (a few thousand words, read wave-uniformly)
   CosetTab ct;
   for (int t = 0; t < 16; t++) { ct.v[t] = coset.g_t[t]; ct.v[16 + t] = coset.zh_t[t]; ct.v[32 + t] = coset.zh_inv_t[t]; }
-  BatchOf<AlphaTabArgs> at{};
-  for (uint32_t b = 0; b < batch; b++) at.a[b] = AlphaTabArgs{const_cast<uint64_t*>(qs[b].apow), qs[b].alpha0, qs[b].alpha1};
+  AlphaTabArgs tabs[MAX_LOCKSTEP];
+  for (uint32_t b = 0; b < batch; b++) tabs[b] = AlphaTabArgs{const_cast<uint64_t*>(qs[b].apow), qs[b].alpha0, qs[b].alpha1};
+  BPG_ARG_BLOCKS(at, tabs, batch, st);
   alpha_table_kernel<<<dim3(ceil_div(q.n_constraints, 256), 2, batch), 256, 0, st>>>(at, q.n_constraints, ct);
   BPG_LAUNCH_CHECK();
   const uint32_t n_units = q.n_air_units + q.n_ctl_units, wg_rows = ceil_div(n_units, q.units_per_wg);
-  const BatchOf<QuotArgs> qb = batch_of(qs, batch);
+  BPG_ARG_BLOCKS(qb, qs, batch, st);
   if (q.n_ports)
-    if (int rc = launch_beta_tables(qb, batch, st)) return rc;
+    if (int rc = launch_beta_tables(qb_dev, batch, st)) return rc;
   dim3 g1(ceil_div(rows, 256), wg_rows, batch);
   // algorithmic bytes: every element of the three LDE matrices read once, the two quotient columns written
   // (AIR 8 is counted with the synthetic recursion-shaped proofs it replaces)
   KernelTimer kt(PROF_K5 + (q.air_id < air::COUNT ? q.air_id : 0), st, 8.0 * (double)rows * ((double)q.n_cols + q.n_aux + q.n_const + 2) * batch, true);
   if (bpg::air::prog::is_registered(q.air_id)) {
-    if (int rc = launch_quotient_program(qb, g1, kt, st)) return rc;
+    if (int rc = launch_quotient_program(qb_dev, q, g1, kt, st)) return rc;
   } else air::dispatch(q.air_id, [&](auto A) { BPG_LAUNCH_TIMED(kt, quotient_air_kernel<A.value>, g1, 256, 0, st, qb); });
   kt.stop();
   if (q.side_rows) {
@@ -1678,7 +1723,8 @@ int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, 
 int launch_quotient_chunks(const ChunkArgs* c, uint32_t batch, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   dim3 grid(ceil_div((uint64_t)1 << c[0].log_n, 256), 2, batch);
-  quotient_chunks_kernel<<<grid, 256, 0, st>>>(batch_of(c, batch));
+  BPG_ARG_BLOCKS(cb, c, batch, st);
+  quotient_chunks_kernel<<<grid, 256, 0, st>>>(cb);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1686,13 +1732,15 @@ int launch_power_vectors(const PowerVecArgs* a, uint32_t batch, uint32_t log_n, 
   if (int rc = check_batch(batch)) return rc;
   if (n_points < 1 || n_points > 3) return fail(BP_ERR_INVALID_INPUT, "launch_power_vectors: 1..3 points");
   dim3 grid(ceil_div((uint64_t)1 << log_n, 256), n_points, batch);
-  power_vector_kernel<<<grid, 256, 0, st>>>(batch_of(a, batch), log_n);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  power_vector_kernel<<<grid, 256, 0, st>>>(ab, log_n);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 int launch_alpha_pows(const AlphaPowArgs* a, uint32_t batch, uint32_t count, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
-  alpha_pows_kernel<<<dim3(ceil_div(count, 256), 1, batch), 256, 0, st>>>(batch_of(a, batch), count);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  alpha_pows_kernel<<<dim3(ceil_div(count, 256), 1, batch), 256, 0, st>>>(ab, count);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1707,8 +1755,9 @@ int launch_openings_multi(const OpenMulti* m, uint32_t batch, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   const uint32_t total = m[0].first_col[m[0].n_segs];  // the proofs of a batch have one shape
   if (!total) return BP_OK;
+  BPG_ARG_BLOCKS(mb, m, batch, st);
   KernelTimer kt(PROF_OPENINGS, st, 8.0 * (double)((uint64_t)1 << m[0].log_n) * total * batch, true);  // every coefficient column once
-  BPG_LAUNCH_TIMED(kt, openings_multi_kernel, dim3(total, 1, batch), 256, 0, st, batch_of(m, batch));
+  BPG_LAUNCH_TIMED(kt, openings_multi_kernel, dim3(total, 1, batch), 256, 0, st, mb);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1722,8 +1771,9 @@ int launch_combine_partial_multi(const CombineMulti* m, uint32_t batch, uint32_t
   if (!total_chunks) return BP_OK;
   if (int rc = check_batch(batch)) return rc;
   dim3 grid(ceil_div((uint64_t)1 << m[0].a[0].log_n, 256), total_chunks, batch);
+  BPG_ARG_BLOCKS(mb, m, batch, st);
   KernelTimer kt(PROF_FRI_COMBINE, st, combine_bytes(m[0]) * batch, true);
-  BPG_LAUNCH_TIMED(kt, fri_combine_partial_multi_kernel, grid, 256, 0, st, batch_of(m, batch));
+  BPG_LAUNCH_TIMED(kt, fri_combine_partial_multi_kernel, grid, 256, 0, st, mb);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1731,22 +1781,25 @@ int launch_combine_all(const CombineMulti* m, uint32_t batch, uint64_t* const* d
   if (int rc = check_batch(batch)) return rc;
   GPtrs gp{};
   for (uint32_t b = 0; b < batch; b++) gp.g[b] = d_g[b];
+  BPG_ARG_BLOCKS(mb, m, batch, st);
   KernelTimer kt(PROF_FRI_COMBINE, st, combine_bytes(m[0]) * batch, true);
-  BPG_LAUNCH_TIMED(kt, fri_combine_all_kernel, dim3(ceil_div((uint64_t)1 << m[0].a[0].log_n, 256), 1, batch), 256, 0, st, batch_of(m, batch), gp);
+  BPG_LAUNCH_TIMED(kt, fri_combine_all_kernel, dim3(ceil_div((uint64_t)1 << m[0].a[0].log_n, 256), 1, batch), 256, 0, st, mb, gp);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 int launch_combine_reduce(const CombineReduceArgs* a, uint32_t batch, uint32_t n_chunks, uint32_t log_n, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   dim3 grid(ceil_div((uint64_t)1 << log_n, 256), 6, batch);
-  fri_combine_reduce_kernel<<<grid, 256, 0, st>>>(batch_of(a, batch), n_chunks, log_n);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  fri_combine_reduce_kernel<<<grid, 256, 0, st>>>(ab, n_chunks, log_n);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 int launch_fri_init(const FriInitArgs* a, uint32_t batch, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   uint64_t rows = (uint64_t)1 << (a[0].log_n + a[0].rate_bits);
-  fri_quotient_values_kernel<<<dim3(ceil_div(rows, 256), 1, batch), 256, 0, st>>>(batch_of(a, batch));
+  BPG_ARG_BLOCKS(ab, a, batch, st);
+  fri_quotient_values_kernel<<<dim3(ceil_div(rows, 256), 1, batch), 256, 0, st>>>(ab);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1757,7 +1810,7 @@ int launch_fri_layer_leaves(const FriLayerArgs* as, uint32_t batch, hipStream_t 
   if (int rc = check_batch(batch)) return rc;
   const FriLayerArgs& a = as[0];
   uint64_t n = (uint64_t)1 << (a.log_nl - a.arity_bits + a.rate_bits);
-  const BatchOf<FriLayerArgs> ab = batch_of(as, batch);
+  BPG_ARG_BLOCKS(ab, as, batch, st);
   // the form follows the work of the whole launch (every proof has its own grid.z slice: no wave spans two proofs)
   if (const int ns = mx_sets(n * batch)) {
     if (ns == 4) fri_layer_leaf_mx_kernel<4><<<dim3(ceil_div(n, 256), 1, batch), 256, 0, st>>>(ab);
@@ -1772,14 +1825,15 @@ int launch_fri_fold(const FriLayerArgs* a, uint32_t batch, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   uint64_t n = (uint64_t)1 << (a[0].log_nl - a[0].arity_bits + a[0].rate_bits);
   // 16 M (1 + 1/arity): the layer's M extension values read, M / arity written
+  BPG_ARG_BLOCKS(ab, a, batch, st);
   KernelTimer kt(PROF_FRI_FOLD, st, 16.0 * (double)n * ((1 << a[0].arity_bits) + 1) * batch, true);
-  BPG_LAUNCH_TIMED(kt, fri_fold_kernel, dim3(ceil_div(n, 256), 1, batch), 256, 0, st, batch_of(a, batch));
+  BPG_LAUNCH_TIMED(kt, fri_fold_kernel, dim3(ceil_div(n, 256), 1, batch), 256, 0, st, ab);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
 int launch_pow(const PowArgs* a, uint32_t batch, uint32_t n_candidates, unsigned long long* d_result, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
-  const BatchOf<PowArgs> ab = batch_of(a, batch);
+  BPG_ARG_BLOCKS(ab, a, batch, st);
   const dim3 grid(n_candidates / 256, 1, batch);
   if (poseidon_mx()) {
     const uint32_t* gtab = group_tables();
@@ -1794,7 +1848,9 @@ int launch_query_initial(const QueryArgs& a, uint32_t batch, uint32_t n_oracles,
   if (int rc = check_batch(batch)) return rc;
   if (!a.n_queries || a.n_queries * batch > MAX_BATCH_QUERIES) return fail(BP_ERR_INVALID_INPUT, "query launch: %u x %u indices, at most %u", a.n_queries, batch, MAX_BATCH_QUERIES);
   dim3 grid(a.n_queries * batch, n_oracles);
-  query_initial_kernel<<<grid, 256, 0, st>>>(a);
+  const QueryArgs* ab = nullptr;
+  if (int rc = arg_put(st, &a, 1, &ab)) return rc;
+  query_initial_kernel<<<grid, 256, 0, st>>>(arg_ptr(ab));
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
@@ -1804,7 +1860,9 @@ int launch_query_layers(const QueryLayerArgs& a, uint32_t batch, uint32_t n_laye
   if (!a.n_queries || a.n_queries * batch > MAX_BATCH_QUERIES || n_layers > MAX_FRI_LAYERS)
     return fail(BP_ERR_INVALID_INPUT, "query launch: %u x %u indices, %u layers", a.n_queries, batch, n_layers);
   dim3 grid(a.n_queries * batch, n_layers);
-  query_layers_kernel<<<grid, 64, 0, st>>>(a);
+  const QueryLayerArgs* ab = nullptr;
+  if (int rc = arg_put(st, &a, 1, &ab)) return rc;
+  query_layers_kernel<<<grid, 64, 0, st>>>(arg_ptr(ab));
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

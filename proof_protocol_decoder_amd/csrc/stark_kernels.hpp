@@ -15,19 +15,31 @@ struct Ctl {
   uint64_t pub[4] = {0, 0, 0, 0};
 };
 
-// Proofs of ONE shape proved in lock-step (the seven per-table recursion chains of a transaction,
-// proofgen.cpp): every kernel below takes the argument blocks of up to MAX_BATCH proofs and runs proof
-// blockIdx.z of them; a lone proof is a batch of one.  The blocks travel as kernel arguments (<= 4 KiB).
+// Proofs of ONE shape proved in lock-step (the per-table recursion chains of a transaction, or of the transactions of
+// a group, proofgen.cpp): every batched kernel below reads one argument block per proof and runs proof blockIdx.z of
+// them; a lone proof is a batch of one.  The blocks lie in the argument ring of the launch's stream (arg_ring.hpp): the
+// launcher copies them there and hands the kernel their device address.
+//   MAX_BATCH: the slots ONE transaction's level takes -- seven chains and a rider (Tune::rec_batch clamps to it);
+//   MAX_LOCKSTEP: what a launch accepts -- the levels of three transactions and their riders.
 constexpr uint32_t MAX_BATCH = 8;
+constexpr uint32_t MAX_LOCKSTEP = 24;
+// prover.cpp: `bytes` bytes of argument blocks into the ring of `st` -- a worker's or a lane's own ring where the
+// stream is one of theirs, else the ring that serves the callers' own streams -- *dev = where the kernel reads them
+int arg_ring_put(hipStream_t st, const void* blocks, size_t bytes, const void** dev);
+// What a batched kernel is handed: the blocks through the CONSTANT address space, as the kernel-argument segment they
+// used to travel in is read -- scalar, invariant loads that may be repeated instead of kept in registers.  The kernel
+// casts back to a plain pointer on entry (BPG_ARG_BATCH); the compiler carries the address space through the cast.
 template <class A>
-struct BatchOf {
-  A a[MAX_BATCH];
-};
+using ArgPtr = const __attribute__((address_space(4))) A*;
 template <class A>
-inline BatchOf<A> batch_of(const A* a, uint32_t n) {
-  BatchOf<A> b{};
-  for (uint32_t i = 0; i < n && i < MAX_BATCH; i++) b.a[i] = a[i];
-  return b;
+inline ArgPtr<A> arg_ptr(const A* dev) { return (ArgPtr<A>)dev; }
+#define BPG_ARG_BATCH(T, args) const T* __restrict__ batch = (const T*)(args)
+template <class A>
+inline int arg_put(hipStream_t st, const A* a, uint32_t n, const A** dev) {
+  const void* d = nullptr;
+  const int rc = arg_ring_put(st, a, sizeof(A) * n, &d);
+  *dev = static_cast<const A*>(d);
+  return rc;
 }
 
 struct QuotArgs {
@@ -135,7 +147,7 @@ struct QueryOracle {
   uint32_t n_cols, out_offset;
 };
 // Query openings of a batch: query q of the launch belongs to proof q / n_queries (MAX_BATCH_QUERIES indices in all)
-constexpr uint32_t MAX_BATCH_QUERIES = 256;
+constexpr uint32_t MAX_BATCH_QUERIES = 672;  // 24 x 28, 8 x 84
 struct QueryProof {
   uint64_t* out;
   QueryOracle oracle[4];
@@ -146,7 +158,7 @@ struct QueryArgs {
   uint64_t query_words;
   uint32_t log_n, rate_bits, cap_height, n_queries;  // n_queries: per proof
   uint32_t leaf_oracle = 0;
-  QueryProof proof[MAX_BATCH];
+  QueryProof proof[MAX_LOCKSTEP];
 };
 struct QueryLayer {
   const uint64_t *values, *digests;
@@ -161,7 +173,7 @@ struct QueryLayerArgs {
   uint64_t x_index[MAX_BATCH_QUERIES];
   uint64_t query_words;
   uint32_t rate_bits, cap_height, arity_bits, n_queries;
-  QueryLayerProof proof[MAX_BATCH];
+  QueryLayerProof proof[MAX_LOCKSTEP];
 };
 
 // stark_kernels.hip.  Launchers that take `const X* a, uint32_t batch` run `batch` proofs of one shape in one launch.
@@ -216,8 +228,9 @@ int launch_quotient(const QuotArgs* q, uint32_t batch, const QuotCoset& coset, h
 inline int launch_quotient(const QuotArgs& q, const QuotCoset& coset, hipStream_t st) { return launch_quotient(&q, 1, coset, st); }
 // air_program.hip: launch_quotient's evaluation launch when q.air_id is a registered program (air_program.hpp)
 struct KernelTimer;
-int launch_quotient_program(const BatchOf<QuotArgs>& qb, dim3 grid, KernelTimer& kt, hipStream_t st);
-int launch_beta_tables(const BatchOf<QuotArgs>& qb, uint32_t batch, hipStream_t st);  // a port program's beta powers, behind apow's 48 coset words
+// qb: the blocks as the device sees them (arg_put), q0: the host copy of the first
+int launch_quotient_program(const QuotArgs* qb, const QuotArgs& q0, dim3 grid, KernelTimer& kt, hipStream_t st);
+int launch_beta_tables(const QuotArgs* qb, uint32_t batch, hipStream_t st);  // a port program's beta powers, behind apow's 48 coset words
 // air_program.hip: launch_aux's first half for a registered program with ports: term_0, term_1 of every port into the
 // port's two auxiliary columns (launch_aux then multiplies them up, aux_suffix_product_kernel<TERMS_IN_COLUMN>)
 // A program with a log port ("BPGAIRP3"): those ports' columns get f / d_c instead, which launch_aux then SUMS

@@ -10,6 +10,7 @@ Tune& tune() {
   return t;
 }
 static_assert(MAX_BATCH == 8, "Tune::rec_batch's default is MAX_BATCH");
+static_assert(MAX_LOCKSTEP >= 3 * MAX_BATCH, "a group of three transactions fills one lock-step batch per level");
 }  // namespace bpg
 
 // every knob, in the order bp_debug_tune_state reports them
@@ -40,6 +41,9 @@ void bp_tune_side_lanes(int n) { bpg::tune().side_lanes.store(n < 0 ? 0 : n); }
 void bp_tune_rec_riders(int on) { bpg::tune().rec_riders.store(on != 0); }
 // Another schedule of the same proofs (tune.hpp): like rec_riders outside bp_debug_tune_state's fixed lines.
 void bp_tune_txn_group(int n) { bpg::tune().txn_group.store(n < 1 ? 0 : (n > (int)bpg::MAX_BATCH ? (int)bpg::MAX_BATCH : n)); }
+// Another schedule of the same proofs (tune.hpp): 0 = a group's recursion levels as lock-step batches over the group,
+// 1 = one transaction's recursion at a time.
+void bp_tune_rec_group(int mode) { bpg::tune().rec_group.store(mode == 1 ? 1 : 0); }
 // The switch point between two forms of one kernel (range_mult.hip); like rec_riders outside bp_debug_tune_state's fixed
 // lines.  Out of range = the default.
 void bp_tune_range_lds_log(int log_range) {
@@ -54,6 +58,7 @@ void bp_tune_reset(void) {
 #undef X
   t.rec_riders.store(defaults.rec_riders.load());
   t.txn_group.store(defaults.txn_group.load());
+  t.rec_group.store(defaults.rec_group.load());
   t.range_lds_log.store(defaults.range_lds_log.load());
 }
 

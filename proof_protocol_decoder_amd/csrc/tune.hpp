@@ -73,13 +73,19 @@ struct Tune {
   // Transactions a thread of bp_prove_shard / bp_prove_shard_gi starts at a time: it leases that many provers whose
   // arenas are neighbours (proofgen.cpp: ProverLease) and proves table t of all of them in lock-step batches wherever
   // their shapes agree (prove_tables), t = 0..6, each transaction on its own transcript; the recursion chains
-  // follow one transaction after the other.  1 = one transaction per thread (the schedule up to this knob).  0 = by the
+  // follow (Tune::rec_group).  1 = one transaction per thread (the schedule up to this knob).  0 = by the
   // state: 3 where bp_state_build saw fewer hardware queues than the state has prover streams, else 1.  Measured on the
   // 256-txn block, 20 streams, three alternating runs each (profiles/txn_groups_ab.txt): at 4 queues 35.22 (1) / 35.39
   // (2) / 37.97 (3) txn-proofs/s -- 3 is +7.8 %, 7.8 x the parent's spread, 2 is inside it --; at 32 queues, where every
   // stream has a queue of its own, 40.04 (1) against 39.39 (3): halving the streams at work costs more there than the
   // launches save.  Read once per call.
   std::atomic<int> txn_group{0};
+  // How the recursion of a group follows its table proofs (proofgen.cpp: group_recursion).  0 = level k of the seven
+  // chains of ALL the group's transactions is one lock-step batch (7 g proofs and the riders that fit, MAX_LOCKSTEP at
+  // most), then level k + 1: the recursion of a group costs the launches and host waits of one transaction's.  1 = one
+  // transaction's recursion after the other, batches of seven and a rider (the schedule up to this knob; A/B runs and
+  // tests).  A group of one is the same either way.  Read once per call.  Measurements: profiles/rec_group_ab.txt.
+  std::atomic<int> rec_group{0};
 
   // ---- range-check multiplicities (range_mult.hip)
   // bp_range_multiplicities counts in a per-workgroup LDS histogram up to 2^k values (1 .. 14: 32-bit counters, 64 KiB at

@@ -132,9 +132,9 @@ def program(limbs_per_unit=LIMBS_PER_UNIT):
 
 def kernel_layout():
     """bp_arithmetic_div_layout: the column map csrc/arithmetic_div.hip stores by, in LAYOUT's order"""
-    from ._lib import check, lib
+    from ._lib import check, own
     out = (C.c_uint32 * len(LAYOUT))()
-    check(lib().bp_arithmetic_div_layout(out, len(LAYOUT)))
+    check(own().bp_arithmetic_div_layout(out, len(LAYOUT)))
     return tuple(int(v) for v in out)
 
 

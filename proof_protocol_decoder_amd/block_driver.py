@@ -8,9 +8,13 @@ the whole path is the gather of the N sub-block proofs (a few hundred KB each) t
 finishes the tree (N-1 aggregation proofs) and makes the block proof.  No field data ever crosses
 GPUs, so there is no all-reduce here by construction.
 """
+import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 
+from . import _abi
 from . import proof_gen as pg
+from ._abi import GiChain, ShardOptions  # noqa: F401
+from ._lib import call_for_buffer, own
 
 
 def shard_bounds(n_items, rank, world_size):
@@ -40,12 +44,8 @@ def aggregation_plan(n, shape="balanced"):
         raise ValueError("nothing to aggregate")
     if shape not in TREE_SHAPES:
         raise ValueError("unknown tree shape %r" % (shape,))
-    import ctypes as C
-    L = pg._bind()
-    L.bp_aggregation_plan.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
-    L.bp_aggregation_plan.restype = C.c_uint32
     pairs = (C.c_uint32 * max(2 * (n - 1), 1))()
-    k = L.bp_aggregation_plan(n, TREE_SHAPES[shape], pairs)
+    k = own().bp_aggregation_plan(n, TREE_SHAPES[shape], pairs)
     if k != n - 1:
         raise ValueError("bp_aggregation_plan refused n = %d, shape %r" % (n, shape))
     return [(pairs[2 * i], pairs[2 * i + 1]) for i in range(k)]
@@ -57,15 +57,10 @@ def run_shard(n, n_threads, shape, leaf_fn, agg_fn):
     callables do the work (leaf_fn(i) -> proof, agg_fn(lhs, rhs) -> proof; any Python objects: the buffers that travel
     through the scheduler carry node ids).  Returns (root, [leaves]).  The first exception raised by a callable ends
     the run and is re-raised."""
-    import ctypes as C
     import itertools
     import threading
-    L = pg._bind()
     libc = C.CDLL(None)
     libc.malloc.restype, libc.malloc.argtypes = C.c_void_p, [C.c_size_t]
-    u8pp, szp = C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)
-    LEAF = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, u8pp, szp)
-    AGG = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, u8pp, szp)
     results, errors, lock, ids = {}, [], threading.Lock(), itertools.count(n)
 
     def emit(nid, value, out, out_len):
@@ -99,12 +94,9 @@ def run_shard(n, n_threads, shape, leaf_fn, agg_fn):
         emit(next(ids), agg_fn(a, b), out, out_len)
         return 0
 
-    class Opt(C.Structure):
-        _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
-    L.bp_run_shard.argtypes = [C.c_uint32, C.POINTER(Opt), LEAF, AGG, C.c_void_p, C.c_void_p, u8pp, szp, C.c_void_p, C.c_void_p]
     root, root_len = C.POINTER(C.c_uint8)(), C.c_size_t()
-    opt = Opt(max(1, n_threads), TREE_SHAPES[shape])
-    rc = L.bp_run_shard(n, C.byref(opt), LEAF(leaf), AGG(agg), None, None, C.byref(root), C.byref(root_len), None, None)
+    opt = ShardOptions(max(1, n_threads), TREE_SHAPES[shape])
+    rc = own().bp_run_shard(n, C.byref(opt), _abi.ShardLeafFn(leaf), _abi.ShardAggFn(agg), None, None, C.byref(root), C.byref(root_len), None, None)
     if errors:
         raise errors[0]
     pg.check(rc)
@@ -243,61 +235,37 @@ class BlockDriver:
         return run_shard(n, self.n_threads if n > 1 else 1, shape, lambda i: self.prove_txn(irs[i]), self.prove_agg)
 
     def _prove_shard_native(self, irs, shape):
-        import ctypes as C
-        L = pg._bind()
         raw = b"".join(ir.to_bytes() if isinstance(ir, pg.TxnProofGenIR) else bytes(ir) for ir in irs)
         n = len(irs)
-
-        class Opt(C.Structure):
-            _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
         u8p = C.POINTER(C.c_uint8)
-        L.bp_prove_shard.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(Opt), C.c_void_p,
-                                     C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(u8p), C.POINTER(C.c_size_t)]
         root, root_len = u8p(), C.c_size_t()
         leaves, lens = (u8p * n)(), (C.c_size_t * n)()
-        opt = Opt(self.n_threads, TREE_SHAPES[shape])
-        pg.check(L.bp_prove_shard(self._native._h, raw, len(raw) // n, n, C.byref(opt), None, C.byref(root), C.byref(root_len),
+        opt = ShardOptions(self.n_threads, TREE_SHAPES[shape])
+        pg.check(own().bp_prove_shard(self._native._h, raw, len(raw) // n, n, C.byref(opt), None, C.byref(root), C.byref(root_len),
                                   leaves, lens))
         txns = [self._decode(pg.take_buffer(leaves[i], C.c_size_t(lens[i]))) for i in range(n)]
         return self._decode(pg.take_buffer(root, root_len)), txns
 
     def _aggregate_native(self, subs):
         """the top of the block's tree over proofs made elsewhere (bp_aggregate_proofs)"""
-        import ctypes as C
         if len(subs) == 1:
             return subs[0]
-        L = pg._bind()
-
-        class Opt(C.Structure):
-            _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
         n = len(subs)
         raws = [bytes(p.intern) for p in subs]
         ptrs = (C.c_char_p * n)(*raws)
         lens = (C.c_size_t * n)(*[len(r) for r in raws])
-        L.bp_aggregate_proofs.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(Opt),
-                                          C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-        out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
-        opt = Opt(self.n_threads, 0)
-        pg.check(L.bp_aggregate_proofs(self._native._h, ptrs, lens, n, C.byref(opt), C.byref(out), C.byref(out_len)))
-        return self._decode(pg.take_buffer(out, out_len))
+        opt = ShardOptions(self.n_threads, 0)
+        return self._decode(call_for_buffer(own().bp_aggregate_proofs, self._native._h, ptrs, lens, n, C.byref(opt)))
 
     def prove_shard_gi(self, geni, first, n, gi_options, shape=None):
         """The same for entries [first, first + n) of a decoded block ("BPGGENI1" bytes, decoding.into_txn_proof_gen_ir
         raw form): bp_prove_shard_gi derives every entry's IR and witness in the library (csrc/gi.cpp).
         gi_options: a GiOptions."""
-        import ctypes as C
-        L = pg._bind()
-
-        class Opt(C.Structure):
-            _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
         u8p = C.POINTER(C.c_uint8)
-        L.bp_prove_shard_gi.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(GiOptions),
-                                        C.POINTER(Opt), C.c_void_p, C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(u8p),
-                                        C.POINTER(C.c_size_t)]
         root, root_len = u8p(), C.c_size_t()
         leaves, lens = (u8p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        opt = Opt(self.n_threads, TREE_SHAPES[shape or self.tree_shape])
-        pg.check(L.bp_prove_shard_gi(self._native._h, geni, len(geni), first, n, C.byref(gi_options), C.byref(opt), None,
+        opt = ShardOptions(self.n_threads, TREE_SHAPES[shape or self.tree_shape])
+        pg.check(own().bp_prove_shard_gi(self._native._h, geni, len(geni), first, n, C.byref(gi_options), C.byref(opt), None,
                                      C.byref(root), C.byref(root_len), leaves, lens))
         txns = [self._decode(pg.take_buffer(leaves[i], C.c_size_t(lens[i]))) for i in range(n)]
         return self._decode(pg.take_buffer(root, root_len)), txns
@@ -405,9 +373,6 @@ def synthetic_block_irs(block_number, n_txns, table_log_n, table_width, seed_bas
     table_width = _widths_with_airs(table_width, keccak_air=keccak_air, logic_air=logic_air, memory_air=memory_air,
                                     arithmetic_air=arithmetic_air, byte_packing_air=byte_packing_air,
                                     keccak_sponge_air=keccak_sponge_air, arithmetic_mul_air=arithmetic_mul_air)
-    import ctypes as C
-    L = pg._bind()
-    L.bp_state_root_after.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     irs, root, gas = [], tuple(root0), 0
     for i in range(n_txns):
         seed = seed_base + (block_number << 20) + i
@@ -416,9 +381,7 @@ def synthetic_block_irs(block_number, n_txns, table_log_n, table_width, seed_bas
                                     memory_air=memory_air, arithmetic_air=arithmetic_air,
                                     byte_packing_air=byte_packing_air, keccak_sponge_air=keccak_sponge_air,
                                     arithmetic_mul_air=arithmetic_mul_air))
-        out = (C.c_uint64 * 4)()
-        pg.check(L.bp_state_root_after((C.c_uint64 * 4)(*root), seed, i, out))
-        root, gas = tuple(out), gas + 21000
+        root, gas = pg.state_root_after(root, seed, i), gas + 21000
     return irs
 
 
@@ -543,44 +506,29 @@ def memory_and_byte_packing_work_of_preimages(preimages):
     return log, seqs
 
 
-import ctypes as _C
-
-
-class GiOptions(_C.Structure):
-    """bp_gi_options (include/bpg.h)"""
-    _fields_ = [("block_number", _C.c_uint64), ("table_log_n", _C.c_uint32 * 7), ("table_width", _C.c_uint32 * 7),
-                ("flags", _C.c_uint32)]
+class GiOptions(_abi.GiOptions):
+    """bp_gi_options with its flags (BP_GI_*) by name"""
     KECCAK_AIR, KECCAK_TRIE_NODES, MEMORY_AIR, BYTE_PACKING_AIR, KECCAK_SPONGE_AIR, LOGIC_AIR = 1, 2, 4, 8, 16, 32
 
     @staticmethod
     def make(block_number, table_log_n, table_width, keccak_air=False, keccak_trie_nodes=False, memory_air=False,
              byte_packing_air=False, keccak_sponge_air=False, logic_air=False):
-        return GiOptions(block_number, (_C.c_uint32 * 7)(*table_log_n), (_C.c_uint32 * 7)(*table_width),
+        return GiOptions(block_number, (C.c_uint32 * 7)(*table_log_n), (C.c_uint32 * 7)(*table_width),
                          (1 if keccak_air else 0) | (2 if keccak_trie_nodes else 0) | (4 if memory_air else 0)
                          | (8 if byte_packing_air else 0) | (16 if keccak_sponge_air else 0) | (32 if logic_air else 0))
-
-
-class GiChain(_C.Structure):
-    """bp_gi_chain (include/bpg.h): txn number, gas and state root where an entry starts"""
-    _fields_ = [("txn_number", _C.c_uint64), ("gas_used", _C.c_uint64), ("state_root", _C.c_uint64 * 4)]
 
 
 def gi_irs(geni, gi_options):
     """The 25-word IRs of every entry of a decoded block as the library derives them (bp_gi_chain_start, bp_gi_entry_ir):
     what irs_from_generation_inputs computes in Python, as bytes."""
-    L = pg._bind()
-    n = _C.c_uint32()
-    L.bp_gi_count.argtypes = [_C.c_char_p, _C.c_size_t, _C.POINTER(_C.c_uint32)]
-    L.bp_gi_chain_start.argtypes = [_C.c_char_p, _C.c_size_t, _C.POINTER(GiChain)]
-    L.bp_gi_entry_ir.argtypes = [_C.c_char_p, _C.c_size_t, _C.c_uint32, _C.POINTER(GiOptions), _C.POINTER(GiChain),
-                                 _C.POINTER(_C.c_uint64)]
-    pg.check(L.bp_gi_count(geni, len(geni), _C.byref(n)))
-    chain = GiChain()
-    pg.check(L.bp_gi_chain_start(geni, len(geni), _C.byref(chain)))
+    L = own()
+    n = C.c_uint32()
+    pg.check(L.bp_gi_count(geni, len(geni), C.byref(n)))
+    chain = gi_chain_start(geni)
     out = []
     for k in range(n.value):
-        ir = (_C.c_uint64 * 25)()
-        pg.check(L.bp_gi_entry_ir(geni, len(geni), k, _C.byref(gi_options), _C.byref(chain), ir))
+        ir = (C.c_uint64 * _abi.BP_IR_WORDS)()
+        pg.check(L.bp_gi_entry_ir(geni, len(geni), k, C.byref(gi_options), C.byref(chain), ir))
         out.append(bytes(ir))
     return out
 
@@ -589,22 +537,14 @@ def generate_txn_proof_gi(p_state, geni, entry, gi_options, chain, abort_signal=
     """generate_txn_proof(&ProverState, GenerationInputs, abort) (proof_gen.rs:39-43) for entry `entry` of a decoded
     block: bp_generate_txn_proof_gi.  chain: a GiChain holding what the entries before left (gi_chain_start for entry
     0); moved past the entry."""
-    L = pg._bind()
-    out, n = pg._out()
-    L.bp_generate_txn_proof_gi.argtypes = [_C.c_void_p, _C.c_char_p, _C.c_size_t, _C.c_uint32, _C.POINTER(GiOptions),
-                                           _C.POINTER(GiChain), _C.c_void_p, _C.POINTER(_C.POINTER(_C.c_uint8)),
-                                           _C.POINTER(_C.c_size_t)]
-    pg.check(L.bp_generate_txn_proof_gi(p_state._h, geni, len(geni), entry, _C.byref(gi_options), _C.byref(chain),
-                                        _C.byref(abort_signal) if abort_signal is not None else None, _C.byref(out), _C.byref(n)))
-    intern = pg.take_buffer(out, n)
+    intern = call_for_buffer(own().bp_generate_txn_proof_gi, p_state._h, geni, len(geni), entry, C.byref(gi_options),
+                             C.byref(chain), C.byref(abort_signal) if abort_signal is not None else None)
     return pg.GeneratedTxnProof(pg.public_values_of(intern)[0], intern)
 
 
 def gi_chain_start(geni):
-    L = pg._bind()
-    L.bp_gi_chain_start.argtypes = [_C.c_char_p, _C.c_size_t, _C.POINTER(GiChain)]
     chain = GiChain()
-    pg.check(L.bp_gi_chain_start(geni, len(geni), _C.byref(chain)))
+    pg.check(own().bp_gi_chain_start(geni, len(geni), C.byref(chain)))
     return chain
 
 

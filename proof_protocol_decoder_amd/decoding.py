@@ -8,12 +8,11 @@ the ABI's byte form and parses the resulting `GenerationInputs` back into object
 `TxnProofGenIR = GenerationInputs` (protocol_decoder/src/types.rs:48); `BlockMetadata` / `BlockHashes` are
 upstream plonky2_evm types and travel as opaque bytes.
 """
-import ctypes as C
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
 from . import trace_protocol as tp
-from ._lib import check, lib, take_buffer
+from ._lib import call_for_buffer, own
 from .partial_trie import PartialTrie, Reader
 
 
@@ -136,12 +135,8 @@ def _parse_ir(r: Reader) -> GenerationInputs:
 def generation_inputs_bytes(bt: "tp.BlockTrace", other: OtherBlockData, code_table=None) -> bytes:
     """`BlockTrace::into_txn_proof_gen_ir` as the library emits it: the "BPGGENI1" buffer (include/bpg.h) that
     bp_generate_txn_proof_gi / bp_prove_shard_gi take as it is."""
-    L = lib()
-    L.bp_decode_block_trace.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     raw = trace_to_binary(bt, other, code_table)
-    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-    check(L.bp_decode_block_trace(raw, len(raw), C.byref(out), C.byref(n)))
-    return take_buffer(out, n)
+    return call_for_buffer(own().bp_decode_block_trace, raw, len(raw))
 
 
 def parse_generation_inputs(geni: bytes, with_final_root=False):
@@ -157,15 +152,4 @@ def parse_generation_inputs(geni: bytes, with_final_root=False):
 def into_txn_proof_gen_ir(bt: "tp.BlockTrace", other: OtherBlockData, code_table=None, with_final_root=False):
     """`BlockTrace::into_txn_proof_gen_ir(p_meta, other_data)` -> Vec<TxnProofGenIR>.  Raises BpgError
     (code -2) where the reference returns a TraceParsingError or panics on a malformed payload."""
-    L = lib()
-    L.bp_decode_block_trace.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    raw = trace_to_binary(bt, other, code_table)
-    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-    check(L.bp_decode_block_trace(raw, len(raw), C.byref(out), C.byref(n)))
-    r = Reader(take_buffer(out, n))
-    if r.take(8) != b"BPGGENI1":
-        raise ValueError("bad magic")
-    irs = [_parse_ir(r) for _ in range(r.u32())]
-    final_root = r.take(32)
-    assert r.done()
-    return (irs, final_root) if with_final_root else irs
+    return parse_generation_inputs(generation_inputs_bytes(bt, other, code_table), with_final_root)

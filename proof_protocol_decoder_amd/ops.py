@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import KNOBS, StarkCfg, check, lib, take_buffer
+from ._lib import KNOBS, StarkCfg, call_for_buffer, check, lib, own  # noqa: F401 (lib: for callers of ops.lib)
 
 NTT_FWD_BR2NAT, NTT_INV_NAT2BR, NTT_FWD_NAT, NTT_INV_NAT = 0, 1, 2, 3
 
@@ -33,7 +33,7 @@ def tuned(**knobs):
     unknown = sorted(set(knobs) - set(KNOBS))
     if unknown:
         raise TypeError("no such knob: %s (there are: %s)" % (", ".join(unknown), ", ".join(KNOBS)))
-    L = lib()
+    L = own()
     _tuned_active = True
     try:
         for name, value in knobs.items():
@@ -47,7 +47,7 @@ def tuned(**knobs):
 def tune_state():
     """bp_debug_tune_state: the current value of every knob, "name=value" lines in a fixed order."""
     buf = C.create_string_buffer(1024)
-    check(lib().bp_debug_tune_state(buf, len(buf)))
+    check(own().bp_debug_tune_state(buf, len(buf)))
     return buf.value.decode()
 
 
@@ -62,7 +62,7 @@ def ntt_batch_(cols, direction):
     """In-place NTT of a [n_cols, n] column-major batch."""
     _require_cuda(cols)
     n_cols, n = cols.shape
-    check(lib().bp_ntt_batch(cols.data_ptr(), n.bit_length() - 1, n_cols, n, direction, _stream()))
+    check(own().bp_ntt_batch(cols.data_ptr(), n.bit_length() - 1, n_cols, n, direction, _stream()))
     return cols
 
 
@@ -71,7 +71,7 @@ def intt_batch(values, out=None):
     _require_cuda(values)
     n_cols, n = values.shape
     out = torch.empty_like(values) if out is None else out
-    check(lib().bp_intt_batch(values.data_ptr(), n, out.data_ptr(), n, n.bit_length() - 1, n_cols, _stream()))
+    check(own().bp_intt_batch(values.data_ptr(), n, out.data_ptr(), n, n.bit_length() - 1, n_cols, _stream()))
     return out
 
 
@@ -81,14 +81,14 @@ def lde_batch(inp, rate_bits, from_coeffs=False):
     n_cols, n = inp.shape
     coeffs = torch.empty_like(inp)
     lde = torch.empty((n_cols, n << rate_bits), dtype=torch.int64, device=inp.device)
-    check(lib().bp_lde_batch(inp.data_ptr(), n, coeffs.data_ptr(), n, lde.data_ptr(), n << rate_bits,
+    check(own().bp_lde_batch(inp.data_ptr(), n, coeffs.data_ptr(), n, lde.data_ptr(), n << rate_bits,
                              n.bit_length() - 1, rate_bits, n_cols, int(from_coeffs), _stream()))
     return coeffs, lde
 
 
 def poseidon_perm_batch_(states):
     _require_cuda(states)
-    check(lib().bp_poseidon_perm_batch(states.data_ptr(), states.numel() // 12, _stream()))
+    check(own().bp_poseidon_perm_batch(states.data_ptr(), states.numel() // 12, _stream()))
     return states
 
 
@@ -98,7 +98,7 @@ def field_ops(a, b):
     _require_cuda(b)
     n = a.numel()
     out = torch.empty((15, n), dtype=torch.int64, device=a.device)
-    check(lib().bp_debug_field_ops(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, _stream()))
+    check(own().bp_debug_field_ops(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, _stream()))
     return out
 
 
@@ -108,7 +108,7 @@ def mul_pow2(a):
     _require_cuda(a)
     n = a.numel()
     out = torch.empty((21, n), dtype=torch.int64, device=a.device)
-    check(lib().bp_debug_mul_pow2(a.data_ptr(), out.data_ptr(), n, _stream()))
+    check(own().bp_debug_mul_pow2(a.data_ptr(), out.data_ptr(), n, _stream()))
     return out
 
 
@@ -135,7 +135,7 @@ def air_describe(air_id, n_cols=0, n_const=0, deg_pow=1):
     """bp_air_describe: shape and constraint list of a built-in AIR."""
     from ._lib import AirDesc
     d = AirDesc()
-    check(lib().bp_air_describe(air_id, n_cols, n_const, deg_pow, C.byref(d)))
+    check(own().bp_air_describe(air_id, n_cols, n_const, deg_pow, C.byref(d)))
     return d
 
 
@@ -145,19 +145,19 @@ def air_register(words):
     Every entry that takes an air_id takes it.  Registering the same words again returns the same id."""
     words = np.ascontiguousarray(words, dtype=np.uint64)
     air_id = C.c_uint32()
-    check(lib().bp_air_register(words.ctypes.data, words.size, C.byref(air_id)))
+    check(own().bp_air_register(words.ctypes.data, words.size, C.byref(air_id)))
     return air_id.value
 
 
 def air_unregister(air_id):
     """bp_air_unregister: forgets a registered program (and frees its device images)."""
-    check(lib().bp_air_unregister(air_id))
+    check(own().bp_air_unregister(air_id))
 
 
 def air_program_digest(air_id):
     """bp_air_program_digest: the Keccak-256 of a registered program's bytes."""
     out = C.create_string_buffer(32)
-    check(lib().bp_air_program_digest(air_id, out))
+    check(own().bp_air_program_digest(air_id, out))
     return out.raw
 
 
@@ -169,7 +169,7 @@ def air_trace(air_id, log_n, seed=0, inputs=None, device="cuda"):
     if inputs is not None:
         _require_cuda(inputs)
         assert inputs.shape == in_shape(log_n)
-    check(getattr(lib(), "bp_%s_trace" % name)(inputs.data_ptr() if inputs is not None else None, seed, log_n, out.data_ptr(),
+    check(getattr(own(), "bp_%s_trace" % name)(inputs.data_ptr() if inputs is not None else None, seed, log_n, out.data_ptr(),
                                                _stream()))
     return out
 
@@ -221,7 +221,7 @@ def arithmetic_div_trace(log_n, inputs, device="cuda"):
             raise ValueError("arithmetic_div_trace: inputs are [%d, 9]: got %s" % (1 << log_n, tuple(inputs.shape)))
         device = inputs.device
     out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=device)
-    check(lib().bp_arithmetic_div_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
+    check(own().bp_arithmetic_div_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
     return out
 
 
@@ -238,10 +238,10 @@ def quotient_eval(cfg, trace_lde, aux_lde, const_lde, ctl, alphas, air_id=AIR_SY
     if const_lde is not None:
         _require_cuda(const_lde)
     rows = trace_lde.shape[1]
-    scratch = torch.empty(int(lib().bp_quotient_scratch_words(air_id, C.byref(cfg))), dtype=torch.int64,
+    scratch = torch.empty(int(own().bp_quotient_scratch_words(air_id, C.byref(cfg))), dtype=torch.int64,
                           device=trace_lde.device)
     out = torch.empty((2, rows), dtype=torch.int64, device=trace_lde.device)
-    check(lib().bp_quotient_eval(air_id, C.byref(cfg), trace_lde.data_ptr(), aux_lde.data_ptr(),
+    check(own().bp_quotient_eval(air_id, C.byref(cfg), trace_lde.data_ptr(), aux_lde.data_ptr(),
                                  const_lde.data_ptr() if const_lde is not None else None,
                                  (C.c_uint64 * 4)(*[int(x) for x in ctl]), (C.c_uint64 * 2)(*[int(x) for x in alphas]),
                                  scratch.data_ptr(), out.data_ptr(), _stream()))
@@ -310,7 +310,7 @@ def check_air_trace(air_id, trace, consts=None, pub=None, max_rows=16, max_viol=
         _require_cuda(consts)
     _check_shapes(n, consts, pub)
     cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, deg_pow)
-    return _check_call(lib().bp_air_check_trace, air_id, cfg, trace.data_ptr(), trace.stride(0),
+    return _check_call(own().bp_air_check_trace, air_id, cfg, trace.data_ptr(), trace.stride(0),
                        consts.data_ptr() if consts is not None else None, pub, max_rows,
                        4 * max_rows + 64 if max_viol is None else max_viol, _stream())
 
@@ -325,7 +325,7 @@ def check_air_trace_host(air_id, trace, consts=None, pub=None, max_rows=16, max_
         consts = np.ascontiguousarray(consts, dtype=np.uint64)
     _check_shapes(n, consts, pub)
     cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, deg_pow)
-    return _check_call(lib().bp_air_check_trace_host, air_id, cfg, trace.ctypes.data, trace.strides[0] // 8,
+    return _check_call(own().bp_air_check_trace_host, air_id, cfg, trace.ctypes.data, trace.strides[0] // 8,
                        consts.ctypes.data if consts is not None else None, pub, max_rows,
                        4 * max_rows + 64 if max_viol is None else max_viol)
 
@@ -334,7 +334,7 @@ def fri_fold(values, log_nl, rate_bits, shift, beta, arity_bits=4):
     """bp_fri_fold: values [n_l << rate_bits, 2] (coset-major ext elements) -> next layer [(n_l >> 4) << rate_bits, 2]."""
     _require_cuda(values)
     out = torch.empty(((1 << (log_nl - arity_bits)) << rate_bits, 2), dtype=torch.int64, device=values.device)
-    check(lib().bp_fri_fold(values.data_ptr(), log_nl, rate_bits, arity_bits, int(shift),
+    check(own().bp_fri_fold(values.data_ptr(), log_nl, rate_bits, arity_bits, int(shift),
                             (C.c_uint64 * 2)(int(beta[0]), int(beta[1])), out.data_ptr(), _stream()))
     return out
 
@@ -347,7 +347,7 @@ def openings(coeffs, z0, z1=None):
     out = torch.zeros((n_cols, 4), dtype=torch.int64, device=coeffs.device)
     a0 = (C.c_uint64 * 2)(int(z0[0]), int(z0[1]))
     a1 = (C.c_uint64 * 2)(int(z1[0]), int(z1[1])) if z1 is not None else None
-    check(lib().bp_openings(coeffs.data_ptr(), n, n.bit_length() - 1, n_cols, a0, a1, pw.data_ptr(), out.data_ptr(),
+    check(own().bp_openings(coeffs.data_ptr(), n, n.bit_length() - 1, n_cols, a0, a1, pw.data_ptr(), out.data_ptr(),
                             _stream()))
     return out
 
@@ -355,7 +355,7 @@ def openings(coeffs, z0, z1=None):
 def pow_grind(state, pos, bits):
     """bp_pow_grind: smallest nonce for the 12-word sponge `state` (host ints) with `bits` leading zeros."""
     nonce = C.c_uint64()
-    check(lib().bp_pow_grind((C.c_uint64 * 12)(*[int(x) for x in state]), pos, bits, C.byref(nonce), _stream()))
+    check(own().bp_pow_grind((C.c_uint64 * 12)(*[int(x) for x in state]), pos, bits, C.byref(nonce), _stream()))
     return nonce.value
 
 
@@ -364,9 +364,9 @@ def merkle_commit(lde, log_n, rate_bits, cap_height):
     _require_cuda(lde)
     n_cols, rows = lde.shape
     assert rows == 1 << (log_n + rate_bits)
-    words = lib().bp_merkle_digest_words(log_n + rate_bits, cap_height)
+    words = own().bp_merkle_digest_words(log_n + rate_bits, cap_height)
     dig = torch.empty((words // 4, 4), dtype=torch.int64, device=lde.device)
-    check(lib().bp_merkle_commit(lde.data_ptr(), rows, n_cols, log_n, rate_bits, cap_height, dig.data_ptr(),
+    check(own().bp_merkle_commit(lde.data_ptr(), rows, n_cols, log_n, rate_bits, cap_height, dig.data_ptr(),
                                  _stream()))
     return dig
 
@@ -377,12 +377,13 @@ def stark_cfg(log_n, n_cols, n_const=0, deg_pow=1, rate_bits=1, cap_height=4, nu
                     final_poly_bits)
 
 
+def _words(proof_bytes):
+    return np.frombuffer(proof_bytes, dtype=np.uint64).copy()
+
+
 def stark_prove_air(air_id, cfg, seed, const_seed=0, device=0):
     """One table proof on AIR `air_id`, witness generated on the device.  Returns proof words (u64)."""
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t()
-    check(lib().bp_stark_prove_air(air_id, C.byref(cfg), seed, const_seed, device, C.byref(out), C.byref(n)))
-    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+    return _words(call_for_buffer(own().bp_stark_prove_air, air_id, C.byref(cfg), seed, const_seed, device))
 
 
 def stark_prove_trace(air_id, cfg, trace, consts=None, pub=None, device=None):
@@ -397,13 +398,10 @@ def stark_prove_trace(air_id, cfg, trace, consts=None, pub=None, device=None):
     if trace.shape[0] != cfg.n_cols or trace.shape[1] != 1 << cfg.log_n:
         raise ValueError("the trace is %s, the configuration says [%d, %d]" % (tuple(trace.shape), cfg.n_cols, 1 << cfg.log_n))
     torch.cuda.synchronize(trace.device)  # the library proves on a stream of its own
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t()
     pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
     dev = trace.device.index if device is None else device
-    check(lib().bp_stark_prove_trace(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
-                                     consts.data_ptr() if consts is not None else None, pub_arr, dev or 0, C.byref(out), C.byref(n)))
-    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+    return _words(call_for_buffer(own().bp_stark_prove_trace, air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
+                                  consts.data_ptr() if consts is not None else None, pub_arr, dev or 0))
 
 
 def air_port_products(air_id, trace, ctl, consts=None, pub=None):
@@ -420,7 +418,7 @@ def air_port_products(air_id, trace, ctl, consts=None, pub=None):
     cfg = _check_cfg(air_id, n_cols, consts.shape[0] if consts is not None else 0, n.bit_length() - 1, 1)
     out = torch.empty((d.n_aux, n), dtype=torch.int64, device=trace.device)
     pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
-    check(lib().bp_air_port_products(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
+    check(own().bp_air_port_products(air_id, C.byref(cfg), trace.data_ptr(), trace.stride(0),
                                      consts.data_ptr() if consts is not None else None, pub_arr,
                                      (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
     return out
@@ -446,7 +444,7 @@ def range_multiplicities(values, log_range, filter=None, out=None):
         raise ValueError("out holds 2^log_range words")
     first_bad = C.c_uint64()
     try:
-        check(lib().bp_range_multiplicities(values.data_ptr(), values.stride(0), n_cols, n_rows,
+        check(own().bp_range_multiplicities(values.data_ptr(), values.stride(0), n_cols, n_rows,
                                             filter.data_ptr() if filter is not None else None, log_range, out.data_ptr(),
                                             C.byref(first_bad), _stream()))
     except BpgError as e:
@@ -463,7 +461,7 @@ def debug_air_aux(air_id, trace, ctl):
     _check_shapes(n, None, None)
     cfg = _check_cfg(air_id, n_cols, 0, n.bit_length() - 1, 1)
     out = torch.empty((air_describe(air_id).n_aux, n), dtype=torch.int64, device=trace.device)
-    check(lib().bp_debug_air_aux(air_id, C.byref(cfg), trace.data_ptr(), (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
+    check(own().bp_debug_air_aux(air_id, C.byref(cfg), trace.data_ptr(), (C.c_uint64 * 4)(*[int(x) for x in ctl]), out.data_ptr(), _stream()))
     return out
 
 
@@ -505,11 +503,8 @@ def stark_prove_table_set(tables, links, skip_link_check=False, device=0):
     ta, la, keep = _set_arguments(tables, links)
     if torch.cuda.is_available():
         torch.cuda.synchronize()  # the library proves on a stream of its own
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t()
-    check(lib().bp_stark_prove_table_set(ta, len(tables), la, len(links), BP_SET_SKIP_LINK_CHECK if skip_link_check else 0,
-                                         device, C.byref(out), C.byref(n)))
-    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+    return _words(call_for_buffer(own().bp_stark_prove_table_set, ta, len(tables), la, len(links),
+                                  BP_SET_SKIP_LINK_CHECK if skip_link_check else 0, device))
 
 
 class SetLinkCheck:
@@ -556,10 +551,10 @@ def check_table_set(tables, links, device=0):
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     rep = SetReport()
-    rc = lib().bp_check_table_set(ta, len(tables), la, len(links), device, C.byref(rep))
+    rc = own().bp_check_table_set(ta, len(tables), la, len(links), device, C.byref(rep))
     message = ""
     if rc != 0:
-        message = lib().bp_last_error().decode("utf-8", "replace")
+        message = own().bp_last_error().decode("utf-8", "replace")
         if rc != BP_ERR_VERIFY:
             raise BpgError(rc, message)
     checks = []
@@ -585,7 +580,7 @@ def stark_verify_table_set(tables, links, proof, const_caps=None):
                 keep.append(cap)
                 caps[k] = cap.ctypes.data_as(C.POINTER(C.c_uint64))
     proof = np.ascontiguousarray(proof, dtype=np.uint64)
-    check(lib().bp_stark_verify_table_set(ta, len(tables), caps, la, len(links), proof.tobytes(), proof.size * 8))
+    check(own().bp_stark_verify_table_set(ta, len(tables), caps, la, len(links), proof.tobytes(), proof.size * 8))
 
 
 def stark_verify_air(air_id, cfg, proof, const_cap=None, pub=None):
@@ -597,12 +592,9 @@ def stark_verify_air(air_id, cfg, proof, const_cap=None, pub=None):
         const_cap = np.ascontiguousarray(const_cap, dtype=np.uint64)
         cap = const_cap.ctypes.data_as(C.POINTER(C.c_uint64))
     pub_arr = (C.c_uint64 * 4)(*[int(x) for x in pub]) if pub is not None else None
-    check(lib().bp_stark_verify_air_pub(air_id, C.byref(cfg), cap, pub_arr, proof.tobytes(), proof.size * 8))
+    check(own().bp_stark_verify_air_pub(air_id, C.byref(cfg), cap, pub_arr, proof.tobytes(), proof.size * 8))
 
 
 def stark_prove_synthetic(cfg, seed, const_seed=0, device=0):
     """One table proof on the synthetic AIR, witness generated on the device.  Returns proof words (u64)."""
-    out = C.POINTER(C.c_uint8)()
-    n = C.c_size_t()
-    check(lib().bp_stark_prove_synthetic(C.byref(cfg), seed, const_seed, device, C.byref(out), C.byref(n)))
-    return np.frombuffer(take_buffer(out, n), dtype=np.uint64).copy()
+    return _words(call_for_buffer(own().bp_stark_prove_synthetic, C.byref(cfg), seed, const_seed, device))

@@ -13,13 +13,17 @@ import ctypes as C
 import struct
 from dataclasses import dataclass
 
-from ._lib import BpgError, check, lib, take_buffer
+from . import _abi
+from ._abi import BpConfig, TxnWitness, WitnessLookup, WitnessTable  # noqa: F401
+from ._lib import BpgError, call_for_buffer, check, lib, own, take_buffer
 
-NUM_TABLES = 7
+NUM_TABLES = _abi.BP_NUM_TABLES
 TABLES = ("arithmetic", "byte_packing", "cpu", "keccak", "keccak_sponge", "logic", "memory")
-IR_WORDS, PV_WORDS = 25, 13
+IR_WORDS, PV_WORDS = _abi.BP_IR_WORDS, _abi.BP_PV_WORDS
 
 ProofGenError = BpgError  # Result<T, ProofGenError(String)> -> exception carrying the message
+_bind = lib   # every prototype is applied when the library is loaded (_abi.PROTOTYPES); the name stays for its callers
+             # outside the package; the calls below go through the package's own handle (_lib.own)
 
 # The AIRs that can prove a table of a transaction instead of the synthetic one (csrc/txn_tables.hpp holds the same rows;
 # include/bpg.h lists them above bp_ir_set_*_air): TxnProofGenIR field, table index, AIR id, setter, the bp_txn_witness
@@ -36,61 +40,6 @@ TXN_TABLE_AIRS = (
 # table index -> (pointer, count, has_* member of bp_txn_witness, words per item)
 WITNESS_FIELDS = {t: (*members, words) for _, t, _, _, members, words in TXN_TABLE_AIRS}
 KECCAK_LANES, SPONGE_ROW_WORDS = WITNESS_FIELDS[3][3], WITNESS_FIELDS[4][3]
-
-
-class BpConfig(C.Structure):
-    """bp_config (include/bpg.h)."""
-    _fields_ = ([("table_log_lo", C.c_uint32 * NUM_TABLES), ("table_log_hi", C.c_uint32 * NUM_TABLES)]
-                + [(n, C.c_uint32) for n in ("stark_rate_bits", "stark_cap_height", "stark_num_queries",
-                                             "stark_pow_bits", "arity_bits", "final_poly_bits", "rec_log_n",
-                                             "rec_n_cols", "rec_n_const", "rec_rate_bits", "rec_num_queries",
-                                             "rec_pow_bits", "shrink_depth", "rec_air_id")]
-                + [("device", C.c_int32), ("n_workers", C.c_uint32), ("arena_bytes", C.c_uint64)])
-
-
-def _bind():
-    L = lib()
-    if getattr(L, "_pg_bound", False):
-        return L
-    vp, u8p, szp = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)
-    L.bp_config_default.argtypes = [C.POINTER(BpConfig)]
-    L.bp_config_default.restype = None
-    L.bp_state_build.argtypes = [C.POINTER(BpConfig), C.POINTER(vp)]
-    L.bp_state_free.argtypes = [vp]
-    L.bp_state_free.restype = None
-    L.bp_state_device_bytes.argtypes = [vp]
-    L.bp_state_device_bytes.restype = C.c_uint64
-    L.bp_state_warnings.argtypes = [vp]
-    L.bp_state_warnings.restype = C.c_char_p
-    L.bp_generate_txn_proof.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(u8p), szp]
-    L.bp_generate_agg_proof.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t, C.c_int,
-                                        C.POINTER(u8p), szp]
-    L.bp_generate_block_proof.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(u8p), szp,
-                                          C.POINTER(C.c_uint64)]
-    L.bp_verifier_state_from_prover.argtypes = [vp, C.POINTER(vp)]
-    L.bp_verifier_state_build.argtypes = [C.POINTER(BpConfig), C.POINTER(vp)]
-    L.bp_verifier_state_from_caps.argtypes = [C.POINTER(BpConfig), C.POINTER(C.c_uint64), C.POINTER(vp)]
-    L.bp_verifier_state_free.argtypes = [vp]
-    L.bp_verifier_state_free.restype = None
-    L.bp_verify_block_proof.argtypes = [vp, C.c_char_p, C.c_size_t]
-    L.bp_verify_proof.argtypes = [vp, C.c_char_p, C.c_size_t]
-    L.bp_ir_encode.argtypes = [C.c_uint64] * 4 + [C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32),
-                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.bp_ir_encode_dummy.argtypes = [C.c_uint64] * 3 + [C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32),
-                                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    for row in TXN_TABLE_AIRS:
-        getattr(L, row[3]).argtypes = [C.POINTER(C.c_uint64), C.c_int]
-    L.bp_keccak256_sponge_rows.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
-                                           C.POINTER(C.c_size_t)]
-    L.bp_keccak256_permutation_inputs.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
-                                                  C.POINTER(C.c_size_t)]
-    L.bp_generate_txn_proof_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    L.bp_generate_txn_proof_keccak.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t,
-                                               C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    L.bp_proof_public_values.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
-    L._pg_bound = True
-    return L
 
 
 @dataclass(frozen=True)
@@ -111,15 +60,13 @@ class PublicValues:
 
 def state_root_after(root_before, seed, txn_number):
     """bp_state_root_after: the synthetic state transition of one (non-dummy) transaction."""
-    L = _bind()
-    L.bp_state_root_after.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     out = (C.c_uint64 * 4)()
-    check(L.bp_state_root_after((C.c_uint64 * 4)(*root_before), seed, txn_number, out))
+    check(own().bp_state_root_after((C.c_uint64 * 4)(*root_before), seed, txn_number, out))
     return tuple(out)
 
 
 def public_values_of(proof_bytes):
-    L = _bind()
+    L = own()
     pv = (C.c_uint64 * PV_WORDS)()
     kind = C.c_int()
     check(L.bp_proof_public_values(proof_bytes, len(proof_bytes), pv, C.byref(kind)))
@@ -152,7 +99,7 @@ class TxnProofGenIR:
                             # seeded witness (bp_generate_txn_proof_witness); like keccak_inputs not part of the 25-word IR
 
     def to_bytes(self):
-        L = _bind()
+        L = own()
         out = (C.c_uint64 * IR_WORDS)()
         root = (C.c_uint64 * 4)(*self.state_root_before)
         logs, widths = (C.c_uint32 * NUM_TABLES)(*self.table_log_n), (C.c_uint32 * NUM_TABLES)(*self.table_width)
@@ -219,17 +166,17 @@ class ProverState:
 
     @property
     def device_bytes(self):
-        return _bind().bp_state_device_bytes(self._h)
+        return own().bp_state_device_bytes(self._h)
 
     @property
     def warnings(self):
         """What bp_state_build found about its environment (GPU_MAX_HW_QUEUES below n_workers, the host-wait mode
         the device was left in); "" when there is nothing to say."""
-        return _bind().bp_state_warnings(self._h).decode("utf-8", "replace") if self._h else ""
+        return own().bp_state_warnings(self._h).decode("utf-8", "replace") if self._h else ""
 
     def close(self):
         if self._h:
-            _bind().bp_state_free(self._h)
+            own().bp_state_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -245,7 +192,7 @@ class ProverStateBuilder:
 
     def __init__(self):
         self.cfg = BpConfig()
-        _bind().bp_config_default(C.byref(self.cfg))
+        own().bp_config_default(C.byref(self.cfg))
 
     def _set(self, idx, size):
         self.cfg.table_log_lo[idx], self.cfg.table_log_hi[idx] = size.start, size.stop
@@ -269,12 +216,12 @@ class ProverStateBuilder:
 
     def build(self):
         h = C.c_void_p()
-        check(_bind().bp_state_build(C.byref(self.cfg), C.byref(h)))
+        check(own().bp_state_build(C.byref(self.cfg), C.byref(h)))
         return ProverState(h, self.cfg)
 
     def build_verifier(self):
         h = C.c_void_p()
-        check(_bind().bp_verifier_state_build(C.byref(self.cfg), C.byref(h)))
+        check(own().bp_verifier_state_build(C.byref(self.cfg), C.byref(h)))
         return VerifierState(h)
 
 
@@ -285,7 +232,7 @@ def _out():
 def keccak256_permutation_inputs(data: bytes):
     """bp_keccak256_permutation_inputs: -> (digest, [n_perms][25] lanes): the states that go into the Keccak-f
     permutations of Keccak-256(data) -- what a Keccak table attesting this hash contains."""
-    L = _bind()
+    L = own()
     n = C.c_size_t()
     check(L.bp_keccak256_permutation_inputs(data, len(data), None, None, 0, C.byref(n)))
     k = KECCAK_LANES
@@ -294,16 +241,10 @@ def keccak256_permutation_inputs(data: bytes):
     return digest.raw, [list(states[k * i:k * i + k]) for i in range(n.value)]
 
 
-class TxnWitness(C.Structure):
-    """bp_txn_witness (include/bpg.h): its members in the header's order"""
-    _fields_ = [(n, t) for table in (3, 5, 6, 0, 1, 4)
-                for n, t in zip(WITNESS_FIELDS[table], (C.c_void_p, C.c_size_t, C.c_int))]
-
-
 def keccak256_sponge_rows(data: bytes):
     """bp_keccak256_sponge_rows: -> (digest, [n_blocks][44] words): the rows a Keccak sponge table (AIR 6) absorbing
     `data` contains -- flags, message bytes in the block, the block as absorbed, the state before it."""
-    L = _bind()
+    L = own()
     n = C.c_size_t()
     check(L.bp_keccak256_sponge_rows(data, len(data), None, None, 0, C.byref(n)))
     k = SPONGE_ROW_WORDS
@@ -319,9 +260,8 @@ def generate_txn_proof(p_state, gen_inputs, abort_signal=None, keccak_inputs=Non
     keccak_air=True (bp_generate_txn_proof_keccak); default: gen_inputs.keccak_inputs if it has any.
     witness: {table index: [[words of an item], ...]} for the tables proven with an AIR (TXN_TABLE_AIRS has the words of
     an item; bp_generate_txn_proof_witness); default: gen_inputs.witness."""
-    L = _bind()
+    L = own()
     ir = gen_inputs.to_bytes() if isinstance(gen_inputs, TxnProofGenIR) else bytes(gen_inputs)
-    out, n = _out()
     flag = C.byref(abort_signal) if abort_signal is not None else None
     if keccak_inputs is None:
         keccak_inputs = getattr(gen_inputs, "keccak_inputs", None)
@@ -329,21 +269,18 @@ def generate_txn_proof(p_state, gen_inputs, abort_signal=None, keccak_inputs=Non
         if abort_signal is not None and C.sizeof(abort_signal) != 1:
             raise ValueError("bp_generate_txn_proof_witness takes the one-byte abort flag")
         w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
-        check(L.bp_generate_txn_proof_witness(p_state._h, ir, len(ir), C.byref(w), flag, C.byref(out), C.byref(n)))
+        intern = call_for_buffer(L.bp_generate_txn_proof_witness, p_state._h, ir, len(ir), C.byref(w), flag)
         del keep
     elif keccak_inputs is not None:
         flat = [int(x) for st in keccak_inputs for x in st]
         arr = (C.c_uint64 * max(len(flat), 1))(*flat)
         if abort_signal is not None and C.sizeof(abort_signal) != 1:
             raise ValueError("bp_generate_txn_proof_keccak takes the one-byte abort flag")
-        check(L.bp_generate_txn_proof_keccak(p_state._h, ir, len(ir), arr, len(flat) // KECCAK_LANES, flag, C.byref(out), C.byref(n)))
+        intern = call_for_buffer(L.bp_generate_txn_proof_keccak, p_state._h, ir, len(ir), arr, len(flat) // KECCAK_LANES, flag)
     elif abort_signal is not None and C.sizeof(abort_signal) == 1:
-        L.bp_generate_txn_proof_u8.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p,
-                                               C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-        check(L.bp_generate_txn_proof_u8(p_state._h, ir, len(ir), flag, C.byref(out), C.byref(n)))
+        intern = call_for_buffer(L.bp_generate_txn_proof_u8, p_state._h, ir, len(ir), flag)
     else:
-        check(L.bp_generate_txn_proof(p_state._h, ir, len(ir), flag, C.byref(out), C.byref(n)))
-    intern = take_buffer(out, n)
+        intern = call_for_buffer(L.bp_generate_txn_proof, p_state._h, ir, len(ir), flag)
     return GeneratedTxnProof(public_values_of(intern)[0], intern)
 
 
@@ -376,22 +313,17 @@ def generate_txn_table_proofs(p_state, gen_inputs, keccak_inputs=None, witness=N
     """What upstream's `prove` yields before the recursion (its AllProof; reached from proof_gen.rs:44-52): the seven
     table proofs of the transaction on their one transcript, with the public values and the lookup challenges, as
     bytes (bp_generate_txn_table_proofs).  Arguments as for generate_txn_proof."""
-    L = _bind()
     ir = gen_inputs.to_bytes() if isinstance(gen_inputs, TxnProofGenIR) else bytes(gen_inputs)
-    out, n = _out()
     w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
-    L.bp_generate_txn_table_proofs.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    check(L.bp_generate_txn_table_proofs(p_state._h, ir, len(ir), C.byref(w) if w is not None else None, None,
-                                         C.byref(out), C.byref(n)))
+    blob = call_for_buffer(own().bp_generate_txn_table_proofs, p_state._h, ir, len(ir), C.byref(w) if w is not None else None, None)
     del keep
-    return take_buffer(out, n)
+    return blob
 
 
 def generate_txn_table_proofs_group(p_state, gen_inputs_list):
     """bp_generate_txn_table_proofs_group: generate_txn_table_proofs for several transactions at a time, table t of those
     whose shapes agree proved in lock-step on one group of provers.  The blobs are the single call's, byte for byte."""
-    L = _bind()
+    L = own()
     irs = [g.to_bytes() if isinstance(g, TxnProofGenIR) else bytes(g) for g in gen_inputs_list]
     n = len(irs)
     if n < 1 or any(len(ir) != len(irs[0]) for ir in irs):
@@ -399,30 +331,14 @@ def generate_txn_table_proofs_group(p_state, gen_inputs_list):
     structs = [_witness_struct(g, None, None) if isinstance(g, TxnProofGenIR) else (None, []) for g in gen_inputs_list]
     data = (C.c_void_p * n)(*[C.addressof(w) if w is not None else None for w, _ in structs])
     outs, lens = (C.POINTER(C.c_uint8) * n)(), (C.c_size_t * n)()
-    L.bp_generate_txn_table_proofs_group.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p]
     raw = b"".join(irs)
     check(L.bp_generate_txn_table_proofs_group(p_state._h, raw, len(irs[0]), n, data, None, outs, lens))
     del structs
     return [take_buffer(outs[i], C.c_size_t(lens[i])) for i in range(n)]
 
 
-class WitnessTable(C.Structure):
-    """bp_witness_table (include/bpg.h)"""
-    from ._lib import AirViolation as _V
-    _fields_ = [("checked", C.c_uint32), ("given", C.c_uint32), ("n_violated_rows", C.c_uint64), ("n_viol", C.c_uint32),
-                ("viol", _V * 8)]
-
-
-class WitnessLookup(C.Structure):
-    """bp_witness_lookup (include/bpg.h)"""
-    _fields_ = [("checked", C.c_uint32), ("holds", C.c_uint32), ("n_looking", C.c_uint64), ("n_looked", C.c_uint64),
-                ("first_looking_row", C.c_int64), ("first_looked_row", C.c_int64)]
-
-
-class WitnessReport(C.Structure):
-    """bp_witness_report (include/bpg.h), with the call's status and message: `ok` when the prover would accept the data"""
-    _fields_ = [("table", WitnessTable * 7), ("lookup", WitnessLookup * 3)]
+class WitnessReport(_abi.WitnessReport):
+    """bp_witness_report with the call's status and message: `ok` when the prover would accept the data"""
     LOOKUPS = ("keccak_sponge -> keccak_f", "byte_packing -> memory", "keccak_sponge -> logic")
     status = 0
     message = ""
@@ -440,7 +356,7 @@ def check_txn_witness(p_state, gen_inputs, keccak_inputs=None, witness=None):
     proving -- the tables' AIRs row by row and the three lookups as multisets.  Arguments as for generate_txn_proof.
     Returns a WitnessReport (status 0 = ok, or BP_ERR_VERIFY with the table / row / constraint or the lookup and its
     first unmatched rows in `message`); raises ProofGenError only where the prover would refuse the input."""
-    L = _bind()
+    L = own()
     ir = gen_inputs.to_bytes() if isinstance(gen_inputs, TxnProofGenIR) else bytes(gen_inputs)
     rep = WitnessReport()
     if keccak_inputs is None:
@@ -448,14 +364,12 @@ def check_txn_witness(p_state, gen_inputs, keccak_inputs=None, witness=None):
     if witness is None and getattr(gen_inputs, "witness", None) is None and keccak_inputs is not None:
         flat = [int(x) for st in keccak_inputs for x in st]
         arr = (C.c_uint64 * max(len(flat), 1))(*flat)
-        L.bp_check_txn_witness_keccak.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         rc = L.bp_check_txn_witness_keccak(p_state._h, ir, len(ir), arr, len(flat) // KECCAK_LANES, C.byref(rep))
     else:
         w, keep = _witness_struct(gen_inputs, keccak_inputs, witness)
-        L.bp_check_txn_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
         rc = L.bp_check_txn_witness(p_state._h, ir, len(ir), C.byref(w) if w is not None else None, C.byref(rep))
         del keep
-    if rc not in (0, -5):   # BP_OK, BP_ERR_VERIFY: a report; anything else is the prover's refusal
+    if rc not in (_abi.BP_OK, _abi.BP_ERR_VERIFY):   # a report; anything else is the prover's refusal
         check(rc)
     rep.status = rc
     rep.message = L.bp_last_error().decode("utf-8", "replace") if rc else ""
@@ -468,31 +382,26 @@ def verify_txn_table_proofs(cfg, table_proofs, gen_inputs=None):
     gen_inputs (a TxnProofGenIR or its bytes): the statement -- which AIR proves each table, the shapes, the public
     values -- is then the verifier's (bp_verify_txn_table_proofs_for); without it the blob's header is taken at its
     word and the caller must check it.  Raises ProofGenError when rejected."""
-    L = _bind()
+    L = own()
     b = bytes(table_proofs)
     if gen_inputs is None:
-        L.bp_verify_txn_table_proofs.argtypes = [C.POINTER(BpConfig), C.c_char_p, C.c_size_t]
         check(L.bp_verify_txn_table_proofs(C.byref(cfg), b, len(b)))
         return
     ir = gen_inputs.to_bytes() if hasattr(gen_inputs, "to_bytes") else bytes(gen_inputs)
-    L.bp_verify_txn_table_proofs_for.argtypes = [C.POINTER(BpConfig), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
     check(L.bp_verify_txn_table_proofs_for(C.byref(cfg), ir, len(ir), b, len(b)))
 
 
 def generate_agg_proof(p_state, lhs_child, rhs_child):
     """proof_gen.rs:61-79."""
-    L = _bind()
     lhs, rhs = _as_aggregatable(lhs_child), _as_aggregatable(rhs_child)
-    out, n = _out()
-    check(L.bp_generate_agg_proof(p_state._h, lhs.intern(), len(lhs.intern()), int(lhs.is_agg()), rhs.intern(),
-                                  len(rhs.intern()), int(rhs.is_agg()), C.byref(out), C.byref(n)))
-    intern = take_buffer(out, n)
+    intern = call_for_buffer(own().bp_generate_agg_proof, p_state._h, lhs.intern(), len(lhs.intern()), int(lhs.is_agg()),
+                             rhs.intern(), len(rhs.intern()), int(rhs.is_agg()))
     return GeneratedAggProof(public_values_of(intern)[0], intern)
 
 
 def generate_block_proof(p_state, prev_opt_parent_b_proof, curr_block_agg_proof):
     """proof_gen.rs:85-110."""
-    L = _bind()
+    L = own()
     parent = prev_opt_parent_b_proof.intern if prev_opt_parent_b_proof is not None else None
     out, n = _out()
     h = C.c_uint64()
@@ -510,7 +419,7 @@ class VerifierState:
     @classmethod
     def from_prover_state(cls, p_state):
         h = C.c_void_p()
-        check(_bind().bp_verifier_state_from_prover(p_state._h, C.byref(h)))
+        check(own().bp_verifier_state_from_prover(p_state._h, C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -518,21 +427,21 @@ class VerifierState:
         """Verifier-only deployment (no GPU): cfg is a BpConfig, caps_words the 3 circuit caps."""
         h = C.c_void_p()
         arr = (C.c_uint64 * len(caps_words))(*[int(x) for x in caps_words])
-        check(_bind().bp_verifier_state_from_caps(C.byref(cfg), arr, C.byref(h)))
+        check(own().bp_verifier_state_from_caps(C.byref(cfg), arr, C.byref(h)))
         return cls(h)
 
     def verify(self, block_proof):
         """verifier_state.rs:56-71.  Raises ProofGenError when the proof is rejected."""
         b = block_proof.intern if isinstance(block_proof, GeneratedBlockProof) else bytes(block_proof)
-        check(_bind().bp_verify_block_proof(self._h, b, len(b)))
+        check(own().bp_verify_block_proof(self._h, b, len(b)))
 
     def verify_any(self, proof):
         b = proof.intern if hasattr(proof, "intern") and not callable(proof.intern) else bytes(proof)
-        check(_bind().bp_verify_proof(self._h, b, len(b)))
+        check(own().bp_verify_proof(self._h, b, len(b)))
 
     def close(self):
         if self._h:
-            _bind().bp_verifier_state_free(self._h)
+            own().bp_verifier_state_free(self._h)
             self._h = None
 
     def __del__(self):

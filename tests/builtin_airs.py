@@ -630,7 +630,6 @@ def product_verify(cfg, air_id, proof, const_cap=None, pub=None):
         cap = np.ascontiguousarray(const_cap, dtype=np.uint64).ctypes.data_as(C.POINTER(C.c_uint64))
     if pub is None:
         return L.bp_stark_verify_air(air_id, C.byref(pc), cap, raw, len(raw))
-    L.bp_stark_verify_air_pub.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     return L.bp_stark_verify_air_pub(air_id, C.byref(pc), cap, (C.c_uint64 * 4)(*[int(x) for x in pub]), raw, len(raw))
 
 

@@ -357,7 +357,6 @@ def test_errors_are_statuses_not_crashes():
     from proof_protocol_decoder_amd._lib import lib
     raw = decoding.trace_to_binary(make_trace(m, [block(m)[0][0]]), other)
     L = lib()
-    L.bp_decode_block_trace.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     for cut in (raw[:-1], raw[:40], b"XXXXXXXX" + raw[8:], raw + b"\x00"):
         out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
         assert L.bp_decode_block_trace(cut, len(cut), C.byref(out), C.byref(n)) == -2
@@ -470,8 +469,6 @@ def test_mutated_payloads_never_crash():
     raw = decoding.trace_to_binary(make_trace(m, [t for t, _ in block(m)], hash_out_storage_of=(E,)),
                                    decoding.OtherBlockData(decoding.BlockLevelData(b"m", b"h", [(B, 5)])))
     L = lib()
-    L.bp_decode_block_trace.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    L.bp_compact_decode_full.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     rng = random.Random(11)
     seen = {0: 0, -2: 0}
     wit = raw[12:12 + int.from_bytes(raw[8:12], "little")]

@@ -117,8 +117,6 @@ def test_air8_with_its_constants_and_public_inputs(bpg, oracle):
     pi = [int(x) for x in np.random.default_rng(8).integers(0, P, size=9, dtype=np.uint64)]
     t = torch.empty((135, 1 << log_n), dtype=torch.int64, device="cuda")
     L = bpg.lib()
-    L.bp_plonk_trace.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Layout), C.POINTER(C.c_uint64),
-                                 C.c_uint32, C.c_void_p, C.c_void_p]
     lay = Layout(len(pi), 0, 0, 0, 0)
     bpg._lib.check(L.bp_plonk_trace(C.c_void_p(k.data_ptr()), C.c_uint64(0x5EED08), (C.c_uint64 * len(pi))(*pi), C.byref(lay),
                                     None, log_n, C.c_void_p(t.data_ptr()), None))

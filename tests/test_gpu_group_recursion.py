@@ -28,11 +28,7 @@ def pg(bpg):
 
 @pytest.fixture(scope="module")
 def L(pg):
-    lib = pg._bind()
-    lib.bp_tune_rec_group.argtypes = [C.c_int]
-    lib.bp_tune_rec_group.restype = None
-    lib.bp_debug_rec_batch_histogram.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_int]
-    return lib
+    return pg._bind()
 
 
 @pytest.fixture

@@ -8,22 +8,17 @@ import numpy as np
 import pytest
 
 from builtin_airs import product_verify
+from proof_protocol_decoder_amd._abi import PlonkLayout as Layout
 from util import P, coset_major_to_natural, rand_field, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 SEED, CSEED = 0x5EED000000000008, 0xC0DE000000000008
 
 
-class Layout(C.Structure):   # include/bpg.h: bp_plonk_layout
-    _fields_ = [("pi_len", C.c_uint32), ("n_paths", C.c_uint32), ("path_depth", C.c_uint32), ("path_pi0", C.c_uint32),
-                ("leaf_len", C.c_uint32)]
-
-
 def dev_constants(bpg, log_n, seed, pi_len=4, n_paths=0, depth=0, path_pi0=0, leaf_len=0):
     import torch
     out = torch.empty((85, 1 << log_n), dtype=torch.int64, device="cuda")
     L = bpg.lib()
-    L.bp_plonk_constants.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(Layout), C.c_void_p, C.c_void_p]
     lay = Layout(pi_len, n_paths, depth, path_pi0, leaf_len)
     bpg._lib.check(L.bp_plonk_constants(C.c_uint64(seed), log_n, C.byref(lay), C.c_void_p(out.data_ptr()), None))
     return out
@@ -69,8 +64,6 @@ def test_constants_and_witness_match_oracle(bpg, oracle, log_n, pi_len, n_paths,
     pi_c = (C.c_uint64 * pi_len)(*[int(x) for x in pi])
     wit_c = (C.c_uint64 * max(1, len(wit or [])))(*[int(x) for x in (wit or [])])
     lay = Layout(pi_len, n_paths, depth, path_pi0, leaf_len)
-    bpg.lib().bp_plonk_trace.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Layout), C.POINTER(C.c_uint64), C.c_uint32,
-                                         C.c_void_p, C.c_void_p]
     bpg._lib.check(bpg.lib().bp_plonk_trace(C.c_void_p(k.data_ptr()), C.c_uint64(SEED + log_n), pi_c, C.byref(lay), wit_c if n_paths else None,
                                             log_n, C.c_void_p(t.data_ptr()), None))
     got = to_host(t)

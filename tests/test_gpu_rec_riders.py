@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from pg_common import LOG_N, SMALL, SMALL_PLONK, WIDTH
+from proof_protocol_decoder_amd._abi import ShardOptions as Opt
 
 pytestmark = pytest.mark.gpu
 
@@ -29,17 +30,11 @@ def build_state(pg, cfg, n_workers=3):
     return b.build()
 
 
-class Opt(C.Structure):
-    _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
-
-
 def prove_shard(pg, st, irs, n_threads, shape, abort=None):
     """bp_prove_shard itself: (root bytes, [txn proof bytes])"""
     from proof_protocol_decoder_amd.block_driver import TREE_SHAPES
     L = pg._bind()
     u8p = C.POINTER(C.c_uint8)
-    L.bp_prove_shard.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(Opt), C.c_void_p,
-                                 C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(u8p), C.POINTER(C.c_size_t)]
     n = len(irs)
     raw = b"".join(ir.to_bytes() for ir in irs)
     root, root_len = u8p(), C.c_size_t()
@@ -56,8 +51,6 @@ def aggregate_proofs(pg, st, raws, n_threads, shape):
     n = len(raws)
     ptrs = (C.c_char_p * n)(*raws)
     lens = (C.c_size_t * n)(*[len(r) for r in raws])
-    L.bp_aggregate_proofs.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(Opt),
-                                      C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
     opt = Opt(n_threads, TREE_SHAPES[shape])
     pg.check(L.bp_aggregate_proofs(st._h, ptrs, lens, n, C.byref(opt), C.byref(out), C.byref(out_len)))

@@ -13,6 +13,7 @@ import pytest
 
 import txn_table_cases as tc
 from pg_common import SMALL, SMALL_PLONK, WIDTH
+from proof_protocol_decoder_amd._abi import ShardOptions as Opt
 
 pytestmark = pytest.mark.gpu
 
@@ -33,16 +34,10 @@ def build_state(pg, cfg, n_workers):
     return b.build()
 
 
-class Opt(C.Structure):
-    _fields_ = [("n_threads", C.c_uint32), ("tree_shape", C.c_uint32)]
-
-
 def prove_shard(pg, st, irs, n_threads, abort=None):
     """bp_prove_shard itself: (root bytes, [txn proof bytes])"""
     L = pg._bind()
     u8p = C.POINTER(C.c_uint8)
-    L.bp_prove_shard.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(Opt), C.c_void_p,
-                                 C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(u8p), C.POINTER(C.c_size_t)]
     n = len(irs)
     raw = b"".join(ir.to_bytes() for ir in irs)
     root, root_len = u8p(), C.c_size_t()
@@ -167,8 +162,6 @@ def group_call(pg, st, cases_words):
     structs = [tc.witness_struct(pg, c) for c, _ in cases_words]
     data = (C.c_void_p * n)(*[C.addressof(w) if w is not None else None for w, _ in structs])
     outs, lens = (C.POINTER(C.c_uint8) * n)(), (C.c_size_t * n)()
-    L.bp_generate_txn_table_proofs_group.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p]
     raw = b"".join(struct.pack("<25Q", *w) for _, w in cases_words)
     rc = L.bp_generate_txn_table_proofs_group(st._h, raw, 200, n, data, None, outs, lens)
     del structs
@@ -280,7 +273,6 @@ def test_decoded_block_through_prove_shard_gi(pg, air_state, group):
 def pg_gi_count(pg, geni):
     L = pg._bind()
     n = C.c_uint32()
-    L.bp_gi_count.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
     pg.check(L.bp_gi_count(geni, len(geni), C.byref(n)))
     return range(n.value)
 

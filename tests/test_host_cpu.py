@@ -153,10 +153,8 @@ def test_product_cpu_verifier_accepts_oracle_proofs_and_rejects_corruption(cpu_c
 def test_host_transcript_permutation_matches_the_oracle_in_both_forms(oracle):
     """poseidon_host (prover.cpp: the challenger's CPU permutation, MDS over 32-bit halves, AVX2 where the CPU has it)
     against the oracle's permutation on random, edge and non-canonical states, in the automatic and the scalar form."""
-    import ctypes as C
     import proof_protocol_decoder_amd as pkg
     L = pkg.lib()
-    L.bp_debug_poseidon_host.argtypes = [C.c_void_p, C.c_size_t]
     P = 0xFFFFFFFF00000001
     rng = np.random.default_rng(5)
     states = rng.integers(0, 2**64, size=(257, 12), dtype=np.uint64)
@@ -276,7 +274,6 @@ def prove_block(parent, agg):
     return pg.GeneratedBlockProof(pg.public_values_of(raw)[0].block_number, raw)
 # a chained 5-txn block: every rank derives the same inputs
 L = pg._bind()
-L.bp_state_root_after.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
 irs, root, gas = [], (1, 2, 3, 4), 0
 N_TXNS, FAIL_RANK, TOP_TREE = {n_txns}, {fail_rank}, {top_tree!r}
 for i in range(N_TXNS):
@@ -467,11 +464,9 @@ def test_witness_entry_points_check_their_arguments_before_any_device_work():
     import proof_protocol_decoder_amd as pkg
     from proof_protocol_decoder_amd import proof_gen as pg
     L = pkg.lib()
-    L.bp_last_error.restype = C.c_char_p
     for name in ("bp_keccak_trace", "bp_logic_trace", "bp_memory_trace", "bp_arithmetic_trace", "bp_byte_packing_trace",
                  "bp_keccak_sponge_trace", "bp_arithmetic_mul_trace"):
         f = getattr(L, name)
-        f.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         assert f(None, 1, 8, None, None) == -2 and name.encode() in L.bp_last_error()
         assert f(None, 1, 2, C.c_void_p(8), None) == -2 and b"log_n" in L.bp_last_error()
         assert f(None, 1, 40, C.c_void_p(8), None) == -2
@@ -481,7 +476,6 @@ def test_witness_entry_points_check_their_arguments_before_any_device_work():
                           ("bp_ir_set_arithmetic_air", b"309"), ("bp_ir_set_byte_packing_air", b"299"),
                           ("bp_ir_set_keccak_sponge_air", b"2414")):
         f = getattr(L, setter)
-        f.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         assert f(ir, 1) == -2 and width in L.bp_last_error()       # the synthetic widths do not fit the AIR
         assert f(ir, 0) == 0 and ir[1] == 1                        # switching it off is always possible
         junk = (C.c_uint64 * 25)()
@@ -497,7 +491,6 @@ def test_witness_entry_points_check_their_arguments_before_any_device_work():
     assert L.bp_ir_set_logic_air(ir, 0) == 0 and ir[1] == 0x3D01
     # the arithmetic table is proven by ONE AIR: the multiplication AIR (flag 0x4000, 1217 columns) instead of AIR 4
     f = L.bp_ir_set_arithmetic_mul_air
-    f.argtypes = [C.POINTER(C.c_uint64), C.c_int]
     assert f(ir, 1) == -2 and b"1217" in L.bp_last_error()
     w[18 + 0] = 1217
     ir2 = (C.c_uint64 * 25)(*w)

@@ -30,7 +30,6 @@ def _round_constants():
 def test_poseidon_mx_c_operand_table():
     """[round][ib][2g + h][reg] = 128 * rowsum(word ib + 4g) + byte 4h + reg of the NEXT round's constant"""
     L = _lib()
-    L.bp_debug_poseidon_mx_cin.argtypes = [C.POINTER(C.c_uint32)]
     buf = (C.c_uint32 * (30 * 4 * 24))()
     assert L.bp_debug_poseidon_mx_cin(buf) == 0
     got = np.frombuffer(buf, dtype=np.uint32).reshape(30, 4, 3, 2, 4)
@@ -88,8 +87,6 @@ def test_ntt_mx_tables_match_the_model():
     -127 * (digit sum) instead of +128 * (digit sum) into the row constant."""
     import ntt_mx_model as m
     L = _lib()
-    L.bp_debug_ntt_mx_tables.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
-                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     for kind in (0, 1):
         in_index = (lambda kb, eps: 4 * eps + kb) if kind else (lambda kb, eps: 2 * kb + eps)
         out_index = (lambda ib, a: (a & 1) + 2 * ib + 8 * (a >> 1)) if kind else (lambda ib, a: 4 * ib + a)
@@ -171,7 +168,6 @@ def test_poseidon_group_tables_match_the_integer_model(K, r0):
     import poseidon_group_model as model
     import proof_protocol_decoder_amd as pkg
     L = pkg.lib()
-    L.bp_debug_poseidon_group_ops.restype = C.c_uint32
     n_ops = L.bp_debug_poseidon_group_ops(K)
     G = model.check(K, r0, n=3)                      # grouped == plain rounds, tile form and device order
     ops, cform, cmain = model.device_images(G)

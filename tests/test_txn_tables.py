@@ -7,29 +7,15 @@ import ctypes as C
 import pytest
 
 import txn_table_cases as tc
+from proof_protocol_decoder_amd._abi import TxnPlan as Plan
 
 U32_MAX = 0xFFFFFFFF
-
-
-class PlanTable(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("air_id", "n_cols", "log_n", "given", "item_words")] + [("capacity", C.c_uint64)]
-
-
-class PlanLookup(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("active", "looking_table", "looking_air", "looked_table", "looked_air")]
-
-
-class Plan(C.Structure):
-    """bp_txn_plan (include/bpg.h)"""
-    _fields_ = [("table", PlanTable * 7), ("lookup", PlanLookup * 3), ("logic_covered", C.c_uint32),
-                ("sponge_row_limit", C.c_uint32)]
 
 
 @pytest.fixture(scope="module")
 def env():
     from proof_protocol_decoder_amd import proof_gen as pg
     L = pg._bind()
-    L.bp_debug_txn_plan.argtypes = [C.POINTER(pg.BpConfig), C.POINTER(C.c_uint64), C.c_size_t, C.c_void_p, C.POINTER(Plan)]
     b = pg.ProverStateBuilder()
     for t, name in enumerate(pg.TABLES):
         getattr(b, "set_%s_circuit_size" % name)(range(tc.CFG["table_log_lo"][t], tc.CFG["table_log_hi"][t]))

@@ -157,7 +157,6 @@ def _call(pg, st, entry, case, words, with_flag):
     import struct
     L = pg._bind()
     f = getattr(L, entry)
-    f.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p] + [C.c_void_p] * with_flag + [C.c_void_p, C.c_void_p]
     ir = struct.pack("<25Q", *(words or ir_words(case)))
     w, keep = witness_struct(pg, case)
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
@@ -179,7 +178,6 @@ def preflight_report(pg, st, case, words=None):
     import ctypes as C
     import struct
     L = pg._bind()
-    L.bp_check_txn_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
     ir = struct.pack("<25Q", *(words or ir_words(case)))
     w, keep = witness_struct(pg, case)
     rep = pg.WitnessReport()

@@ -1,9 +1,8 @@
-import sys, os, time, ctypes as C
+import sys, os, time
 sys.path.insert(0, os.getcwd())
 import numpy as np
 import proof_protocol_decoder_amd as pkg
 L = pkg.lib()
-L.bp_debug_poseidon_host.argtypes = [C.c_void_p, C.c_size_t]
 s = np.arange(12 * 20000, dtype=np.uint64).reshape(-1, 12)
 for mode in (0, 1):
     with pkg.ops.tuned(host_poseidon=mode):

@@ -40,7 +40,6 @@ def main():
         runpy.run_path(sys.argv[0], run_name="__main__")
     finally:
         out = (C.c_uint64 * 32)()
-        L.bp_debug_rec_batch_histogram.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_int]
         L.bp_debug_rec_batch_histogram(out, 32, 0)
         print("knobs %s, GPU_MAX_HW_QUEUES=%s; recursion batches by size: %s"
               % (knobs or "default", os.environ.get("GPU_MAX_HW_QUEUES"), {b: int(c) for b, c in enumerate(out) if c}), file=sys.stderr)

@@ -14,7 +14,6 @@ def main():
     import txn_table_cases as tc
     from proof_protocol_decoder_amd import proof_gen as pg
     L = pg._bind()
-    L.bp_check_txn_witness.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
     print("# wall time per call in milliseconds, median (min, max) of %d calls; engine clock not sampled" % CALLS)
     six = next(c for c in tc.ACCEPTED if c.name == "six_together")
     tall = six._replace(name="six_tall", log_n=(6, 9, 7, 14, 12, 15, 13))

@@ -563,6 +563,34 @@ int bp_arithmetic_div_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* 
  * bits per carry, the first column of the r + d + 1 carry bits.  No device is needed.  The program in arithmetic_div.py
  * states the same map a second time; its register() compares the two and refuses to go on when they differ. */
 int bp_arithmetic_div_layout(uint32_t* out, size_t n_words);
+/* Witness of the MODULAR table: ADDMOD and MULMOD on 256-bit words, one operation per row.  Like the division table it has
+ * no built-in air_id: its AIR is a constraint program shipped with the Python package (proof_protocol_decoder_amd/
+ * arithmetic_mod.py, which registers it with bp_air_register; AIRS.md section 2, "Modular (a shipped program)", lists the
+ * columns).  Every row proves: with U = a + b under is_addmod, U = a b under is_mulmod and U = 0 on a row with neither flag
+ * -- OVER THE INTEGERS, 257 and 512 bits, never reduced modulo 2^256 on the way -- there are q in [0, 2^512) and r in
+ * [0, 2^256) with U = q M + r, where M = m + z 2^256 and z = [m = 0]; r < m unless m = 0; res = (1 - z) r, which is (a + b)
+ * mod m or (a b) mod m, and 0 when m = 0 (the EVM's convention); at most one flag is set, a row with neither is a padding row
+ * (res = 0), and the filter g of the table's one product port, which exposes (is_addmod, is_mulmod, the sixteen 16-bit limbs
+ * of a, of b, of m, of res: 66 elements), may be 1 only on a row with a flag.
+ * The M convention: a zero modulus is divided by as 2^256, so the honest witness there is q = U >> 256, r = U mod 2^256, and
+ * no constraint has to switch the left side off (which would cost a degree).
+ * n = 2^log_n rows (log_n 4 .. 26) x 2560 columns, column-major.  d_inputs: [n][13] = word 0: the operation in its low byte
+ * (1 addmod, 2 mulmod, anything else a padding row, whose other words are ignored) | exposed << 8 (bit 8: the row's g; bits
+ * 9 .. 63 are ignored); then the four 64-bit words of a, of b and of m, least significant first.  Any u64 is accepted and
+ * every 256-bit operand is a valid one.  There is no seeded draw: d_inputs == NULL is BP_ERR_INVALID_INPUT.
+ * Carries: over 16-bit limbs, column k = 0 .. 31 is L_k - R_k + c_{k-1} = 2^16 c_k with L_k = is_mulmod sum_{i+j=k} a_i b_j +
+ * is_addmod (a_k + b_k), R_k = sum_{i+j=k} q_i M_j + r_k (M_16 = z), c_{-1} = 0 and no c_31; the products of columns 32 .. 47
+ * are the one constraint sum_{i+j>=32} q_i M_j = 0.  The carries are SIGNED: c_k is the left side's own unsigned carry minus
+ * the right side's.  The left side has at most 16 products in a column; q M <= U < 2^512 lets q and M have at most 33 limbs
+ * between them, so the right side has at most 16 that are not zero: both carries are at most 16 (2^16 - 1) + 1 and
+ * |c_k| < 2^20.  The columns hold c_k + 2^20 in 21 bits.  MULMOD (2^256 - 2, 2^255, 2^256 - 1) reaches -0xEFFF1 and MULMOD
+ * (2^256 - 1, 2^256 - 1, 0) reaches +0xFFFEF. */
+int bp_arithmetic_mod_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* d_trace_out, void* stream);
+/* The column map bp_arithmetic_mod_trace stores by, 21 words (n_words: the room in `out`, at least 21): n_cols, then the
+ * first column of is_addmod, is_mulmod, g, z, inv, the a / b / m / res / q limbs, the a / b / m / q / r / d bits, the carry
+ * bits, the bits per carry, the offset the carry columns add (2^20), the first column of the r + d + 1 carry bits.  No
+ * device is needed.  arithmetic_mod.py states the same map a second time; its register() refuses to go on when they differ. */
+int bp_arithmetic_mod_layout(uint32_t* out, size_t n_words);
 
 /* AIR 8 (plonk): the 85 preprocessed constant columns of the fixed circuit (selectors, gate constants drawn from `seed`,
  * the Poseidon-row selector, the 80 sigmas of its copy permutation), n = 2^log_n rows, column-major, for a circuit that

@@ -10,3 +10,4 @@ from . import proof_gen  # noqa: F401
 from . import compact  # noqa: F401
 from . import trace_protocol  # noqa: F401
 from . import arithmetic_div  # noqa: F401
+from . import arithmetic_mod  # noqa: F401

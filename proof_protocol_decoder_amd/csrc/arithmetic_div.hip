@@ -7,6 +7,7 @@
 // arithmetic_div.register() can refuse to run when the two differ.
 #include "common.hpp"
 #include "gl.hpp"
+#include "word256.cuh"
 
 namespace {
 
@@ -22,43 +23,11 @@ constexpr uint32_t LAYOUT[] = {N_COLS, COL_IS_DIV, COL_IS_MOD, COL_G, COL_Z, COL
 constexpr uint32_t LAYOUT_WORDS = sizeof(LAYOUT) / sizeof(LAYOUT[0]);
 }  // namespace dv
 
-// A 256-bit word as four named 64-bit registers, least significant first: no array, so nothing a lane could index at
-// run time and the compiler could send to scratch.
-struct U256 {
-  uint64_t a, b, c, d;
-};
-__device__ __forceinline__ U256 sub256(const U256& x, const U256& y, uint32_t* borrow_out) {
-  U256 r;
-  r.a = x.a - y.a;
-  uint32_t bw = x.a < y.a;
-  uint64_t t = x.b - y.b;
-  uint32_t b2 = (x.b < y.b) | (t < bw);
-  r.b = t - bw;
-  t = x.c - y.c;
-  uint32_t b3 = (x.c < y.c) | (t < b2);
-  r.c = t - b2;
-  t = x.d - y.d;
-  *borrow_out = (x.d < y.d) | (t < b3);
-  r.d = t - b3;
-  return r;
-}
-// limb K (16 bits) of a word, K a compile-time number
-template <uint32_t K>
-__device__ __forceinline__ uint32_t limb(const U256& w) {
-  const uint64_t v = K < 4 ? w.a : K < 8 ? w.b : K < 12 ? w.c : w.d;
-  return (uint32_t)(v >> (16 * (K & 3))) & 0xFFFFu;
-}
-
-struct Row {
-  uint64_t* t;  // the trace at this lane's row: column c at t[c * n]
-  uint64_t n;
-  __device__ __forceinline__ void put(uint32_t col, uint64_t v) const { t[(uint64_t)col * n] = v; }
-  // `count` bit columns from `col`: bit j of v at col + j
-  __device__ __forceinline__ void put_bits(uint32_t col, uint32_t v, uint32_t count) const {
-#pragma unroll 1
-    for (uint32_t j = 0; j < count; j++) put(col + j, (v >> j) & 1u);
-  }
-};
+// the 256-bit word in named registers, its limbs and the lane's row: shared with arithmetic_mod.hip
+using word256::limb;
+using word256::Row;
+using word256::sub256;
+using word256::U256;
 
 // what a row stores for limb K of x, y, q, r, d and the result, and the product column K: the carry out of it (columns
 // 0 .. 14; the honest carry out of column 15 is zero because q y + r = x < 2^256) and the carry bit of r + d + 1

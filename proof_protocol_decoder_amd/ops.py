@@ -225,6 +225,22 @@ def arithmetic_div_trace(log_n, inputs, device="cuda"):
     return out
 
 
+def arithmetic_mod_trace(log_n, inputs, device="cuda"):
+    """bp_arithmetic_mod_trace: the witness [2560, 2^log_n] of the modular table (arithmetic_mod.py: a shipped program,
+    no built-in air_id); inputs [2^log_n, 13] int64 on the device (op 1 addmod / 2 mulmod / else padding | exposed << 8,
+    the four words of a, of b, of m: arithmetic_mod.pack_inputs).  There is no seeded draw: inputs=None is refused by the
+    library."""
+    from .arithmetic_mod import N_COLS
+    if inputs is not None:
+        _require_cuda(inputs)
+        if tuple(inputs.shape) != (1 << log_n, 13):
+            raise ValueError("arithmetic_mod_trace: inputs are [%d, 13]: got %s" % (1 << log_n, tuple(inputs.shape)))
+        device = inputs.device
+    out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=device)
+    check(own().bp_arithmetic_mod_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
+    return out
+
+
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""

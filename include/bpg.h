@@ -643,6 +643,11 @@ int bp_pow_grind(const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t
  * against the oracle.  Transcript prologue: observe constants cap (if n_const), observe trace cap,
  * draw 4 CTL challenges.  The witness is generated on the device from (seed, const_seed).
  * *out receives orc-identical proof words (little-endian u64), *out_len their byte length.
+ * Accepted (anything else is BP_ERR_INVALID_INPUT before any device work): arity_bits = 4, cap_height 0..8 with
+ * log_n + rate_bits >= cap_height (equal: the cap is the leaf level, queries open rows without a path), final_poly_bits
+ * 0..8.  A polynomial of 2^d coefficients is folded while d > final_poly_bits, d >= arity_bits and the folded layer's
+ * tree still holds a cap (d + rate_bits >= cap_height + arity_bits): the final polynomial (header word 10) has at most
+ * 2^10 coefficients -- a tall cap, not final_poly_bits, is what allows the longest.
  * ------------------------------------------------------------------------------------------ */
 typedef struct bp_stark_cfg {
   uint32_t log_n, n_cols, n_const, deg_pow, rate_bits, cap_height, num_queries, pow_bits, arity_bits,
@@ -822,7 +827,12 @@ typedef struct bp_config {
   /* per-table supported log2 trace heights, Range<usize> lo..hi, hi exclusive (constants.rs:6-18) */
   uint32_t table_log_lo[BP_NUM_TABLES], table_log_hi[BP_NUM_TABLES];
   /* StarkConfig::standard_fast_config(): rate_bits 1, cap_height 4, 84 queries, 16 PoW bits,
-   * ConstantArityBits(4, 5)  [UPSTREAM-UNVERIFIED values, runtime parameters here] */
+   * ConstantArityBits(4, 5)  [UPSTREAM-UNVERIFIED values, runtime parameters here].  bp_state_build refuses
+   * (BP_ERR_INVALID_INPUT, before it looks for a device) a cap taller than the smallest table's tree
+   * (table_log_lo + stark_rate_bits < stark_cap_height) or than the recursion shape's, and, with rec_air_id = 8, a
+   * shape whose circuits do not fit 2^rec_log_n rows: every Merkle path a circuit walks needs at least one level
+   * (table_log_lo + stark_rate_bits > stark_cap_height, rec_log_n + rec_rate_bits > stark_cap_height) and one row per
+   * level -- seven paths in the root circuit, 96 Merkle rows at most. */
   uint32_t stark_rate_bits, stark_cap_height, stark_num_queries, stark_pow_bits, arity_bits, final_poly_bits;
   /* CircuitConfig::standard_recursion_config() shaped proofs: 2^13 rows x 135 wires, rate_bits 3, 28 queries; 84
    * preprocessed constant columns (4 gate constants + 80 sigmas) for the PLONK-shaped circuit, which is the default */

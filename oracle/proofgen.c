@@ -60,7 +60,61 @@ static orc_stark_cfg table_cfg_of(const orc_pg_config* c, uint32_t log_n, uint32
   return r;
 }
 
-orc_pg_state* orc_pg_state_build(const orc_pg_config* cfg) {
+/* What libbpg refuses in bp_state_build, this state refuses too: the code below indexes Merkle levels, circuit rows and
+ * caps by these numbers without looking again.  NULL = the configuration can be proven; else the reason. */
+static const char* stark_cfg_error(const orc_stark_cfg* c) { /* check_cfg (csrc/prover.cpp), the bounds on the shape */
+  if (c->deg_pow != 1 && c->deg_pow != 3) return "deg_pow must be 1 or 3";
+  if (c->rate_bits > 3 || (1u << c->rate_bits) != 3 * c->deg_pow - 1) return "quotient degree factor 3*deg_pow-1 must equal 2^rate_bits";
+  if (c->n_cols < 8 || c->n_cols > 65536) return "n_cols out of range";
+  if (c->log_n < 4 || c->log_n + c->rate_bits > 30) return "log_n out of range";
+  if (c->log_n + c->rate_bits < c->cap_height) return "cap_height above the tree: log_n + rate_bits < cap_height";
+  if (c->arity_bits != 4) return "only arity_bits = 4 is built";
+  if (c->num_queries == 0 || c->num_queries > 128) return "num_queries out of range";
+  if (c->pow_bits > 32) return "pow_bits out of range";
+  if (c->cap_height > 8) return "cap_height must be <= 8";
+  if (c->final_poly_bits > 8) return "final_poly_bits must be <= 8";
+  if (c->n_const > 4096) return "n_const out of range";
+  if (orc_cfg_n_layers(c) > 8) return "too many FRI layers";
+  return NULL;
+}
+/* plonk_air.c lays a circuit out as: 4 + 13 rows for the public-input list (8 words a row: 104 words at most), one row per
+ * level of every Merkle path (96 at most), ceil(leaf_len / 8) rows per hashed leaf (120 at most), then, from the next
+ * multiple of four, at least one group of four arithmetic rows -- all within 2^log_n rows. */
+static int plonk_layout_ok(unsigned log_n, unsigned pi_len, unsigned n_paths, unsigned depth, unsigned path_pi0, unsigned leaf_len) {
+  const unsigned mrows = n_paths * depth, lrows = leaf_len ? n_paths * ((leaf_len + 7) / 8) : 0;
+  return pi_len >= 1 && pi_len <= 104 && mrows <= 96 && (n_paths == 0 || depth >= 1) && path_pi0 + 8 * n_paths <= pi_len &&
+         (leaf_len == 0 || (leaf_len > 8 && n_paths >= 1)) && lrows <= 120 && ((17 + mrows + lrows + 3) & ~3u) + 4 <= (1u << log_n);
+}
+const char* orc_pg_config_error(const orc_pg_config* c) {
+  if (!c) return "null configuration";
+  const orc_stark_cfg rec = rec_cfg_of(c);
+  const char* why = stark_cfg_error(&rec);
+  if (why) return why;
+  if (c->rec_air_id != ORC_AIR_SYNTHETIC && c->rec_air_id != ORC_AIR_PLONK) return "rec_air_id must be 0 (synthetic) or 8 (PLONK-shaped)";
+  if (c->rec_air_id == ORC_AIR_PLONK && (c->rec_n_cols != 135 || c->rec_n_const != 85)) return "the PLONK-shaped circuit has 135 wires and 85 constant columns";
+  if (c->shrink_depth < 1) return "shrink_depth must be at least 1";
+  for (int t = 0; t < NUM_TABLES; t++) {
+    if (c->table_log_lo[t] >= c->table_log_hi[t] || c->table_log_hi[t] > 31) return "empty or invalid range for a table";
+    const orc_stark_cfg tc = table_cfg_of(c, c->table_log_lo[t], 8); /* the smallest tree of the table: the cap must fit it */
+    if ((why = stark_cfg_error(&tc))) return why;
+  }
+  if (c->rec_air_id != ORC_AIR_PLONK) return NULL;
+  /* the circuits of special_circuit / shrink_circuit / table_circuit below, with the same numbers */
+  for (int t = 0; t < NUM_TABLES; t++)
+    for (uint32_t d = c->table_log_lo[t]; d < c->table_log_hi[t]; d++)
+      if (!plonk_layout_ok(rec.log_n, 6 + 8, 1, d + c->stark_rate_bits - c->stark_cap_height, 6, 0))
+        return "a table's Merkle rows do not fit the recursion circuit";
+  const unsigned depth = rec.log_n + rec.rate_bits - rec.cap_height;
+  static const unsigned PI_LEN[4] = {4 * NUM_TABLES + 8 * NUM_TABLES + PV_WORDS, 10 + 16 + PV_WORDS, 9 + 8 + PV_WORDS, 6 + 8};
+  static const unsigned PATHS[4] = {NUM_TABLES, 2, 1, 1}, AT[4] = {4 * NUM_TABLES, 10, 9, 6};
+  for (int k = 0; k < 4; k++) /* root, aggregation, block, shrink: without the leaf rows where those do not fit (leaf_len_of) */
+    if (!plonk_layout_ok(rec.log_n, PI_LEN[k], PATHS[k], depth, AT[k], 0))
+      return "the recursion shape's Merkle rows do not fit 2^rec_log_n rows";
+  return NULL;
+}
+
+orc_pg_state* orc_pg_state_build(const orc_pg_config* cfg) { /* NULL: orc_pg_config_error says why */
+  if (orc_pg_config_error(cfg)) return NULL;
   orc_pg_state* s = (orc_pg_state*)calloc(1, sizeof(*s));
   s->cfg = *cfg;
   s->rec = rec_cfg_of(cfg);

@@ -111,6 +111,8 @@ def lib():
     L.orc_proof_digest.argtypes = [cfgp, u64p, u64p]
     L.orc_pg_state_build.argtypes = [C.POINTER(PgConfig)]
     L.orc_pg_state_build.restype = vp
+    L.orc_pg_config_error.argtypes = [C.POINTER(PgConfig)]
+    L.orc_pg_config_error.restype = C.c_char_p
     L.orc_pg_state_free.argtypes = [vp]
     L.orc_pg_txn.argtypes = [vp, u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(sz)]
     L.orc_pg_txn_keccak.argtypes = [vp, u64p, vp, sz, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(sz)]
@@ -472,7 +474,13 @@ class PgState:
             else:
                 setattr(cfg, k, v)
         self.cfg = cfg
+        self.h = None
+        why = lib().orc_pg_config_error(C.byref(cfg))   # what bp_state_build refuses, the checker refuses too
+        if why is not None:
+            raise ValueError("orc_pg_state_build refuses the configuration: %s" % why.decode())
         self.h = lib().orc_pg_state_build(C.byref(cfg))
+        if not self.h:
+            raise ValueError("orc_pg_state_build refuses the configuration")
 
     def _take(self, ptr, n):
         out = np.ctypeslib.as_array(ptr, shape=(n.value,)).copy()

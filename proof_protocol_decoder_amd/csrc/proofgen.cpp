@@ -524,6 +524,36 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
     if ((r = check_cfg(tc))) return r;
     n_circ += cfg->table_log_hi[t] - cfg->table_log_lo[t];
   }
+  // Every recursion circuit walks one Merkle path per child: root (seven chains), aggregation (two children: their
+  // paths' words follow the digests and flags), block (the aggregation child's), a table's shrink circuit (the level below)
+  const uint32_t depth = rc.log_n + rc.rate_bits - rc.cap_height;
+  // Every circuit whose children are recursion-shaped proofs (all but level 0 of a chain, whose child is a table's STARK
+  // proof of up to 2432 columns) also HASHES the row each child opens (its leaf: the child's n_cols trace values) before
+  // it walks up from it -- merkle_proofs::verify_merkle_proof_to_cap whole -- where the circuit has the rows for it (a
+  // 2^6-row test circuit has them for one child, not for seven: both sides take the same decision from the shape alone)
+  auto with_leaf = [&](air::plonk::Layout lay) {
+    air::plonk::Layout l = lay;
+    l.leaf_len = rc.n_cols;
+    return (rc.air_id == air::PLONK && air::plonk::layout_ok(l, 1u << rc.log_n)) ? l : lay;
+  };
+  air::plonk::Layout special[3] = {with_leaf({ROOT_PATH_PI0 + 8 * BP_NUM_TABLES + BP_PV_WORDS, BP_NUM_TABLES, depth, ROOT_PATH_PI0}),
+                                   with_leaf({AGG_PATH_PI0 + 2 * 8 + BP_PV_WORDS, 2, depth, AGG_PATH_PI0}),
+                                   with_leaf({BLOCK_PATH_PI0 + 8 + BP_PV_WORDS, 1, depth, BLOCK_PATH_PI0})};
+  const air::plonk::Layout shrink_lay = with_leaf(air::plonk::Layout{CHAIN_PATH_PI0 + 8, 1, depth, CHAIN_PATH_PI0});
+  // ... and every circuit's rows must fit 2^rec_log_n: said here, from the shapes alone, before any device is looked for
+  // (launch_plonk_constants would refuse the same layouts, after the arenas are allocated)
+  if (rc.air_id == air::PLONK) {
+    for (int t = 0; t < BP_NUM_TABLES; t++)
+      for (uint32_t d = cfg->table_log_lo[t]; d < cfg->table_log_hi[t]; d++)
+        if (!air::plonk::layout_ok(air::plonk::Layout{CHAIN_PATH_PI0 + 8, 1, d + cfg->stark_rate_bits - cfg->stark_cap_height, CHAIN_PATH_PI0}, 1u << rc.log_n))
+          return fail(BP_ERR_INVALID_INPUT, "table %s at 2^%u rows: a Merkle path of %u levels (cap_height %u) does not fit the recursion circuit of 2^%u rows",
+                      TABLES[t].name, d, d + cfg->stark_rate_bits - cfg->stark_cap_height, cfg->stark_cap_height, rc.log_n);
+    const air::plonk::Layout all[4] = {special[0], special[1], special[2], shrink_lay};
+    for (const air::plonk::Layout& l : all)
+      if (!air::plonk::layout_ok(l, 1u << rc.log_n))
+        return fail(BP_ERR_INVALID_INPUT, "the recursion shape's Merkle rows (%u paths of %u levels: log_n %u + rate_bits %u - cap_height %u) do not fit "
+                    "a circuit of 2^%u rows", l.n_paths, l.depth, rc.log_n, rc.rate_bits, rc.cap_height, rc.log_n);
+  }
   if (cfg->n_workers == 0 || cfg->n_workers > 64) return fail(BP_ERR_INVALID_INPUT, "n_workers out of range");
   int n_dev = bp_device_count();
   if (n_dev <= 0) return fail(BP_ERR_DEVICE, "no HIP device visible: the hot path has no CPU fallback");
@@ -574,24 +604,9 @@ int bp_state_build(const bp_config* cfg, bp_state** out) try {
                              air::plonk::Layout{CHAIN_PATH_PI0 + 8, 1, d + cfg->stark_rate_bits - cfg->stark_cap_height, CHAIN_PATH_PI0},
                              &s->table_circuits[idx]))) return r;
   }
-  // Every recursion circuit walks one Merkle path per child: root (seven chains), aggregation (two children: their
-  // paths' words follow the digests and flags), block (the aggregation child's), a table's shrink circuit (the level below)
-  const uint32_t depth = rc.log_n + rc.rate_bits - rc.cap_height;
-  // Every circuit whose children are recursion-shaped proofs (all but level 0 of a chain, whose child is a table's STARK
-  // proof of up to 2432 columns) also HASHES the row each child opens (its leaf: the child's n_cols trace values) before
-  // it walks up from it -- merkle_proofs::verify_merkle_proof_to_cap whole -- where the circuit has the rows for it (a
-  // 2^6-row test circuit has them for one child, not for seven: both sides take the same decision from the shape alone)
-  auto with_leaf = [&](air::plonk::Layout lay) {
-    air::plonk::Layout l = lay;
-    l.leaf_len = rc.n_cols;
-    return (rc.air_id == air::PLONK && air::plonk::layout_ok(l, 1u << rc.log_n)) ? l : lay;
-  };
   for (int t = 0; t < BP_NUM_TABLES; t++)
-    if ((r = build_circuit(s->builder, rc, circuit_seed(t, SHRINK_SEED_DEGREE), with_leaf(air::plonk::Layout{CHAIN_PATH_PI0 + 8, 1, depth, CHAIN_PATH_PI0}),
+    if ((r = build_circuit(s->builder, rc, circuit_seed(t, SHRINK_SEED_DEGREE), shrink_lay,
                            &s->shrink_circuits[t]))) return r;
-  air::plonk::Layout special[3] = {with_leaf({ROOT_PATH_PI0 + 8 * BP_NUM_TABLES + BP_PV_WORDS, BP_NUM_TABLES, depth, ROOT_PATH_PI0}),
-                                   with_leaf({AGG_PATH_PI0 + 2 * 8 + BP_PV_WORDS, 2, depth, AGG_PATH_PI0}),
-                                   with_leaf({BLOCK_PATH_PI0 + 8 + BP_PV_WORDS, 1, depth, BLOCK_PATH_PI0})};
   for (uint32_t k = 0; k < 3; k++)
     if ((r = build_circuit(s->builder, rc, circuit_seed(CIRCUIT_ROOT + k, 0), special[k], &s->special[k]))) return r;
   BPG_HIP(hipStreamSynchronize(s->builder.stream));

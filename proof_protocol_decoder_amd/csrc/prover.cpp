@@ -239,7 +239,15 @@ int check_cfg(const StarkCfg& c) {
   if (c.arity_bits != 4) return fail(BP_ERR_UNSUPPORTED, "only arity_bits = 4 is built");
   if (c.num_queries == 0 || c.num_queries > 128) return fail(BP_ERR_INVALID_INPUT, "num_queries out of range");
   if (c.pow_bits > 32 || c.cap_height > 8) return fail(BP_ERR_INVALID_INPUT, "pow_bits/cap_height out of range");
-  // the final polynomial is interpolated on the host in O(len^2): at most 256 points by design
+  // The last FRI layer is interpolated on the host in O(points^2), from the mailbox.  final_poly_bits does not bound it
+  // alone: folding stops at the first d (log2 of the polynomial's length) with d <= final_poly_bits, or
+  // d + rate_bits < cap_height + arity_bits (the folded layer's tree would be smaller than a cap), or d < arity_bits.  A
+  // config accepted here has arity_bits = 4, cap_height <= 8, final_poly_bits <= 8, so with one of the three true
+  //   d + rate_bits <= max(final_poly_bits + rate_bits, cap_height + 3, 3 + rate_bits) <= 11:
+  // at most 2^11 points, a final polynomial of at most 2^10 coefficients (log_n = 10 or 14, rate_bits = 1, cap_height = 8)
+  // -- not 2^final_poly_bits.  MAX_LOCKSTEP = 24 proofs' last layers are 2 * 2^11 * 24 = 98304 words of the 2^22-word
+  // mailbox, so prove_batch's "final FRI layer does not fit the mailbox" cannot be reached by an accepted config; the
+  // interpolation costs 2^22 multiply-adds per extension limb and proof at the worst.
   if (c.final_poly_bits > 8) return fail(BP_ERR_INVALID_INPUT, "final_poly_bits must be <= 8");
   if (c.n_const > 4096) return fail(BP_ERR_INVALID_INPUT, "n_const out of range");
   if (n_fri_layers(c) > 8) return fail(BP_ERR_INVALID_INPUT, "too many FRI layers");

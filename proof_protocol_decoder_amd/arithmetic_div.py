@@ -10,16 +10,12 @@ layout and the soundness notes; include/bpg.h the statement and the input words.
 Every row proves q y + r = x over the integers, r < y unless y = 0, and res = 0 (y = 0), q (is_div), r (is_mod).  The
 one product port exposes (is_div, is_mod, x limbs, y limbs, res limbs) on the rows whose filter column g is 1.
 """
-import ctypes as C
-
-import numpy as np
-
+from . import word_table
 from .air_program import ALL_ROWS, Builder
+from .word_table import BASE, EXPOSED, LIMB_BITS, _word, bits_sum, bits_value, remainder_limb
 
 OP_NONE, OP_DIV, OP_MOD = 0, 1, 2
-EXPOSED = 1 << 8          # bit 8 of input word 0: the row's filter g
-LIMBS, LIMB_BITS, CARRY_BITS, N_CARRIES = 16, 16, 19, 15
-BASE = 1 << LIMB_BITS
+LIMBS, CARRY_BITS, N_CARRIES = 16, 19, 15
 
 # ---- the column map (bp_arithmetic_div_layout states the kernel's)
 COL_IS_DIV, COL_IS_MOD, COL_G, COL_Z, COL_INV = 0, 1, 2, 3, 4
@@ -60,7 +56,7 @@ LIMBS_PER_UNIT = 2
 
 def first_index(name):
     """the constraint index at which family `name` starts"""
-    return sum(count for _, count, _ in FAMILIES[:FAMILY_INDEX[name]])
+    return word_table.first_index(FAMILIES, name)
 
 
 def program(limbs_per_unit=LIMBS_PER_UNIT):
@@ -71,19 +67,8 @@ def program(limbs_per_unit=LIMBS_PER_UNIT):
     is_div, is_mod, g, z = b.loc(COL_IS_DIV), b.loc(COL_IS_MOD), b.loc(COL_G), b.loc(COL_Z)
     not_zero = 1 - z
 
-    def bits_value(col, n, cidx):
-        v = 0
-        for j in range(n - 1, -1, -1):
-            bit = b.loc(col + j)
-            b.emit(cidx + j, bit * bit - bit)
-            v = (v + v) + bit
-        return v
-
     b.unit()
-    for j, f in enumerate((is_div, is_mod, z)):
-        b.emit(at["flags"] + j, f * f - f)
-    b.emit(at["one_flag"], is_div * is_mod)
-    b.emit(at["filter"], g * (1 - is_div - is_mod))
+    word_table.flags(b, at, is_div, is_mod, g, z)
     # T_i = y_15 + ... + y_(16 - i): q_i T_i sums the products of q_i that land in columns 16 .. 30; T_16 = S
     suffix, high = 0, 0
     for i in range(1, LIMBS + 1):
@@ -91,23 +76,20 @@ def program(limbs_per_unit=LIMBS_PER_UNIT):
         if i < LIMBS:
             high = high + b.loc(COL_Q + i) * suffix
     b.emit(at["high"], high)
-    b.emit(at["zero"], z * suffix)
-    b.emit(at["zero"] + 1, suffix * b.loc(COL_INV) - not_zero)
+    word_table.zero_test(b, at, z, suffix, b.loc(COL_INV), not_zero)
 
     carry = borrow = 0
     for k in range(LIMBS):
         if k % limbs_per_unit == 0:
             b.unit()
             if k:   # the carries into this unit's first limb, summed again here: registers do not live across units
-                carry = 0
-                for j in range(CARRY_BITS - 1, -1, -1):
-                    carry = (carry + carry) + b.loc(COL_CARRY + CARRY_BITS * (k - 1) + j)
+                carry = bits_sum(b, COL_CARRY + CARRY_BITS * (k - 1), CARRY_BITS)
                 borrow = b.loc(COL_BORROW + k - 1)
-        xk = bits_value(COL_X_BITS + LIMB_BITS * k, LIMB_BITS, at["x_bits"] + LIMB_BITS * k)
-        yk = bits_value(COL_Y_BITS + LIMB_BITS * k, LIMB_BITS, at["y_bits"] + LIMB_BITS * k)
-        qk = bits_value(COL_Q_BITS + LIMB_BITS * k, LIMB_BITS, at["q_bits"] + LIMB_BITS * k)
-        rk = bits_value(COL_R_BITS + LIMB_BITS * k, LIMB_BITS, at["r_bits"] + LIMB_BITS * k)
-        dk = bits_value(COL_D_BITS + LIMB_BITS * k, LIMB_BITS, at["d_bits"] + LIMB_BITS * k)
+        xk = bits_value(b, COL_X_BITS + LIMB_BITS * k, LIMB_BITS, at["x_bits"] + LIMB_BITS * k)
+        yk = bits_value(b, COL_Y_BITS + LIMB_BITS * k, LIMB_BITS, at["y_bits"] + LIMB_BITS * k)
+        qk = bits_value(b, COL_Q_BITS + LIMB_BITS * k, LIMB_BITS, at["q_bits"] + LIMB_BITS * k)
+        rk = bits_value(b, COL_R_BITS + LIMB_BITS * k, LIMB_BITS, at["r_bits"] + LIMB_BITS * k)
+        dk = bits_value(b, COL_D_BITS + LIMB_BITS * k, LIMB_BITS, at["d_bits"] + LIMB_BITS * k)
         b.emit(at["x_limbs"] + k, b.loc(COL_X + k) - xk)
         b.emit(at["y_limbs"] + k, b.loc(COL_Y + k) - yk)
         b.emit(at["q_limbs"] + k, b.loc(COL_Q + k) - qk)
@@ -115,15 +97,12 @@ def program(limbs_per_unit=LIMBS_PER_UNIT):
         for i in range(k + 1):
             conv = conv + b.loc(COL_Q + i) * b.loc(COL_Y + k - i)
         if k < N_CARRIES:
-            out = bits_value(COL_CARRY + CARRY_BITS * k, CARRY_BITS, at["carry_bits"] + CARRY_BITS * k)
+            out = bits_value(b, COL_CARRY + CARRY_BITS * k, CARRY_BITS, at["carry_bits"] + CARRY_BITS * k)
             b.emit(at["product"] + k, (conv + rk + carry) - (xk + BASE * out))
             carry = out
         else:
             b.emit(at["product"] + k, (conv + rk + carry) - xk)
-        bk = b.loc(COL_BORROW + k)
-        b.emit(at["borrow_bits"] + k, bk * bk - bk)
-        b.emit(at["remainder"] + k, not_zero * ((rk + dk + (1 if k == 0 else borrow)) - (yk + BASE * bk)))
-        borrow = bk
+        borrow = remainder_limb(b, at, k, rk, dk, yk, borrow, COL_BORROW, not_zero)
         b.emit(at["result"] + k, b.loc(COL_RES + k) - not_zero * (is_div * b.loc(COL_Q + k) + is_mod * rk))
     b.emit(at["remainder_top"], not_zero * borrow)
     b.port(g, [b.loc(c) for c in TUPLE_COLS])
@@ -132,46 +111,20 @@ def program(limbs_per_unit=LIMBS_PER_UNIT):
 
 def kernel_layout():
     """bp_arithmetic_div_layout: the column map csrc/arithmetic_div.hip stores by, in LAYOUT's order"""
-    from ._lib import check, own
-    out = (C.c_uint32 * len(LAYOUT))()
-    check(own().bp_arithmetic_div_layout(out, len(LAYOUT)))
-    return tuple(int(v) for v in out)
-
-
-_registered = None
+    return word_table.kernel_layout("bp_arithmetic_div_layout", len(LAYOUT))
 
 
 def register():
     """Assembles and registers the program (once per process) and returns its air_id.  The column map exists twice, here
     and in the witness kernel: RuntimeError if the two disagree."""
-    global _registered
-    if _registered is None:
-        from . import ops
-        got = kernel_layout()
-        if got != LAYOUT:
-            raise RuntimeError("arithmetic_div: the witness kernel's column map %s is not the program's %s" % (got, LAYOUT))
-        _registered = ops.air_register(program().assemble())
-    return _registered
+    return word_table.register("arithmetic_div", LAYOUT, "bp_arithmetic_div_layout", program)
 
 
 def pack_inputs(ops_list):
     """[(op, x, y, exposed), ...] of Python integers -> the [n, 9] uint64 input words of bp_arithmetic_div_trace: word 0
     = op (1 div, 2 mod, else a padding row) | exposed << 8, then the four 64-bit words of x and of y, least significant
     first"""
-    out = np.zeros((len(ops_list), 9), dtype=np.uint64)
-    for i, (op, x, y, exposed) in enumerate(ops_list):
-        if not (0 <= op < 256 and 0 <= x < 1 << 256 and 0 <= y < 1 << 256):
-            raise ValueError("row %d: op is a byte, x and y are 256-bit words" % i)
-        out[i, 0] = op | (EXPOSED if exposed else 0)
-        for w in range(4):
-            out[i, 1 + w] = (x >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
-            out[i, 5 + w] = (y >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
-    return out
-
-
-def _word(cells, col, width, n, step=1):
-    """sum of the `n` values at col, col + step, ..., each `width` bits wide"""
-    return sum(int(cells[col + step * k]) << (width * k) for k in range(n))
+    return word_table.pack_inputs(ops_list, 2, "x and y")
 
 
 def unpack_row(trace, i):

@@ -11,16 +11,12 @@ Every row proves U = q M + r over the integers -- U = a + b (257 bits) or a b (5
 the way, M = m + z 2^256 with z = [m = 0] --, r < m unless m = 0, and res = (1 - z) r.  The one product port exposes
 (is_addmod, is_mulmod, a limbs, b limbs, m limbs, res limbs) on the rows whose filter column g is 1.
 """
-import ctypes as C
-
-import numpy as np
-
+from . import word_table
 from .air_program import ALL_ROWS, Builder
+from .word_table import BASE, EXPOSED, LIMB_BITS, _word, bits_sum, bits_value, remainder_limb
 
 OP_NONE, OP_ADDMOD, OP_MULMOD = 0, 1, 2
-EXPOSED = 1 << 8          # bit 8 of input word 0: the row's filter g
-LIMBS, Q_LIMBS, LIMB_BITS, CARRY_BITS, N_CARRIES = 16, 32, 16, 21, 31
-BASE = 1 << LIMB_BITS
+LIMBS, Q_LIMBS, CARRY_BITS, N_CARRIES = 16, 32, 21, 31
 CARRY_OFFSET = 1 << 20    # a carry column group holds c_k + 2^20: the carries are signed, |c_k| < 2^20
 
 # ---- the column map (bp_arithmetic_mod_layout states the kernel's)
@@ -66,7 +62,7 @@ COLS_PER_UNIT = 1
 
 def first_index(name):
     """the constraint index at which family `name` starts"""
-    return sum(count for _, count, _ in FAMILIES[:FAMILY_INDEX[name]])
+    return word_table.first_index(FAMILIES, name)
 
 
 def program(cols_per_unit=COLS_PER_UNIT):
@@ -78,22 +74,11 @@ def program(cols_per_unit=COLS_PER_UNIT):
     is_addmod, is_mulmod, g, z = b.loc(COL_IS_ADDMOD), b.loc(COL_IS_MULMOD), b.loc(COL_G), b.loc(COL_Z)
     not_zero = 1 - z
 
-    def bits_value(col, n, cidx):
-        v = 0
-        for j in range(n - 1, -1, -1):
-            bit = b.loc(col + j)
-            b.emit(cidx + j, bit * bit - bit)
-            v = (v + v) + bit
-        return v
-
     def modulus(j):   # limb j of M = m + z 2^256
         return z if j == LIMBS else b.loc(COL_M + j)
 
     b.unit()
-    for j, f in enumerate((is_addmod, is_mulmod, z)):
-        b.emit(at["flags"] + j, f * f - f)
-    b.emit(at["one_flag"], is_addmod * is_mulmod)
-    b.emit(at["filter"], g * (1 - is_addmod - is_mulmod))
+    word_table.flags(b, at, is_addmod, is_mulmod, g, z)
     # T_i = M_16 + M_15 + ... + M_(32 - i): q_i T_i sums the products of q_i that land in columns 32 .. 47
     suffix, high = 0, 0
     for i in range(LIMBS, Q_LIMBS):
@@ -103,21 +88,17 @@ def program(cols_per_unit=COLS_PER_UNIT):
     s = 0
     for j in range(LIMBS):
         s = s + b.loc(COL_M + j)
-    b.emit(at["zero"], z * s)
-    b.emit(at["zero"] + 1, s * b.loc(COL_INV) - not_zero)
+    word_table.zero_test(b, at, z, s, b.loc(COL_INV), not_zero)
 
     carry = borrow = 0
     for k in range(Q_LIMBS):
         if k % cols_per_unit == 0:
             b.unit()
             if k:   # the carry into this unit's first column, summed again here: registers do not live across units
-                carry = 0
-                for j in range(CARRY_BITS - 1, -1, -1):
-                    carry = (carry + carry) + b.loc(COL_CARRY + CARRY_BITS * (k - 1) + j)
-                carry = carry - CARRY_OFFSET
+                carry = bits_sum(b, COL_CARRY + CARRY_BITS * (k - 1), CARRY_BITS) - CARRY_OFFSET
                 if k < LIMBS:
                     borrow = b.loc(COL_BORROW + k - 1)
-        qk = bits_value(COL_Q_BITS + LIMB_BITS * k, LIMB_BITS, at["q_bits"] + LIMB_BITS * k)
+        qk = bits_value(b, COL_Q_BITS + LIMB_BITS * k, LIMB_BITS, at["q_bits"] + LIMB_BITS * k)
         b.emit(at["q_limbs"] + k, b.loc(COL_Q + k) - qk)
         left = right = 0
         for i in range(max(0, k - LIMBS + 1), min(k, LIMBS - 1) + 1):
@@ -126,23 +107,20 @@ def program(cols_per_unit=COLS_PER_UNIT):
         for j in range(max(0, k - Q_LIMBS + 1), min(k, LIMBS) + 1):
             right = right + b.loc(COL_Q + k - j) * modulus(j)
         if k < LIMBS:
-            ak = bits_value(COL_A_BITS + LIMB_BITS * k, LIMB_BITS, at["a_bits"] + LIMB_BITS * k)
-            bk = bits_value(COL_B_BITS + LIMB_BITS * k, LIMB_BITS, at["b_bits"] + LIMB_BITS * k)
-            mk = bits_value(COL_M_BITS + LIMB_BITS * k, LIMB_BITS, at["m_bits"] + LIMB_BITS * k)
-            rk = bits_value(COL_R_BITS + LIMB_BITS * k, LIMB_BITS, at["r_bits"] + LIMB_BITS * k)
-            dk = bits_value(COL_D_BITS + LIMB_BITS * k, LIMB_BITS, at["d_bits"] + LIMB_BITS * k)
+            ak = bits_value(b, COL_A_BITS + LIMB_BITS * k, LIMB_BITS, at["a_bits"] + LIMB_BITS * k)
+            bk = bits_value(b, COL_B_BITS + LIMB_BITS * k, LIMB_BITS, at["b_bits"] + LIMB_BITS * k)
+            mk = bits_value(b, COL_M_BITS + LIMB_BITS * k, LIMB_BITS, at["m_bits"] + LIMB_BITS * k)
+            rk = bits_value(b, COL_R_BITS + LIMB_BITS * k, LIMB_BITS, at["r_bits"] + LIMB_BITS * k)
+            dk = bits_value(b, COL_D_BITS + LIMB_BITS * k, LIMB_BITS, at["d_bits"] + LIMB_BITS * k)
             b.emit(at["abm_limbs"] + 3 * k, b.loc(COL_A + k) - ak)
             b.emit(at["abm_limbs"] + 3 * k + 1, b.loc(COL_B + k) - bk)
             b.emit(at["abm_limbs"] + 3 * k + 2, b.loc(COL_M + k) - mk)
             left = left + is_addmod * (b.loc(COL_A + k) + b.loc(COL_B + k))
             right = right + rk
-            wk = b.loc(COL_BORROW + k)
-            b.emit(at["borrow_bits"] + k, wk * wk - wk)
-            b.emit(at["remainder"] + k, not_zero * ((rk + dk + (1 if k == 0 else borrow)) - (mk + BASE * wk)))
-            borrow = wk
+            borrow = remainder_limb(b, at, k, rk, dk, mk, borrow, COL_BORROW, not_zero)
             b.emit(at["result"] + k, b.loc(COL_RES + k) - not_zero * rk)
         if k < N_CARRIES:
-            out = bits_value(COL_CARRY + CARRY_BITS * k, CARRY_BITS, at["carry_bits"] + CARRY_BITS * k) - CARRY_OFFSET
+            out = bits_value(b, COL_CARRY + CARRY_BITS * k, CARRY_BITS, at["carry_bits"] + CARRY_BITS * k) - CARRY_OFFSET
             b.emit(at["product"] + k, (left + carry) - (right + BASE * out))
             carry = out
         else:
@@ -155,47 +133,20 @@ def program(cols_per_unit=COLS_PER_UNIT):
 
 def kernel_layout():
     """bp_arithmetic_mod_layout: the column map csrc/arithmetic_mod.hip stores by, in LAYOUT's order"""
-    from ._lib import check, own
-    out = (C.c_uint32 * len(LAYOUT))()
-    check(own().bp_arithmetic_mod_layout(out, len(LAYOUT)))
-    return tuple(int(v) for v in out)
-
-
-_registered = None
+    return word_table.kernel_layout("bp_arithmetic_mod_layout", len(LAYOUT))
 
 
 def register():
     """Assembles and registers the program (once per process) and returns its air_id.  The column map exists twice, here
     and in the witness kernel: RuntimeError if the two disagree."""
-    global _registered
-    if _registered is None:
-        from . import ops
-        got = kernel_layout()
-        if got != LAYOUT:
-            raise RuntimeError("arithmetic_mod: the witness kernel's column map %s is not the program's %s" % (got, LAYOUT))
-        _registered = ops.air_register(program().assemble())
-    return _registered
+    return word_table.register("arithmetic_mod", LAYOUT, "bp_arithmetic_mod_layout", program)
 
 
 def pack_inputs(ops_list):
     """[(op, a, b, m, exposed), ...] of Python integers -> the [n, 13] uint64 input words of bp_arithmetic_mod_trace:
     word 0 = op (1 addmod, 2 mulmod, else a padding row) | exposed << 8, then the four 64-bit words of a, of b and of m,
     least significant first"""
-    out = np.zeros((len(ops_list), 13), dtype=np.uint64)
-    for i, (op, a, b, m, exposed) in enumerate(ops_list):
-        if not (0 <= op < 256 and all(0 <= v < 1 << 256 for v in (a, b, m))):
-            raise ValueError("row %d: op is a byte, a, b and m are 256-bit words" % i)
-        out[i, 0] = op | (EXPOSED if exposed else 0)
-        for w in range(4):
-            out[i, 1 + w] = (a >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
-            out[i, 5 + w] = (b >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
-            out[i, 9 + w] = (m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
-    return out
-
-
-def _word(cells, col, width, n):
-    """sum of the `n` values at col, col + 1, ..., each `width` bits wide"""
-    return sum(int(cells[col + k]) << (width * k) for k in range(n))
+    return word_table.pack_inputs(ops_list, 3, "a, b and m")
 
 
 def unpack_row(trace, i):

@@ -4,9 +4,8 @@
 // words, AIRS.md section 2 ("Division (a shipped program)") the columns and why the constraints are sound.
 //
 // The column map below exists a second time, in the Python program; bp_arithmetic_div_layout hands this one out so that
-// arithmetic_div.register() can refuse to run when the two differ.
-#include "common.hpp"
-#include "gl.hpp"
+// arithmetic_div.register() can refuse to run when the two differ.  Everything a quotient / remainder / slack table
+// over 16-bit limbs has in common with the next one is in word256.cuh: this file keeps the map, q y + r = x and the kernel.
 #include "word256.cuh"
 
 namespace {
@@ -20,13 +19,11 @@ constexpr uint32_t COL_X_BITS = COL_Q + LIMBS, COL_Y_BITS = COL_X_BITS + 256, CO
 constexpr uint32_t COL_CARRY = COL_D_BITS + 256, COL_BORROW = COL_CARRY + N_CARRIES * CARRY_BITS, N_COLS = COL_BORROW + LIMBS;
 constexpr uint32_t LAYOUT[] = {N_COLS, COL_IS_DIV, COL_IS_MOD, COL_G, COL_Z, COL_INV, COL_X, COL_Y, COL_RES, COL_Q, COL_X_BITS,
                                COL_Y_BITS, COL_Q_BITS, COL_R_BITS, COL_D_BITS, COL_CARRY, CARRY_BITS, COL_BORROW};
-constexpr uint32_t LAYOUT_WORDS = sizeof(LAYOUT) / sizeof(LAYOUT[0]);
+constexpr word256::SharedCols SHARED = {COL_IS_DIV, COL_IS_MOD, COL_G, COL_Z, COL_INV, COL_R_BITS, COL_D_BITS, COL_BORROW};
 }  // namespace dv
 
-// the 256-bit word in named registers, its limbs and the lane's row: shared with arithmetic_mod.hip
 using word256::limb;
 using word256::Row;
-using word256::sub256;
 using word256::U256;
 
 // what a row stores for limb K of x, y, q, r, d and the result, and the product column K: the carry out of it (columns
@@ -34,7 +31,7 @@ using word256::U256;
 template <uint32_t K>
 __device__ __forceinline__ void store_limb(const Row& row, const U256& x, const U256& y, const U256& q, const U256& r, const U256& d,
                                            const U256& res, uint64_t conv, uint64_t& carry, uint32_t& borrow, bool y_zero) {
-  const uint32_t xk = limb<K>(x), yk = limb<K>(y), qk = limb<K>(q), rk = limb<K>(r), dk = limb<K>(d);
+  const uint32_t xk = limb<K>(x), yk = limb<K>(y), qk = limb<K>(q);
   row.put(dv::COL_X + K, xk);
   row.put(dv::COL_Y + K, yk);
   row.put(dv::COL_Q + K, qk);
@@ -42,14 +39,10 @@ __device__ __forceinline__ void store_limb(const Row& row, const U256& x, const 
   row.put_bits(dv::COL_X_BITS + 16 * K, xk, 16);
   row.put_bits(dv::COL_Y_BITS + 16 * K, yk, 16);
   row.put_bits(dv::COL_Q_BITS + 16 * K, qk, 16);
-  row.put_bits(dv::COL_R_BITS + 16 * K, rk, 16);
-  row.put_bits(dv::COL_D_BITS + 16 * K, dk, 16);
   // conv + r_k + carry in = x_k + 2^16 carry out: below 16 * 2^32 + 2^16 + 2^19, and at least x_k on an honest row
-  carry = (conv + rk + carry - xk) >> 16;
+  carry = (conv + limb<K>(r) + carry - xk) >> 16;
   if constexpr (K < dv::N_CARRIES) row.put_bits(dv::COL_CARRY + dv::CARRY_BITS * K, (uint32_t)carry, dv::CARRY_BITS);
-  // r_k + d_k + [K = 0] + carry bit in = y_k + 2^16 carry bit out; all zero when y = 0 (d = 0 there, the bits too)
-  borrow = y_zero ? 0u : (rk + dk + (K == 0 ? 1u : borrow)) >> 16;
-  row.put(dv::COL_BORROW + K, borrow);
+  row.template put_remainder_limb<K>(dv::SHARED, r, d, y_zero, borrow);
 }
 
 // sum_{i + j = K} q_i y_j, K and every limb number a compile-time number
@@ -68,12 +61,6 @@ __device__ __forceinline__ void store_limbs(const Row& row, const U256& x, const
   }
 }
 
-template <uint32_t K = 0>
-__device__ __forceinline__ uint32_t limb_sum(const U256& w) {
-  if constexpr (K == dv::LIMBS) return 0;
-  else return limb<K>(w) + limb_sum<K + 1>(w);
-}
-
 // One operation per row, one lane per row.  inputs: [row][9] (include/bpg.h).  The lane divides by shift and subtract
 // over the register pair (r : q) -- q starts as x and gives a dividend bit to r at the top as it takes a quotient bit
 // at the bottom --, then derives every column from q and r.  Stores are column-major, so a wave's are contiguous.
@@ -83,49 +70,27 @@ arithmetic_div_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t* in = inputs + (uint64_t)i * 9;
-  const uint64_t w0 = in[0];
-  const uint32_t op = (uint32_t)w0 & 0xFFu;
-  const bool is_div = op == 1, is_mod = op == 2, live = is_div | is_mod;
+  const word256::Head h(in[0]);
   // a padding row ignores its operand words and its exposed bit: it is the all-zero row with z = 1
   const U256 zero{0, 0, 0, 0};
-  const U256 x = live ? U256{in[1], in[2], in[3], in[4]} : zero;
-  const U256 y = live ? U256{in[5], in[6], in[7], in[8]} : zero;
-  const bool y_zero = (y.a | y.b | y.c | y.d) == 0;
+  const U256 x = word256::operand<0>(in, h.live), y = word256::operand<1>(in, h.live);
+  const bool y_zero = word256::is_zero(y);
 
   U256 q = x, r = zero;
 #pragma unroll 1
   for (uint32_t it = 0; it < 256; it++) {
-    const uint32_t over = (uint32_t)(r.d >> 63);  // r < y before the shift, so 2 r + 1 may need a 257th bit
-    r.d = (r.d << 1) | (r.c >> 63);
-    r.c = (r.c << 1) | (r.b >> 63);
-    r.b = (r.b << 1) | (r.a >> 63);
-    r.a = (r.a << 1) | (q.d >> 63);
-    q.d = (q.d << 1) | (q.c >> 63);
-    q.c = (q.c << 1) | (q.b >> 63);
-    q.b = (q.b << 1) | (q.a >> 63);
-    q.a <<= 1;
-    uint32_t below;
-    const U256 diff = sub256(r, y, &below);
-    if (over | !below) {  // 2^256 over + r >= y: the difference is right modulo 2^256 and below y
-      r = diff;
-      q.a |= 1;
-    }
+    const uint64_t bit = word256::shift_in(q, 0);
+    word256::subtract_step(r, y, bit, q.a);
   }
   if (y_zero) {  // the loop subtracted zero 256 times: q is all ones, r is x.  The EVM's x / 0: q = 0, r = x
     q = zero;
     r = x;
   }
-  uint32_t unused;
-  // the slack of r < y: r + d + 1 = y
-  const U256 d = y_zero ? zero : sub256(sub256(y, r, &unused), U256{1, 0, 0, 0}, &unused);
-  const U256 res = y_zero ? zero : is_div ? q : r;  // (a padding row has y = 0)
+  const U256 d = word256::slack(y, r, y_zero);
+  const U256 res = y_zero ? zero : h.op_a ? q : r;  // (a padding row has y = 0)
 
   const Row row{t + i, n};
-  row.put(dv::COL_IS_DIV, is_div);
-  row.put(dv::COL_IS_MOD, is_mod);
-  row.put(dv::COL_G, live & (uint32_t)((w0 >> 8) & 1));
-  row.put(dv::COL_Z, y_zero);
-  row.put(dv::COL_INV, y_zero ? 0 : gl::inv((uint64_t)limb_sum(y)));
+  row.put_head(dv::SHARED, h, y, y_zero);
   uint64_t carry = 0;
   uint32_t borrow = 0;
   store_limbs<0>(row, x, y, q, r, d, res, carry, borrow, y_zero);
@@ -135,20 +100,10 @@ arithmetic_div_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
 
 extern "C" {
 
-int bp_arithmetic_div_layout(uint32_t* out, size_t n_words) {
-  if (!out || n_words < dv::LAYOUT_WORDS)
-    return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_div_layout: the layout is %u words", dv::LAYOUT_WORDS);
-  for (uint32_t k = 0; k < dv::LAYOUT_WORDS; k++) out[k] = dv::LAYOUT[k];
-  return BP_OK;
-}
+int bp_arithmetic_div_layout(uint32_t* out, size_t n_words) { return word256::layout_entry("bp_arithmetic_div_layout", dv::LAYOUT, out, n_words); }
 
 int bp_arithmetic_div_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_inputs) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_div_trace: null inputs (this table has no seeded draw)");
-  if (!d_trace_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_div_trace: null output");
-  if (log_n < 4 || log_n > 26) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_div_trace: log_n out of range");
-  arithmetic_div_trace_kernel<<<bpg::ceil_div((uint64_t)1 << log_n, 256), 256, 0, bpg::as_stream(stream)>>>(d_trace_out, d_inputs, log_n);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
+  return word256::trace_entry("bp_arithmetic_div_trace", arithmetic_div_trace_kernel, d_inputs, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_arithmetic_div_trace")
 

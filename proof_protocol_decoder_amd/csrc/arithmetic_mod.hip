@@ -4,9 +4,8 @@
 // ("Modular (a shipped program)") the columns and why the constraints are sound.
 //
 // The column map below exists a second time, in the Python program; bp_arithmetic_mod_layout hands this one out so that
-// arithmetic_mod.register() can refuse to run when the two differ.
-#include "common.hpp"
-#include "gl.hpp"
+// arithmetic_mod.register() can refuse to run when the two differ.  What this table has in common with the division
+// table is in word256.cuh: this file keeps the map, U = a + b or a b in 512 bits, the signed product columns and the kernel.
 #include "word256.cuh"
 
 namespace {
@@ -21,13 +20,12 @@ constexpr uint32_t COL_CARRY = COL_D_BITS + 256, COL_BORROW = COL_CARRY + N_CARR
 constexpr uint32_t LAYOUT[] = {N_COLS, COL_IS_ADDMOD, COL_IS_MULMOD, COL_G, COL_Z, COL_INV, COL_A, COL_B, COL_M, COL_RES, COL_Q,
                                COL_A_BITS, COL_B_BITS, COL_M_BITS, COL_Q_BITS, COL_R_BITS, COL_D_BITS, COL_CARRY, CARRY_BITS,
                                CARRY_OFFSET, COL_BORROW};
-constexpr uint32_t LAYOUT_WORDS = sizeof(LAYOUT) / sizeof(LAYOUT[0]);
+constexpr word256::SharedCols SHARED = {COL_IS_ADDMOD, COL_IS_MULMOD, COL_G, COL_Z, COL_INV, COL_R_BITS, COL_D_BITS, COL_BORROW};
 static_assert(N_COLS == 2560, "AIRS.md section 2 lists 2560 columns");
 }  // namespace md
 
 using word256::limb;
 using word256::Row;
-using word256::sub256;
 using word256::U256;
 
 // A 512-bit word as eight named registers (two U256): the intermediate U and the quotient
@@ -108,7 +106,7 @@ __device__ __forceinline__ void store_column(const Row& row, const U256& a, cons
   row.put_bits(md::COL_Q_BITS + 16 * K, qk, 16);
   int64_t acc = carry + (int64_t)(is_mulmod ? conv_left<K>(a, b) : 0) - (int64_t)conv_right<K>(q, m, m_zero);
   if constexpr (K < md::LIMBS) {
-    const uint32_t ak = limb<K>(a), bk = limb<K>(b), mk = limb<K>(m), rk = limb<K>(r), dk = limb<K>(d);
+    const uint32_t ak = limb<K>(a), bk = limb<K>(b), mk = limb<K>(m), rk = limb<K>(r);
     row.put(md::COL_A + K, ak);
     row.put(md::COL_B + K, bk);
     row.put(md::COL_M + K, mk);
@@ -116,12 +114,8 @@ __device__ __forceinline__ void store_column(const Row& row, const U256& a, cons
     row.put_bits(md::COL_A_BITS + 16 * K, ak, 16);
     row.put_bits(md::COL_B_BITS + 16 * K, bk, 16);
     row.put_bits(md::COL_M_BITS + 16 * K, mk, 16);
-    row.put_bits(md::COL_R_BITS + 16 * K, rk, 16);
-    row.put_bits(md::COL_D_BITS + 16 * K, dk, 16);
+    row.template put_remainder_limb<K>(md::SHARED, r, d, m_zero, borrow);
     acc += (int64_t)(is_addmod ? ak + bk : 0u) - (int64_t)rk;
-    // r_k + d_k + [K = 0] + carry bit in = m_k + 2^16 carry bit out; all zero when m = 0 (d = 0 there)
-    borrow = m_zero ? 0u : (rk + dk + (K == 0 ? 1u : borrow)) >> 16;
-    row.put(md::COL_BORROW + K, borrow);
   }
   carry = acc >> 16;  // arithmetic: the carries are signed
   if constexpr (K < md::N_CARRIES) row.put_bits(md::COL_CARRY + md::CARRY_BITS * K, (uint32_t)(carry + (int64_t)md::CARRY_OFFSET), md::CARRY_BITS);
@@ -136,12 +130,6 @@ __device__ __forceinline__ void store_columns(const Row& row, const U256& a, con
   }
 }
 
-template <uint32_t K = 0>
-__device__ __forceinline__ uint32_t limb_sum(const U256& w) {
-  if constexpr (K == md::LIMBS) return 0;
-  else return limb<K>(w) + limb_sum<K + 1>(w);
-}
-
 // One operation per row, one lane per row.  inputs: [row][13] (include/bpg.h).  The lane forms U = a + b or a b in eight
 // registers and divides by shift and subtract over (r : U) -- U gives a dividend bit to r at the top as it takes a
 // quotient bit at the bottom, 512 steps --, then derives every column from q and r.  Stores are column-major.
@@ -151,15 +139,12 @@ arithmetic_mod_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t* in = inputs + (uint64_t)i * 13;
-  const uint64_t w0 = in[0];
-  const uint32_t op = (uint32_t)w0 & 0xFFu;
-  const bool is_addmod = op == 1, is_mulmod = op == 2, live = is_addmod | is_mulmod;
+  const word256::Head h(in[0]);
+  const bool is_addmod = h.op_a, is_mulmod = h.op_b;
   // a padding row ignores its operand words and its exposed bit: U = 0, z = 1, the carry columns hold the offset
   const U256 zero{0, 0, 0, 0};
-  const U256 a = live ? U256{in[1], in[2], in[3], in[4]} : zero;
-  const U256 b = live ? U256{in[5], in[6], in[7], in[8]} : zero;
-  const U256 m = live ? U256{in[9], in[10], in[11], in[12]} : zero;
-  const bool m_zero = (m.a | m.b | m.c | m.d) == 0;
+  const U256 a = word256::operand<0>(in, h.live), b = word256::operand<1>(in, h.live), m = word256::operand<2>(in, h.live);
+  const bool m_zero = word256::is_zero(m);
 
   U512 q = is_mulmod ? mul256(a, b) : add256(a, b);   // U now, the quotient after the loop
   U256 r = zero;
@@ -170,37 +155,14 @@ arithmetic_mod_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
   } else {
 #pragma unroll 1
     for (uint32_t it = 0; it < 512; it++) {
-      const uint32_t over = (uint32_t)(r.d >> 63);  // r < m before the shift, so 2 r + 1 may need a 257th bit
-      r.d = (r.d << 1) | (r.c >> 63);
-      r.c = (r.c << 1) | (r.b >> 63);
-      r.b = (r.b << 1) | (r.a >> 63);
-      r.a = (r.a << 1) | (q.hi.d >> 63);
-      q.hi.d = (q.hi.d << 1) | (q.hi.c >> 63);
-      q.hi.c = (q.hi.c << 1) | (q.hi.b >> 63);
-      q.hi.b = (q.hi.b << 1) | (q.hi.a >> 63);
-      q.hi.a = (q.hi.a << 1) | (q.lo.d >> 63);
-      q.lo.d = (q.lo.d << 1) | (q.lo.c >> 63);
-      q.lo.c = (q.lo.c << 1) | (q.lo.b >> 63);
-      q.lo.b = (q.lo.b << 1) | (q.lo.a >> 63);
-      q.lo.a <<= 1;
-      uint32_t below;
-      const U256 diff = sub256(r, m, &below);
-      if (over | !below) {  // 2^256 over + r >= m: the difference is right modulo 2^256 and below m
-        r = diff;
-        q.lo.a |= 1;
-      }
+      const uint64_t bit = word256::shift_in(q.hi, word256::shift_in(q.lo, 0));
+      word256::subtract_step(r, m, bit, q.lo.a);
     }
   }
-  uint32_t unused;
-  // the slack of r < m: r + d + 1 = m
-  const U256 d = m_zero ? zero : sub256(sub256(m, r, &unused), U256{1, 0, 0, 0}, &unused);
+  const U256 d = word256::slack(m, r, m_zero);
 
   const Row row{t + i, n};
-  row.put(md::COL_IS_ADDMOD, is_addmod);
-  row.put(md::COL_IS_MULMOD, is_mulmod);
-  row.put(md::COL_G, live & (uint32_t)((w0 >> 8) & 1));
-  row.put(md::COL_Z, m_zero);
-  row.put(md::COL_INV, m_zero ? 0 : gl::inv((uint64_t)limb_sum(m)));
+  row.put_head(md::SHARED, h, m, m_zero);
   int64_t carry = 0;
   uint32_t borrow = 0;
   store_columns<0>(row, a, b, m, q, r, d, is_addmod, is_mulmod, m_zero, carry, borrow);
@@ -210,20 +172,10 @@ arithmetic_mod_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
 
 extern "C" {
 
-int bp_arithmetic_mod_layout(uint32_t* out, size_t n_words) {
-  if (!out || n_words < md::LAYOUT_WORDS)
-    return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mod_layout: the layout is %u words", md::LAYOUT_WORDS);
-  for (uint32_t k = 0; k < md::LAYOUT_WORDS; k++) out[k] = md::LAYOUT[k];
-  return BP_OK;
-}
+int bp_arithmetic_mod_layout(uint32_t* out, size_t n_words) { return word256::layout_entry("bp_arithmetic_mod_layout", md::LAYOUT, out, n_words); }
 
 int bp_arithmetic_mod_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* d_trace_out, void* stream) try {
-  if (!d_inputs) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mod_trace: null inputs (this table has no seeded draw)");
-  if (!d_trace_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mod_trace: null output");
-  if (log_n < 4 || log_n > 26) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_arithmetic_mod_trace: log_n out of range");
-  arithmetic_mod_trace_kernel<<<bpg::ceil_div((uint64_t)1 << log_n, 256), 256, 0, bpg::as_stream(stream)>>>(d_trace_out, d_inputs, log_n);
-  BPG_LAUNCH_CHECK();
-  return BP_OK;
+  return word256::trace_entry("bp_arithmetic_mod_trace", arithmetic_mod_trace_kernel, d_inputs, log_n, d_trace_out, stream);
 }
 BPG_ABI_CATCH("bp_arithmetic_mod_trace")
 

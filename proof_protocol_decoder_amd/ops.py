@@ -210,19 +210,24 @@ def arithmetic_mul_trace(log_n, seed=0, inputs=None, device="cuda"):
     return air_trace(7, log_n, seed, inputs, device)
 
 
+def _word_table_trace(name, n_words, n_cols, log_n, inputs, device):
+    """bp_<name>: the witness [n_cols, 2^log_n] of a shipped table from inputs [2^log_n, n_words] on the device"""
+    if inputs is not None:
+        _require_cuda(inputs)
+        if tuple(inputs.shape) != (1 << log_n, n_words):
+            raise ValueError("%s: inputs are [%d, %d]: got %s" % (name, 1 << log_n, n_words, tuple(inputs.shape)))
+        device = inputs.device
+    out = torch.empty((n_cols, 1 << log_n), dtype=torch.int64, device=device)
+    check(getattr(own(), "bp_" + name)(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
+    return out
+
+
 def arithmetic_div_trace(log_n, inputs, device="cuda"):
     """bp_arithmetic_div_trace: the witness [1650, 2^log_n] of the division table (arithmetic_div.py: a shipped program,
     no built-in air_id); inputs [2^log_n, 9] int64 on the device (op 1 div / 2 mod / else padding | exposed << 8, the four
     words of x, of y: arithmetic_div.pack_inputs).  There is no seeded draw: inputs=None is refused by the library."""
     from .arithmetic_div import N_COLS
-    if inputs is not None:
-        _require_cuda(inputs)
-        if tuple(inputs.shape) != (1 << log_n, 9):
-            raise ValueError("arithmetic_div_trace: inputs are [%d, 9]: got %s" % (1 << log_n, tuple(inputs.shape)))
-        device = inputs.device
-    out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=device)
-    check(own().bp_arithmetic_div_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
-    return out
+    return _word_table_trace("arithmetic_div_trace", 9, N_COLS, log_n, inputs, device)
 
 
 def arithmetic_mod_trace(log_n, inputs, device="cuda"):
@@ -231,14 +236,7 @@ def arithmetic_mod_trace(log_n, inputs, device="cuda"):
     the four words of a, of b, of m: arithmetic_mod.pack_inputs).  There is no seeded draw: inputs=None is refused by the
     library."""
     from .arithmetic_mod import N_COLS
-    if inputs is not None:
-        _require_cuda(inputs)
-        if tuple(inputs.shape) != (1 << log_n, 13):
-            raise ValueError("arithmetic_mod_trace: inputs are [%d, 13]: got %s" % (1 << log_n, tuple(inputs.shape)))
-        device = inputs.device
-    out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=device)
-    check(own().bp_arithmetic_mod_trace(inputs.data_ptr() if inputs is not None else None, log_n, out.data_ptr(), _stream()))
-    return out
+    return _word_table_trace("arithmetic_mod_trace", 13, N_COLS, log_n, inputs, device)
 
 
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):

@@ -2,20 +2,16 @@
 shared by tests/test_arithmetic_div.py and tests/test_gpu_arithmetic_div.py.  It works from the statement in
 include/bpg.h and the column list in AIRS.md section 2 ("Division (a shipped program)") over Python integers (divmod):
 it imports nothing of the package, so the column map below is a third statement of it and the tests compare it with the
-package's.
+package's.  What it shares with the modular table's model is in tests/word_table_model.py, as independent as this file.
 
     w = honest(op, x, y, exposed)     the witness of one operation: a dict of what a row holds
     cells(w)                          the 1650 cells of its row
     CATALOGUE                         wrong witnesses, each otherwise consistent: (name, operation, forge, families broken)
 """
-import random
+import word_table_model as base
+from word_table_model import B, M256, P, limbs, word  # noqa: F401 (the tests read them here)
 
-import numpy as np
-
-P = 0xFFFFFFFF00000001
 NONE, DIV, MOD = 0, 1, 2
-B = 1 << 16
-M256 = (1 << 256) - 1
 CARRY_BITS = 19
 
 # AIRS.md section 2: five single columns, four limb blocks, five bit blocks, 15 carries of 19 bits, 16 carry bits of r + d + 1
@@ -28,14 +24,6 @@ FAMILIES = [("flags", 3), ("one_flag", 1), ("filter", 1), ("zero", 2), ("high", 
             ("q_bits", 256), ("r_bits", 256), ("d_bits", 256), ("carry_bits", 285), ("borrow_bits", 16), ("x_limbs", 16),
             ("y_limbs", 16), ("q_limbs", 16), ("product", 16), ("remainder", 16), ("remainder_top", 1), ("result", 16)]
 N_CONSTRAINTS = sum(c for _, c in FAMILIES)   # 1686
-
-
-def limbs(v):
-    return [(v >> (16 * k)) & 0xFFFF for k in range(16)]
-
-
-def word(ls):
-    return sum(int(l) << (16 * k) for k, l in enumerate(ls))
 
 
 def honest(op, x, y, exposed):
@@ -54,19 +42,14 @@ def honest(op, x, y, exposed):
 def chains(w):
     """(Re)derives what follows from the rest of the witness: the carries of the product columns, the carry bits of
     r + d + 1, and the inverse of the zero test.  A forged witness stays consistent wherever it can."""
-    xb, rb, db = limbs(w["xb"]), limbs(w["rb"]), limbs(w["db"])
+    xb, rb = limbs(w["xb"]), limbs(w["rb"])
     carry, c = [], 0
     for k in range(15):
         total = sum(w["ql"][i] * w["yl"][k - i] for i in range(k + 1)) + rb[k] + c - xb[k]
         assert total < 1 << 38
         c = (total >> 16) % (1 << CARRY_BITS)
         carry.append(c)
-    borrow, bw = [], 1
-    for k in range(16):
-        bw = (rb[k] + db[k] + bw) >> 16 if not w["z"] else 0
-        borrow.append(bw)
-    s = sum(w["yl"])
-    w.update(carry=carry, borrow=borrow, inv=pow(s, P - 2, P) if not w["z"] else 0)
+    w.update(carry=carry, **base.remainder_chain(w, w["yl"]))
     return w
 
 
@@ -77,21 +60,13 @@ def cells(w):
     for k in range(16):
         row[X + k], row[Y + k], row[RES + k], row[Q + k] = w["xl"][k], w["yl"][k], w["resl"][k], w["ql"][k]
         row[BORROW + k] = w["borrow"][k]
-    for col, name in ((X_BITS, "xb"), (Y_BITS, "yb"), (Q_BITS, "qb"), (R_BITS, "rb"), (D_BITS, "db")):
-        for j in range(256):
-            row[col + j] = (w[name] >> j) & 1
-    for k in range(15):
-        for j in range(CARRY_BITS):
-            row[CARRY + CARRY_BITS * k + j] = (w["carry"][k] >> j) & 1
-    for col, v in w.get("poke", {}).items():      # single cells a forgery writes last
-        row[col] = v
-    return [v % P for v in row]
+    blocks = ((X_BITS, "xb", 256), (Y_BITS, "yb", 256), (Q_BITS, "qb", 256), (R_BITS, "rb", 256), (D_BITS, "db", 256))
+    return base.put_blocks(row, w, blocks, CARRY, CARRY_BITS)
 
 
 def trace_of(ops):
     """[1650, len(ops)] uint64: the model trace of a list of (op, x, y, exposed)"""
-    rows = [cells(honest(*o)) for o in ops]
-    return np.array(rows, dtype=np.uint64).T.copy()
+    return base.trace_of(honest, cells, ops)
 
 
 # ---------------------------------------------------------------------------------------------- the edge list
@@ -117,12 +92,7 @@ PADDING = [(NONE, MAX, 3, 1), (3, 1 << 200 | 5, MAX, 1), (0xFF, 7, 0, 0), (0x80,
 
 def random_ops(n, seed):
     """seeded operations whose operands have every length from 0 to 256 bits, a padding row now and then"""
-    rng = random.Random(seed)
-    out = []
-    for _ in range(n):
-        x, y = rng.getrandbits(rng.randint(0, 256)), rng.getrandbits(rng.randint(0, 256))
-        out.append((rng.choice((DIV, DIV, MOD, MOD, NONE, 3)), x, y, rng.randint(0, 1)))
-    return out
+    return base.random_ops(n, seed, 2, (DIV, DIV, MOD, MOD, NONE, 3))
 
 
 def edge_ops():
@@ -214,19 +184,8 @@ CATALOGUE = [("wrapped_quotient", (DIV,) + _XY + (1,), _wrapped_quotient, {"prod
 
 def forged(entry):
     """the cells of a catalogue entry's row"""
-    _, op, forge, _ = entry
-    w = honest(*op)
-    forge(w)
-    poke = w.pop("poke", None)
-    chains(w)
-    if poke:
-        w["poke"] = poke
-    return cells(w)
+    return base.forged(honest, chains, cells, entry)
 
 
 def family_of(index):
-    for k, (name, count) in enumerate(FAMILIES):
-        if index < count:
-            return k, name
-        index -= count
-    raise ValueError("past the program's own constraints")
+    return base.family_of(FAMILIES, index)

@@ -2,20 +2,16 @@
 shared by tests/test_arithmetic_mod.py and tests/test_gpu_arithmetic_mod.py.  It works from the statement in
 include/bpg.h and the column list in AIRS.md section 2 ("Modular (a shipped program)") over Python integers (divmod, %):
 it imports nothing of the package, so the column map below is a third statement of it and the tests compare it with the
-package's.
+package's.  What it shares with the division table's model is in tests/word_table_model.py, as independent as this file.
 
     w = honest(op, a, b, m, exposed)  the witness of one operation: a dict of what a row holds
     cells(w)                          the 2560 cells of its row
     CATALOGUE                         wrong witnesses, each otherwise consistent: (name, operation, forge, families broken)
 """
-import random
+import word_table_model as base
+from word_table_model import B, M256, P, limbs, word  # noqa: F401 (the tests read them here)
 
-import numpy as np
-
-P = 0xFFFFFFFF00000001
 NONE, ADDMOD, MULMOD = 0, 1, 2
-B = 1 << 16
-M256 = (1 << 256) - 1
 CARRY_BITS, CARRY_OFFSET = 21, 1 << 20
 
 # AIRS.md section 2: five single columns, four blocks of 16 limbs and one of 32, six bit blocks, 31 carries of 21 bits, 16
@@ -29,14 +25,6 @@ FAMILIES = [("flags", 3), ("one_flag", 1), ("filter", 1), ("zero", 2), ("high", 
             ("m_bits", 256), ("q_bits", 512), ("r_bits", 256), ("d_bits", 256), ("carry_bits", 651), ("borrow_bits", 16),
             ("abm_limbs", 48), ("q_limbs", 32), ("product", 32), ("remainder", 16), ("remainder_top", 1), ("result", 16)]
 N_CONSTRAINTS = sum(c for _, c in FAMILIES)   # 2612
-
-
-def limbs(v, n=16):
-    return [(v >> (16 * k)) & 0xFFFF for k in range(n)]
-
-
-def word(ls):
-    return sum(int(l) << (16 * k) for k, l in enumerate(ls))
 
 
 def intermediate(is_addmod, is_mulmod, a, b):
@@ -61,7 +49,7 @@ def honest(op, a, b, m, exposed):
 def chains(w):
     """(Re)derives what follows from the rest of the witness: the signed carries of the product columns, the carry bits
     of r + d + 1, and the inverse of the zero test.  A forged witness stays consistent wherever it can."""
-    rb, db = limbs(w["rb"]), limbs(w["db"])
+    rb = limbs(w["rb"])
     big_m = w["ml"] + [w["z"]]                                   # the 17 limbs of M = m + z 2^256
     carry, signed, c = [], [], 0
     for k in range(31):
@@ -75,12 +63,7 @@ def chains(w):
         c = total >> 16                                          # floor: exact on an honest row
         signed.append(c)
         carry.append((c + CARRY_OFFSET) % (1 << CARRY_BITS))
-    borrow, bw = [], 1
-    for k in range(16):
-        bw = (rb[k] + db[k] + bw) >> 16 if not w["z"] else 0
-        borrow.append(bw)
-    s = sum(w["ml"])
-    w.update(carry=carry, signed_carry=signed, borrow=borrow, inv=pow(s, P - 2, P) if not w["z"] else 0)
+    w.update(carry=carry, signed_carry=signed, **base.remainder_chain(w, w["ml"]))
     return w
 
 
@@ -93,22 +76,14 @@ def cells(w):
         row[BORROW + k] = w["borrow"][k]
     for k in range(32):
         row[Q + k] = w["ql"][k]
-    for col, name, n in ((A_BITS, "ab", 256), (B_BITS, "bb", 256), (M_BITS, "mb", 256), (Q_BITS, "qb", 512), (R_BITS, "rb", 256),
-                         (D_BITS, "db", 256)):
-        for j in range(n):
-            row[col + j] = (w[name] >> j) & 1
-    for k in range(31):
-        for j in range(CARRY_BITS):
-            row[CARRY + CARRY_BITS * k + j] = (w["carry"][k] >> j) & 1
-    for col, v in w.get("poke", {}).items():      # single cells a forgery writes last
-        row[col] = v
-    return [v % P for v in row]
+    blocks = ((A_BITS, "ab", 256), (B_BITS, "bb", 256), (M_BITS, "mb", 256), (Q_BITS, "qb", 512), (R_BITS, "rb", 256),
+              (D_BITS, "db", 256))
+    return base.put_blocks(row, w, blocks, CARRY, CARRY_BITS)
 
 
 def trace_of(ops):
     """[2560, len(ops)] uint64: the model trace of a list of (op, a, b, m, exposed)"""
-    rows = [cells(honest(*o)) for o in ops]
-    return np.array(rows, dtype=np.uint64).T.copy()
+    return base.trace_of(honest, cells, ops)
 
 
 # ---------------------------------------------------------------------------------------------- the edge list
@@ -137,12 +112,7 @@ PADDING = [(NONE, MAX, 3, G1, 1), (3, 1 << 200 | 5, MAX, 0, 1), (0xFF, 7, 0, MAX
 
 def random_ops(n, seed):
     """seeded operations whose operands have every length from 0 to 256 bits, a padding row now and then"""
-    rng = random.Random(seed)
-    out = []
-    for _ in range(n):
-        a, b, m = (rng.getrandbits(rng.randint(0, 256)) for _ in range(3))
-        out.append((rng.choice((ADDMOD, ADDMOD, MULMOD, MULMOD, MULMOD, NONE, 3)), a, b, m, rng.randint(0, 1)))
-    return out
+    return base.random_ops(n, seed, 3, (ADDMOD, ADDMOD, MULMOD, MULMOD, MULMOD, NONE, 3))
 
 
 def edge_ops():
@@ -266,19 +236,8 @@ CATALOGUE = [("addmod_of_the_wrapped_sum", (ADDMOD,) + _ABM + (1,), _reduced_fir
 
 def forged(entry):
     """the cells of a catalogue entry's row"""
-    _, op, forge, _ = entry
-    w = honest(*op)
-    forge(w)
-    poke = w.pop("poke", None)
-    chains(w)
-    if poke:
-        w["poke"] = poke
-    return cells(w)
+    return base.forged(honest, chains, cells, entry)
 
 
 def family_of(index):
-    for k, (name, count) in enumerate(FAMILIES):
-        if index < count:
-            return k, name
-        index -= count
-    raise ValueError("past the program's own constraints")
+    return base.family_of(FAMILIES, index)

@@ -25,16 +25,17 @@ def wg_rows(n_units):
     return -(-n_units // per_row)
 
 
-def summary(out_dir):
+def kernel_medians(out_dir, kernels):
+    """prints one line per (kernel, grid) of the trace under out_dir whose name holds one of `kernels`; {(name, grid x,
+    grid y): median us}.  tools/arithmetic_div_probe.py reads its trace with it too."""
     import csv
-    from proof_protocol_decoder_amd import arithmetic_div as ad, arithmetic_mod as am
     files = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
     assert files, "no kernel trace under " + out_dir
     times = {}
     for f in files:
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"]
-            if any(name in k for name in KERNELS):
+            if any(name in k for name in kernels):
                 key = (k.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0], int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0),
                        int(r.get("Grid_Size_Y") or 1))
                 times.setdefault(key, []).append((float(r["End_Timestamp"]) - float(r["Start_Timestamp"])) / 1e3)
@@ -44,6 +45,12 @@ def summary(out_dir):
         t = times[key][1:] if len(times[key]) > 2 else times[key]
         med[key] = statistics.median(t)
         print("%-44s grid=(%d,%d)  launches %2d  median %9.1f  min %9.1f  max %9.1f" % (key[0], key[1], key[2], len(t), med[key], min(t), max(t)))
+    return med
+
+
+def summary(out_dir):
+    from proof_protocol_decoder_amd import arithmetic_div as ad, arithmetic_mod as am
+    med = kernel_medians(out_dir, KERNELS)
     cells = am.N_COLS / ad.N_COLS
     # K5 packs a program's units (and the library's one for the port) into workgroup rows, grid.y: at most 16 at this height
     k5 = {key[2]: v for key, v in med.items() if "quotient_program_kernel" in key[0]}
@@ -71,15 +78,17 @@ def inputs_for(n, words, seed):
     return inputs
 
 
-def median_proofs(bpg, torch, tables):
-    """tables: [(name, air_id, cfg, trace)]; PROOFS + 1 alternating rounds, the first dropped; {name: [ms]}"""
-    wall = {name: [] for name, _, _, _ in tables}
-    for _ in range(PROOFS + 1):
-        for name, air_id, cfg, trace in tables:
+def median_proofs(torch, provers, after_round=lambda k: None):
+    """provers: [(name, prove(k))]; PROOFS + 1 alternating rounds, round k ending with after_round(k), the first dropped;
+    {name: [ms]}.  tools/arithmetic_div_probe.py times its pair with it too."""
+    wall = {name: [] for name, _ in provers}
+    for k in range(PROOFS + 1):
+        for name, prove in provers:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            bpg.ops.stark_prove_trace(air_id, cfg, trace)
+            prove(k)
             wall[name].append((time.perf_counter() - t0) * 1e3)
+        after_round(k)
     return {name: t[1:] for name, t in wall.items()}
 
 
@@ -98,15 +107,17 @@ def main(units):
         for c in (1, 2, 4):
             words = am.program(c).assemble()
             air_id = bpg.ops.air_register(words)
-            tables.append(("%d columns a unit (%d units, n_regs %d)" % (c, int(words[8]), int(words[7])), air_id, cases.cfg_for(air_id, LOG_N), trace))
-        for name, t in median_proofs(bpg, torch, tables).items():
+            tables.append(("%d columns a unit (%d units, n_regs %d)" % (c, int(words[8]), int(words[7])),
+                           lambda k, a=air_id, cfg=cases.cfg_for(air_id, LOG_N): bpg.ops.stark_prove_trace(a, cfg, trace)))
+        for name, t in median_proofs(torch, tables).items():
             print("modular table, %s: median of %d proofs %.2f ms (min %.2f, max %.2f)" % (name, PROOFS, statistics.median(t), min(t), max(t)))
         return
     words = am.program().assemble()
     print("modular: program 0x%08x, %d columns, %d code words, n_regs %d, %d units; division: %d columns; 2^%d rows, %d proofs each"
           % (reg, am.N_COLS, int(words[9]), int(words[7]), int(words[8]), ad.N_COLS, LOG_N, PROOFS), flush=True)
     cfg, cfg_div = cases.cfg_for(reg, LOG_N), cases.cfg_for(reg_div, LOG_N)
-    wall = median_proofs(bpg, torch, [("mod", reg, cfg, trace), ("div", reg_div, cfg_div, trace_div)])
+    wall = median_proofs(torch, [("mod", lambda k: bpg.ops.stark_prove_trace(reg, cfg, trace)),
+                                 ("div", lambda k: bpg.ops.stark_prove_trace(reg_div, cfg_div, trace_div))])
     for _ in range(PROOFS):                                      # the two witness kernels, for the kernel trace
         bpg.ops.arithmetic_mod_trace(LOG_N, d_mod)
         bpg.ops.arithmetic_div_trace(LOG_N, d_div)

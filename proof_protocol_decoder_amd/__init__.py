@@ -11,3 +11,4 @@ from . import compact  # noqa: F401
 from . import trace_protocol  # noqa: F401
 from . import arithmetic_div  # noqa: F401
 from . import arithmetic_mod  # noqa: F401
+from . import arithmetic_shift  # noqa: F401

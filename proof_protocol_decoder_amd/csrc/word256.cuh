@@ -1,7 +1,9 @@
-// word256.cuh -- what the witness kernels of the shipped tables (arithmetic_div.hip, arithmetic_mod.hip) share: a
-// 256-bit word in named registers, its 16-bit limbs by compile-time number, the shift-and-subtract step, a lane's view
-// of its trace row with the stores every quotient / remainder / slack table makes, and the host side of the two C
-// entries a table has.  A table's .hip file keeps its column map, its product columns and its kernel.
+// word256.cuh -- what the witness kernels of the shipped tables (arithmetic_div.hip, arithmetic_mod.hip,
+// arithmetic_shift.hip) share: a 256-bit word in named registers, its 16-bit limbs by compile-time number, the
+// shift-and-subtract step, a lane's view of its trace row with the stores every quotient / remainder / slack table
+// makes, and the host side of the two C entries a table has.  A table's .hip file keeps its column map, its product
+// columns and its kernel.  The shift table, which has no quotient, uses U256, limb, Head3, operand, Row::put / put_bits
+// and the two entries.
 #pragma once
 #include <cstdint>
 
@@ -79,6 +81,15 @@ struct Head {
   __device__ __forceinline__ explicit Head(uint64_t word0)
       : w0(word0), op_a(((uint32_t)word0 & 0xFFu) == 1), op_b(((uint32_t)word0 & 0xFFu) == 2), live(op_a | op_b) {}
   __device__ __forceinline__ uint32_t g() const { return live & (uint32_t)((w0 >> 8) & 1); }  // exposed, on a live row only
+};
+// the same for a table of three operations (op bytes 1, 2, 3)
+struct Head3 {
+  uint64_t w0;
+  bool op_a, op_b, op_c, live;
+  __device__ __forceinline__ explicit Head3(uint64_t word0)
+      : w0(word0), op_a(((uint32_t)word0 & 0xFFu) == 1), op_b(((uint32_t)word0 & 0xFFu) == 2), op_c(((uint32_t)word0 & 0xFFu) == 3),
+        live(op_a | op_b | op_c) {}
+  __device__ __forceinline__ uint32_t g() const { return live & (uint32_t)((w0 >> 8) & 1); }
 };
 // operand J of the row at `in`; a padding row ignores its operand words: they read as zero
 template <uint32_t J>

@@ -239,6 +239,15 @@ def arithmetic_mod_trace(log_n, inputs, device="cuda"):
     return _word_table_trace("arithmetic_mod_trace", 13, N_COLS, log_n, inputs, device)
 
 
+def arithmetic_shift_trace(log_n, inputs, device="cuda"):
+    """bp_arithmetic_shift_trace: the witness [1143, 2^log_n] of the shift table (arithmetic_shift.py: a shipped program,
+    no built-in air_id); inputs [2^log_n, 9] int64 on the device (op 1 shl / 2 shr / 3 sar / else padding | exposed << 8,
+    the four words of the shift count s, of the value x: arithmetic_shift.pack_inputs).  There is no seeded draw:
+    inputs=None is refused by the library."""
+    from .arithmetic_shift import N_COLS
+    return _word_table_trace("arithmetic_shift_trace", 9, N_COLS, log_n, inputs, device)
+
+
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""

@@ -616,6 +616,34 @@ int bp_arithmetic_shift_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t
  * one-hot e (31 columns, offset d at + 15 + d), the s / x / lo / hi bits.  No device is needed.  arithmetic_shift.py states
  * the same map a second time; its register() refuses to go on when they differ. */
 int bp_arithmetic_shift_layout(uint32_t* out, size_t n_words);
+/* Witness of the SIGNED table: SDIV and SMOD on 256-bit words, one operation per row.  Like the other three shipped tables it
+ * has no built-in air_id: its AIR is a constraint program shipped with the Python package (proof_protocol_decoder_amd/
+ * arithmetic_sdiv.py, which registers it with bp_air_register; AIRS.md section 2, "Signed (a shipped program)", lists the
+ * columns).  A row holds x, y and res as 256-bit words in two's complement.  With sx, sy their bits 255 and X = x - sx 2^256,
+ * Y = y - sy 2^256, every row proves OVER THE INTEGERS: under is_sdiv res = 0 when Y = 0, else trunc(X / Y) mod 2^256, the
+ * quotient ROUNDED TOWARD ZERO (not floored: -7 / 2 is -3), so SDIV(-2^255, -1) is the word 2^255; under is_smod res = 0 when
+ * Y = 0, else (X - Y trunc(X / Y)) mod 2^256, the remainder with THE SIGN OF X (not of Y: -7 % 2 is -1); at most one flag is
+ * set, a row with neither has res = 0 (the kernel writes the all-zero row with z = 1 there), and the filter g of the table's
+ * one product port, which exposes (is_sdiv, is_smod, the sixteen 16-bit limbs of x, of y, of res: 50 elements, the division
+ * table's tuple), may be 1 only on a row with a flag.  Every tuple element is range-checked by the table, by bits of its own.
+ * How: ax = |X| and ay = |Y|, both at most 2^255, are tied to x and y by a conditional negation over the 16-bit limbs
+ * (v_k + w_k + c_{k-1} = 2^16 c_k where the sign is set, w_k = v_k where it is not; sixteen carry bits a chain); q ay + r = ax
+ * and r < ay unless y = 0 are the division table's columns, carries and bounds on the magnitudes (19 bits a carry, still all
+ * needed: |X| = (2^127 - 1)(2^128 - 1) + 2^128 - 2 over |Y| = 2^128 - 1 reaches 0x77FF8 out of column 7); the magnitude m = 0
+ * (y = 0), q (is_sdiv), r (is_smod) and the sign neg = sx xor sy (is_sdiv), sx (is_smod) are columns, and a third such
+ * negation gives res from m under neg.  Its last carry bit is free: m + res = 2^256 c_15 has res = m = 0 when c_15 = 0, so
+ * -0 = 0 needs no zero test of its own.
+ * n = 2^log_n rows (log_n 4 .. 26) x 2499 columns, column-major.  d_inputs: [n][9], bp_arithmetic_div_trace's format = word 0:
+ * the operation in its low byte (1 sdiv, 2 smod, anything else a padding row, whose other words are ignored) | exposed << 8
+ * (bit 8: the row's g; bits 9 .. 63 are ignored); then the four 64-bit words of x and of y, least significant first.  Any u64
+ * is accepted and every 256-bit operand is a valid one.  There is no seeded draw: d_inputs == NULL is BP_ERR_INVALID_INPUT. */
+int bp_arithmetic_sdiv_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t* d_trace_out, void* stream);
+/* The column map bp_arithmetic_sdiv_trace stores by, 27 words (n_words: the room in `out`, at least 27): n_cols, then the
+ * first column of is_sdiv, is_smod, g, z, inv, neg, the x / y / res / q / ay / m limbs, the x / y / res / ax / ay / q / r / d
+ * bits, the carry bits, the bits per carry, the first column of the r + d + 1 carry bits and of the carry bits of x + ax, of
+ * y + ay and of m + res.  No device is needed.  arithmetic_sdiv.py states the same map a second time; its register() refuses
+ * to go on when they differ. */
+int bp_arithmetic_sdiv_layout(uint32_t* out, size_t n_words);
 
 /* AIR 8 (plonk): the 85 preprocessed constant columns of the fixed circuit (selectors, gate constants drawn from `seed`,
  * the Poseidon-row selector, the 80 sigmas of its copy permutation), n = 2^log_n rows, column-major, for a circuit that

@@ -12,3 +12,4 @@ from . import trace_protocol  # noqa: F401
 from . import arithmetic_div  # noqa: F401
 from . import arithmetic_mod  # noqa: F401
 from . import arithmetic_shift  # noqa: F401
+from . import arithmetic_sdiv  # noqa: F401

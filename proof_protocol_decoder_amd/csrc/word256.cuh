@@ -1,9 +1,9 @@
 // word256.cuh -- what the witness kernels of the shipped tables (arithmetic_div.hip, arithmetic_mod.hip,
-// arithmetic_shift.hip) share: a 256-bit word in named registers, its 16-bit limbs by compile-time number, the
-// shift-and-subtract step, a lane's view of its trace row with the stores every quotient / remainder / slack table
-// makes, and the host side of the two C entries a table has.  A table's .hip file keeps its column map, its product
+// arithmetic_shift.hip, arithmetic_sdiv.hip) share: a 256-bit word in named registers, its 16-bit limbs by compile-time
+// number, the shift-and-subtract step, a lane's view of its trace row with the stores every quotient / remainder / slack
+// table makes, and the host side of the two C entries a table has.  A table's .hip file keeps its column map, its product
 // columns and its kernel.  The shift table, which has no quotient, uses U256, limb, Head3, operand, Row::put / put_bits
-// and the two entries.
+// and the two entries; the signed table adds negate / magnitude to what the division table uses.
 #pragma once
 #include <cstdint>
 
@@ -34,6 +34,12 @@ __device__ __forceinline__ U256 sub256(const U256& x, const U256& y, uint32_t* b
   r.d = t - b3;
   return r;
 }
+// -w modulo 2^256, and |W| of the two's-complement word w = W mod 2^256 (2^255 for the most negative one)
+__device__ __forceinline__ U256 negate(const U256& w) {
+  uint32_t unused;
+  return sub256(U256{0, 0, 0, 0}, w, &unused);
+}
+__device__ __forceinline__ U256 magnitude(const U256& w) { return (w.d >> 63) ? negate(w) : w; }
 // limb K (16 bits) of a word, K a compile-time number
 template <uint32_t K>
 __device__ __forceinline__ uint32_t limb(const U256& w) {

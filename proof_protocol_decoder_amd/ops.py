@@ -248,6 +248,15 @@ def arithmetic_shift_trace(log_n, inputs, device="cuda"):
     return _word_table_trace("arithmetic_shift_trace", 9, N_COLS, log_n, inputs, device)
 
 
+def arithmetic_sdiv_trace(log_n, inputs, device="cuda"):
+    """bp_arithmetic_sdiv_trace: the witness [2499, 2^log_n] of the signed table (arithmetic_sdiv.py: a shipped program,
+    no built-in air_id); inputs [2^log_n, 9] int64 on the device (op 1 sdiv / 2 smod / else padding | exposed << 8, the
+    four words of x, of y, two's complement: arithmetic_sdiv.pack_inputs).  There is no seeded draw: inputs=None is
+    refused by the library."""
+    from .arithmetic_sdiv import N_COLS
+    return _word_table_trace("arithmetic_sdiv_trace", 9, N_COLS, log_n, inputs, device)
+
+
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""

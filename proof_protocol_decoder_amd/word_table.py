@@ -1,5 +1,6 @@
-"""What the shipped tables over 256-bit words (arithmetic_div.py, arithmetic_mod.py) share: the pieces of a constraint
-program every quotient / remainder / slack table over 16-bit limbs is made of, and the plumbing between such a module,
+"""What the shipped tables over 256-bit words (arithmetic_div.py, arithmetic_mod.py, arithmetic_sdiv.py) share: the
+pieces of a constraint program every quotient / remainder / slack table over 16-bit limbs is made of, the conditional
+negation the signed table takes its magnitudes and its result by, and the plumbing between such a module,
 its witness kernel and the library.  Plain functions over the table's air_program.Builder `b`, its family bases `at`
 (name -> first constraint index; the shared families carry the same names in every table) and its column numbers.  A
 table module states its column map, LAYOUT, FAMILIES and the part of program() that is its own.
@@ -59,6 +60,18 @@ def remainder_limb(b, at, k, rk, dk, yk, borrow_in, col_borrow, not_zero):
     b.emit(at["borrow_bits"] + k, bk * bk - bk)
     b.emit(at["remainder"] + k, not_zero * ((rk + dk + (1 if k == 0 else borrow_in)) - (yk + BASE * bk)))
     return bk
+
+
+def negation_limb(b, k, sign, vk, wk, col_carry, cidx_bit, cidx):
+    """limb k of the conditional negation w = -v mod 2^256 where the bit `sign` is 1, w = v where it is 0: sign (v_k + w_k
+    + c_(k-1) - 2^16 c_k) + (1 - sign) (w_k - v_k), stated as (w_k - v_k) + sign (2 v_k + c_(k-1) - 2^16 c_k), the same
+    polynomial with one product.  c_k is the bit column col_carry + k (constraint cidx_bit + k), the chain's equation
+    constraint cidx + k.  Nothing closes the chain: v + w = 2^256 c_15 with both words below 2^256 leaves c_15 free -- 0
+    only for v = w = 0 -- and c_(k-1) is read from its column, so a unit may start at any limb."""
+    ck = b.loc(col_carry + k)
+    b.emit(cidx_bit + k, ck * ck - ck)
+    carry_in = b.loc(col_carry + k - 1) if k else 0
+    b.emit(cidx + k, (wk - vk) + sign * ((vk + vk + carry_in) - BASE * ck))
 
 
 def first_index(families, name):

@@ -644,6 +644,35 @@ int bp_arithmetic_sdiv_trace(const uint64_t* d_inputs, uint32_t log_n, uint64_t*
  * y + ay and of m + res.  No device is needed.  arithmetic_sdiv.py states the same map a second time; its register() refuses
  * to go on when they differ. */
 int bp_arithmetic_sdiv_layout(uint32_t* out, size_t n_words);
+/* Witness of the EXPONENTIATION table: EXP on 256-bit words, ONE EXPONENT BIT PER ROW.  Like the other four shipped tables it
+ * has no built-in air_id: its AIR is a constraint program shipped with the Python package (proof_protocol_decoder_amd/
+ * arithmetic_exp.py, which registers it with bp_air_register; AIRS.md section 2, "Exponentiation (a shipped program)", lists
+ * the columns).  It is the first shipped program whose statement spans rows: an operation is a chain of rows(e) = max(1, bit
+ * length of the exponent e) CONSECUTIVE rows, binary exponentiation from the least significant bit.  A row holds the running
+ * square p, the running result r, the exponent e still to consume and the chain's final result res.  With bit = e's bit 0
+ * every row proves OVER THE INTEGERS m = r p mod 2^256 and s = p p mod 2^256 (truncated schoolbook products over sixteen
+ * 16-bit limbs, sixteen carries of 20 bits each, the last one -- discarded -- range-checked like the rest) and out = bit ? m :
+ * r; a row whose flag `last` is 0 is followed by p' = s, r' = out, e' = e >> 1, res' = res; a `last` row has e < 2 and res =
+ * out; a `first` row has r = 1; the trace's last row has last = 1.  So r p^e = base^exponent mod 2^256 on a first row and after
+ * every step, and the row exposed by the table's one product port -- (the sixteen limbs of p, of e, of res: 48 elements), its
+ * filter g allowed on a first row only -- states res = base^exponent mod 2^256, THE WHOLE 256-BIT EXPONENT deciding and 0^0 =
+ * 1.  A padding row is all zero except last = 1.
+ * n = 2^log_n rows (log_n 4 .. 26) x 2003 columns, column-major.  d_ops: [n_ops][9] = word 0: the operation in its low byte
+ * (1 exp; any other byte turns the operation's rows into padding rows, its other words ignored) | exposed << 8 (bit 8: the g of
+ * the operation's first row; bits 9 .. 63 are ignored); then the four 64-bit words of the base and of the exponent, least
+ * significant first.  d_starts: [n_ops + 1], the exclusive prefix sum of the operations' rows(e) -- starts[0] = 0, starts[n_ops]
+ * <= n, computed by the caller; rows from starts[n_ops] on are padding.  n_ops = 0 gives an all-padding trace and reads neither
+ * array.  One lane per row finds its operation in d_starts by binary search and replays the operation's steps; it reads
+ * d_ops[op] for op < n_ops and d_starts[k] for k <= n_ops only and writes its own row only, whatever the arrays hold, and takes
+ * `last` from the exponent, so wrong prefix sums yield a trace the checker refuses, not a wrong statement.  NULL d_trace_out,
+ * log_n outside 4 .. 26, n_ops > n, and with n_ops > 0 a NULL d_ops or d_starts are BP_ERR_INVALID_INPUT before any launch. */
+int bp_arithmetic_exp_trace(const uint64_t* d_ops, uint32_t n_ops, const uint32_t* d_starts, uint32_t log_n, uint64_t* d_trace_out,
+                            void* stream);
+/* The column map bp_arithmetic_exp_trace stores by, 17 words (n_words: the room in `out`, at least 17): n_cols, then the first
+ * column of g, first, last, the p / e / res / r / out limbs, the p / r / e / m / s bits, the carry bits of r p and of p p, the
+ * bits per carry.  No device is needed.  arithmetic_exp.py states the same map a second time; its register() refuses to go on
+ * when they differ. */
+int bp_arithmetic_exp_layout(uint32_t* out, size_t n_words);
 
 /* AIR 8 (plonk): the 85 preprocessed constant columns of the fixed circuit (selectors, gate constants drawn from `seed`,
  * the Poseidon-row selector, the 80 sigmas of its copy permutation), n = 2^log_n rows, column-major, for a circuit that

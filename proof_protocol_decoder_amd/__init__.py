@@ -13,3 +13,4 @@ from . import arithmetic_div  # noqa: F401
 from . import arithmetic_mod  # noqa: F401
 from . import arithmetic_shift  # noqa: F401
 from . import arithmetic_sdiv  # noqa: F401
+from . import arithmetic_exp  # noqa: F401

@@ -229,6 +229,8 @@ PROTOTYPES = {
     "bp_arithmetic_shift_layout": (i, [u32p, sz]),
     "bp_arithmetic_sdiv_trace": (i, [vp, u32, vp, vp]),
     "bp_arithmetic_sdiv_layout": (i, [u32p, sz]),
+    "bp_arithmetic_exp_trace": (i, [vp, u32, vp, u32, vp, vp]),
+    "bp_arithmetic_exp_layout": (i, [u32p, sz]),
     "bp_plonk_constants": (i, [u64, u32, P(PlonkLayout), vp, vp]),
     "bp_plonk_trace": (i, [vp, u64, u64p, P(PlonkLayout), u64p, u32, vp, vp]),
     "bp_fri_fold": (i, [vp, u32, u32, u32, u64, u64p, vp, vp]),

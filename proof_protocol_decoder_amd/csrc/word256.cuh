@@ -3,7 +3,8 @@
 // number, the shift-and-subtract step, a lane's view of its trace row with the stores every quotient / remainder / slack
 // table makes, and the host side of the two C entries a table has.  A table's .hip file keeps its column map, its product
 // columns and its kernel.  The shift table, which has no quotient, uses U256, limb, Head3, operand, Row::put / put_bits
-// and the two entries; the signed table adds negate / magnitude to what the division table uses.
+// and the two entries; the signed table adds negate / magnitude to what the division table uses; the exponentiation table
+// (arithmetic_exp.hip), whose rows are steps of a chain, uses U256, limb, mul_low, Row::put / put_bits and layout_entry.
 #pragma once
 #include <cstdint>
 
@@ -40,6 +41,30 @@ __device__ __forceinline__ U256 negate(const U256& w) {
   return sub256(U256{0, 0, 0, 0}, w, &unused);
 }
 __device__ __forceinline__ U256 magnitude(const U256& w) { return (w.d >> 63) ? negate(w) : w; }
+// x y modulo 2^256: the schoolbook product over 64-bit words, columns 0 .. 3 only.  `carry` counts the wraps of a column's
+// sum, which belong to the next column; the last column wraps freely.
+__device__ __forceinline__ void add_wrapping(uint64_t& acc, uint64_t& carry, uint64_t v) {
+  acc += v;
+  carry += acc < v;
+}
+__device__ __forceinline__ U256 mul_low(const U256& x, const U256& y) {
+  U256 r;
+  r.a = x.a * y.a;
+  uint64_t acc = __umul64hi(x.a, y.a), carry = 0;
+  add_wrapping(acc, carry, x.a * y.b);
+  add_wrapping(acc, carry, x.b * y.a);
+  r.b = acc;
+  acc = carry;
+  carry = 0;
+  add_wrapping(acc, carry, __umul64hi(x.a, y.b));
+  add_wrapping(acc, carry, __umul64hi(x.b, y.a));
+  add_wrapping(acc, carry, x.a * y.c);
+  add_wrapping(acc, carry, x.b * y.b);
+  add_wrapping(acc, carry, x.c * y.a);
+  r.c = acc;
+  r.d = carry + __umul64hi(x.a, y.c) + __umul64hi(x.b, y.b) + __umul64hi(x.c, y.a) + x.a * y.d + x.b * y.c + x.c * y.b + x.d * y.a;
+  return r;
+}
 // limb K (16 bits) of a word, K a compile-time number
 template <uint32_t K>
 __device__ __forceinline__ uint32_t limb(const U256& w) {

@@ -257,6 +257,29 @@ def arithmetic_sdiv_trace(log_n, inputs, device="cuda"):
     return _word_table_trace("arithmetic_sdiv_trace", 9, N_COLS, log_n, inputs, device)
 
 
+def arithmetic_exp_trace(log_n, words, starts):
+    """bp_arithmetic_exp_trace: the witness [2003, 2^log_n] of the exponentiation table (arithmetic_exp.py: a shipped
+    program, no built-in air_id, one exponent bit per row); words [n_ops, 9] int64 on the device (op 1 exp / else padding |
+    exposed << 8, the four words of the base, of the exponent) and starts [n_ops + 1] int32 on the device, the exclusive
+    prefix sum of the operations' rows: arithmetic_exp.pack_ops.  No operations (words [0, 9], starts [1]) is an all-padding
+    trace."""
+    from .arithmetic_exp import N_COLS
+    _require_cuda(words)
+    if words.dim() != 2 or words.shape[1] != 9:
+        raise ValueError("arithmetic_exp_trace: words are [n_ops, 9]: got %s" % (tuple(words.shape),))
+    n_ops = words.shape[0]
+    if not starts.is_cuda or starts.dtype != torch.int32 or not starts.is_contiguous():
+        raise ValueError("arithmetic_exp_trace: starts is a contiguous int32 device tensor holding u32 bit patterns")
+    if starts.device != words.device:
+        raise ValueError("arithmetic_exp_trace: words are on %s, starts on %s" % (words.device, starts.device))
+    if tuple(starts.shape) != (n_ops + 1,):
+        raise ValueError("arithmetic_exp_trace: starts is [%d]: got %s" % (n_ops + 1, tuple(starts.shape)))
+    out = torch.empty((N_COLS, 1 << log_n), dtype=torch.int64, device=words.device)
+    check(own().bp_arithmetic_exp_trace(words.data_ptr() if n_ops else None, n_ops, starts.data_ptr() if n_ops else None, log_n,
+                                        out.data_ptr(), _stream()))
+    return out
+
+
 def keccak_trace(log_n, seed=0, inputs=None, device="cuda"):
     """bp_keccak_trace: the AIR-1 witness [2431, 2^log_n]; inputs [n_perm, 25] int64 lanes on the device, or drawn
     from `seed`."""

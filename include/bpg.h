@@ -125,6 +125,12 @@ int bp_debug_copy_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, void* s
  * (a, b) * (b, a^b); then the interleaved group forms the NTT butterflies use: a + canon(b), a - canon(b),
  * canon(a), canon(b). */
 int bp_debug_field_ops(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
+/* The lazily reduced forms of the same arithmetic -- those that return ANY 64-bit representative of the residue -- on n
+ * operand pairs, the words stored exactly as the form returns them (NOT canonical), so that a test can see which
+ * representative a form hands on.  d_a/d_b: any u64 values; d_out: 12 planes of n words: a*b by the one-element carry
+ * chain (plane 0), by the groups of four (1..4: the pair in every slot of its group) and of three (5..7), a + canon(b)
+ * (8), a - canon(b) (9), 7*a (10), a^7 by the one-element S-box (11). */
+int bp_debug_lazy_forms(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
 /* The multiplications by 2^(12k), k = 1..7, of the NTT's shift-only 16-point DFTs (gl::mul_pow2_n) on n words
  * (any u64).  d_out: 21 planes of n canonical words, plane 3(k-1) + f: a * 2^(12k) by the groups of four (f = 0), the
  * groups of three (f = 1) and the one-element form (f = 2). */

@@ -171,6 +171,7 @@ PROTOTYPES = {
     "bp_lde_batch": (i, [vp, u64, vp, u64, vp, u64, u32, u32, u32, i, vp]),
     "bp_debug_copy_u64": (i, [vp, vp, u64, vp]),
     "bp_debug_field_ops": (i, [vp, vp, vp, u64, vp]),
+    "bp_debug_lazy_forms": (i, [vp, vp, vp, u64, vp]),
     "bp_debug_mul_pow2": (i, [vp, vp, u64, vp]),
     "bp_tune_quad_threshold": (None, [u64]),
     "bp_tune_merkle_fused": _knob,

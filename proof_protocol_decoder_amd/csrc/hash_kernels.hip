@@ -578,6 +578,30 @@ __global__ void __launch_bounds__(256) field_ops_kernel(const uint64_t* __restri
   }
 }
 
+// The lazily reduced forms, words stored exactly as each form returns them (no canon): what the tests read to see
+// WHICH representative a form hands on.  The group forms get the same pair in every slot of their group.
+__global__ void __launch_bounds__(256) lazy_forms_kernel(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                         uint64_t* __restrict__ out, uint64_t n) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t x = a[i], y = b[i], cb = gl::canon(y);
+  const uint64_t x4[4] = {x, x, x, x}, y4[4] = {y, y, y, y}, x3[3] = {x, x, x}, y3[3] = {y, y, y};
+  uint64_t r4[4], r3[3];
+  gl::mul_n<4>(x4, y4, r4);
+  __builtin_amdgcn_sched_barrier(0);  // one group of carry masks at a time (field_ops_kernel)
+  gl::mul_n<3>(x3, y3, r3);
+  __builtin_amdgcn_sched_barrier(0);
+  out[0 * n + i] = gl::mul(x, y);
+#pragma unroll
+  for (int k = 0; k < 4; k++) out[(1 + k) * n + i] = r4[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[(5 + k) * n + i] = r3[k];
+  out[8 * n + i] = gl::add(x, cb);
+  out[9 * n + i] = gl::sub(x, cb);
+  out[10 * n + i] = gl::mul7(x);
+  out[11 * n + i] = poseidon::sbox(x);
+}
+
 }  // namespace
 
 namespace bpg {
@@ -792,6 +816,14 @@ int bp_debug_field_ops(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out
   if (!n) return BP_OK;
   if (!d_a || !d_b || !d_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_field_ops: null buffer");
   field_ops_kernel<<<bpg::ceil_div(bpg::ceil_div(n, 4), 256), 256, 0, bpg::as_stream(stream)>>>(d_a, d_b, d_out, n);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+
+int bp_debug_lazy_forms(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream) {
+  if (!n) return BP_OK;
+  if (!d_a || !d_b || !d_out) return bpg::fail(BP_ERR_INVALID_INPUT, "bp_debug_lazy_forms: null buffer");
+  lazy_forms_kernel<<<bpg::ceil_div(n, 256), 256, 0, bpg::as_stream(stream)>>>(d_a, d_b, d_out, n);
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }

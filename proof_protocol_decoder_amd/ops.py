@@ -102,6 +102,18 @@ def field_ops(a, b):
     return out
 
 
+def lazy_forms(a, b):
+    """bp_debug_lazy_forms: [12, n] planes of the words the lazily reduced forms return, as they return them (any u64
+    representative): a*b by gl::mul, the four slots of gl::mul_n<4>, the three of gl::mul_n<3>, a + canon(b),
+    a - canon(b), 7*a, a^7; a, b: any u64 patterns."""
+    _require_cuda(a)
+    _require_cuda(b)
+    n = a.numel()
+    out = torch.empty((12, n), dtype=torch.int64, device=a.device)
+    check(own().bp_debug_lazy_forms(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, _stream()))
+    return out
+
+
 def mul_pow2(a):
     """bp_debug_mul_pow2: [21, n] planes, plane 3(k-1) + f = a * 2^(12k) mod p (canonical), k = 1..7, by the groups of
     four (f = 0), of three (f = 1) and the one-element form (f = 2); a: any u64 patterns."""

@@ -126,6 +126,12 @@ def test_field_ops_against_big_integers(bpg):
     # a block of all-ones operands drives the accumulator's wrap counters
     a += [(1 << 64) - 1] * 8
     b += [(1 << 64) - 1] * 8
+    # generic factors whose product is small, and a challenge times a sigma chosen against it: the lazy products behind
+    # every plane then come back in the upper representative r + p (tests/lazy_operands.py)
+    import lazy_operands
+    for x, y in lazy_operands.generic_small_pairs(rng, 1024) + lazy_operands.beta_small_pairs(rng, 1024):
+        a.append(x)
+        b.append(y)
     n = len(a)
     av, bv = np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64)
     out = to_host(bpg.ops.field_ops(to_dev(av), to_dev(bv)))

@@ -131,6 +131,14 @@ int bp_debug_field_ops(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out
  * chain (plane 0), by the groups of four (1..4: the pair in every slot of its group) and of three (5..7), a + canon(b)
  * (8), a - canon(b) (9), 7*a (10), a^7 by the one-element S-box (11). */
 int bp_debug_lazy_forms(const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
+/* The weights with which the quotient of AIR 8 folds its Poseidon gate (csrc/plonk_hash_fold.hpp: the MDS layers act on
+ * the alpha powers, once per quotient, not on every row's state) for one pair of canonical challenges, exactly as a
+ * quotient's launch leaves them on the device.  d_out: 238 words: for pair p < 118 (the wire of constraint 90 + p and
+ * the S-box output that goes with it) the words 2p, 2p + 1 = -C_0[p], -C_1[p], the S-box output's weights under the two
+ * challenges; then K_0, K_1.  The call returns when the words are there.  bp_debug_plonk_hash_fold_host: host only, the
+ * same words by the recurrences. */
+int bp_debug_plonk_hash_fold(const uint64_t alphas[2], uint64_t* d_out, void* stream);
+int bp_debug_plonk_hash_fold_host(const uint64_t alphas[2], uint64_t* out);
 /* The multiplications by 2^(12k), k = 1..7, of the NTT's shift-only 16-point DFTs (gl::mul_pow2_n) on n words
  * (any u64).  d_out: 21 planes of n canonical words, plane 3(k-1) + f: a * 2^(12k) by the groups of four (f = 0), the
  * groups of three (f = 1) and the one-element form (f = 2). */

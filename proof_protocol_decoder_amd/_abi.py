@@ -172,6 +172,8 @@ PROTOTYPES = {
     "bp_debug_copy_u64": (i, [vp, vp, u64, vp]),
     "bp_debug_field_ops": (i, [vp, vp, vp, u64, vp]),
     "bp_debug_lazy_forms": (i, [vp, vp, vp, u64, vp]),
+    "bp_debug_plonk_hash_fold": (i, [u64p, vp, vp]),
+    "bp_debug_plonk_hash_fold_host": (i, [u64p, u64p]),
     "bp_debug_mul_pow2": (i, [vp, vp, u64, vp]),
     "bp_tune_quad_threshold": (None, [u64]),
     "bp_tune_merkle_fused": _knob,

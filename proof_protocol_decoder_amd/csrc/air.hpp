@@ -1022,6 +1022,10 @@ constexpr uint32_t G0 = 0, G1 = 20, G2 = 64, G3 = 86, G4 = 90, G5 = 208;
 constexpr uint32_t HASH_ROW0 = 4, HASH_ROWS_MAX = 13, ZERO_ROW = 1, MAX_PI = 8 * HASH_ROWS_MAX;
 constexpr uint32_t MERKLE_ROW0 = HASH_ROW0 + HASH_ROWS_MAX, MERKLE_ROWS_MAX = 96, MERKLE_ZERO_COL = 79, LEAF_ROWS_MAX = 120;
 constexpr uint32_t H_IN = 0, H_OUT = 12, H_FULL1 = 24, H_PART = 60, H_FULL2 = 82, H_SWAP = 130, H_DELTA = 131, H_WIRES = 135;
+// the Poseidon gate's round constraints G4 .. G4 + 117 as the device's quotient folds them (plonk_hash_fold.hpp): 118
+// (wire, S-box output) pairs; the S-box outputs' weights (two challenges a pair) and two constants follow the coset
+// constants of QuotArgs::apow
+constexpr uint32_t HASH_FOLD_PAIRS = 118, HASH_FOLD_WORDS = 2 * HASH_FOLD_PAIRS + 2;
 // What a circuit of this family does besides its arithmetic groups: it hashes a public-input list of pi_len words
 // (rows 4 ..), and it walks n_paths Merkle paths of `depth` levels each (rows 12 ..): path p's leaf digest is list words
 // path_pi0 + 8p .. + 3, the cap entry it must arrive at is list words path_pi0 + 8p + 4 .. + 7.
@@ -1173,6 +1177,10 @@ GL_HD uint64_t chunk_shift(uint32_t u) {
 // workgroups with nothing to spread.)  Every constraint keeps its index, so the quotient is the same polynomial.
 // Unit 10: the Poseidon gate (G4).  The wires of the row are taken at their word: every constraint compares a wire with
 // what the round function makes of the wires before it, so a hash row is a chain of 118 local checks (+ 5 for the swap).
+// This is the statement of the gate (the host verifier, the oracle comparison, air_check_plonk_hash_kernel).  The
+// device's quotient evaluates the same folded sum in transposed form -- the MDS layers applied to the alpha weights,
+// once per quotient, instead of to every row's state: plonk_hash_fold.hpp, quotient_plonk_hash_kernel
+// (stark_kernels.hip), model tools/plonk_hash_fold_model.py.
 template <class T, class Row, class Emit, bool SELECTOR = true>
 GL_HD void eval_hash_unit(const Row& row, Emit& out) {
   // SELECTOR = false: the differences go out bare and the caller multiplies the folded sum by q_hash once

@@ -620,6 +620,10 @@ int quotient_args(const StarkCfg& cfg, const Ctl& ctl, uint64_t alpha0, uint64_t
   qa.n_constraints = qa.n_air_constraints + air::any_n_ctl_constraints(shape);
   qa.side_rows = cfg.air_id == air::PLONK ? 1 : 0;
   qa.n_air_units = air::any_n_units(shape) - qa.side_rows;
+  if (qa.side_rows) {  // the table its launch makes the gate's fold weights from: built on first use, like tw_n above
+    const uint64_t* fold = nullptr;
+    TRY(get_hash_fold_table(&fold));
+  }
   qa.aux_per_unit = cfg.air_id == air::SYNTHETIC ? std::max<uint32_t>(16, (A + 15) / 16) : A;
   // (AIR 8's copy constraints ride in its own ten units, next to the gates that read the same wires: no lookup unit)
   qa.n_ctl_units = cfg.air_id == air::PLONK ? 0 : (A + qa.aux_per_unit - 1) / qa.aux_per_unit;

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 #include "caller_table.hpp"
+#include "plonk_hash_fold.hpp"
 
 using namespace bpg;
 
@@ -47,6 +48,28 @@ int bp_debug_poseidon_host(uint64_t* states, size_t n) try {
   return BP_OK;
 }
 BPG_ABI_CATCH("bp_debug_poseidon_host")
+
+// AIR 8's fold block (plonk_hash_fold.hpp) for one pair of challenges: as the quotient's launch makes it on the device,
+// and by the recurrences on the host.
+static int hash_fold_alphas(const char* who, const uint64_t alphas[2], const void* out) {
+  if (!alphas || !out) return bpg::fail(BP_ERR_INVALID_INPUT, "%s: null argument", who);
+  if (alphas[0] >= gl::P || alphas[1] >= gl::P) return bpg::fail(BP_ERR_INVALID_INPUT, "%s: non-canonical alpha", who);
+  return BP_OK;
+}
+int bp_debug_plonk_hash_fold(const uint64_t alphas[2], uint64_t* d_out, void* stream) try {
+  if (int rc = hash_fold_alphas("bp_debug_plonk_hash_fold", alphas, d_out)) return rc;
+  if (int rc = init_ntt_kernels()) return rc;
+  return debug_plonk_hash_fold(alphas[0], alphas[1], d_out, as_stream(stream));
+}
+BPG_ABI_CATCH("bp_debug_plonk_hash_fold")
+int bp_debug_plonk_hash_fold_host(const uint64_t alphas[2], uint64_t* out) try {
+  if (int rc = hash_fold_alphas("bp_debug_plonk_hash_fold_host", alphas, out)) return rc;
+  uint64_t block[air::plonk::HASH_FOLD_WORDS];
+  air::plonk::hash_fold_block_host(air::plonk::N_CONSTRAINTS + air::ctl::PLONK_N_CONSTRAINTS, alphas[0], alphas[1], block);
+  std::memcpy(out, block, sizeof(block));
+  return BP_OK;
+}
+BPG_ABI_CATCH("bp_debug_plonk_hash_fold_host")
 
 void bp_release_cached_memory(void) { release_parked_workers(); }
 

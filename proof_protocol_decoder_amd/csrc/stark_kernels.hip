@@ -11,6 +11,9 @@
 //   * FRI: alpha-combination in coefficient space (one pass over all coefficients), division by
 //     (X - z) pointwise on the coset, folding in the EVALUATION domain (upstream folds
 //     coefficients and re-FFTs every layer).
+#include <map>
+#include <mutex>
+#include <vector>
 #include "common.hpp"
 #include "gl.hpp"
 #include "poseidon.cuh"
@@ -19,6 +22,7 @@
 #include "arg_ring.hpp"
 #include "quotient_dev.cuh"
 #include "air_program.hpp"
+#include "plonk_hash_fold.hpp"
 
 namespace {
 
@@ -857,8 +861,12 @@ __global__ void __launch_bounds__(256) plonk_partial_products_kernel(bpg::ArgPtr
 // "AIR units, then CTL units".
 // The Keccak-f evaluator wants 193 VGPRs (two waves per SIMD); held to 168 (three waves, 26 registers in scratch) it is
 // 10 % faster alone on the chip (700 -> 628 us at 2^14 rows; four waves at 128 VGPRs: 795 us).
+// AIR 8's Poseidon-gate pass in transposed form carries no twelve-word state: left at two waves it takes 130 VGPRs,
+// held to four 126 with the same instruction count (no scratch, no SGPR spill either way).  Alone the two measure the
+// same; in a lock-step batch of seven the four-wave form is 7 % faster (196.6 against 211.5 us) and the block is level
+// or slightly ahead with it (profiles/plonk_hash_fold_ab.txt, section 4, set 3).
 #ifndef BPG_PLONK_HASH_WAVES
-#define BPG_PLONK_HASH_WAVES 2
+#define BPG_PLONK_HASH_WAVES 4
 #endif
 template <uint32_t AIR>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AIR == bpg::air::KECCAK_F ? 3 : 1)))
@@ -898,10 +906,113 @@ quotient_air_kernel(bpg::ArgPtr<bpg::QuotArgs> args) {
     q.partial[((uint64_t)blockIdx.y * 2 + 1) * rows + pos] = r1;
   }
 }
+// AIR 8's Poseidon gate in transposed form (plonk_hash_fold.hpp): the folded sum of plonk::eval_hash_unit's 123
+// differences, selector left out, with the MDS layers on the weights.  N pairs at a time: the wires of columns col0 ..
+// are S-box inputs AND terms of their own, acc[0], acc[1] += A_j wire, acc[2], acc[3] += (-C_j) x^7.  The S-box outputs
+// go into the dot product as poseidon::sbox_n leaves them (reduced, any representative: dot_mad4 takes any u64); the
+// weights are wave-uniform reads: the wires' from the alpha table as DevEmit::push reads them, the S-box outputs' from
+// the fold block.
+struct HashFoldWeights {
+  const uint64_t* a;   // a[-p], a[T - p]: alpha_0, alpha_1 to the power of constraint G4 + p
+  const uint64_t* nc;  // nc[2 p], nc[2 p + 1]: -C_0, -C_1 of pair p; then K_0, K_1
+  uint32_t T;
+};
+template <int N>
+__device__ __forceinline__ void hash_fold_pairs(const uint64_t (&wire)[N], uint64_t (&x)[N], const HashFoldWeights& fw,
+                                                uint32_t p0, gl::DotAcc (&acc)[4]) {
+  __builtin_amdgcn_sched_barrier(0);  // one group's carry masks at a time (air.hpp, Ops<uint64_t>::mul4)
+  poseidon::sbox_n<N>(x);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const uint64_t *ap = fw.a - (p0 + i), *k = fw.nc + 2 * (size_t)(p0 + i);
+    const uint64_t a[4] = {wire[i], wire[i], x[i], x[i]};
+    const uint64_t w[4] = {ap[0], ap[fw.T], k[0], k[1]};
+    gl::dot_mad4(acc, a, w);
+  }
+}
+template <int N>
+__device__ __forceinline__ void hash_fold_wires(const DevRow& row, uint32_t col0, const HashFoldWeights& fw, uint32_t p0,
+                                                gl::DotAcc (&acc)[4]) {
+  uint64_t wire[N], x[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) wire[i] = x[i] = row.loc(col0 + i);
+  hash_fold_pairs<N>(wire, x, fw, p0, acc);
+}
+__device__ __forceinline__ void eval_hash_fold(const DevRow& row, const uint64_t* __restrict__ apow, uint32_t T,
+                                               uint64_t& r0, uint64_t& r1) {
+  namespace pk = bpg::air::plonk;
+  typedef bpg::air::Ops<uint64_t> F;
+  typedef bpg::air::PoseidonOps<uint64_t> H;
+  const HashFoldWeights fw{apow + (T - 1 - pk::G4), apow + 2 * (size_t)T + 48, T};
+  gl::DotAcc acc[4] = {gl::dot_zero(), gl::dot_zero(), gl::dot_zero(), gl::dot_zero()};
+  {
+    // the swap (G5) and round 0's S-box inputs in +- delta + rc_0, as eval_hash_unit forms them; round 0's S-box
+    // outputs are paired with the output wires
+    const uint64_t sw = row.loc(pk::H_SWAP);
+    uint64_t lhs[4], rhs[4], dl[4], pr[4], g[4], d[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+      lhs[i] = row.loc(pk::H_IN + i);
+      rhs[i] = row.loc(pk::H_IN + 4 + i);
+      dl[i] = row.loc(pk::H_DELTA + i);
+      pr[i] = F::sub(rhs[i], lhs[i]);
+    }
+    const uint64_t s4[4] = {sw, sw, sw, sw};
+    F::mul4(s4, pr, g);
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) d[i] = F::sub(dl[i], g[i]);
+    const uint64_t bit = F::mul(sw, F::sub(sw, F::k(1)));
+    const uint64_t* a0 = apow + (T - 1 - pk::G5 - 4);  // alpha_0^e of constraints G5 + 4, G5 + 3, .., G5
+    const uint64_t* a1 = a0 + T;
+    {
+      const uint64_t a[4] = {d[0], d[0], d[1], d[1]}, w[4] = {a0[3], a1[3], a0[2], a1[2]};
+      gl::dot_mad4(acc, a, w);
+    }
+    {
+      const uint64_t a[4] = {d[2], d[2], d[3], d[3]}, w[4] = {a0[1], a1[1], a0[0], a1[0]};
+      gl::dot_mad4(acc, a, w);
+    }
+    {
+      const uint64_t a[4] = {bit, bit, 0, 0}, w[4] = {a0[4], a1[4], 0, 0};
+      gl::dot_mad4(acc, a, w);
+    }
+    uint64_t wire[4], x[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+      wire[i] = row.loc(pk::H_OUT + i);
+      x[i] = H::add_rc0(F::add(lhs[i], dl[i]), i);
+    }
+    hash_fold_pairs<4>(wire, x, fw, 106, acc);
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+      wire[i] = row.loc(pk::H_OUT + 4 + i);
+      x[i] = H::add_rc0(F::sub(rhs[i], dl[i]), 4 + i);
+    }
+    hash_fold_pairs<4>(wire, x, fw, 110, acc);
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+      wire[i] = row.loc(pk::H_OUT + 8 + i);
+      x[i] = H::add_rc0(row.loc(pk::H_IN + 8 + i), 8 + i);
+    }
+    hash_fold_pairs<4>(wire, x, fw, 114, acc);
+  }
+  // pairs 0 .. 105: the wires of rounds 1..3, of the 22 partial rounds and of rounds 26..29, in column order
+  // (gl::mul_n has groups of four and of three: 106 = 25 x 4 + 2 x 3)
+  constexpr uint32_t N4 = 25;
+  static_assert(pk::H_SWAP - pk::H_FULL1 == 4 * N4 + 6 && pk::HASH_FOLD_PAIRS == 118, "the pair layout of plonk_hash_fold.hpp");
+#pragma unroll 1
+  for (uint32_t g = 0; g < N4; g++) hash_fold_wires<4>(row, pk::H_FULL1 + 4 * g, fw, 4 * g, acc);
+  hash_fold_wires<3>(row, pk::H_FULL1 + 4 * N4, fw, 4 * N4, acc);
+  hash_fold_wires<3>(row, pk::H_FULL1 + 4 * N4 + 3, fw, 4 * N4 + 3, acc);
+  const uint64_t* K = fw.nc + 2 * pk::HASH_FOLD_PAIRS;
+  r0 = gl::subc(gl::addc(gl::dot_reduce(acc[0]), gl::dot_reduce(acc[2])), K[0]);
+  r1 = gl::subc(gl::addc(gl::dot_reduce(acc[1]), gl::dot_reduce(acc[3])), K[1]);
+}
 // AIR 8's Poseidon gate: 118 local checks of one permutation's wires per row, folded bare and multiplied by the
-// selector once; its sums are row `wg_row` of `partial`.  About ten times the instructions of a chunk unit and another
-// register budget (the twelve-word state and the layer's accumulators), hence its own kernel: the chunk units keep three
-// waves per SIMD.   grid = (rows / 256, 1, batch)
+// selector once; its sums are row `wg_row` of `partial`.  A pass of its own with a register budget of its own: the chunk
+// units keep three waves per SIMD.  The fold is the transposed one (eval_hash_fold): 118 S-boxes and 241 dot terms a
+// row, the same field element as eval_hash_unit's sum.   grid = (rows / 256, 1, batch)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BPG_PLONK_HASH_WAVES)))
 quotient_plonk_hash_kernel(bpg::ArgPtr<bpg::QuotArgs> args, uint32_t wg_row) {
   BPG_ARG_BATCH(bpg::QuotArgs, args);
@@ -910,16 +1021,13 @@ quotient_plonk_hash_kernel(bpg::ArgPtr<bpg::QuotArgs> args, uint32_t wg_row) {
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
   const uint64_t pos = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (pos >= rows) return;
-  const uint32_t n = 1u << q.log_n;
-  const uint32_t t = (uint32_t)(pos >> q.log_n), m = (uint32_t)(pos & (n - 1));
-  DevEmit out{q.apow, q.n_constraints, row_point(q, t, m),
-              {gl::dot_zero(), gl::dot_zero(), gl::dot_zero(), gl::dot_zero()}, 0, 0, false};
-  DevRow row{q.trace_lde, q.aux_lde, q.const_lde, q.trace_stride, q.aux_stride, q.const_stride, pos,
-             ((uint64_t)t << q.log_n) | ((m + 1) & (n - 1)), out.rp.x, q.ctl.pub};
-  bpg::air::plonk::eval_hash_unit<uint64_t, DevRow, DevEmit, false>(row, out);
+  // (the gate reads this row only, and neither the point nor the public inputs)
+  DevRow row{q.trace_lde, q.aux_lde, q.const_lde, q.trace_stride, q.aux_stride, q.const_stride, pos, pos, 0, q.ctl.pub};
+  uint64_t r0, r1;
+  eval_hash_fold(row, q.apow, q.n_constraints, r0, r1);
   const uint64_t qh = row.cst(bpg::air::plonk::CST_HASH);
-  q.partial[((uint64_t)wg_row * 2) * rows + pos] = gl::mulc(out.result(0), qh);
-  q.partial[((uint64_t)wg_row * 2 + 1) * rows + pos] = gl::mulc(out.result(1), qh);
+  q.partial[((uint64_t)wg_row * 2) * rows + pos] = gl::mulc(r0, qh);
+  q.partial[((uint64_t)wg_row * 2 + 1) * rows + pos] = gl::mulc(r1, qh);
 }
 // qvals = (sum of the workgroup rows' partial sums) / Z_H.   grid = (rows / 256, 2 challenges)
 __global__ void __launch_bounds__(256) quotient_sum_kernel(bpg::ArgPtr<bpg::QuotArgs> args, uint32_t n_wg_rows) {
@@ -942,12 +1050,50 @@ struct AlphaTabArgs {
   uint64_t* out;
   uint64_t a0, a1;
 };
+// AIR 8 (fold != nullptr, T <= 256): grid.x = plonk::HASH_FOLD_BLOCKS workgroups per challenge, each of which makes all
+// T powers (a lane each; workgroup 0 writes them and the coset constants out) and then its share of the Poseidon gate's
+// fold weights behind the coset constants -- [118][2] = {-C_0, -C_1}, then K_0, K_1 (plonk_hash_fold.hpp; `fold` is
+// hash_fold_table()): a lane per piece of at most four powers against constant coefficients, then a lane per output
+// adds its pieces.
 __global__ void __launch_bounds__(256)
-alpha_table_kernel(bpg::ArgPtr<AlphaTabArgs> args, uint32_t T, CosetTab ct) {
+alpha_table_kernel(bpg::ArgPtr<AlphaTabArgs> args, uint32_t T, CosetTab ct, const uint64_t* __restrict__ fold) {
   BPG_ARG_BATCH(AlphaTabArgs, args);
   if (gridDim.x * gridDim.y * gridDim.z <= 64) __builtin_amdgcn_s_setprio(3);  // small launch = latency-critical: issue first
   uint64_t* __restrict__ out = batch[blockIdx.z].out;
   const uint64_t a0 = batch[blockIdx.z].a0, a1 = batch[blockIdx.z].a1;
+  if (fold) {
+    namespace pk = bpg::air::plonk;
+    __shared__ uint64_t pw[256], part[256];
+    const uint32_t l = threadIdx.x, j = blockIdx.y, e0 = T - 1 - pk::G4;  // A_k = alpha^(e0 - k)
+    // the lane's piece, its coefficients (at a fixed place: no load waits for another) and its output, asked for before
+    // the power is made
+    const uint32_t lane = 256 * blockIdx.x + l;
+    const uint64_t piece = fold[lane], o = fold[256 * pk::HASH_FOLD_BLOCKS + lane];
+    uint64_t coef[pk::HASH_FOLD_PIECE_TERMS];
+#pragma unroll
+    for (uint32_t i = 0; i < pk::HASH_FOLD_PIECE_TERMS; i++) coef[i] = fold[pk::HASH_FOLD_COEF0 + pk::HASH_FOLD_PIECE_TERMS * lane + i];
+    const uint64_t p = l < T ? gl::pow(j ? a1 : a0, l) : 0;
+    pw[l] = p;
+    if (blockIdx.x == 0) {
+      if (j == 0 && l < 48) out[2 * (uint64_t)T + l] = ct.v[l];
+      if (l < T) out[(uint64_t)j * T + l] = p;
+    }
+    __syncthreads();
+    const uint32_t terms = (uint32_t)piece & 0xff, k0 = (uint32_t)(piece >> 8) & 0xff;
+    uint64_t acc = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < pk::HASH_FOLD_PIECE_TERMS; i++)
+      if (i < terms) acc = gl::addc(acc, gl::mulc(coef[i], pw[e0 - k0 - i]));
+    part[l] = acc;
+    __syncthreads();
+    const uint32_t pieces = (uint32_t)o & 0xff, first = (uint32_t)(o >> 8) & 0xff, slot = (uint32_t)(o >> 16);
+    if (!pieces) return;
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < pieces; i++) sum = gl::addc(sum, part[first + i]);
+    uint64_t* __restrict__ w = out + 2 * (uint64_t)T + 48;
+    w[2 * slot + j] = slot < pk::HASH_FOLD_PAIRS ? gl::negc(sum) : sum;
+    return;
+  }
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.y == 0 && e < 48) out[2 * (uint64_t)T + e] = ct.v[e];
   if (e >= T) return;
@@ -1683,18 +1829,71 @@ int launch_aux(const AuxArgs* a, uint32_t batch, uint32_t air_id, uint32_t n_col
   BPG_LAUNCH_CHECK();
   return BP_OK;
 }
+// The constant table of alpha_table_kernel's fold workgroups (plonk_hash_fold.hpp), one device image per device, built
+// once and kept for the process lifetime, as the twiddle tables are: quotient_args asks for it where it asks for those
+// (get_table), so that the upload and its wait are the first use's, not a launch's.
+int get_hash_fold_table(const uint64_t** out) {
+  static std::mutex mu;
+  static std::map<int, const uint64_t*> tabs;
+  int dev = 0;
+  BPG_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = tabs.find(dev);
+  if (it == tabs.end()) {
+    static const std::vector<uint64_t> host = air::plonk::hash_fold_table();
+    if (host.empty()) return fail(BP_ERR_DEVICE, "the Poseidon gate's fold table does not fit its workgroups");
+    uint64_t* d = nullptr;
+    BPG_HIP(hipMalloc(reinterpret_cast<void**>(&d), host.size() * 8));
+    BPG_HIP(hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    it = tabs.emplace(dev, d).first;
+  }
+  *out = it->second;
+  return BP_OK;
+}
+// the alpha-power table of every proof's two challenges (a few thousand words, read wave-uniformly), the per-coset
+// constants behind it and, for AIR 8, the Poseidon gate's fold weights behind those (the same launch)
+static int launch_alpha_tables(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, hipStream_t st) {
+  const QuotArgs& q = qs[0];
+  CosetTab ct;
+  for (int t = 0; t < 16; t++) { ct.v[t] = coset.g_t[t]; ct.v[16 + t] = coset.zh_t[t]; ct.v[32 + t] = coset.zh_inv_t[t]; }
+  const uint64_t* fold = nullptr;
+  if (q.side_rows) {
+    if (q.n_constraints < air::plonk::HASH_FOLD_T_MIN || q.n_constraints > air::plonk::HASH_FOLD_T_MAX)
+      return fail(BP_ERR_INVALID_INPUT, "the Poseidon gate's fold weights are made for a constraint list of %u..%u entries, not %u",
+                  air::plonk::HASH_FOLD_T_MIN, air::plonk::HASH_FOLD_T_MAX, q.n_constraints);
+    if (int rc = get_hash_fold_table(&fold)) return rc;
+  }
+  AlphaTabArgs tabs[MAX_LOCKSTEP];
+  for (uint32_t b = 0; b < batch; b++) tabs[b] = AlphaTabArgs{const_cast<uint64_t*>(qs[b].apow), qs[b].alpha0, qs[b].alpha1};
+  BPG_ARG_BLOCKS(at, tabs, batch, st);
+  alpha_table_kernel<<<dim3(fold ? air::plonk::HASH_FOLD_BLOCKS : ceil_div(q.n_constraints, 256), 2, batch), 256, 0, st>>>(at, q.n_constraints, ct, fold);
+  BPG_LAUNCH_CHECK();
+  return BP_OK;
+}
+int debug_plonk_hash_fold(uint64_t alpha0, uint64_t alpha1, uint64_t* d_out, hipStream_t st) {
+  // the launch a quotient of AIR 8 makes, on a table of its own; the fold block is copied out on the same stream
+  QuotArgs q{};
+  q.n_constraints = air::plonk::N_CONSTRAINTS + air::ctl::PLONK_N_CONSTRAINTS;
+  q.side_rows = 1;
+  q.alpha0 = alpha0; q.alpha1 = alpha1;
+  struct Table {
+    uint64_t* d = nullptr;
+    ~Table() { (void)hipFree(d); }
+  } tab;
+  BPG_HIP(hipMalloc(reinterpret_cast<void**>(&tab.d), quotient_table_words(q) * 8));
+  q.apow = tab.d;
+  if (int rc = launch_alpha_tables(&q, 1, QuotCoset{}, st)) return rc;
+  BPG_HIP(hipMemcpyAsync(d_out, tab.d + 2 * (size_t)q.n_constraints + 48, air::plonk::HASH_FOLD_WORDS * 8, hipMemcpyDeviceToDevice, st));
+  BPG_HIP(hipStreamSynchronize(st));
+  return BP_OK;
+}
 int launch_quotient(const QuotArgs* qs, uint32_t batch, const QuotCoset& coset, hipStream_t st) {
   if (int rc = check_batch(batch)) return rc;
   const QuotArgs& q = qs[0];
   const uint64_t rows = (uint64_t)1 << (q.log_n + q.rate_bits);
-  // the alpha-power table of every proof's two challenges (a few thousand words, read wave-uniformly)
-  CosetTab ct;
-  for (int t = 0; t < 16; t++) { ct.v[t] = coset.g_t[t]; ct.v[16 + t] = coset.zh_t[t]; ct.v[32 + t] = coset.zh_inv_t[t]; }
-  AlphaTabArgs tabs[MAX_LOCKSTEP];
-  for (uint32_t b = 0; b < batch; b++) tabs[b] = AlphaTabArgs{const_cast<uint64_t*>(qs[b].apow), qs[b].alpha0, qs[b].alpha1};
-  BPG_ARG_BLOCKS(at, tabs, batch, st);
-  alpha_table_kernel<<<dim3(ceil_div(q.n_constraints, 256), 2, batch), 256, 0, st>>>(at, q.n_constraints, ct);
-  BPG_LAUNCH_CHECK();
+  // the beta powers of a port program and the gate's fold weights both start right behind the coset constants
+  if (q.n_ports && q.side_rows) return fail(BP_ERR_INVALID_INPUT, "launch_quotient: lookup ports and a side row in one table");
+  if (int rc = launch_alpha_tables(qs, batch, coset, st)) return rc;
   const uint32_t n_units = q.n_air_units + q.n_ctl_units, wg_rows = ceil_div(n_units, q.units_per_wg);
   BPG_ARG_BLOCKS(qb, qs, batch, st);
   if (q.n_ports)

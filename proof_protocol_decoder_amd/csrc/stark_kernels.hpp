@@ -47,7 +47,7 @@ struct QuotArgs {
   uint64_t trace_stride, aux_stride, const_stride;
   uint64_t *partial, *qvals;  // partial: [wg rows][2][rows], only when the units are spread over grid.y
   const uint64_t* tw_n;       // w_n^e, e < n/2
-  const uint64_t* apow;       // [2][n_constraints] alpha_j^e, then 48 per-coset words; filled by launch_quotient
+  const uint64_t* apow;       // [2][n_constraints] alpha_j^e, then 48 per-coset words (AIR 8: then the Poseidon gate's fold weights); filled by launch_quotient
   uint32_t air_id, log_n, rate_bits, n_cols, n_const, n_aux, deg_pow;
   // the constraint list (air.hpp): AIR constraints, then two per aux column; units = AIR units, then CTL units
   uint32_t n_air_constraints, n_constraints, n_air_units, n_ctl_units, aux_per_unit, units_per_wg;
@@ -60,8 +60,12 @@ struct QuotArgs {
   uint64_t alpha0, alpha1, g, g_inv, n_inv;
   Ctl ctl;
 };
-// the words of QuotArgs::apow: the alpha powers, the per-coset constants, a port program's beta powers
-inline size_t quotient_table_words(const QuotArgs& q) { return 2 * (size_t)q.n_constraints + 48 + (q.n_ports ? 256 : 0); }
+// the words of QuotArgs::apow: the alpha powers, the per-coset constants, then a port program's beta powers or (AIR 8,
+// whose Poseidon gate is the side row) the gate's fold weights (plonk_hash_fold.hpp) -- one or the other at offset
+// 2 T + 48: a registered program is never AIR 8, and launch_quotient refuses a table with both
+inline size_t quotient_table_words(const QuotArgs& q) {
+  return 2 * (size_t)q.n_constraints + 48 + (q.n_ports ? 256 : 0) + (q.side_rows ? air::plonk::HASH_FOLD_WORDS : 0);
+}
 struct QuotCoset {  // per coset: 7*w_M^t, g_t^n - 1 and its inverse (the same for every proof of a shape)
   uint64_t g_t[16], zh_t[16], zh_inv_t[16];
 };
@@ -230,6 +234,9 @@ inline int launch_quotient(const QuotArgs& q, const QuotCoset& coset, hipStream_
 struct KernelTimer;
 // qb: the blocks as the device sees them (arg_put), q0: the host copy of the first
 int launch_quotient_program(const QuotArgs* qb, const QuotArgs& q0, dim3 grid, KernelTimer& kt, hipStream_t st);
+// what launch_quotient leaves in AIR 8's fold block (plonk::HASH_FOLD_WORDS words) for one pair of challenges, on the device
+int get_hash_fold_table(const uint64_t** out);  // the constant table the fold weights are made from, on the current device
+int debug_plonk_hash_fold(uint64_t alpha0, uint64_t alpha1, uint64_t* d_out, hipStream_t st);
 int launch_beta_tables(const QuotArgs* qb, uint32_t batch, hipStream_t st);  // a port program's beta powers, behind apow's 48 coset words
 // air_program.hip: launch_aux's first half for a registered program with ports: term_0, term_1 of every port into the
 // port's two auxiliary columns (launch_aux then multiplies them up, aux_suffix_product_kernel<TERMS_IN_COLUMN>)

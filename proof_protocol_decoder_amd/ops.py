@@ -114,6 +114,26 @@ def lazy_forms(a, b):
     return out
 
 
+PLONK_HASH_FOLD_WORDS = 2 * 118 + 2   # plonk::HASH_FOLD_WORDS of csrc/air.hpp (tests/test_plonk_hash_fold_model.py compares them)
+
+
+def plonk_hash_fold(alphas, device="cuda"):
+    """bp_debug_plonk_hash_fold: the 238 words with which AIR 8's quotient weighs the S-box outputs of its Poseidon gate
+    for the challenge pair `alphas`, as the quotient's launch leaves them on the device: [118][2] = {-C_0, -C_1}, then
+    K_0, K_1 (tools/plonk_hash_fold_model.py: pair_table)."""
+    out = torch.empty(PLONK_HASH_FOLD_WORDS, dtype=torch.int64, device=device)
+    check(own().bp_debug_plonk_hash_fold((C.c_uint64 * 2)(*[int(x) for x in alphas]), out.data_ptr(), _stream()))
+    return out
+
+
+def plonk_hash_fold_host(alphas):
+    """bp_debug_plonk_hash_fold_host: the same words by the recurrences on the host (no device is touched)"""
+    out = np.zeros(PLONK_HASH_FOLD_WORDS, dtype=np.uint64)
+    check(own().bp_debug_plonk_hash_fold_host((C.c_uint64 * 2)(*[int(x) for x in alphas]),
+                                              out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
 def mul_pow2(a):
     """bp_debug_mul_pow2: [21, n] planes, plane 3(k-1) + f = a * 2^(12k) mod p (canonical), k = 1..7, by the groups of
     four (f = 0), of three (f = 1) and the one-element form (f = 2); a: any u64 patterns."""

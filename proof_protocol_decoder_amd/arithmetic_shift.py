@@ -15,7 +15,7 @@ one product port exposes (is_shl, is_shr, is_sar, s limbs, x limbs, res limbs) o
 """
 from . import word_table
 from .air_program import ALL_ROWS, Builder
-from .word_table import BASE, EXPOSED, LIMB_BITS, _word, bits_sum, bits_value  # noqa: F401 (EXPOSED: the input format's)
+from .word_table import BASE, EXPOSED, LIMB_BITS, _word, bits_sum, bits_value, flags3  # noqa: F401 (EXPOSED: the input format's)
 
 OP_NONE, SHL, SHR, SAR = 0, 1, 2, 3
 LIMBS, OFFSETS = 16, 31       # e_d for the limb offsets d = -15 .. 15 at COL_E + 15 + d
@@ -65,17 +65,6 @@ LIMBS_PER_UNIT = 1
 def first_index(name):
     """the constraint index at which family `name` starts"""
     return word_table.first_index(FAMILIES, name)
-
-
-def flags3(b, at, flags, g, z):
-    """families flags, one_flag, filter for a table of three operations: the flags and z are bits, at most one flag, g
-    only on a live row; returns the sum of the flags"""
-    for j, f in enumerate(flags + (z,)):
-        b.emit(at["flags"] + j, f * f - f)
-    live = flags[0] + flags[1] + flags[2]
-    b.emit(at["one_flag"], live * (live - 1))
-    b.emit(at["filter"], g * (1 - live))
-    return live
 
 
 def program(limbs_per_unit=LIMBS_PER_UNIT):

@@ -45,25 +45,17 @@ __device__ __forceinline__ void store_limb(const Row& row, const U256& x, const 
   row.template put_remainder_limb<K>(dv::SHARED, r, d, y_zero, borrow);
 }
 
-// sum_{i + j = K} q_i y_j, K and every limb number a compile-time number
-template <uint32_t K, uint32_t I = 0>
-__device__ __forceinline__ uint64_t conv(const U256& q, const U256& y) {
-  if constexpr (I > K) return 0;
-  else return (uint64_t)limb<I>(q) * limb<K - I>(y) + conv<K, I + 1>(q, y);
-}
-
 template <uint32_t K>
 __device__ __forceinline__ void store_limbs(const Row& row, const U256& x, const U256& y, const U256& q, const U256& r, const U256& d,
                                             const U256& res, uint64_t& carry, uint32_t& borrow, bool y_zero) {
   if constexpr (K < dv::LIMBS) {
-    store_limb<K>(row, x, y, q, r, d, res, conv<K>(q, y), carry, borrow, y_zero);
+    store_limb<K>(row, x, y, q, r, d, res, word256::conv<K>(q, y), carry, borrow, y_zero);
     store_limbs<K + 1>(row, x, y, q, r, d, res, carry, borrow, y_zero);
   }
 }
 
 // One operation per row, one lane per row.  inputs: [row][9] (include/bpg.h).  The lane divides by shift and subtract
-// over the register pair (r : q) -- q starts as x and gives a dividend bit to r at the top as it takes a quotient bit
-// at the bottom --, then derives every column from q and r.  Stores are column-major, so a wave's are contiguous.
+// (word256::divide), then derives every column from q and r.  Stores are column-major, so a wave's are contiguous.
 __global__ void __launch_bounds__(256)
 arithmetic_div_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict__ inputs, uint32_t log_n) {
   const uint32_t n = 1u << log_n;
@@ -75,18 +67,7 @@ arithmetic_div_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict
   const U256 zero{0, 0, 0, 0};
   const U256 x = word256::operand<0>(in, h.live), y = word256::operand<1>(in, h.live);
   const bool y_zero = word256::is_zero(y);
-
-  U256 q = x, r = zero;
-#pragma unroll 1
-  for (uint32_t it = 0; it < 256; it++) {
-    const uint64_t bit = word256::shift_in(q, 0);
-    word256::subtract_step(r, y, bit, q.a);
-  }
-  if (y_zero) {  // the loop subtracted zero 256 times: q is all ones, r is x.  The EVM's x / 0: q = 0, r = x
-    q = zero;
-    r = x;
-  }
-  const U256 d = word256::slack(y, r, y_zero);
+  const auto [q, r, d] = word256::divide(x, y, y_zero);
   const U256 res = y_zero ? zero : h.op_a ? q : r;  // (a padding row has y = 0)
 
   const Row row{t + i, n};

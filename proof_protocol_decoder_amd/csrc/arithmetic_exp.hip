@@ -52,13 +52,6 @@ __device__ __forceinline__ void step(State& s) {
   s.e.d >>= 1;
 }
 
-// sum_{i + j = K} x_i y_j, K and every limb number a compile-time number: below 16 (2^16 - 1)^2
-template <uint32_t K, uint32_t I = 0>
-__device__ __forceinline__ uint64_t conv(const U256& x, const U256& y) {
-  if constexpr (I > K) return 0;
-  else return (uint64_t)limb<I>(x) * limb<K - I>(y) + conv<K, I + 1>(x, y);
-}
-
 // what a row stores for limb K of p, e, res, r, out, m, s, and the carries out of column K of r p and of p p: column +
 // carry in = limb + 2^16 carry out, below 2^37, so a carry is below 2^21 and on an honest row below 2^20 (AIRS.md)
 template <uint32_t K>
@@ -76,8 +69,8 @@ __device__ __forceinline__ void store_limbs(const Row& row, const State& s, cons
     row.put_bits(ex::COL_E_BITS + 16 * K, ek, 16);
     row.put_bits(ex::COL_M_BITS + 16 * K, mk, 16);
     row.put_bits(ex::COL_S_BITS + 16 * K, sk, 16);
-    carry_m = (conv<K>(s.r, s.p) + carry_m - mk) >> 16;
-    carry_s = (conv<K>(s.p, s.p) + carry_s - sk) >> 16;
+    carry_m = (word256::conv<K>(s.r, s.p) + carry_m - mk) >> 16;
+    carry_s = (word256::conv<K>(s.p, s.p) + carry_s - sk) >> 16;
     row.put_bits(ex::COL_M_CARRY + ex::CARRY_BITS * K, (uint32_t)carry_m, ex::CARRY_BITS);
     row.put_bits(ex::COL_S_CARRY + ex::CARRY_BITS * K, (uint32_t)carry_s, ex::CARRY_BITS);
     store_limbs<K + 1>(row, s, res, out, m, sq, carry_m, carry_s);

@@ -81,12 +81,6 @@ __device__ __forceinline__ U512 add256(const U256& x, const U256& y) {
   return u;
 }
 
-// sum_{i + j = K, i < 16, j < 16} a_i b_j, every limb number a compile-time number
-template <uint32_t K, uint32_t I = (K < 16 ? 0 : K - 15)>
-__device__ __forceinline__ uint64_t conv_left(const U256& a, const U256& b) {
-  if constexpr (I > K || I > 15) return 0;
-  else return (uint64_t)limb<I>(a) * limb<K - I>(b) + conv_left<K, I + 1>(a, b);
-}
 // sum_{i + j = K, i < 32, j <= 16} q_i M_j with M = m + z 2^256 (M_16 = z)
 template <uint32_t K, uint32_t J = (K < 32 ? 0 : K - 31)>
 __device__ __forceinline__ uint64_t conv_right(const U512& q, const U256& m, uint32_t z) {
@@ -104,7 +98,7 @@ __device__ __forceinline__ void store_column(const Row& row, const U256& a, cons
   const uint32_t qk = limb<K>(q);
   row.put(md::COL_Q + K, qk);
   row.put_bits(md::COL_Q_BITS + 16 * K, qk, 16);
-  int64_t acc = carry + (int64_t)(is_mulmod ? conv_left<K>(a, b) : 0) - (int64_t)conv_right<K>(q, m, m_zero);
+  int64_t acc = carry + (int64_t)(is_mulmod ? word256::conv<K>(a, b) : 0) - (int64_t)conv_right<K>(q, m, m_zero);
   if constexpr (K < md::LIMBS) {
     const uint32_t ak = limb<K>(a), bk = limb<K>(b), mk = limb<K>(m), rk = limb<K>(r);
     row.put(md::COL_A + K, ak);

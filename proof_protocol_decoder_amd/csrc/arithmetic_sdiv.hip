@@ -72,26 +72,18 @@ __device__ __forceinline__ void store_limb(const Row& row, const U256& x, const 
   put_chain_limb<K>(row, sd::COL_RES_CHAIN, neg, m, res, chains.res);
 }
 
-// sum_{i + j = K} q_i ay_j, K and every limb number a compile-time number
-template <uint32_t K, uint32_t I = 0>
-__device__ __forceinline__ uint64_t conv(const U256& q, const U256& ay) {
-  if constexpr (I > K) return 0;
-  else return (uint64_t)limb<I>(q) * limb<K - I>(ay) + conv<K, I + 1>(q, ay);
-}
-
 template <uint32_t K>
 __device__ __forceinline__ void store_limbs(const Row& row, const U256& x, const U256& y, const U256& ax, const U256& ay, const U256& q,
                                             const U256& r, const U256& d, const U256& m, const U256& res, uint64_t& carry,
                                             uint32_t& borrow, Chains& chains, bool sx, bool sy, bool neg, bool y_zero) {
   if constexpr (K < sd::LIMBS) {
-    store_limb<K>(row, x, y, ax, ay, q, r, d, m, res, conv<K>(q, ay), carry, borrow, chains, sx, sy, neg, y_zero);
+    store_limb<K>(row, x, y, ax, ay, q, r, d, m, res, word256::conv<K>(q, ay), carry, borrow, chains, sx, sy, neg, y_zero);
     store_limbs<K + 1>(row, x, y, ax, ay, q, r, d, m, res, carry, borrow, chains, sx, sy, neg, y_zero);
   }
 }
 
 // One operation per row, one lane per row.  inputs: [row][9] (include/bpg.h).  The lane takes the magnitudes of x and y,
-// divides them by shift and subtract over the register pair (r : q) -- the division kernel's loop: q starts as ax and
-// gives a dividend bit to r at the top as it takes a quotient bit at the bottom --, picks the magnitude m of the result,
+// divides them by shift and subtract (word256::divide, as the division kernel does), picks the magnitude m of the result,
 // negates it under the result's sign, then derives every column.  Stores are column-major, so a wave's are contiguous.
 __global__ void __launch_bounds__(256)
 arithmetic_sdiv_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restrict__ inputs, uint32_t log_n) {
@@ -106,18 +98,7 @@ arithmetic_sdiv_trace_kernel(uint64_t* __restrict__ t, const uint64_t* __restric
   const bool sx = x.d >> 63, sy = y.d >> 63;
   const U256 ax = word256::magnitude(x), ay = word256::magnitude(y);
   const bool y_zero = word256::is_zero(y);
-
-  U256 q = ax, r = zero;
-#pragma unroll 1
-  for (uint32_t it = 0; it < 256; it++) {
-    const uint64_t bit = word256::shift_in(q, 0);
-    word256::subtract_step(r, ay, bit, q.a);
-  }
-  if (y_zero) {  // the loop subtracted zero 256 times: q is all ones, r is ax.  The EVM's x / 0: q = 0, r = ax
-    q = zero;
-    r = ax;
-  }
-  const U256 d = word256::slack(ay, r, y_zero);
+  const auto [q, r, d] = word256::divide(ax, ay, y_zero);
   // the quotient rounds toward zero and the remainder has the sign of x; -0 = 0 comes out of the negation by itself
   const bool neg = h.op_a ? sx != sy : h.op_b & sx;
   const U256 m = y_zero ? zero : h.op_a ? q : r;  // (a padding row has y = 0)

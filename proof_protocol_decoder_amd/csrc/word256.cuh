@@ -1,10 +1,12 @@
-// word256.cuh -- what the witness kernels of the shipped tables (arithmetic_div.hip, arithmetic_mod.hip,
-// arithmetic_shift.hip, arithmetic_sdiv.hip) share: a 256-bit word in named registers, its 16-bit limbs by compile-time
-// number, the shift-and-subtract step, a lane's view of its trace row with the stores every quotient / remainder / slack
-// table makes, and the host side of the two C entries a table has.  A table's .hip file keeps its column map, its product
-// columns and its kernel.  The shift table, which has no quotient, uses U256, limb, Head3, operand, Row::put / put_bits
-// and the two entries; the signed table adds negate / magnitude to what the division table uses; the exponentiation table
-// (arithmetic_exp.hip), whose rows are steps of a chain, uses U256, limb, mul_low, Row::put / put_bits and layout_entry.
+// word256.cuh -- what the witness kernels of the five shipped tables (arithmetic_div.hip, arithmetic_mod.hip,
+// arithmetic_shift.hip, arithmetic_sdiv.hip, arithmetic_exp.hip) share: a 256-bit word in named registers, its 16-bit limbs
+// by compile-time number, a column of the limb product (conv), the shift-and-subtract step and the whole 256-bit division
+// made of it (divide), a lane's view of its trace row with the stores every quotient / remainder / slack table makes, and
+// the host side of the two C entries a table has.  A table's .hip file keeps its column map, its store_limb(s) and its
+// kernel.  The shift table, which has no quotient, uses U256, limb, Head3, operand, Row::put / put_bits and the two
+// entries; the division and the signed table divide by divide, the signed one between negate / magnitude; the modular
+// table has a 512-bit loop of its own over shift_in / subtract_step; the exponentiation table, whose rows are steps of a
+// chain, uses U256, limb, conv, mul_low, Row::put / put_bits and layout_entry.
 #pragma once
 #include <cstdint>
 
@@ -76,6 +78,13 @@ __device__ __forceinline__ uint32_t limb_sum(const U256& w) {
   if constexpr (K == 16) return 0;
   else return limb<K>(w) + limb_sum<K + 1>(w);
 }
+// sum_{i + j = K, i < 16, j < 16} x_i y_j, column K of the limb product: K and every limb number a compile-time number,
+// at most sixteen terms, so below 16 (2^16 - 1)^2
+template <uint32_t K, uint32_t I = (K < 16 ? 0 : K - 15)>
+__device__ __forceinline__ uint64_t conv(const U256& x, const U256& y) {
+  if constexpr (I > K || I > 15) return 0;
+  else return (uint64_t)limb<I>(x) * limb<K - I>(y) + conv<K, I + 1>(x, y);
+}
 
 // ---- division by shift and subtract
 // w = 2 w + in; returns the bit that leaves at the top.  A dividend of 512 bits is two of these, the low half's bit out
@@ -103,6 +112,26 @@ __device__ __forceinline__ void subtract_step(U256& r, const U256& divisor, uint
 __device__ __forceinline__ U256 slack(const U256& y, const U256& r, bool y_zero) {
   uint32_t unused;
   return y_zero ? U256{0, 0, 0, 0} : sub256(sub256(y, r, &unused), U256{1, 0, 0, 0}, &unused);
+}
+// q, r and the slack d of dividend = q divisor + r, r + d + 1 = divisor, over the register pair (r : q): q starts as the
+// dividend and gives a dividend bit to r at the top as it takes a quotient bit at the bottom.  The EVM's x / 0 is q = 0,
+// r = x, d = 0; the caller has tested the divisor already and says so in `divisor_zero`.
+struct Division {
+  U256 q, r, d;
+};
+__device__ __forceinline__ Division divide(const U256& dividend, const U256& divisor, bool divisor_zero) {
+  Division v{dividend, U256{0, 0, 0, 0}, U256{0, 0, 0, 0}};
+#pragma unroll 1
+  for (uint32_t it = 0; it < 256; it++) {
+    const uint64_t bit = shift_in(v.q, 0);
+    subtract_step(v.r, divisor, bit, v.q.a);
+  }
+  if (divisor_zero) {  // the loop subtracted zero 256 times: q is all ones, r is the dividend
+    v.q = U256{0, 0, 0, 0};
+    v.r = dividend;
+  }
+  v.d = slack(divisor, v.r, divisor_zero);
+  return v;
 }
 
 // ---- a row's inputs: word 0 = op byte | exposed << 8, then four words per operand (include/bpg.h)

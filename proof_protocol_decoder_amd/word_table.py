@@ -1,9 +1,11 @@
-"""What the shipped tables over 256-bit words (arithmetic_div.py, arithmetic_mod.py, arithmetic_sdiv.py) share: the
-pieces of a constraint program every quotient / remainder / slack table over 16-bit limbs is made of, the conditional
-negation the signed table takes its magnitudes and its result by, and the plumbing between such a module,
-its witness kernel and the library.  Plain functions over the table's air_program.Builder `b`, its family bases `at`
-(name -> first constraint index; the shared families carry the same names in every table) and its column numbers.  A
-table module states its column map, LAYOUT, FAMILIES and the part of program() that is its own.
+"""What the five shipped tables over 256-bit words (arithmetic_div.py, arithmetic_mod.py, arithmetic_shift.py,
+arithmetic_sdiv.py, arithmetic_exp.py) share.  All five: the range-checked bit blocks (bits_value, bits_sum), first_index
+and the plumbing between such a module, its witness kernel and the library.  The four tables of one operation per row:
+the flags of two operations (flags) or of three (flags3, the shift table's) and the zero test.  The quotient / remainder
+/ slack tables over 16-bit limbs -- division, modular, signed -- : remainder_limb; the signed table alone the conditional
+negation it takes its magnitudes and its result by.  Plain functions over the table's air_program.Builder `b`, its
+family bases `at` (name -> first constraint index; the shared families carry the same names in every table) and its
+column numbers.  A table module states its column map, LAYOUT, FAMILIES and the part of program() that is its own.
 
 The Builder numbers registers and orders code by the order of Python operations, and a program's id is a digest of its
 words: these helpers perform the operations the tables performed before they were factored out, in the same order
@@ -44,6 +46,17 @@ def flags(b, at, op_a, op_b, g, z):
         b.emit(at["flags"] + j, f * f - f)
     b.emit(at["one_flag"], op_a * op_b)
     b.emit(at["filter"], g * (1 - op_a - op_b))
+
+
+def flags3(b, at, flags, g, z):
+    """families flags, one_flag, filter for a table of three operations: the flags and z are bits, at most one flag, g
+    only on a live row; returns the sum of the flags"""
+    for j, f in enumerate(flags + (z,)):
+        b.emit(at["flags"] + j, f * f - f)
+    live = flags[0] + flags[1] + flags[2]
+    b.emit(at["one_flag"], live * (live - 1))
+    b.emit(at["filter"], g * (1 - live))
+    return live
 
 
 def zero_test(b, at, z, s, inv, not_zero):

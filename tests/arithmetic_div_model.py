@@ -12,6 +12,7 @@ import word_table_model as base
 from word_table_model import B, M256, P, limbs, word  # noqa: F401 (the tests read them here)
 
 NONE, DIV, MOD = 0, 1, 2
+LIVE = (DIV, MOD)
 CARRY_BITS = 19
 
 # AIRS.md section 2: five single columns, four limb blocks, five bit blocks, 15 carries of 19 bits, 16 carry bits of r + d + 1

@@ -17,6 +17,7 @@ P = 2 ** 64 - 2 ** 32 + 1
 B = 1 << 16
 M256 = (1 << 256) - 1
 NONE, EXP = 0, 1
+LIVE = (EXP,)
 CARRY_BITS = 20
 
 # AIRS.md section 2: three flags, five limb blocks, five bit blocks, twice sixteen carries of 20 bits

@@ -12,6 +12,7 @@ import word_table_model as base
 from word_table_model import B, M256, P, limbs, word  # noqa: F401 (the tests read them here)
 
 NONE, ADDMOD, MULMOD = 0, 1, 2
+LIVE = (ADDMOD, MULMOD)
 CARRY_BITS, CARRY_OFFSET = 21, 1 << 20
 
 # AIRS.md section 2: five single columns, four blocks of 16 limbs and one of 32, six bit blocks, 31 carries of 21 bits, 16

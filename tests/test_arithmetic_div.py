@@ -1,15 +1,14 @@
 """The division table on the CPU: the shipped program (proof_protocol_decoder_amd/arithmetic_div.py) against the
 independent row model of tests/arithmetic_div_model.py -- the column maps, Builder.evaluate over Python integers, the
 library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  The fixtures and the
-tests it has in common with the modular table are word_tables.cpu_tests over this table's record; its own follow.
+tests it has in common with the other shipped tables are word_tables.cpu_tests over this table's record; its own follow.
 Nothing here needs a GPU; the device side is tests/test_gpu_arithmetic_div.py."""
 import arithmetic_div_model as model
-from word_tables import DIVISION, cpu_tests
+from word_tables import DIVISION, cpu_tests, renamed
 
-program, reg, edge_trace, test_the_three_column_maps_agree, test_the_layout_entry_refuses_a_short_buffer, \
-    test_the_program_fits_the_format_and_registers_once, test_the_program_vanishes_on_every_model_row, \
-    test_the_host_checker_is_clean_on_the_model_trace, test_unpack_row_and_pack_inputs_give_back_divmod, \
-    test_a_wrong_witness_is_named_at_its_row_and_family = cpu_tests(DIVISION)
+globals().update(renamed(cpu_tests(DIVISION),
+                         test_the_layout_entry_refuses_a_short_or_null_buffer="test_the_layout_entry_refuses_a_short_buffer",
+                         test_unpack_row_and_pack_inputs_give_back_the_operations="test_unpack_row_and_pack_inputs_give_back_divmod"))
 
 
 def test_the_largest_carry_is_reached_and_fits():

@@ -1,31 +1,19 @@
 """The exponentiation table on the CPU: the shipped program (proof_protocol_decoder_amd/arithmetic_exp.py) against the
 independent model of tests/arithmetic_exp_model.py -- the column maps, Builder.evaluate over Python integers on every row
-and next row, the library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  The
-bodies restate word_tables.cpu_tests for a table whose operations span rows: a forgery is a trace, not a row, and the
-kinds of the families (transition, last row) are part of what is compared.  Nothing here needs a GPU; the device side is
+and next row, the library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  What
+holds for every shipped table -- the layout entry, the program's format and registration, with the kinds of the families
+(transition, last row) compared -- is word_tables.program_tests over this table's record; the rest is its own, because
+the operations span rows: a forgery is a trace, not a row.  Nothing here needs a GPU; the device side is
 tests/test_gpu_arithmetic_exp.py."""
 import numpy as np
 import pytest
 
 import arithmetic_exp_model as model
-from proof_protocol_decoder_amd import arithmetic_div, arithmetic_exp as ex, arithmetic_mod, arithmetic_sdiv, arithmetic_shift
-from proof_protocol_decoder_amd.air_program import ALL_ROWS, LAST_ROW, MAX_FAMILIES_WITH_PORTS, MAX_REGS, TRANSITION
+from proof_protocol_decoder_amd import arithmetic_div, arithmetic_exp as ex
+from word_tables import EXPONENTIATION, program_tests
 
-N_COLS, WIDTH, LAYOUT_WORDS, N_FAMILIES, N_CONSTRAINTS, N_UNITS = 2003, 48, 17, 17, 2357, 17   # AIRS.md section 2
-MODEL_LAYOUT = (model.N_COLS, model.G, model.FIRST, model.LAST, model.P_, model.E, model.RES, model.R, model.OUT, model.P_BITS,
-                model.R_BITS, model.E_BITS, model.M_BITS, model.S_BITS, model.M_CARRY, model.S_CARRY, model.CARRY_BITS)
-
-
-@pytest.fixture(scope="module")
-def program():
-    return ex.program()
-
-
-@pytest.fixture(scope="module")
-def reg():
-    import proof_protocol_decoder_amd as pkg
-    pkg.lib()
-    return ex.register()
+globals().update(program_tests(EXPONENTIATION))
+N_COLS, WIDTH = EXPONENTIATION.n_cols, EXPONENTIATION.width
 
 
 @pytest.fixture(scope="module")
@@ -43,10 +31,6 @@ def edge_traces():
     return ts
 
 
-def kind_of(name):
-    return TRANSITION if name in model.TRANSITIONS else LAST_ROW if name == "last_row" else ALL_ROWS
-
-
 def builder_violations(program, trace, rows):
     """{(row, family)} by Builder.evaluate over `rows`, the families' kinds applied as the library applies them"""
     n = trace.shape[1]
@@ -60,50 +44,14 @@ def builder_violations(program, trace, rows):
 def test_the_three_column_maps_agree():
     """the module's constants, the kernel's (its layout entry) and the model's, which is written from AIRS.md"""
     assert ex.kernel_layout() == ex.LAYOUT
-    assert MODEL_LAYOUT == ex.LAYOUT and len(ex.LAYOUT) == LAYOUT_WORDS
+    assert EXPONENTIATION.model_layout == ex.LAYOUT and len(ex.LAYOUT) == EXPONENTIATION.layout_words
     assert [(n, c) for n, c, _, _ in ex.FAMILIES] == model.FAMILIES
-    assert [k for _, _, k, _ in ex.FAMILIES] == [kind_of(n) for n, _ in model.FAMILIES]
+    assert [k for _, _, k, _ in ex.FAMILIES] == [EXPONENTIATION.kind_of(n) for n, _ in model.FAMILIES]
+    assert [ex.first_index(n) for n, _ in model.FAMILIES] == [model.FIRST_INDEX[n] for n, _ in model.FAMILIES]
     assert list(ex.TUPLE_COLS) == model.TUPLE and len(ex.TUPLE_COLS) == WIDTH and ex.N_COLS == N_COLS == model.N_COLS
     assert ex.OP_EXP == model.EXP == 1 and ex.MAX_ROWS == 256
     for e in (0, 1, 2, 3, 255, 256, (1 << 64) + 1, model.M256):
         assert ex.rows_of(e) == model.rows_of(e) == max(1, e.bit_length())
-
-
-def test_the_layout_entry_refuses_a_short_or_null_buffer():
-    import ctypes as C
-    import proof_protocol_decoder_amd as pkg
-    entry = pkg.lib().bp_arithmetic_exp_layout
-    out = (C.c_uint32 * 32)()
-    assert entry(out, len(ex.LAYOUT) - 1) == -2
-    assert b"%d words" % LAYOUT_WORDS in pkg.lib().bp_last_error()
-    assert entry(out, 0) == -2 and not any(out)
-    assert entry(None, 32) == -2
-    assert entry(out, 32) == 0 and tuple(out[:len(ex.LAYOUT)]) == ex.LAYOUT
-
-
-def test_the_program_fits_the_format_and_registers_once(program, reg):
-    import proof_protocol_decoder_amd as pkg
-    words = program.assemble()
-    assert int(words[0]) == int.from_bytes(b"BPGAIRP2", "little")
-    assert int(words[7]) <= MAX_REGS and len(program.units) == N_UNITS <= 256
-    assert len(program.families) == N_FAMILIES <= MAX_FAMILIES_WITH_PORTS
-    assert reg & 0x80000000 and ex.register() == reg and pkg.ops.air_register(words) == reg
-    assert pkg.lib().bp_air_count() == 9                                       # no built-in was added
-    others = {arithmetic_div.register(), arithmetic_mod.register(), arithmetic_shift.register(), arithmetic_sdiv.register()}
-    assert len(others | {reg}) == 5                                            # ... and every table keeps its own id
-    d = pkg.ops.air_describe(reg)
-    assert (d.n_cols, d.degree, d.n_aux, d.n_air_constraints, d.n_units) == (N_COLS, 3, 2, model.N_CONSTRAINTS, N_UNITS)
-    fams = [(f.first_index, f.count, f.kind, f.degree) for f in d.families[:d.n_families]]
-    first = 0
-    for (name, count, kind, degree), got in zip(ex.FAMILIES, fams):
-        assert got == (first, count, kind, degree), name
-        assert ex.first_index(name) == first == model.FIRST_INDEX[name]
-        first += count
-    # the library's five constraints of the product port follow the program's own
-    assert first == model.N_CONSTRAINTS == N_CONSTRAINTS and d.n_families == N_FAMILIES + 5
-    assert sum(f[1] for f in fams[N_FAMILIES:]) == 5 == d.n_ctl_constraints and fams[N_FAMILIES][0] == first
-    # the families that span rows, which no shipped program had before
-    assert {f[2] for f in fams[:N_FAMILIES]} == {ALL_ROWS, TRANSITION, LAST_ROW}
 
 
 def test_every_unit_cut_states_the_same_constraints(small_trace):

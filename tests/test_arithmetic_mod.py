@@ -1,16 +1,13 @@
 """The modular table on the CPU: the shipped program (proof_protocol_decoder_amd/arithmetic_mod.py) against the
 independent row model of tests/arithmetic_mod_model.py -- the column maps, Builder.evaluate over Python integers, the
 library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  The fixtures and the
-tests it has in common with the division table are word_tables.cpu_tests over this table's record; its own follow.
+tests it has in common with the other shipped tables are word_tables.cpu_tests over this table's record; its own follow.
 Nothing here needs a GPU; the device side is tests/test_gpu_arithmetic_mod.py."""
 import arithmetic_mod_model as model
 from proof_protocol_decoder_amd import arithmetic_mod as am
 from word_tables import MODULAR, cpu_tests
 
-program, reg, edge_trace, test_the_three_column_maps_agree, test_the_layout_entry_refuses_a_short_or_null_buffer, \
-    test_the_program_fits_the_format_and_registers_once, test_the_program_vanishes_on_every_model_row, \
-    test_the_host_checker_is_clean_on_the_model_trace, test_unpack_row_and_pack_inputs_give_back_the_operations, \
-    test_a_wrong_witness_is_named_at_its_row_and_family = cpu_tests(MODULAR)
+globals().update(cpu_tests(MODULAR))
 
 
 def test_a_padding_row_is_zero_but_for_z_and_the_carry_offsets():

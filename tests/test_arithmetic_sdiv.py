@@ -1,92 +1,26 @@
 """The signed table on the CPU: the shipped program (proof_protocol_decoder_amd/arithmetic_sdiv.py) against the
 independent row model of tests/arithmetic_sdiv_model.py -- the column maps, Builder.evaluate over Python integers, the
-library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  The bodies restate
-word_tables.cpu_tests for this table's record (four shipped tables, its own family count).  Nothing here needs a GPU; the
-device side is tests/test_gpu_arithmetic_sdiv.py."""
+library's host checker -- and a catalogue of wrong witnesses, each named at its row and family.  The fixtures and the
+tests it has in common with the other shipped tables are word_tables.cpu_tests over this table's record; its own follow.
+Nothing here needs a GPU; the device side is tests/test_gpu_arithmetic_sdiv.py."""
 import math
 from fractions import Fraction
 
-import numpy as np
 import pytest
 
 import arithmetic_sdiv_model as model
-from proof_protocol_decoder_amd import arithmetic_div, arithmetic_mod, arithmetic_sdiv as sd, arithmetic_shift
-from proof_protocol_decoder_amd.air_program import MAX_FAMILIES_WITH_PORTS, MAX_REGS
+from proof_protocol_decoder_amd import arithmetic_div, arithmetic_sdiv as sd
+from word_tables import SIGNED, cpu_tests, signed
 
-N_COLS, WIDTH, LAYOUT_WORDS, N_FAMILIES, N_CONSTRAINTS, N_UNITS = 2499, 50, 27, 19, 2583, 17   # AIRS.md section 2
-MODEL_LAYOUT = (model.N_COLS, model.IS_SDIV, model.IS_SMOD, model.G, model.Z, model.INV, model.NEG, model.X, model.Y, model.RES,
-                model.Q, model.AY, model.M, model.X_BITS, model.Y_BITS, model.RES_BITS, model.AX_BITS, model.AY_BITS, model.Q_BITS,
-                model.R_BITS, model.D_BITS, model.CARRY, model.CARRY_BITS, model.BORROW, model.X_CHAIN, model.Y_CHAIN,
-                model.RES_CHAIN)
+globals().update(cpu_tests(SIGNED))
 
 
-@pytest.fixture(scope="module")
-def program():
-    return sd.program()
-
-
-@pytest.fixture(scope="module")
-def reg():
-    import proof_protocol_decoder_amd as pkg
-    pkg.lib()
-    return sd.register()
-
-
-@pytest.fixture(scope="module")
-def edge_trace():
-    t = model.trace_of(model.edge_ops())
-    t.setflags(write=False)
-    return t
-
-
-def signed(v):
-    return v - (v >> 255 << 256)
-
-
-def test_the_three_column_maps_agree():
-    """the module's constants, the kernel's (its layout entry) and the model's, which is written from AIRS.md"""
-    assert sd.kernel_layout() == sd.LAYOUT
-    assert MODEL_LAYOUT == sd.LAYOUT and len(sd.LAYOUT) == LAYOUT_WORDS
-    assert [(n, c) for n, c, _ in sd.FAMILIES] == model.FAMILIES
-    assert len(sd.TUPLE_COLS) == WIDTH and sd.N_COLS == N_COLS == model.N_COLS
-    assert (sd.OP_SDIV, sd.OP_SMOD) == (model.SDIV, model.SMOD) == (1, 2)
-    # the division table's port: the same flags-and-three-words tuple, so a table that looks divisions up fits this one
-    assert len(arithmetic_div.TUPLE_COLS) == WIDTH
-
-
-def test_the_layout_entry_refuses_a_short_or_null_buffer():
-    import ctypes as C
-    import proof_protocol_decoder_amd as pkg
-    entry = pkg.lib().bp_arithmetic_sdiv_layout
-    out = (C.c_uint32 * 32)()
-    assert entry(out, len(sd.LAYOUT) - 1) == -2
-    assert b"%d words" % LAYOUT_WORDS in pkg.lib().bp_last_error()
-    assert entry(out, 0) == -2 and not any(out)
-    assert entry(None, 32) == -2
-    assert entry(out, 32) == 0 and tuple(out[:len(sd.LAYOUT)]) == sd.LAYOUT
-
-
-def test_the_program_fits_the_format_and_registers_once(program, reg):
-    import proof_protocol_decoder_amd as pkg
-    words = program.assemble()
-    assert int(words[0]) == int.from_bytes(b"BPGAIRP2", "little")
-    assert int(words[7]) <= MAX_REGS and len(program.units) == N_UNITS <= 256
-    assert len(program.families) == N_FAMILIES <= MAX_FAMILIES_WITH_PORTS
-    assert reg & 0x80000000 and sd.register() == reg and pkg.ops.air_register(words) == reg
-    assert pkg.lib().bp_air_count() == 9                                       # no built-in was added
-    others = {arithmetic_div.register(), arithmetic_mod.register(), arithmetic_shift.register()}
-    assert len(others | {reg}) == 4                                            # ... and every table keeps its own id
-    d = pkg.ops.air_describe(reg)
-    assert (d.n_cols, d.degree, d.n_aux, d.n_air_constraints, d.n_units) == (N_COLS, 3, 2, model.N_CONSTRAINTS, N_UNITS)
-    fams = [(f.first_index, f.count, f.kind, f.degree) for f in d.families[:d.n_families]]
-    first = 0
-    for (name, count, degree), got in zip(sd.FAMILIES, fams):
-        assert got == (first, count, 0, degree), name
-        assert sd.first_index(name) == first
-        first += count
-    # the library's five constraints of the product port follow the program's own
-    assert first == model.N_CONSTRAINTS == N_CONSTRAINTS and d.n_families == N_FAMILIES + 5
-    assert sum(f[1] for f in fams[N_FAMILIES:]) == 5 == d.n_ctl_constraints and fams[N_FAMILIES][0] == first
+def test_a_table_that_looks_divisions_up_fits_this_one():
+    """the division table's port has the same width -- the same flags-and-three-words tuple -- and its input words are
+    this table's"""
+    assert len(arithmetic_div.TUPLE_COLS) == len(sd.TUPLE_COLS) == SIGNED.width
+    ops = model.edge_ops()
+    assert (sd.pack_inputs(ops) == arithmetic_div.pack_inputs(ops)).all()
 
 
 def test_every_unit_cut_states_the_same_constraints():
@@ -123,22 +57,6 @@ def test_the_edge_list_covers_what_the_statement_singles_out():
     assert all((op, x, y, e) in full for x, y in model.EDGE_PAIRS for op in model.LIVE for e in (0, 1))
     negative = sum(1 for o in model.random_ops(1000, 1) if o[1] >> 255)
     assert 400 < negative < 600
-
-
-def test_the_program_vanishes_on_every_model_row(program):
-    """every edge under both flags, exposed and not, the padding rows, random operations: 2^7 rows"""
-    for i, op in enumerate(model.edge_ops_full()):
-        row = model.cells(model.honest(*op))
-        bad = [k for k, v in enumerate(program.evaluate(row, row)) if v]
-        assert not bad, (i, op, [model.family_of(k) for k in bad[:4]])
-        (f, tup), = program.evaluate_ports(row, row)
-        want_g = int(op[0] in model.LIVE and bool(op[3]))
-        assert f == want_g == row[model.G] and len(tup) == WIDTH and tup == [row[c] for c in sd.TUPLE_COLS]
-        if op[0] in model.LIVE:
-            want = [int(op[0] == o) for o in model.LIVE] + model.limbs(op[1]) + model.limbs(op[2]) + model.limbs(model.statement(*op[:3]))
-            assert tup == want
-        else:   # a padding row, as the kernel writes it: all zero except z = 1
-            assert [c for c, v in enumerate(row) if v] == [model.Z] and row[model.Z] == 1
 
 
 def test_the_model_rows_state_the_evm_operations():
@@ -182,52 +100,6 @@ def test_the_largest_values_are_below_the_field():
     assert w["axb"] == 1 << 255 == w["qb"] == w["resb"] and w["neg"] == 0 and w["cx"][15] == 1
 
 
-def test_the_host_checker_is_clean_on_the_model_trace(reg, edge_trace):
-    import proof_protocol_decoder_amd as pkg
-    assert edge_trace.shape == (N_COLS, 32)
-    got = pkg.ops.check_air_trace_host(reg, edge_trace)
-    assert got.ok and got.n_violations == 0, got
-
-
-def test_unpack_row_and_pack_inputs_give_back_the_operations(edge_trace):
-    """(op, x, y, q, r, res, g) of every row of the edge list, against the statement"""
-    ops = model.edge_ops()
-    words = sd.pack_inputs(ops)
-    assert words.shape == (32, 9) and words.dtype == np.uint64
-    assert (words == arithmetic_div.pack_inputs(ops)).all()                    # the division table's input format
-    for i, (op, x, y, exposed) in enumerate(ops):
-        assert int(words[i, 0]) == op | (bool(exposed) << 8)
-        for j, v in enumerate((x, y)):
-            assert sum(int(words[i, 1 + 4 * j + k]) << (64 * k) for k in range(4)) == v
-        got = sd.unpack_row(edge_trace, i)
-        if op not in model.LIVE:
-            assert got == (0,) * 7
-            continue
-        ax, ay = abs(signed(x)), abs(signed(y))
-        q, r = divmod(ax, ay) if ay else (0, ax)
-        assert got == (op, x, y, q, r, model.statement(op, x, y), int(bool(exposed)))
-    with pytest.raises(ValueError):
-        sd.pack_inputs([(1, 1 << 256, 1, 0)])
-
-
 def test_the_catalogue_breaks_every_family():
     assert set().union(*(e[3] for e in model.CATALOGUE)) == {name for name, _ in model.FAMILIES}
     assert len({e[0] for e in model.CATALOGUE}) == len(model.CATALOGUE)
-
-
-@pytest.mark.parametrize("entry", model.CATALOGUE, ids=[e[0] for e in model.CATALOGUE])
-def test_a_wrong_witness_is_named_at_its_row_and_family(program, reg, edge_trace, entry):
-    """the forged row replaces row 9 of the edge trace; Python integers and the host checker name the same constraints,
-    all of them in the families the forgery means to break"""
-    import proof_protocol_decoder_amd as pkg
-    name, _, _, families = entry
-    row = model.forged(entry)
-    broken = [k for k, v in enumerate(program.evaluate(row, row)) if v]
-    assert broken and {model.family_of(k)[1] for k in broken} == families, (name, [model.family_of(k) for k in broken])
-    t = edge_trace.copy()
-    t[:, 9] = np.array(row, dtype=np.uint64)
-    got = pkg.ops.check_air_trace_host(reg, t, max_viol=512)
-    assert got.n_violated_rows == 1 and got.rows == [9] and got.n_violations == len(broken)
-    assert sorted(v.constraint for v in got.violations) == broken and {v.row for v in got.violations} == {9}
-    assert {sd.FAMILIES[v.family][0] for v in got.violations} == families
-    assert all(model.family_of(v.constraint)[0] == v.family for v in got.violations)

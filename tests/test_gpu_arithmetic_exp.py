@@ -2,24 +2,24 @@
 tests/arithmetic_exp_model.py word for word, then the shipped program -- the first whose families span rows -- through
 the run-time stack: the device checker, the prover and the verifier, the port's running products, and table sets in which
 a caller's table looks exponentiations up.  Everything is exact.  2^5 rows, except where an operation needs more: the
-edge lists with their 256-row operations take 2^9, the claim about an exponent of 65 bits 2^7.  The bodies restate
-word_tables.gpu_tests for a table whose operations span rows; the accept and refuse helpers are imported from there.
-CPU side: tests/test_arithmetic_exp.py."""
+edge lists with their 256-row operations take 2^9, the claim about an exponent of 65 bits 2^7.  What holds for every
+shipped table -- the proof of the 2^5-row trace, the port's running products -- is word_tables.proof_tests over this
+table's record, and the looking table and the accept and refuse helpers are imported from there; the rest is its own,
+because the operations span rows.  CPU side: tests/test_arithmetic_exp.py."""
 import numpy as np
 import pytest
 
 import air_program_cases as cases
-import air_program_port_cases as pc
 import arithmetic_exp_model as model
 from air_program_port_cases import LINK, cfg_of
 from proof_protocol_decoder_amd import arithmetic_exp as ex
 from util import to_dev, to_host
-from word_tables import (assert_equal_word_for_word, proves_and_verifies, refused_by_the_pre_flight_the_prover_and_the_verifier,
-                         with_traces)
+from word_tables import (EXPONENTIATION, assert_equal_word_for_word, dev_starts, proof_tests, proves_and_verifies,
+                         refused_by_the_pre_flight_the_prover_and_the_verifier, renamed, table_set, with_traces)
 
-pytestmark = pytest.mark.gpu
+globals().update(renamed(proof_tests(EXPONENTIATION), test_the_edge_trace_proves_and_verifies="test_the_small_trace_proves_and_verifies"))
 
-N_COLS, WIDTH, LOOKER_COLS = 2003, 48, 54
+N_COLS, device_trace = EXPONENTIATION.n_cols, EXPONENTIATION.device_trace
 # one wrong witness per family group: the chain's two ends, its four transitions, the two products, the choice of out, the
 # flags, the range checks
 REJECTED = ("chain_cut_short", "chain_off_the_traces_end", "r_not_one_on_a_first_row", "next_p_not_the_square",
@@ -28,29 +28,6 @@ REJECTED = ("chain_cut_short", "chain_off_the_traces_end", "r_not_one_on_a_first
             "non_bit_in_e", "non_bit_in_m", "g_on_a_row_that_is_not_first", "flag_that_is_no_bit")
 GROUPS = [e for e in model.CATALOGUE if e[0] in REJECTED]
 assert len(GROUPS) == len(REJECTED) and {f for e in GROUPS for _, f in e[2]} == {name for name, _ in model.FAMILIES}
-
-
-def dev_starts(starts):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(starts).view(np.int32)).cuda()
-
-
-def device_trace(bpg, ops, log_n):
-    words, starts = ex.pack_ops(ops, log_n)
-    return bpg.ops.arithmetic_exp_trace(log_n, to_dev(words), dev_starts(starts))
-
-
-@pytest.fixture(scope="module")
-def reg(bpg):
-    return ex.register()
-
-
-@pytest.fixture(scope="module")
-def small(bpg):
-    """(operations, device trace) of the 2^5-row list"""
-    ops = model.small_ops()
-    return ops, device_trace(bpg, ops, 5)
-
 
 LISTS = {"edges-2^9": (model.edge_ops, 9), "a-multiply-on-every-row-2^9": (model.edge_ops_tail, 9), "small-2^5": (model.small_ops, 5),
          "to-the-last-row-2^5": (model.small_ops_to_the_end, 5), "random-2^5": (lambda: model.random_ops(32, 0xE8B1), 5)}
@@ -104,22 +81,12 @@ def test_wrong_prefix_sums_give_a_trace_the_checker_refuses(bpg, reg):
     assert [i for i in range(32) if (host[:, i] != want[:, i]).any()] == [9] and not host[model.LAST, 8]
 
 
-def test_the_small_trace_proves_and_verifies(bpg, reg, small):
-    _, t = small
-    cfg = cases.cfg_for(reg, 5)
-    assert (cfg.n_cols, cfg.rate_bits, cfg.deg_pow) == (N_COLS, 1, 1)
-    proof = bpg.ops.stark_prove_trace(reg, cfg, t)
-    assert int(proof[4]) == 2 and int(proof[14]) == reg                         # two auxiliary columns: the port's products
-    bpg.ops.stark_verify_air(reg, cfg, proof)
-    assert cases.verify(7, cases.cfg_for(7, 5), proof) == -5                    # ... under its own id only
-
-
 @pytest.mark.parametrize("entry", GROUPS, ids=[e[0] for e in GROUPS])
-def test_the_proof_of_a_wrong_witness_is_rejected(bpg, reg, small, entry):
+def test_the_proof_of_a_wrong_witness_is_rejected(bpg, reg, at_2_5, entry):
     """the rows a forgery rewrites -- one, or two that follow each other, or a chain's -- replace those of the device's
     trace: the device checker names the rows and the families, the prover proves what it is given, the verifier rejects at
     zeta"""
-    ops, t = small
+    ops, t = at_2_5
     honest, forged = model.trace_of(ops, 5), model.forged(entry)
     rows = [i for i in range(32) if (honest[:, i] != forged[:, i]).any()]
     assert rows
@@ -134,29 +101,7 @@ def test_the_proof_of_a_wrong_witness_is_rejected(bpg, reg, small, entry):
     assert b"constraint check at zeta" in bpg.lib().bp_last_error()
 
 
-def test_the_ports_running_products_are_the_builders(bpg, reg, small):
-    ops, t = small
-    assert 0 < sum(1 for op in ops if op[0] == model.EXP and op[3]) < len(ops)
-    rng = np.random.default_rng(0xE87C)
-    ctl = [int(v) for v in rng.integers(2, model.P, size=4, dtype=np.uint64)]
-    got = to_host(bpg.ops.air_port_products(reg, t, ctl))
-    want = ex.program().port_running_columns(model.trace_of(ops, 5), ctl)
-    assert got.shape == (2, 32) and [[int(v) for v in col] for col in got] == want
-    assert int(got[0, 0]) not in (0, 1) and int(got[0, 0]) != int(got[1, 0])
-
-
 # ---------------------------------------------------------------------------------------------- table sets
-def table_set(bpg, reg, ops, log_n, claims, seed):
-    """(statement, [looking trace (numpy), the table's trace (device)], looking rows): a 2^log_n-row table of `ops` and a
-    2^4-row table -- pc.flag_program's flag column and the port's tuple -- that sends `claims` = [(base, exponent, res), ...]"""
-    looker = bpg.ops.air_register(pc.flag_program(width=WIDTH, n_cols=LOOKER_COLS).assemble())
-    rng = np.random.default_rng(seed)
-    rows = pc.rows_of(4, rng, len(claims))
-    a = pc.flagged(4, rows, [model.tuple_of(*c) for c in claims], rng, width=WIDTH, n_cols=LOOKER_COLS)
-    tables = [{"air_id": looker, "cfg": cfg_of(looker, 4)}, {"air_id": reg, "cfg": cfg_of(reg, log_n)}]
-    return tables, [a, device_trace(bpg, ops, log_n)], rows
-
-
 # one looking table claims one operation, the only one of its table: (base, exponent, the classic wrong result, log_n)
 STORIES = {"the_exponent_masked_to_a_byte": (2, 256, 1, 4),                      # 2^(256 mod 256)
            "the_exponent_masked_to_64_bits": (3, (1 << 64) + 1, 3, 7),           # 3^((2^64 + 1) mod 2^64)
@@ -168,7 +113,7 @@ def test_a_callers_table_looks_the_operations_up(bpg, reg):
     ops = model.small_ops()
     asked = [(o[1], o[2], pow(o[1], o[2], 1 << 256)) for o in ops if o[0] == model.EXP and o[3]]
     assert len(asked) == 5
-    tables, traces, _ = table_set(bpg, reg, ops, 5, asked[::-1], 0xE875)
+    tables, traces, _ = table_set(bpg, EXPONENTIATION, reg, ops, asked[::-1], 0xE875)
     got = bpg.ops.check_table_set(with_traces(tables, traces), LINK)
     assert got.ok and got.links[0].holds and (got.links[0].n_looking, got.links[0].n_looked) == (5, 5), got
     proves_and_verifies(bpg, tables, traces)
@@ -177,7 +122,7 @@ def test_a_callers_table_looks_the_operations_up(bpg, reg):
 @pytest.mark.parametrize("story", STORIES)
 def test_an_honest_claim_is_accepted(bpg, reg, story):
     base, e, _, log_n = STORIES[story]
-    tables, traces, _ = table_set(bpg, reg, [(model.EXP, base, e, 1)], log_n, [(base, e, pow(base, e, 1 << 256))], 0xE876)
+    tables, traces, _ = table_set(bpg, EXPONENTIATION, reg, [(model.EXP, base, e, 1)], [(base, e, pow(base, e, 1 << 256))], 0xE876, log_n)
     proves_and_verifies(bpg, tables, traces)
 
 
@@ -186,12 +131,12 @@ def test_a_wrong_claim_is_refused(bpg, reg, story):
     """EXP(2, 256) = 1, EXP(3, 2^64 + 1) = 3, EXP(0, 0) = 0: the whole exponent decides, and 0^0 = 1"""
     base, e, wrong, log_n = STORIES[story]
     assert wrong != pow(base, e, 1 << 256)
-    tables, traces, rows = table_set(bpg, reg, [(model.EXP, base, e, 1)], log_n, [(base, e, wrong)], 0xE877)
+    tables, traces, rows = table_set(bpg, EXPONENTIATION, reg, [(model.EXP, base, e, 1)], [(base, e, wrong)], 0xE877, log_n)
     refused_by_the_pre_flight_the_prover_and_the_verifier(bpg, tables, traces, rows[0], 0)
 
 
 def test_an_operation_that_is_not_exposed_cannot_be_looked_up(bpg, reg):
-    tables, traces, rows = table_set(bpg, reg, [(model.EXP, 3, 5, 0)], 4, [(3, 5, 243)], 0xE878)
+    tables, traces, rows = table_set(bpg, EXPONENTIATION, reg, [(model.EXP, 3, 5, 0)], [(3, 5, 243)], 0xE878, 4)
     refused_by_the_pre_flight_the_prover_and_the_verifier(bpg, tables, traces, rows[0], -1)
 
 
